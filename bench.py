@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mvoxel/s of the per-voxel T2 fit on a synthetic 256^3 x 8 TE volume.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one pass of the hot path over the volume: the fit kernel over voxels x 8 echoes already resident in HBM
@@ -23,6 +23,12 @@ The JSON line also carries
                  voxels/s at the bench volume's mask fill), with the fitted-voxel rates of both beside it.
   cpu_baseline_native : SURVEY.md 8d (ii): the build's own lane solver (the headers the kernels are compiled from, built
                  by g++ into tests/hostsim: test infrastructure, never loaded by the product) on all host cores.
+
+`--dump-outputs DIR` writes what the LAST timed step left in the buffers a caller of the step reads, the four float32 maps
+t2 / k / sigma / res, as DIR/<name>.npy on rank 0, taken right after the timed region and before any secondary
+measurement reuses the buffers.  The volume is seeded, so two builds run with the same arguments can be compared map for
+map.  Maps of more than DUMP_MAX_VOXELS voxels are written at a fixed sample of that many flat voxel indices (sorted;
+numpy's frozen RandomState(DUMP_SEED).permutation(n)[:DUMP_MAX_VOXELS]), the same index set for the four maps.
 """
 import argparse
 import ctypes as C
@@ -59,6 +65,35 @@ def host_cores():
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s HBM3E peak
 CLOCK_MHZ, N_SIMD = 2400.0, 256 * 4  # MI355X_MICROARCH.md: 2400 MHz max clock, 256 CUs x 4 SIMD16
 VEC_F64_PEAK_TFLOPS = 256 * 4 * 16 * 2 * 2.4e9 / 1e12  # vector (non-MFMA) float64 FMA peak: 78.6 TFLOP/s
+DUMP_NAMES = ("t2", "k", "sigma", "res")  # rows of the packed output of a step
+DUMP_MAX_VOXELS = 1 << 21  # four float32 maps of 2^21 voxels: 32 MiB per dump
+DUMP_SEED = 20250103
+
+
+def dump_index(n):
+    """Flat voxel indices a dump of n-voxel maps holds: all of them, or the fixed sorted sample (module docstring)."""
+    import numpy as np
+
+    if n <= DUMP_MAX_VOXELS:
+        return None
+    return np.sort(np.random.RandomState(DUMP_SEED).permutation(n)[:DUMP_MAX_VOXELS])
+
+
+def dump_outputs(out_dir, maps4):
+    """maps4: [4, n] float32 tensor (t2, k, sigma, res of one step) -> out_dir/<name>.npy; returns what was written."""
+    import numpy as np
+    import torch
+
+    n = int(maps4.shape[1])
+    idx = dump_index(n)
+    if idx is not None:
+        maps4 = maps4.index_select(1, torch.from_numpy(idx).to(maps4.device))
+    host = maps4.to("cpu", torch.float32).numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, row in zip(DUMP_NAMES, host):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(row))
+    return {"dir": out_dir, "arrays": list(DUMP_NAMES), "dtype": "float32", "voxels_written": int(host.shape[1]), "voxels": n,
+            "sample": None if idx is None else f"sorted RandomState({DUMP_SEED}).permutation({n})[:{DUMP_MAX_VOXELS}]"}
 
 
 def alu_view(key, kernel_ms):
@@ -111,6 +146,9 @@ def parse():
                         "auto = on for N > 1 (where a rank's share is small and the drain is a third of the launch), off for N = 1")
     p.add_argument("--pipeline-streams", type=int, default=2, help="streams the steps rotate over when pipelined (N = 1 runs; N > 1 uses two)")
     p.add_argument("--reserve-cus-ab", type=int, default=8, help="the other setting measured for `reserve_cus_ab` (N > 1)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the maps of the last timed step (t2, k, sigma, res; float32) as DIR/<name>.npy "
+                        "on rank 0: whole maps up to 2^21 voxels, a fixed seeded sample of 2^21 voxels of larger ones")
     return p.parse_args()
 
 
@@ -353,6 +391,20 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
 
+    # --dump-outputs: the maps of the last timed step as its caller holds them (N > 1 with the all-gather: the gathered
+    # maps in voxel order, as every rank has them; otherwise this rank's packed buffer), before anything below writes there again
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        last = (step_no[0] - 1) % (len(packed) if (pipelined or do_gather) else 1)
+        if not do_gather:
+            result = packed[last]
+        elif ordered is not None:
+            result = ordered[last][:, :n_vol]
+        else:  # strong scaling in slabs: the ranks' ranges end to end (the last one padded); weak: one volume per rank
+            result = gathered[last].permute(1, 0, 2).reshape(4, world * n_vox)[:, : n_vol if strong else world * n_vol]
+        dumped = dump_outputs(a.dump_outputs, result)
+        log(f"maps of the last timed step written to {a.dump_outputs} ({dumped['voxels_written']} of {dumped['voxels']} voxels)")
+
     # N = 1: the same K steps rotating over two streams, after the timed region: the drain of a launch (the last voxels in
     # flight, ~0.8 ms) then overlaps the start of the next launch.  Reported beside `value`, never as `value`: the headline
     # stays the plain one-stream figure whose kernel time is the roofline's.
@@ -526,6 +578,8 @@ def main():
                                   "eight one-wave workgroups per CU, two per SIMD), not HBM bound: see DESIGN.md section 6 "
                                   "and `alu`; bytes_per_voxel counts what THIS kernel moves (samples, mask, three maps)")},
         }
+        if dumped is not None:
+            out["outputs_dumped"] = dumped
         if piped is not None:
             piped["value"] = round(total_vox / (piped["ms_per_step"] * 1e-3) / 1e6, 3)
             piped["note"] = ("the same steps rotating over two streams (the drain of a launch overlaps the start of the next one), "
