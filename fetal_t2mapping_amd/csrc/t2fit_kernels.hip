@@ -56,7 +56,6 @@ int g_persistent_blocks = 2048;  // grid of the persistent kernel (T2FIT_PERSIST
 std::atomic<bool> g_reserve_set{false};  // t2fit_set_reserve_cus() was called: it wins over the environment
 std::atomic<int> g_reserve_cus{0};       // T2FIT_RESERVE_CUS: CUs' worth of workgroups the L-BFGS-B kernel is launched short
 bool g_nte_special = true;       // T2FIT_NTE_SPECIAL=0: always the generic-echo-count lane (A/B switch)
-int g_park_min = 1;              // T2FIT_PARK_MIN: lanes of a wave that must be waiting for begin() before it runs (A/B switch)
 
 thread_local std::string g_err;
 thread_local bool g_timing = false;
@@ -350,7 +349,7 @@ template <int MODEL, int NTE = 0, bool GSPLIT = false> struct LbfgsbLane {
   // r03_exp6_refill_take.txt), 256^3 x 8 TE: 1 -> 12.48 ms, 4 -> 12.13, 8 -> 12.03, 12 -> 12.20, 16 -> 12.42; the Rician
   // likelihood, whose evaluation is four times as long (an idle lane costs more): 4 -> 19.77, 8 -> 20.01, 16 -> 20.76
   static constexpr int kRefillMin = MODEL == T2FIT_MODEL_RICIAN ? 4 : 8;
-  static constexpr bool kSplit = true;   // advance() = digest() + begin(): the kernel may batch begin() (T2FIT_PARK_MIN)
+  static constexpr bool kSplit = true;   // advance() = digest() + begin_pass(): the kernel calls the two halves itself
   __device__ static void init(Solver& s, const ObjCtx&, const double* x0, const double* lb, const double* ub,
                               double* hist, int hstride, double* ghist) { s.init(x0, lb, ub, hist, hstride, ghist, 64); }
   __device__ static void result(const Solver& s, const ObjCtx&, LaneResult& r) { s.result(r); }
@@ -380,8 +379,7 @@ template <typename T, int NPAR, int NTE = 0> struct LmLaneAdaptor {
 template <class A, int kChunk, bool kTrace, bool kExtras, int kWg = kBlock, bool kRegs = false>
 __device__ __forceinline__ void persistent_fit(const LaneParams& P, const float* __restrict__ echoes, int layout,
                                                const uint8_t* __restrict__ mask, int64_t n_vox, const DevMaps& m,
-                                               unsigned long long* next_chunk, int refill_min, int park_min, int take,
-                                               double* ghist_all) {
+                                               unsigned long long* next_chunk, int refill_min, int take, double* ghist_all) {
   extern __shared__ float lds[];
   constexpr int NP = A::NP;
   // kRegs: samples and voxel queue in registers, LDS for the correction pairs only -- the form launched as one-wave
@@ -431,7 +429,7 @@ __device__ __forceinline__ void persistent_fit(const LaneParams& P, const float*
     if (lane == 0 && w < (unsigned)kPlaceWords) next_chunk[16 + kDiagWords + w] = 0x100000000ull | ((unsigned long long)(xcc & 0xf) << 20) | (hw & 0xfffff);
   }
 #endif
-  bool parked = false;  // split solvers: digest() done, begin() pending (see park_min below)
+  bool parked = false;  // split solvers: digest() done, begin_pass() asked to be run again (see the round below)
   int pend = 0;
   // kWaveWg: the chunk queue is read two steps ahead, so that taking a chunk never waits for memory -- chunk A has
   // its base and its mask bytes (loaded when the chunk before it was taken), chunk B its counter value (lane 0)
@@ -649,39 +647,10 @@ __device__ __forceinline__ void persistent_fit(const LaneParams& P, const float*
     }
     if (__ballot(busy) == 0ull) break;  // nothing running and nothing left to take
     if constexpr (A::kSplit) {
-#if defined(T2_PARK_SWITCH)
-      // One round: every lane with a point to evaluate evaluates it (uniform code) and digests the result; lanes
-      // whose line search has ended then run begin() (B, Cauchy point, subspace step, line-search set-up).
-      // park_min > 1 holds those lanes back until that many of the wave are waiting (or no lane has anything to
-      // evaluate), so that begin() runs with more lanes active; results do not depend on it.
-      if (busy && !parked) {
-        T2_BLK_T0(t_ev)
-        s.eval(c);
-        T2_BLK_END(c, 7, t_ev)
-        pend = s.digest(c);
-        if (pend == A::Solver::GO_DONE) { busy = false; done = true; }
-        else if (pend != A::Solver::GO_TRIAL) parked = true;
-      }
-      const unsigned long long pb = __ballot(parked);
-      if (pb != 0ull && (__popcll(pb) >= park_min || __ballot(busy && !parked) == 0ull)) {
-        if (parked) {
-          T2_BLK_T0(t_bg)
-          pend = s.begin_pass(c, pend);
-          T2_BLK_END(c, 9, t_bg)
-          // GO_BEGIN / GO_FAIL: the iteration has to be begun again (memory dropped, line search could not start):
-          // the lane stays parked and comes back here in the next round
-          if (pend == A::Solver::GO_DONE) { parked = false; busy = false; done = true; }
-          else if (pend == A::Solver::GO_TRIAL) parked = false;
-        }
-      }
-#else
       // One round: every lane with a point to evaluate evaluates it (uniform code) and digests the result; lanes whose
       // line search has ended then run begin_pass() (B, Cauchy point, subspace step, line-search set-up).  `parked`: the
       // pass asked to be run again (memory dropped, line search could not start: rare) -- the lane comes back in the next
       // round and skips the evaluation.  One region under `busy`, so that the solver state has one version per round.
-      // (-DT2_PARK_SWITCH: the round-2 form with T2FIT_PARK_MIN, which held the lanes that need begin_pass() back until
-      // that many of a wave were waiting; measured twice, never paid.)
-      (void)park_min;
       if (busy) {
         if (!parked) {
           T2_BLK_T0(t_ev)
@@ -697,7 +666,6 @@ __device__ __forceinline__ void persistent_fit(const LaneParams& P, const float*
         parked = pend == A::Solver::GO_BEGIN || pend == A::Solver::GO_FAIL;
         if (pend == A::Solver::GO_DONE) { busy = false; done = true; }
       }
-#endif
     } else {
       if (busy) s.eval(c);
       if (busy && s.advance(c)) {
@@ -726,8 +694,8 @@ __global__ __launch_bounds__(kWg, kWavesPerSimd) void fit_persistent_kernel(cons
                                                                     const float* __restrict__ echoes, int layout,
                                                                     const uint8_t* __restrict__ mask, int64_t n_vox,
                                                                     DevMaps m, unsigned long long* next_chunk, int refill_min,
-                                                                    int park_min, int take, double* ghist) {
-  persistent_fit<A, kChunk, kTrace, kExtras, kWg, kRegs>(P, echoes, layout, mask, n_vox, m, next_chunk, refill_min, park_min, take, ghist);
+                                                                    int take, double* ghist) {
+  persistent_fit<A, kChunk, kTrace, kExtras, kWg, kRegs>(P, echoes, layout, mask, n_vox, m, next_chunk, refill_min, take, ghist);
 }
 
 // Residual map (utils/t2map_utils.py:62-89) and optional R^2 from float32 maps already on the device.
@@ -926,6 +894,52 @@ FitKernel pick_kernel(const t2fit_config& c) {
   return nullptr;  // the L-BFGS-B solver runs in the persistent kernel
 }
 
+// The global part of the correction-pair ring (one-wave-workgroup kernels with three parameters: M x 64 doubles per wave,
+// 10 MiB for a whole chip) is kept between launches: one buffer per (device, stream), grown on demand.  Launches on one
+// stream run one after the other, so they may share a buffer; launches on different streams may overlap and must not
+// (the kernel keeps live solver state in it).  A buffer is given back when its stream's context is destroyed
+// (ring_part_release); buffers of caller-owned streams live as long as the process.
+struct RingPart { int device; hipStream_t stream; double* p; size_t bytes; };
+std::mutex g_ring_mutex;
+std::vector<RingPart> g_ring_parts;
+
+hipError_t ring_part_get(hipStream_t st, size_t bytes, double** out) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  std::lock_guard<std::mutex> g(g_ring_mutex);
+  RingPart* r = nullptr;
+  for (RingPart& c : g_ring_parts)
+    if (c.device == dev && c.stream == st) r = &c;
+  if (!r) {
+    g_ring_parts.push_back(RingPart{dev, st, nullptr, 0});
+    r = &g_ring_parts.back();
+  }
+  if (r->bytes < bytes) {
+    if (r->p) {  // (a kernel queued earlier on this stream may still be using it)
+      if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+      (void)hipFree(r->p);
+      r->p = nullptr;
+      r->bytes = 0;
+    }
+    if ((e = hipMalloc((void**)&r->p, bytes)) != hipSuccess) return e;
+    r->bytes = bytes;
+  }
+  *out = r->p;
+  return hipSuccess;
+}
+
+// the stream is about to be destroyed (and has been synchronised)
+void ring_part_release(int device, hipStream_t st) {
+  std::lock_guard<std::mutex> g(g_ring_mutex);
+  for (size_t i = 0; i < g_ring_parts.size(); ++i)
+    if (g_ring_parts[i].device == device && g_ring_parts[i].stream == st) {
+      if (g_ring_parts[i].p) (void)hipFree(g_ring_parts[i].p);
+      g_ring_parts.erase(g_ring_parts.begin() + i);
+      return;
+    }
+}
+
 // kLargeOnly: instantiate the two large-volume kernels only (the echo-count specialisations; small volumes and
 // traced voxel batches use the generic lane, where compile time buys nothing)
 // kWaveOnly: instantiate the one-wave-workgroup kernels of A only (the less common echo counts: compile time); where
@@ -975,18 +989,12 @@ hipError_t launch_persistent(unsigned grid, size_t lds_samples, hipStream_t st, 
       const unsigned n_wg = grid * per_cu;
       double* ghist = nullptr;
       if constexpr (AW::kGlobalPart) {  // M x 64 doubles per wave (5 KiB; 10 MiB for the whole chip: it lives in L2)
-        e = hipMallocAsync((void**)&ghist, (size_t)n_wg * (wg / 64) * AW::Solver::M * 64 * sizeof(double), st);
+        e = ring_part_get(st, (size_t)n_wg * (wg / 64) * AW::Solver::M * 64 * sizeof(double), &ghist);
         if (e != hipSuccess) return e;
       }
       hipLaunchKernelGGL(k64, dim3(n_wg), dim3(wg), lds64, st, P, echoes, layout, mask, n_vox, dm, counter,
-                         g_refill_min > 0 ? g_refill_min : AW::kRefillMin, g_park_min,
-                         g_take > 0 ? g_take : 2, ghist);
-      e = hipGetLastError();
-      if (ghist) {
-        const hipError_t e2 = hipFreeAsync(ghist, st);
-        if (e == hipSuccess) e = e2;
-      }
-      return e;
+                         g_refill_min > 0 ? g_refill_min : AW::kRefillMin, g_take > 0 ? g_take : 2, ghist);
+      return hipGetLastError();
     }
   }
 #endif
@@ -1011,7 +1019,7 @@ hipError_t launch_persistent(unsigned grid, size_t lds_samples, hipStream_t st, 
                                      (int)lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, P, echoes, layout, mask, n_vox, dm, counter,
-                     g_refill_min > 0 ? g_refill_min : A::kRefillMin, g_park_min, 1, (double*)nullptr);
+                     g_refill_min > 0 ? g_refill_min : A::kRefillMin, 1, (double*)nullptr);
   return hipGetLastError();
   }
 }
@@ -1069,7 +1077,6 @@ int launch_fit(const t2fit_config* cfg, const float* echoes, int layout, const u
     if (const char* e = std::getenv("T2FIT_NTE_SPECIAL")) g_nte_special = std::atoi(e) != 0;
     if (const char* e = std::getenv("T2FIT_TAKE")) g_take = std::max(0, std::min(64, std::atoi(e)));
     if (const char* e = std::getenv("T2FIT_SMALL_VOLUME")) kSmallVolume = std::max<int64_t>(0, std::atoll(e));
-    if (const char* e = std::getenv("T2FIT_PARK_MIN")) g_park_min = std::min(64, std::max(1, std::atoi(e)));
     if (const char* e = std::getenv("T2FIT_WAVE_WG")) g_wave_wg = std::max(0, std::atoi(e));
     if (const char* e = std::getenv("T2FIT_WAVES_PER_CU")) g_waves_per_cu = std::max(0, std::atoi(e));
     return true;
@@ -1321,6 +1328,7 @@ int t2fit_destroy(t2fit_context* c) {
     (void)hipStreamSynchronize(c->s_in);
     (void)hipStreamSynchronize(c->s_fit);
     (void)hipStreamSynchronize(c->s_out);
+    ring_part_release(c->device, c->s_fit);
     for (auto ev : c->events) (void)hipEventDestroy(ev);
     for (int j = 0; j < 2; ++j) {
       if (c->pin_in[j]) (void)hipHostFree(c->pin_in[j]);

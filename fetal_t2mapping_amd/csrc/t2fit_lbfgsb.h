@@ -172,28 +172,35 @@ T2_HD void dcstep(double& stx, double& fx, double& dx, double& sty, double& fy, 
   double arg = ts * ts - t2_div_by_rcp(da, s, rs) * t2_div_by_rcp(dp, s, rs);
   arg = c3 ? lb_max(0.0, arg) : arg;
   double gamma = s * t2_sqrt_core(arg);
-  const bool flip = c1 ? stp < stx : (c4 ? stp > sty : stp > stx);
+  const bool lt_x = stp < stx, gt_x = stp > stx, gt_y = stp > sty;
+  const bool flip = (c1 & lt_x) | (!c1 & ((c4 & gt_y) | (!c4 & gt_x)));
   gamma = flip ? -gamma : gamma;
   const double gd1 = c1 ? dx : dp;  // the slope subtracted from gamma
   const double p = (gamma - gd1) + theta;
-  const double q = c3 ? (gamma + (dx - dp)) + gamma : ((gamma - gd1) + gamma) + (c1 ? dp : (c2 ? dx : dy));
+  const double q3 = (gamma + (dx - dp)) + gamma, gd2 = c1 ? dp : (c2 ? dx : dy), q124 = ((gamma - gd1) + gamma) + gd2;
+  const double q = c3 ? q3 : q124;
   const double r = t2_fdiv(p, q);
-  const double far_end = stp > stx ? stpmax : stpmin;
+  const double far_end = gt_x ? stpmax : stpmin;
   // cubic step
-  double stpc = c1 ? stx + r * (stp - stx) : stp + r * (sta - stp);
-  stpc = (c3 && !(r < 0.0 && gamma != 0.0)) ? far_end : stpc;
+  const double stpc1 = stx + r * (stp - stx), stpc234 = stp + r * (sta - stp);
+  double stpc = c1 ? stpc1 : stpc234;
+  const bool r_neg = r < 0.0, g_nz = gamma != 0.0;
+  stpc = (c3 & !(r_neg & g_nz)) ? far_end : stpc;
   // quadratic (case 1) or secant (cases 2, 3) step: one division chain on operands selected by case
   //   case 1: ((dx / ((fx - fp) / (stp - stx) + dx)) / 2) ; otherwise dp / (dp - dx)
-  const double qden = c1 ? t2_fdiv(fx - fp, stp - stx) + dx : dp - dx;
+  const double qden1 = t2_fdiv(fx - fp, stp - stx) + dx, qden23 = dp - dx;  // (both by every lane: no region around a division)
+  const double qden = c1 ? qden1 : qden23;
   const double qq = t2_fdiv(c1 ? dx : dp, qden);
   const double quad = c1 ? qq * 0.5 : qq;
-  const double stpq = c1 ? stx + quad * (stp - stx) : stp + quad * (stx - stp);
+  const double stpq1 = stx + quad * (stp - stx), stpq23 = stp + quad * (stx - stp);
+  const double stpq = c1 ? stpq1 : stpq23;
   // the step taken
   const double dc = lb_abs(stpc - stp), dq = lb_abs(stpq - stp);
   const double f1 = lb_abs(stpc - stx) < lb_abs(stpq - stx) ? stpc : stpc + (stpq - stpc) * 0.5;
   const double farther = dc > dq ? stpc : stpq, nearer = dc < dq ? stpc : stpq;
   const double lim = stp + 0.66 * (sty - stp);
-  const double f3b = stp > stx ? lb_min(lim, nearer) : lb_max(lim, nearer);
+  const double f3lo = lb_min(lim, nearer), f3hi = lb_max(lim, nearer);
+  const double f3b = gt_x ? f3lo : f3hi;
   const double f3u = lb_max(stpmin, lb_min(stpmax, farther));
   const double f4 = brackt ? stpc : far_end;
   const double stpf = c1 ? f1 : (c2 ? farther : (c3 ? (brackt ? f3b : f3u) : f4));
@@ -232,13 +239,16 @@ T2_HD void dcsrch_start(double f, double g, double stp, double ftol, double stpm
 T2_HD int dcsrch_tests(double f, double g, double stp, double gtol, double xtol, double stpmin, double stpmax,
                        LsState& s) {
   const double ftest = s.finit + stp * s.gtest;
-  if (s.stage == 1 && f <= ftest && g >= 0.0) s.stage = 2;
-  int task = LS_FG;
-  if (s.brackt && (stp <= s.stmin || stp >= s.stmax)) task = LS_WARN;   // rounding errors prevent progress
-  if (s.brackt && s.stmax - s.stmin <= xtol * s.stmax) task = LS_WARN;  // xtol test satisfied
-  if (stp == stpmax && f <= ftest && g <= s.gtest) task = LS_WARN;      // stp = stpmax
-  if (stp == stpmin && (f > ftest || g >= s.gtest)) task = LS_WARN;     // stp = stpmin
-  if (f <= ftest && lb_abs(g) <= gtol * (-s.ginit)) task = LS_CONV;
+  // (every comparison is made by every lane and the predicates are combined bit-wise: `&&` / `||` would evaluate the
+  // right-hand comparison under a narrowed execution mask -- three scalar instructions and a region per operator)
+  const bool f_ok = f <= ftest, g_pos = g >= 0.0, g_le = g <= s.gtest, g_ge = g >= s.gtest;
+  s.stage = ((s.stage == 1) & f_ok & g_pos) ? 2 : s.stage;
+  const bool outside = (stp <= s.stmin) | (stp >= s.stmax);              // rounding errors prevent progress
+  const bool narrow = s.stmax - s.stmin <= xtol * s.stmax;              // xtol test satisfied
+  const bool at_max = (stp == stpmax) & f_ok & g_le;                    // stp = stpmax
+  const bool at_min = (stp == stpmin) & ((f > ftest) | g_ge);           // stp = stpmin
+  const bool conv = f_ok & (lb_abs(g) <= gtol * (-s.ginit));
+  const int task = conv ? LS_CONV : (((s.brackt & (outside | narrow)) | at_max | at_min) ? LS_WARN : LS_FG);
   s.task = task;
   return task;
 }
@@ -247,7 +257,7 @@ T2_HD void dcsrch_update(double f, double g, double& stp, double xtol, double st
   const double xtrapl = 1.1, xtrapu = 4.0, p5 = 0.5, p66 = 0.66;
   const double ftest = s.finit + stp * s.gtest;
   // stage 1 works on the modified function psi(stp) = f(stp) - f(0) - ftol*stp*f'(0)
-  const bool modified = s.stage == 1 && f <= s.fx && f > ftest;
+  const bool modified = (s.stage == 1) & (f <= s.fx) & (f > ftest);
   const double gt = modified ? s.gtest : 0.0;
   double fm = modified ? f - stp * gt : f, gm = modified ? g - gt : g;
   double fxm = modified ? s.fx - s.stx * gt : s.fx, fym = modified ? s.fy - s.sty * gt : s.fy;
@@ -259,7 +269,7 @@ T2_HD void dcsrch_update(double f, double g, double& stp, double xtol, double st
   s.gy = modified ? gym + gt : gym;
   const double span = lb_abs(s.sty - s.stx);
   const double mid = s.stx + p5 * (s.sty - s.stx);
-  stp = (s.brackt && span >= p66 * s.width1) ? mid : stp;
+  stp = (s.brackt & (span >= p66 * s.width1)) ? mid : stp;
   s.width1 = s.brackt ? s.width : s.width1;
   s.width = s.brackt ? span : s.width;
   const double lo_b = lb_min(s.stx, s.sty), hi_b = lb_max(s.stx, s.sty);
@@ -268,7 +278,7 @@ T2_HD void dcsrch_update(double f, double g, double& stp, double xtol, double st
   s.stmax = s.brackt ? hi_b : hi_u;
   stp = lb_max(stp, stpmin);
   stp = lb_min(stp, stpmax);
-  const bool stuck = s.brackt && ((stp <= s.stmin || stp >= s.stmax) || (s.stmax - s.stmin <= xtol * s.stmax));
+  const bool stuck = s.brackt & ((stp <= s.stmin) | (stp >= s.stmax) | (s.stmax - s.stmin <= xtol * s.stmax));
   stp = stuck ? s.stx : stp;
   s.task = LS_FG;
 }
@@ -436,10 +446,11 @@ struct Lbfgsb {
         h = 1.4901161193847656e-08 * (x[i] >= 0 ? 1.0 : -1.0) * lb_max(1.0, lb_abs(x[i]));
       const double lower = x[i] - lb[i], upper = ub[i] - x[i];
       const double xs = x[i] + h;
-      const bool violated = xs < lb[i] || xs > ub[i];
+      const bool violated = (xs < lb[i]) | (xs > ub[i]);
       const bool fitting = lb_abs(h) <= lb_max(lower, upper);
-      if (violated && fitting) h = -h;
-      if (!fitting) h = upper >= lower ? upper : -lower;
+      h = (violated & fitting) ? -h : h;
+      const double h_far = upper >= lower ? upper : -lower;
+      h = fitting ? h : h_far;
       x1[i] = x[i] + h;
       dx[i] = x1[i] - x[i];
     }
@@ -490,8 +501,9 @@ struct Lbfgsb {
       // (2^-22: the coupled Newton step of t2_sqrt_near then lands 2^-45 from the root and the correction 2^-39 ulp from it;
       // the reference's steps are 1e-8 on k >= 550, sigma >= 2 and T2 >= 10 ms: 2^-36, 2^-28 and, at 300 ms, 2^-24)
       const double tol = 0x1p-22;
-      const bool near = 2.0 * lb_abs(dx[0]) <= tol * lb_abs(x[0]) && 2.0 * lb_abs(dx[N - 1]) <= tol * lb_abs(x[N - 1]) &&
-                        2.0 * P.te_max * lb_abs(dx[1]) <= tol * (t2 * t2p) && sg2 > 0.0;
+      const bool near_k = 2.0 * lb_abs(dx[0]) <= tol * lb_abs(x[0]), near_s = 2.0 * lb_abs(dx[N - 1]) <= tol * lb_abs(x[N - 1]);
+      const bool near_t = 2.0 * P.te_max * lb_abs(dx[1]) <= tol * (t2 * t2p), s_pos = sg2 > 0.0;
+      const bool near = near_k & near_s & near_t & s_pos;
       if (T2_WAVE_ANY(!near)) {
         // the rare way round: independent roots, one echo at a time in a real loop (compact code beside the straight-line
         // block below, whose registers it must not add to); same operations, same summation order (RowSums4)
@@ -603,8 +615,8 @@ struct Lbfgsb {
     T2_UNROLL
     for (int i = 0; i < N; ++i) {
       double gi = g[i];
-      if (gi < 0.0) gi = lb_max(x[i] - ub[i], gi);
-      else gi = lb_min(x[i] - lb[i], gi);
+      const double g_up = lb_max(x[i] - ub[i], gi), g_lo = lb_min(x[i] - lb[i], gi);
+      gi = gi < 0.0 ? g_up : g_lo;
       nrm = lb_max(nrm, lb_abs(gi));
     }
     return nrm;
@@ -717,6 +729,9 @@ struct Lbfgsb {
     for (int i = 0; i < N; ++i) xcp[i] = x[i];
     // (no early exits in here either -- see begin_pass(): a lane with nothing to do computes along and keeps nothing)
     const bool live = sbgnrm > 0.0;
+    // tbk[i]: the breakpoint of variable i along the projected path, +inf where it has none (or none any more): the
+    // next breakpoint is then a three-element minimum (v_min_f64: no NaN here, see lb_min) and the variable it belongs
+    // to the first one that equals it -- the order the library's heap gives (ties: lowest index)
     double d[N], tbk[N], zfix[N];
     bool hasbk[N];
     int nbreak = 0;
@@ -727,19 +742,19 @@ struct Lbfgsb {
       const double tl = x[i] - lb[i], tu = ub[i] - x[i];
       {
         const bool xlower = tl <= 0.0, xupper = tu <= 0.0;
-        const int iw = xlower ? (neggi <= 0.0 ? 1 : 0) : (xupper ? (neggi >= 0.0 ? 2 : 0) : (lb_abs(neggi) <= 0.0 ? -3 : 0));
-        iwhere[i] = (live && iwhere[i] != 3) ? iw : iwhere[i];
+        const int iw_l = neggi <= 0.0 ? 1 : 0, iw_u = neggi >= 0.0 ? 2 : 0, iw_f = lb_abs(neggi) <= 0.0 ? -3 : 0;
+        const int iw = xlower ? iw_l : (xupper ? iw_u : iw_f);
+        iwhere[i] = (live & (iwhere[i] != 3)) ? iw : iwhere[i];
       }
-      d[i] = 0.0; tbk[i] = 0.0; zfix[i] = 0.0; hasbk[i] = false;
-      if (iwhere[i] == 0) {
-        d[i] = neggi;
-        f1 = fma(-neggi, neggi, f1);
-        if (neggi != 0.0) {  // one division on the selected numerator instead of one per branch
-          tbk[i] = t2_fdiv(neggi < 0.0 ? tl : tu, lb_abs(neggi));
-          hasbk[i] = true;
-          ++nbreak;
-        }
-      }
+      const bool moves = iwhere[i] == 0;
+      hasbk[i] = moves & (neggi != 0.0);
+      d[i] = moves ? neggi : 0.0;
+      f1 = moves ? fma(-neggi, neggi, f1) : f1;
+      // (one division on the selected numerator instead of one per branch; a variable without a breakpoint divides too)
+      const double tq = t2_fdiv(neggi < 0.0 ? tl : tu, lb_abs(neggi));
+      tbk[i] = hasbk[i] ? tq : (double)INFINITY;
+      zfix[i] = 0.0;
+      nbreak += hasbk[i];
     }
     const bool start = live && nbreak > 0;  // nbreak == 0: every moving variable is box-bounded here, so d == 0
     const double f2_org = -theta * f1;
@@ -757,46 +772,41 @@ struct Lbfgsb {
     int nleft = nbreak;
     bool all_fixed = false;
     // at most N breakpoints: N copies of the segment step instead of a loop (a back-edge here costs scalar registers
-    // across the whole begin-iteration block); `go` turns false where the loop would have been left
+    // across the whole begin-iteration block); `go`: the walk is still on (false where the loop would have been left)
     bool go = start;
     T2_UNROLL
     for (int seg = 0; seg < N; ++seg) {
-      if (!(go && nleft > 0)) continue;
-      // next breakpoint: one-hot flags rather than an index, so that no local array is ever
-      // indexed by a run-time value (the compiler would move it to scratch memory)
-      bool pick[N];
-      bool any = false;
-      double tmin = 0.0;
+      double tmin = tbk[0];
       T2_UNROLL
-      for (int i = 0; i < N; ++i) {
-        pick[i] = hasbk[i] && (!any || tbk[i] < tmin);
-        if (pick[i]) {
-          T2_UNROLL
-          for (int j = 0; j < N; ++j)
-            if (j < i) pick[j] = false;
-          any = true;
-          tmin = tbk[i];
-        }
-      }
-      const double tj0 = tj;
-      tj = tmin;
-      const double dt = tj - tj0;
-      if (dtm < dt) { go = false; continue; }
+      for (int i = 1; i < N; ++i) tmin = lb_min(tmin, tbk[i]);
+      const double dt = tmin - tj;
+      // the minimiser lies before the next breakpoint (or there is none left): the walk ends in this segment
+      go = go && nleft > 0 && !(dtm < dt);
+      if (!go) continue;
       T2_BLK_T0(t_bp)
       T2_BLK_END((*this), 1, t_bp)
+      tj = tmin;
       tsum += dt;
       --nleft;
-      double dibp = 0.0;
+      bool earlier = false;
       T2_UNROLL
-      for (int i = 0; i < N; ++i)
-        if (pick[i]) {
-          dibp = d[i];
-          d[i] = 0.0;
-          hasbk[i] = false;
-          if (dibp > 0.0) { zfix[i] = ub[i] - x[i]; xcp[i] = ub[i]; iwhere[i] = 2; }
-          else { zfix[i] = lb[i] - x[i]; xcp[i] = lb[i]; iwhere[i] = 1; }
-        }
-      if (nleft == 0 && nbreak == N) { all_fixed = true; go = false; continue; }
+      for (int i = 0; i < N; ++i) {
+        const bool pick = !earlier & hasbk[i] & (tbk[i] == tmin);
+        earlier = earlier | pick;
+        const bool up = d[i] > 0.0;
+        const double bnd = up ? ub[i] : lb[i];
+        zfix[i] = pick ? bnd - x[i] : zfix[i];
+        xcp[i] = pick ? bnd : xcp[i];
+        iwhere[i] = pick ? (up ? 2 : 1) : iwhere[i];
+        d[i] = pick ? 0.0 : d[i];
+        tbk[i] = pick ? (double)INFINITY : tbk[i];
+        hasbk[i] = hasbk[i] & !pick;
+      }
+      // every variable with a breakpoint is now at its bound and none is left to move: the walk ends here (what is computed
+      // below is not used then: commit is false and go ends the later segments)
+      const bool fixed_now = (nleft == 0) & (nbreak == N);
+      all_fixed = all_fixed | fixed_now;
+      go = !fixed_now;
       // derivatives of the quadratic model along the remaining direction, z = xcp - x so far
       double z[N];
       T2_UNROLL
@@ -810,8 +820,11 @@ struct Lbfgsb {
         f1 = fma(d[i], g[i] + bz, f1);
       }
       f2 = lb_max(epsmch * f2_org, dBd(d));
-      if (nleft > 0) dtm = t2_fdiv(-f1, f2);
-      else { f1 = 0.0; f2 = 0.0; dtm = 0.0; }  // all remaining variables are box-bounded
+      const bool more = nleft > 0;  // else: all remaining variables are box-bounded
+      const double dtm_n = t2_fdiv(-f1, f2);
+      dtm = more ? dtm_n : 0.0;
+      f1 = more ? f1 : 0.0;
+      f2 = more ? f2 : 0.0;
     }
     const bool commit = start && !all_fixed;
     dtm = lb_max(dtm, 0.0);
@@ -854,7 +867,7 @@ struct Lbfgsb {
     const double d2 = fma(-l21, a21, fma(-l20, A[2][0], A[2][2])), r2 = t2_fast_rcp(d2);
     // (no early exit on a non-positive pivot: the step is computed anyway -- NaN or nonsense then, thrown away by the
     // caller, which begins the iteration again -- so that this is one straight block)
-    const bool pos_def = d0 > 0.0 && d1 > 0.0 && d2 > 0.0;
+    const bool pos_def = (d0 > 0.0) & (d1 > 0.0) & (d2 > 0.0);
     const double y0 = rr[0], y1 = fma(-l10, y0, rr[1]), y2 = fma(-l21, y1, fma(-l20, y0, rr[2]));
     const double u2 = y2 * r2, u1 = fma(-l21, u2, y1 * r1);
     const double u0 = fma(-l20, u2, fma(-l10, u1, y0 * r0));
@@ -866,11 +879,9 @@ struct Lbfgsb {
     T2_UNROLL
     for (int i = 0; i < N; ++i) {
       xp[i] = z[i];
-      if (fr[i]) {
-        const double xk = lb_max(lb[i], z[i] + du[i]);
-        z[i] = lb_min(ub[i], xk);
-        if (z[i] == lb[i] || z[i] == ub[i]) projected = true;
-      }
+      const double xk = lb_min(ub[i], lb_max(lb[i], z[i] + du[i]));
+      z[i] = fr[i] ? xk : z[i];
+      projected = projected | (fr[i] & ((xk == lb[i]) | (xk == ub[i])));
     }
     double ddp = 0.0;
     T2_UNROLL
@@ -975,8 +986,8 @@ struct Lbfgsb {
     for (int i = 0; i < N; ++i) gdn += g[i] * d[i];
     LsState lsn = ls;
     const int task = dcsrch_tests(f, gdn, stp, 0.9, 0.1, 0.0, stpmx, lsn);
-    const bool cont = !was_first && task == LS_FG;   // line search continues
-    const bool newit = !was_first && task != LS_FG;  // a new iterate
+    const bool cont = !was_first & (task == LS_FG);   // line search continues
+    const bool newit = !was_first & (task != LS_FG);  // a new iterate
     // -- line search continues: next trial step --
     double stpn = stp;
     dcsrch_update(f, gdn, stpn, 0.1, 0.0, stpmx, lsn);
@@ -984,8 +995,8 @@ struct Lbfgsb {
     const double sb = projgr(x, g);
     const double tol = P.lbfgsb_tol;  // factr * epsmch = (ftol / epsmch) * epsmch, formed on the host
     const int nit1 = nit + 1;
-    const bool out_of_budget = nit1 >= P.maxiter || nfev > P.maxfun;  // scipy: STOP, success False
-    const bool converged = sb <= P.gtol || (!was_first && (fold - f) <= tol * t2_max3(lb_abs(fold), lb_abs(f), 1.0));
+    const bool out_of_budget = (nit1 >= P.maxiter) | (nfev > P.maxfun);  // scipy: STOP, success False
+    const bool converged = (sb <= P.gtol) | (!was_first & ((fold - f) <= tol * t2_max3(lb_abs(fold), lb_abs(f), 1.0)));
     double rn[N], dn[N], rr = 0.0;
     T2_UNROLL
     for (int i = 0; i < N; ++i) { rn[i] = g[i] - r[i]; rr += rn[i] * rn[i]; }
@@ -998,8 +1009,8 @@ struct Lbfgsb {
     // rank-one term of each update is a plain outer product (three multiplications, a dot product and a reciprocal
     // less per pair and iteration); theta keeps the unscaled y
     const double rsy = t2_fast_rsqrt(dr);
-    const bool iterate_on = newit && !out_of_budget && !converged;
-    const bool store_pair = iterate_on && !(dr <= epsmch * ddum);  // else: curvature too small, skip the update
+    const bool iterate_on = newit & !out_of_budget & !converged;
+    const bool store_pair = iterate_on & !(dr <= epsmch * ddum);  // else: curvature too small, skip the update
     // -- keep what belongs to this lane's state --
     if (!was_first) gd = gdn;
     if (cont) { ls = lsn; stp = stpn; ++ifun; }
@@ -1029,19 +1040,21 @@ struct Lbfgsb {
       theta = theta_n;
     }
     if ((was_first || newit) && converged && !(newit && out_of_budget)) status = T2FIT_ST_CONVERGED;
-    int next;
-    if (cont) next = ifun - 1 >= P.maxls ? GO_FAIL : GO_TRIAL;
-    else if (was_first) next = converged ? GO_DONE : GO_BEGIN;
-    else next = (out_of_budget || converged) ? GO_DONE : GO_BEGIN;
+    const int next_ls = ifun - 1 >= P.maxls ? GO_FAIL : GO_TRIAL;
+    const int next_it = (converged | (!was_first & out_of_budget)) ? GO_DONE : GO_BEGIN;
+    const int next = cont ? next_ls : next_it;
     T2_BLK_END(c, 0, t_dig)
-    if (next == GO_TRIAL) set_trial();
+    set_trial(next == GO_TRIAL);
     return next;
   }
 
   // x = the trial point of the running line search
-  T2_HD void set_trial() {
+  T2_HD void set_trial(bool on = true) {
     T2_UNROLL
-    for (int i = 0; i < N; ++i) x[i] = stp == 1.0 ? z[i] : stp * d[i] + t[i];
+    for (int i = 0; i < N; ++i) {
+      const double xt = stp * d[i] + t[i];
+      x[i] = on ? (stp == 1.0 ? z[i] : xt) : x[i];
+    }
   }
 
   // One pass of the begin-iteration work.  `next` is GO_BEGIN or GO_FAIL (what digest() or an earlier pass returned).
@@ -1127,7 +1140,7 @@ struct Lbfgsb {
     T2_BLK_END(c, 6, t_l)
     // what this pass amounts to, by value selects (no early exits above: the block is one straight line)
     const int out = ended ? GO_DONE : (restart ? GO_BEGIN : ((ls.task != LS_FG || ifun - 1 >= P.maxls) ? GO_FAIL : GO_TRIAL));
-    if (out == GO_TRIAL) set_trial();
+    set_trial(out == GO_TRIAL);
     return out;
   }
 
