@@ -3,7 +3,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 MAX_TE = 32
 
 OK, E_INVALID, E_HIP, E_BOUNDS = 0, -1, -2, -3
@@ -58,6 +58,8 @@ SYMBOLS = [
     ("t2fit_union_mask_dev", C.c_int, [_P, C.c_int, C.c_int64, _P, _P, _P, _P]),
     ("t2fit_residuals_dev", C.c_int, [C.POINTER(T2FitConfig), _P, C.c_int, _P, C.c_int64, _P, _P, _P, _P, _P]),
     ("t2fit_label_stats_dev", C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, _P]),
+    ("t2fit_roi_erode_dev", C.c_int, [_P, _P, C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    ("t2fit_roi_stats_dev", C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P]),
     ("t2fit_set_timing", C.c_int, [C.c_int]),
     ("t2fit_set_reserve_cus", C.c_int, [C.c_int]),
     ("t2fit_kernel_ms", C.c_double, [C.c_int]),

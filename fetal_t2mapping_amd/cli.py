@@ -2,6 +2,7 @@
 
     python -m fetal_t2mapping_amd.cli --path /data/qMRI --csv 2024083017_17510000.csv \
         --in_vivo --gaussian --lf --sim 1 [--TEs 114 202 299] [--no_prior] [--solver lbfgsb|lm|loglin] [--gpus N]
+        [--roi_stats ho:2 --roi_stats jhu:3 --roi_stats feta] [--roi_connectivity 3] [--roi_erosion 1]
 
 --gpus N (N > 1) starts one process per GPU (torch.distributed.run, RCCL) before anything touches a GPU: with at
 least N subjects in the CSVs each rank streams its own subjects (dist.subjects_of_rank: nothing is exchanged,
@@ -13,6 +14,9 @@ Same flags, metadata CSVs, input/output file names and maps as the reference
 (run_t2mapping.py:483-576, utils/metadata_utils.py, utils/qmri_utils.py:13-33,
 utils/t2map_utils.py:18-59); the voxel loop (:411-461) is one call into the HIP library.  NIfTI I/O
 stays SimpleITK on the host, as in the reference (nifti.py stands in where SimpleITK is not installed).
+--roi_stats NAME[:TISSUE] (repeatable) adds, after the maps, the per-region table of the atlas image recon_1mm_<NAME>
+(mean / std / median of t2, k, sigma over the eroded regions, inside FeTA tissue TISSUE when given): the loops of
+utils/ada_utils.py:130-216 and :885-968 on the GPU (t2map.roi_table).
 The convergence-study figures (:465-468) are written on request (--plots, convergence.py).  ``--csv prj-004``
 (prj-003, prj-002) stands for the session logs of that project of the reference's paper, as in
 utils/metadata_utils.py:19-85.
@@ -33,6 +37,7 @@ recon_dirname = "recon_1mm"
 mask_dirname = "recon_1mm_mask"
 phantom_labels_dirname = "recon_1mm_label"
 t2map_dirname = recon_dirname + "_t2map"
+feta_dirname = recon_dirname + "_feta"  # FeTA tissue segmentation (utils/ada_utils.py:908): 2 = grey, 3 = white matter
 
 
 def _sitk():
@@ -258,6 +263,64 @@ def save_phantom_csv(t2_map, k_map, sigma_map, label, id, gt, bids_path, acq, di
     phantom_frame(stats, id, gt).to_csv(path, index=False)
 
 
+def parse_roi_spec(spec: str):
+    """``--roi_stats NAME[:TISSUE]`` -> ``(NAME, TISSUE or None)``: the label image is the one of derivative directory
+    ``recon_1mm_<NAME>``; with TISSUE only voxels whose FeTA label (``recon_1mm_feta``) equals it are taken."""
+    name, sep, tissue = str(spec).partition(":")
+    if not name or not all(ch.isalnum() or ch == "-" for ch in name):  # becomes part of a directory and a file name
+        raise ValueError(f"--roi_stats {spec!r}: NAME must be made of letters, digits and '-'")
+    if not sep:
+        return name, None
+    try:
+        return name, int(tissue)
+    except ValueError:
+        raise ValueError(f"--roi_stats {spec!r}: TISSUE must be an integer FeTA label") from None
+
+
+def roi_csv_path(bids_path, acq, dirname, sim, analysis, name):
+    """The per-region table of atlas `name`, beside the maps: the phantom CSV's naming rule with ROI_<name>."""
+    return get_img_path(bids_path, acq, dirname).replace("t2map.nii.gz", f"sim-{sim}_ROI_{name}_ada-{analysis}.csv")
+
+
+def _read_label_image(sitk, bids_path, acqs, dirname):
+    """The integer label volume of derivative directory `dirname` for this (sub, ses), or None when there is no such
+    file.  The name carries an echo time, like the phantom's label image: the last echo's is looked for first (as
+    phantom_labels_dirname is), then the other echoes' from the first on (utils/ada_utils.py:908 names the FeTA image
+    after the first echo)."""
+    for acq in [acqs[-1]] + list(acqs[:-1]):
+        path = get_img_path(bids_path, acq, dirname).replace(" ", "")
+        if os.path.exists(path):
+            arr = np.asarray(sitk.GetArrayFromImage(sitk.ReadImage(path)))
+            return (arr if arr.dtype.kind in "iu" else np.rint(arr)).astype(np.int32)
+    return None
+
+
+def save_roi_csvs(t2_map, k_map, sigma_map, specs, connectivity, erosion, bids_path, acqs, dirname, sim, analysis, device=0):
+    """One CSV per ``--roi_stats`` entry: t2map.roi_table over t2 / k / sigma on the regions of the atlas image, eroded
+    `erosion` times with generate_binary_structure(3, connectivity) (get_t2_per_roi, utils/ada_utils.py:130-216;
+    compute_t2_per_tissue_feta, :885-968).  The maps are on disk by now: a label image that is missing or does not fit
+    costs its table and a warning, nothing else.  Returns the paths written."""
+    sitk = _sitk()
+    maps = {"t2": t2_map, "k": k_map, "sigma": sigma_map}
+    written = []
+    for name, tissue in specs:
+        label = _read_label_image(sitk, bids_path, acqs, recon_dirname + "_" + name)
+        feta = _read_label_image(sitk, bids_path, acqs, feta_dirname) if tissue is not None else None
+        if label is None or (tissue is not None and feta is None):
+            missing = recon_dirname + "_" + name if label is None else feta_dirname
+            print(f"Warning: no {missing} label image for {acqs[-1]['sub']}_{acqs[-1]['ses']}. ROI table '{name}' is skipped.")
+            continue
+        if label.shape != t2_map.shape or (feta is not None and feta.shape != t2_map.shape):
+            print(f"Warning: label image of '{name}' does not have the maps' shape {t2_map.shape}. ROI table '{name}' is skipped.")
+            continue
+        frame = t2map.roi_table(maps, label, feta, tissue, connectivity=connectivity, iterations=erosion, device=device)
+        path = roi_csv_path(bids_path, acqs[-1], dirname, sim, analysis, name)
+        frame.to_csv(path, index=False)
+        written.append(path)
+        print(f"ROI table '{name}' saved as csv file in {dirname}")
+    return written
+
+
 # ---- driver ------------------------------------------------------------------------------------
 def _fit_subject(vols, masks, keep, te_eff, fit, fit_params, prior, norm, solver, precision, device, numpy_legacy=False):
     """One (sub, ses): union mask + flat indices on the device (bit-identical to
@@ -395,9 +458,11 @@ def _one_block(vols):
 
 
 def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field, prior, fast, norm, sim,
-                   solver="lbfgsb", precision="f64", device=0, plots=False, plot_seed=None, numpy_legacy=False):
+                   solver="lbfgsb", precision="f64", device=0, plots=False, plot_seed=None, numpy_legacy=False,
+                   roi_specs=(), roi_connectivity=3, roi_erosion=1):
     """run_t2mapping.py:333-479 with the voxel loop on the GPU.  ``plots``: also write the reference's
-    convergence-study figures (:465-468) under <prj>/ada/convergence_analysis."""
+    convergence-study figures (:465-468) under <prj>/ada/convergence_analysis.  ``roi_specs``: (name, tissue) pairs
+    of --roi_stats; each adds a per-region table after the maps (save_roi_csvs)."""
     sitk = _sitk()
     tes_s = [x / 1000 for x in TEs]
     metadata = metadata[metadata["EchoTime"].isin(tes_s)]
@@ -413,9 +478,10 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
         for (sub, ses), sub_md in prj_md.groupby(["sub", "ses"]):
             if (prj, sub, ses) not in mine:
                 continue
-            recon_paths, mask_paths, te_eff, label_path = [], [], [], None
+            recon_paths, mask_paths, te_eff, label_path, acqs = [], [], [], None, []
             for echotime, acq in sub_md.groupby("EchoTime"):
                 te_eff.append(echotime * 1000)
+                acqs.append(acq.iloc[0])
                 recon_paths.append(get_img_path(bids_path, acq.iloc[0], recon_dirname).replace(" ", ""))
                 mask_paths.append(get_img_path(bids_path, acq.iloc[0], mask_dirname).replace(" ", ""))
                 if phantom:
@@ -485,6 +551,9 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
                 id_, gt_ = set_phantom_gt(low_field)
                 save_phantom_csv(t2_map, k_map, sigma_map, label, id_, gt_, bids_path, acq, t2map_dirname, sim, fit,
                                  device=device)
+            if roi_specs:  # (only the writer rank gets here; the maps are complete on it)
+                save_roi_csvs(t2_map, k_map, sigma_map, roi_specs, roi_connectivity, roi_erosion, bids_path, acqs,
+                              t2map_dirname, sim, fit, device=device)
 
 
 def dist_subjects_of_rank(n_subjects, rank, world):
@@ -534,7 +603,21 @@ def parse_arguments(argv=None):
                    help="write the reference's convergence-study PNGs (run_t2mapping.py:465-468) under "
                         "<prj>/ada/convergence_analysis; off by default, the reference always draws them")
     p.add_argument("--plot_seed", type=int, default=None, help="seed of the voxel sample in the figures")
-    return p.parse_args(argv)
+    p.add_argument("--roi_stats", action="append", default=[], metavar="NAME[:TISSUE]",
+                   help="after the maps, write the per-region table (mean / std / median of t2, k, sigma over the eroded "
+                        "regions) of the label image recon_1mm_<NAME>, inside FeTA tissue TISSUE (recon_1mm_feta) when given; "
+                        "repeatable: --roi_stats ho:2 --roi_stats jhu:3 --roi_stats feta are the reference's ROI routines")
+    p.add_argument("--roi_connectivity", type=int, choices=[1, 2, 3], default=3,
+                   help="erosion element generate_binary_structure(3, c): 6 / 18 / 26 neighbours (default 3, the reference's)")
+    p.add_argument("--roi_erosion", type=int, default=1, help="erosion iterations of the regions, 0..8 (default 1)")
+    args = p.parse_args(argv)
+    try:
+        args.roi_specs = [parse_roi_spec(spec) for spec in args.roi_stats]
+    except ValueError as e:
+        p.error(str(e))
+    if not 0 <= args.roi_erosion <= 8:
+        p.error("--roi_erosion must be in 0..8")
+    return args
 
 
 def _relaunch_per_gpu(args, argv):
@@ -589,7 +672,8 @@ def main(argv=None):
     try:
         process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field, not args.no_prior, fast,
                        bool(args.norm), args.sim, solver=args.solver, precision=args.precision, device=args.device,
-                       plots=args.plots, plot_seed=args.plot_seed, numpy_legacy=args.numpy_legacy)
+                       plots=args.plots, plot_seed=args.plot_seed, numpy_legacy=args.numpy_legacy,
+                       roi_specs=args.roi_specs, roi_connectivity=args.roi_connectivity, roi_erosion=args.roi_erosion)
     finally:
         if world > 1:
             import torch.distributed as dist

@@ -30,6 +30,7 @@
 #include "t2fit_config.h"
 #include "t2fit_context.h"
 #include "t2fit_dispatch.h"
+#include "t2fit_error.h"
 
 using namespace t2fit;
 
@@ -65,18 +66,6 @@ constexpr int kEvRing = 16;
 thread_local hipEvent_t g_ev0[kEvRing] = {}, g_ev1[kEvRing] = {}, g_ev2[kEvRing] = {};  // start, end of the fit kernel, end of the epilogue pass
 thread_local long g_ev_count = 0;   // timed launches so far
 thread_local int g_ev_slot = 0;     // ring slot of the launch being queued
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-#define T2_HIP(call)                                                                            \
-  do {                                                                                          \
-    hipError_t e_ = (call);                                                                     \
-    if (e_ != hipSuccess)                                                                       \
-      return fail(T2FIT_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));             \
-  } while (0)
 
 struct DevMaps {
   float *t2, *k, *sigma, *res, *r2, *fun, *se;
@@ -1220,6 +1209,12 @@ int launch_fit(const t2fit_config* cfg, const float* echoes, int layout, const u
 }
 
 }  // namespace
+
+// t2fit_error.h: the one error string of the library (the other translation units report through it too)
+int t2fit::fail(int code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
 
 extern "C" {
 

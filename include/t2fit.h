@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define T2FIT_ABI_VERSION 4
+#define T2FIT_ABI_VERSION 5
 #define T2FIT_MAX_TE 32
 
 /* error codes */
@@ -203,6 +203,39 @@ int t2fit_residuals_dev(const t2fit_config *cfg, const float *echoes_dev, int la
  * Asynchronous on `stream`; the result does not depend on the launch (fixed summation order). */
 int t2fit_label_stats_dev(const float *map_dev, const int32_t *label_dev, int64_t n_vox, int n_labels,
                           double *mean_out, double *std_out, int64_t *count_out, void *stream);
+
+/* In-vivo atlas ROIs, step 1: the eroded region of every label at once.  Replaces, for all labels L in 1..n_labels,
+ *   binary_erosion((tissue == tissue_value) & (label == L), structure=generate_binary_structure(3, connectivity),
+ *                  iterations=iterations)
+ * of utils/ada_utils.py:165-169, :192-196 (get_t2_per_roi: Harvard-Oxford labels in FeTA grey matter, JHU labels in FeTA
+ * white matter) and :925-933 (compute_t2_per_tissue_feta).  The masks of one atlas are disjoint, so all of them are eroded
+ * by one stencil pass per iteration over the class volume  cls = (tissue == tissue_value) ? label : 0:  a voxel keeps its
+ * class iff every neighbour of the element lies inside the volume and has the same class (scipy's border_value = 0: voxels
+ * on the faces of the volume are always eroded).
+ *   label_dev    : int32 [nz, ny, nx] (C order, x innermost); values outside 1..n_labels are background
+ *   tissue_dev   : int32, same shape, or NULL (every voxel qualifies)
+ *   n_labels     : 1..256
+ *   connectivity : 1, 2, 3 = 6, 18, 26 neighbours (|dz| + |dy| + |dx| <= connectivity); the reference uses 3
+ *   iterations   : 0..8; 0 = the class volume alone, no erosion
+ *   roi_out      : int32 [nz * ny * nx]: the surviving class, or 0; must not be one of the inputs
+ * nz * ny * nx below 2^32.  Asynchronous on `stream`; the result is a function of the inputs alone. */
+int t2fit_roi_erode_dev(const int32_t *label_dev, const int32_t *tissue_dev, int32_t tissue_value, int nz, int ny, int nx,
+                        int n_labels, int connectivity, int iterations, int32_t *roi_out, void *stream);
+
+/* In-vivo atlas ROIs, step 2: np.mean / np.std / np.median / len of the map values of every region
+ * (utils/ada_utils.py:171-189, :198-216, :935-960) for a map that is on the device.
+ *   map_dev    : float32 [n_vox]
+ *   roi_dev    : int32 [n_vox], e.g. roi_out of t2fit_roi_erode_dev; voxels with values 1..n_labels (<= 256) are tallied
+ *   mean_out, std_out : device float64 [n_labels]: mean and population standard deviation (ddof = 0), numpy's two rounds
+ *   median_out : device float64 [n_labels] or NULL: the exact median (the mean of the two middle values for an even count)
+ *   count_out  : device int64 [n_labels]: voxels of the region (the reference's `nvoxel`)
+ *   valid_out  : device int64 [n_labels] or NULL: those whose map value is not NaN
+ * The statistics are over the non-NaN values, as in t2fit_label_stats_dev (np.mean of a region holding a NaN -- a
+ * T2FIT_ST_INFEASIBLE voxel -- is NaN in the reference; count_out != valid_out tells the caller so); a region without
+ * any gives NaN.  n_vox in 1..2^32-1.  Asynchronous on `stream`; two calls on the same inputs return the same bits, on
+ * any launch geometry (integer counting sort in voxel order, fixed summation tree, exact selection). */
+int t2fit_roi_stats_dev(const float *map_dev, const int32_t *roi_dev, int64_t n_vox, int n_labels, double *mean_out,
+                        double *std_out, double *median_out, int64_t *count_out, int64_t *valid_out, void *stream);
 
 /* Kernel timing for benchmarks (no reference counterpart).  With timing enabled (t2fit_set_timing(1)) every
  * t2fit_volume_dev call of this thread records HIP events around its fit kernel on the launch stream.
