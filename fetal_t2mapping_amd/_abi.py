@@ -42,6 +42,17 @@ class T2FitMaps(C.Structure):
     ]
 
 
+BOOT_NOISE_RICIAN, BOOT_NOISE_GAUSSIAN = 0, 1
+BOOT_NOISES = {"rician": BOOT_NOISE_RICIAN, "gaussian": BOOT_NOISE_GAUSSIAN}
+BOOT_PARAMS = {"t2": 0, "k": 1, "sigma": 2}  # index into T2FitBootMaps; the which_params bit is 1 << index
+BOOT_MAX_INTERVAL_REPLICAS = 512
+
+
+class T2FitBootMaps(C.Structure):
+    _fields_ = [("mean", C.c_void_p * 3), ("bias", C.c_void_p * 3), ("std", C.c_void_p * 3),
+                ("ci_lo", C.c_void_p * 3), ("ci_hi", C.c_void_p * 3), ("n_ok", C.c_void_p)]
+
+
 # every symbol include/t2fit.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -60,6 +71,12 @@ SYMBOLS = [
     ("t2fit_label_stats_dev", C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, _P]),
     ("t2fit_roi_erode_dev", C.c_int, [_P, _P, C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     ("t2fit_roi_stats_dev", C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P]),
+    ("t2fit_boot_background_dev", C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int64, C.POINTER(C.c_double),
+                                            C.POINTER(C.c_int64), _P]),
+    ("t2fit_boot_synth_dev", C.c_int, [C.POINTER(T2FitConfig), _P, _P, C.c_double, _P, _P, C.c_int64, C.c_int64, C.c_uint64,
+                                       C.c_int, C.c_int, _P, _P]),
+    ("t2fit_bootstrap_dev", C.c_int, [_P, C.POINTER(T2FitConfig), _P, _P, _P, C.c_double, _P, C.c_int, _P, C.c_int64, C.c_int,
+                                      C.c_uint64, C.c_double, C.c_int, C.POINTER(T2FitBootMaps), C.c_int, _P]),
     ("t2fit_set_timing", C.c_int, [C.c_int]),
     ("t2fit_set_reserve_cus", C.c_int, [C.c_int]),
     ("t2fit_kernel_ms", C.c_double, [C.c_int]),
@@ -70,9 +87,16 @@ SYMBOLS = [
 ]
 
 
+# entry points added to ABI 5 after its first release: another build of the same ABI (T2FIT_LIB) may lack them
+ADDITIVE = ("t2fit_boot_background_dev", "t2fit_boot_synth_dev", "t2fit_bootstrap_dev")
+
+
 def bind(lib: C.CDLL) -> C.CDLL:
-    """Attach prototypes; raises AttributeError if the library lacks a declared symbol."""
+    """Attach prototypes; raises AttributeError if the library lacks a declared symbol (the ADDITIVE ones are looked
+    up: a library without them binds, and t2map raises when one is called)."""
     for name, res, args in SYMBOLS:
+        if name in ADDITIVE and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

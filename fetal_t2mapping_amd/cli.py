@@ -3,6 +3,7 @@
     python -m fetal_t2mapping_amd.cli --path /data/qMRI --csv 2024083017_17510000.csv \
         --in_vivo --gaussian --lf --sim 1 [--TEs 114 202 299] [--no_prior] [--solver lbfgsb|lm|loglin] [--gpus N]
         [--roi_stats ho:2 --roi_stats jhu:3 --roi_stats feta] [--roi_connectivity 3] [--roi_erosion 1]
+        [--bootstrap 100 [--bootstrap_seed 0] [--bootstrap_alpha 0.05] [--bootstrap_noise background|sigma_map|<float>]]
 
 --gpus N (N > 1) starts one process per GPU (torch.distributed.run, RCCL) before anything touches a GPU: with at
 least N subjects in the CSVs each rank streams its own subjects (dist.subjects_of_rank: nothing is exchanged,
@@ -17,6 +18,9 @@ stays SimpleITK on the host, as in the reference (nifti.py stands in where Simpl
 --roi_stats NAME[:TISSUE] (repeatable) adds, after the maps, the per-region table of the atlas image recon_1mm_<NAME>
 (mean / std / median of t2, k, sigma over the eroded regions, inside FeTA tissue TISSUE when given): the loops of
 utils/ada_utils.py:130-216 and :885-968 on the GPU (t2map.roi_table).
+--bootstrap R adds, after the maps, R replicas of the parametric bootstrap (t2map.bootstrap_volume): the T2 standard
+deviation, bias, percentile interval and replica count of every voxel as ..._T2stdmap / T2biasmap / T2cilomap /
+T2cihimap / T2nokmap_ada-<fit>.nii.gz beside the four maps.
 The convergence-study figures (:465-468) are written on request (--plots, convergence.py).  ``--csv prj-004``
 (prj-003, prj-002) stands for the session logs of that project of the reference's paper, as in
 utils/metadata_utils.py:19-85.
@@ -321,6 +325,55 @@ def save_roi_csvs(t2_map, k_map, sigma_map, specs, connectivity, erosion, bids_p
     return written
 
 
+BOOT_TAGS = ("T2std", "T2bias", "T2cilo", "T2cihi", "T2nok")
+
+
+def parse_bootstrap_noise(text: str):
+    """``--bootstrap_noise``: ``background`` / ``sigma_map`` as they are, anything else a noise level > 0."""
+    if text in ("background", "sigma_map"):
+        return text
+    try:
+        level = float(text)
+    except ValueError:
+        raise ValueError(f"--bootstrap_noise {text!r}: expected 'background', 'sigma_map' or a number") from None
+    if not (level > 0.0 and np.isfinite(level)):
+        raise ValueError(f"--bootstrap_noise {text!r}: the noise level must be a positive number")
+    return level
+
+
+def boot_map_path(bids_path, acq, dirname, sim, analysis, tag):
+    """A bootstrap map beside the four maps: their naming rule (save_nifti_maps) with tag T2std / T2bias / ..."""
+    return get_img_path(bids_path, acq, dirname).replace("t2map.nii.gz", f"sim-{sim}_{tag}map_ada-{analysis}.nii.gz")
+
+
+def save_bootstrap_maps(vols, mask, maps4, te_eff, fit, fit_params, prior, solver, precision, numpy_legacy, n_replicas, seed,
+                        alpha, noise, recon_img, bids_path, acq, dirname, sim, device=0):
+    """``--bootstrap R``: t2map.bootstrap_volume of the maps just written (the volume is not fitted again), then the
+    T2 standard deviation, bias, interval bounds and replica counts as NIfTI maps with the T2 map's geometry.  Prints one
+    line: noise level, R, seconds, replicas per second.  Returns the paths written."""
+    sitk = _sitk()
+    t2_map, k_map, sigma_map, res_map = maps4
+    echoes = np.stack([np.asarray(v, np.float32) for v in vols])
+    t0 = time.time()
+    boot = t2map.bootstrap_volume(echoes, mask, te_eff, fit, fit_params, prior=prior, n_replicas=n_replicas, seed=seed,
+                                  alpha=alpha, noise_sigma=noise, solver=solver, precision=precision,
+                                  maps=t2map.T2Maps(t2_map, k_map, sigma_map, res_map), numpy_legacy=numpy_legacy, device=device)
+    dt = time.time() - t0
+    level = "the fitted sigma map" if boot.noise_sigma is None else f"{boot.noise_sigma:.6g}"
+    print(f"Bootstrap: noise level {level} ({noise if isinstance(noise, str) else 'given'}), {n_replicas} replicas in "
+          f"{dt:.3f} sec ({n_replicas / max(dt, 1e-9):.1f} replicas/sec)")
+    items = []
+    for tag, arr in zip(BOOT_TAGS, (boot.boot_std, boot.boot_bias, boot.ci_lo, boot.ci_hi, boot.n_ok)):
+        img = sitk.GetImageFromArray(arr)
+        img.SetSpacing(recon_img.GetSpacing())
+        img.SetOrigin(recon_img.GetOrigin())
+        img.SetDirection(recon_img.GetDirection())
+        items.append((img, boot_map_path(bids_path, acq, dirname, sim, fit, tag)))
+    for img, path in items:
+        sitk.WriteImage(img, path)
+    return [path for _, path in items]
+
+
 # ---- driver ------------------------------------------------------------------------------------
 def _fit_subject(vols, masks, keep, te_eff, fit, fit_params, prior, norm, solver, precision, device, numpy_legacy=False):
     """One (sub, ses): union mask + flat indices on the device (bit-identical to
@@ -459,10 +512,12 @@ def _one_block(vols):
 
 def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field, prior, fast, norm, sim,
                    solver="lbfgsb", precision="f64", device=0, plots=False, plot_seed=None, numpy_legacy=False,
-                   roi_specs=(), roi_connectivity=3, roi_erosion=1):
+                   roi_specs=(), roi_connectivity=3, roi_erosion=1, bootstrap=0, bootstrap_seed=0, bootstrap_alpha=0.05,
+                   bootstrap_noise="background"):
     """run_t2mapping.py:333-479 with the voxel loop on the GPU.  ``plots``: also write the reference's
     convergence-study figures (:465-468) under <prj>/ada/convergence_analysis.  ``roi_specs``: (name, tissue) pairs
-    of --roi_stats; each adds a per-region table after the maps (save_roi_csvs)."""
+    of --roi_stats; each adds a per-region table after the maps (save_roi_csvs).  ``bootstrap`` > 0: that many
+    replicas of the parametric bootstrap after the maps (save_bootstrap_maps)."""
     sitk = _sitk()
     tes_s = [x / 1000 for x in TEs]
     metadata = metadata[metadata["EchoTime"].isin(tes_s)]
@@ -554,6 +609,12 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
             if roi_specs:  # (only the writer rank gets here; the maps are complete on it)
                 save_roi_csvs(t2_map, k_map, sigma_map, roi_specs, roi_connectivity, roi_erosion, bids_path, acqs,
                               t2map_dirname, sim, fit, device=device)
+            if bootstrap and vols is None:
+                print("Warning: --bootstrap is not run on a volume that is shared by several ranks. Bootstrap maps are skipped.")
+            elif bootstrap:
+                save_bootstrap_maps(vols, mask, maps4, te_eff, fit, fit_params, prior, solver, precision, numpy_legacy,
+                                    bootstrap, bootstrap_seed, bootstrap_alpha, bootstrap_noise, recon_img, bids_path,
+                                    acq.iloc[0], t2map_dirname, sim, device=device)
 
 
 def dist_subjects_of_rank(n_subjects, rank, world):
@@ -610,7 +671,33 @@ def parse_arguments(argv=None):
     p.add_argument("--roi_connectivity", type=int, choices=[1, 2, 3], default=3,
                    help="erosion element generate_binary_structure(3, c): 6 / 18 / 26 neighbours (default 3, the reference's)")
     p.add_argument("--roi_erosion", type=int, default=1, help="erosion iterations of the regions, 0..8 (default 1)")
+    p.add_argument("--bootstrap", type=int, default=0, metavar="R",
+                   help="after the maps, R replicas of the parametric bootstrap (simulate from the fitted k, T2 with noise, refit "
+                        "with the same solver and bounds): writes the T2std, T2bias, T2cilo, T2cihi and T2nok maps beside them")
+    p.add_argument("--bootstrap_seed", type=int, default=0, help="seed of the replica stream (default 0)")
+    p.add_argument("--bootstrap_alpha", type=float, default=0.05,
+                   help="the interval maps are the alpha/2 and 1 - alpha/2 percentiles (default 0.05: a 95 %% interval)")
+    p.add_argument("--bootstrap_noise", default="background", metavar="{background,sigma_map,<float>}",
+                   help="noise level of the replicas: measured on the voxels outside the mask (default), the fitted sigma of "
+                        "every voxel (3-parameter fits only), or a number")
     args = p.parse_args(argv)
+    if args.bootstrap:
+        try:
+            args.bootstrap_noise = parse_bootstrap_noise(args.bootstrap_noise)
+        except ValueError as e:
+            p.error(str(e))
+        if not 2 <= args.bootstrap <= 512:
+            p.error("--bootstrap needs 2..512 replicas (the interval maps are percentiles over them)")
+        if not 0.0 < args.bootstrap_alpha < 1.0:
+            p.error("--bootstrap_alpha must lie in (0, 1)")
+        if args.norm:
+            p.error("--bootstrap cannot be combined with --norm: the maps of a normalised fit are in per-voxel units, and the "
+                    "noise level would have to be too")
+        if args.in_vitro_fast:
+            p.error("--bootstrap cannot be combined with --in_vitro_fast: the noise level is measured outside the mask, and the "
+                    "fast phantom run masks everything but the vials; use --in_vitro")
+        if args.bootstrap_noise == "sigma_map" and args.gaussian:
+            p.error("--bootstrap_noise sigma_map needs a fitted sigma: use it with --gaussian_rician or --rician")
     try:
         args.roi_specs = [parse_roi_spec(spec) for spec in args.roi_stats]
     except ValueError as e:
@@ -673,7 +760,9 @@ def main(argv=None):
         process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field, not args.no_prior, fast,
                        bool(args.norm), args.sim, solver=args.solver, precision=args.precision, device=args.device,
                        plots=args.plots, plot_seed=args.plot_seed, numpy_legacy=args.numpy_legacy,
-                       roi_specs=args.roi_specs, roi_connectivity=args.roi_connectivity, roi_erosion=args.roi_erosion)
+                       roi_specs=args.roi_specs, roi_connectivity=args.roi_connectivity, roi_erosion=args.roi_erosion,
+                       bootstrap=args.bootstrap, bootstrap_seed=args.bootstrap_seed, bootstrap_alpha=args.bootstrap_alpha,
+                       bootstrap_noise=args.bootstrap_noise)
     finally:
         if world > 1:
             import torch.distributed as dist

@@ -1,5 +1,6 @@
 // t2fit_context.h -- the host seam's long-lived state ("t2fit_create/destroy for a context holding
-// streams ... and pinned staging").  Included by t2fit_kernels.hip only (one translation unit).
+// streams ... and pinned staging").  Defined inline throughout: t2fit_kernels.hip owns the contexts, t2fit_boot.hip
+// borrows their streams.
 //
 // A numpy-in / numpy-out fit of one volume is three transfers around one kernel: pageable host memory -> HBM,
 // fit, HBM -> pageable host memory.  Done naively (round 1: hipMalloc, three stream creates, 2 x slabs event

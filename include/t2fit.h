@@ -237,6 +237,84 @@ int t2fit_roi_erode_dev(const int32_t *label_dev, const int32_t *tissue_dev, int
 int t2fit_roi_stats_dev(const float *map_dev, const int32_t *roi_dev, int64_t n_vox, int n_labels, double *mean_out,
                         double *std_out, double *median_out, int64_t *count_out, int64_t *valid_out, void *stream);
 
+/* ---- Parametric bootstrap: per-voxel bias / standard deviation / percentile interval of the fit as it is run --------
+ * No reference counterpart (the reference has no uncertainty map).  The acquisition is simulated from the fitted (k, T2)
+ * with noise of a given level, refitted by t2fit_volume_dev with the same cfg (solver, bounds, prior, stop rules) and
+ * mask, R times; the distribution of the R refits of every voxel is reduced on the device.  Additive to ABI 5: new
+ * symbols and one new struct, t2fit_config and t2fit_maps are as they were (look the symbols up to detect them).
+ * cfg.norm = 1 is refused by all of them: the maps of a normalised fit are in per-voxel units of the largest sample,
+ * and the noise level would have to be too.
+ *
+ * The replica stream (the definition; fetal_t2mapping_amd/_philox.py restates it in numpy):
+ *   (w0, w1, w2, w3) = Philox4x32-10(counter = (v low, v high, j, r), key = (seed low, seed high))
+ *       v = voxel_offset + flat index of the voxel, j = echo, r = replica; w2 and w3 are not used
+ *   u1 = ((w0 >> 9) + 0.5) 2^-23,  u2 = ((w1 >> 9) + 0.5) 2^-23      (exact in float32, never 0 or 1)
+ *   n1 = sqrt(-2 ln u1) cos(2 pi u2),  n2 = sqrt(-2 ln u1) sin(2 pi u2)          (|n| <= 5.77)
+ *   S = k[v] exp(-TE[j] / T2[v]),  s = noise level of the voxel
+ *   sample = sqrt((S + s n1)^2 + (s n2)^2)  (T2FIT_BOOT_NOISE_RICIAN)   or   S + s n1  (T2FIT_BOOT_NOISE_GAUSSIAN)
+ * evaluated in float32.  A sample depends on (seed, v, j, r) alone: not on the launch, the mask, a slab partition or the
+ * order of the replicas. */
+#define T2FIT_BOOT_NOISE_RICIAN 0
+#define T2FIT_BOOT_NOISE_GAUSSIAN 1
+
+#define T2FIT_BOOT_PARAM_T2 1 /* which_params: a set of these; index into t2fit_boot_maps = 0, 1, 2 */
+#define T2FIT_BOOT_PARAM_K 2
+#define T2FIT_BOOT_PARAM_SIGMA 4
+
+/* Output maps of t2fit_bootstrap_dev: device float32 [n_vox] each, index 0 = T2, 1 = k, 2 = sigma; NULL = not wanted.
+ * Zeros outside the mask.  With n_ok counted replicas of the voxel: mean and bias = mean - fitted value (NaN when
+ * n_ok = 0), std with ddof = 1 (NaN when n_ok < 2), ci_lo / ci_hi = numpy's default ("linear") percentiles at
+ * 100 alpha / 2 and 100 (1 - alpha / 2) of the counted replicas (NaN when n_ok = 0).  The call is in interval mode when
+ * a ci_lo or ci_hi pointer of a requested parameter is set. */
+typedef struct t2fit_boot_maps {
+  float *mean[3];
+  float *bias[3];
+  float *std[3];
+  float *ci_lo[3];
+  float *ci_hi[3];
+  int32_t *n_ok; /* int32 [n_vox]: replicas that count: status T2FIT_ST_CONVERGED and every requested value finite */
+} t2fit_boot_maps;
+
+/* Noise level from the background: sigma = sqrt(sum S^2 / (2 M)) over the M samples (all echoes) of the voxels whose
+ * mask is 0 -- the second moment of the Rayleigh distribution a magnitude image has where there is no signal (what the
+ * reference's unused estimate_in_vitro_noise, utils/t2map_utils.py:92-112, reaches for).  float64, fixed summation tree:
+ * the same bits from call to call.  mask_dev is required; M = 0 is T2FIT_E_INVALID.  *sigma_out, *count_out are HOST
+ * pointers; the call waits for `stream`. */
+int t2fit_boot_background_dev(const float *echoes_dev, int layout, const uint8_t *mask_dev, int n_te, int64_t n_vox,
+                              double *sigma_out, int64_t *count_out, void *stream);
+
+/* One replica of the acquisition (the stream defined above), as a dense te-major (n_te, n_vox) float32 block that
+ * t2fit_volume_dev fits as it stands; unmasked voxels are written as 0.
+ *   t2_dev, k_dev  : the fitted maps, float32 [n_vox]
+ *   noise_scalar   : the noise level s, used when noise_map_dev is NULL; noise_map_dev: float32 [n_vox], s per voxel
+ *   mask_dev       : uint8 [n_vox] or NULL (every voxel)
+ *   voxel_offset   : flat index of this block's voxel 0 in the volume the stream is defined on (0 for a whole volume;
+ *                    z0 * ny * nx for a slab, which then equals the same rows of the whole volume bit for bit)
+ * Uses cfg for n_te and te_ms only (and refuses cfg.norm).  Asynchronous on `stream`. */
+int t2fit_boot_synth_dev(const t2fit_config *cfg, const float *t2_dev, const float *k_dev, double noise_scalar,
+                         const float *noise_map_dev, const uint8_t *mask_dev, int64_t n_vox, int64_t voxel_offset,
+                         uint64_t seed, int replica, int noise_kind, float *echoes_out_dev, void *stream);
+
+/* The whole loop: for r in 0..n_replicas-1  synthesise replica r -> t2fit_volume_dev(cfg) -> accumulate, then finalise
+ * into `out`.  Two replica blocks and two streams: replica r + 1 is synthesised while replica r is fitted.
+ *   ctx          : its streams are used (one call at a time per context), or NULL: two streams are made for the call
+ *   sigma_dev    : the fitted sigma map, needed (non-NULL) only with T2FIT_BOOT_PARAM_SIGMA, which the 2-parameter
+ *                  gaussian model refuses
+ *   mask_dev     : required (a mask of ones takes every voxel)
+ *   n_replicas   : >= 1; in interval mode 2..512 (the values of 64 voxels are staged on chip for the rank select)
+ *   alpha        : in (0, 1) in interval mode, e.g. 0.05 for a 95 % interval
+ *   flags        : reserved, must be 0
+ * Arguments are checked, and the workspace is sized and compared with the free device memory, before any device work;
+ * it is allocated once per call and freed on every way out:
+ *   n_vox (8 n_te + 26) + n_masked (4 + n_par (24 + 4 n_replicas [interval mode]))  bytes
+ * (the check bounds n_masked by n_vox: the mask has not been read yet; the environment variable T2FIT_BOOT_MEM_LIMIT, in
+ * bytes, caps what a call may take whatever is free, and is compared before the HIP runtime is touched).  Synchronous: work queued on `stream` before the
+ * call is waited for, and the maps are complete on return.  Results are a function of the arguments alone. */
+int t2fit_bootstrap_dev(t2fit_context *ctx, const t2fit_config *cfg, const float *t2_dev, const float *k_dev,
+                        const float *sigma_dev, double noise_scalar, const float *noise_map_dev, int noise_kind,
+                        const uint8_t *mask_dev, int64_t n_vox, int n_replicas, uint64_t seed, double alpha,
+                        int which_params, const t2fit_boot_maps *out, int flags, void *stream);
+
 /* Kernel timing for benchmarks (no reference counterpart).  With timing enabled (t2fit_set_timing(1)) every
  * t2fit_volume_dev call of this thread records HIP events around its fit kernel on the launch stream.
  * t2fit_kernel_ms(k): duration in milliseconds of the fit kernel launched k timed calls ago (0 = the most recent;
