@@ -6,12 +6,12 @@ in hand-written HIP kernels (csrc/) behind the C ABI of include/t2fit.h; this pa
 Python host side that mirrors the reference's function surface.  There is no CPU execution path.
 """
 from ._philox import philox4x32_10
-from .t2map import (BootMaps, BootStats, RoiStats, T2Maps, bootstrap_volume, compute_residuals, dense_labels,
+from .t2map import (BootMaps, BootStats, RoiStats, T2Maps, bootstrap_volume, compute_residuals, denoise_tv, dense_labels,
                     estimate_background_sigma, fit_table, fit_volume, fit_voxel, fit_voxels, fit_voxels_trace, label_stats,
                     make_config, roi_erode, roi_frame, roi_stats, roi_table, set_fit_params, stack_mask_flatten,
                     synth_replica, union_mask_dev)
 
-__all__ = ["BootMaps", "BootStats", "RoiStats", "T2Maps", "bootstrap_volume", "compute_residuals", "dense_labels",
+__all__ = ["BootMaps", "BootStats", "RoiStats", "T2Maps", "bootstrap_volume", "compute_residuals", "denoise_tv", "dense_labels",
            "estimate_background_sigma", "fit_table", "fit_volume", "fit_voxel", "fit_voxels", "fit_voxels_trace", "label_stats",
            "make_config", "philox4x32_10", "roi_erode", "roi_frame", "roi_stats", "roi_table", "set_fit_params",
            "stack_mask_flatten", "synth_replica", "union_mask_dev"]

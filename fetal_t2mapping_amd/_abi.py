@@ -53,6 +53,11 @@ class T2FitBootMaps(C.Structure):
                 ("ci_lo", C.c_void_p * 3), ("ci_hi", C.c_void_p * 3), ("n_ok", C.c_void_p)]
 
 
+class T2FitTvParams(C.Structure):
+    _fields_ = [("weight", C.c_double), ("eps", C.c_double), ("max_iter", C.c_int32), ("dims", C.c_int32),
+                ("precision", C.c_int32), ("flags", C.c_int32)]
+
+
 # every symbol include/t2fit.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -77,6 +82,10 @@ SYMBOLS = [
                                        C.c_int, C.c_int, _P, _P]),
     ("t2fit_bootstrap_dev", C.c_int, [_P, C.POINTER(T2FitConfig), _P, _P, _P, C.c_double, _P, C.c_int, _P, C.c_int64, C.c_int,
                                       C.c_uint64, C.c_double, C.c_int, C.POINTER(T2FitBootMaps), C.c_int, _P]),
+    ("t2fit_tv_params_default", C.c_int, [C.POINTER(T2FitTvParams)]),
+    ("t2fit_tv_workspace_bytes", C.c_int, [C.POINTER(T2FitTvParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    ("t2fit_tv_denoise_dev", C.c_int, [C.POINTER(T2FitTvParams), _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t,
+                                       _P, _P, _P]),
     ("t2fit_set_timing", C.c_int, [C.c_int]),
     ("t2fit_set_reserve_cus", C.c_int, [C.c_int]),
     ("t2fit_kernel_ms", C.c_double, [C.c_int]),
@@ -88,7 +97,8 @@ SYMBOLS = [
 
 
 # entry points added to ABI 5 after its first release: another build of the same ABI (T2FIT_LIB) may lack them
-ADDITIVE = ("t2fit_boot_background_dev", "t2fit_boot_synth_dev", "t2fit_bootstrap_dev")
+ADDITIVE = ("t2fit_boot_background_dev", "t2fit_boot_synth_dev", "t2fit_bootstrap_dev",
+            "t2fit_tv_params_default", "t2fit_tv_workspace_bytes", "t2fit_tv_denoise_dev")
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

@@ -1,0 +1,83 @@
+"""Chambolle's projection algorithm for the ROF total-variation model, restated in numpy: the executable statement of
+the definition in include/t2fit.h (t2fit_tv_denoise_dev), which is scikit-image 0.22's ``denoise_tv_chambolle`` on a
+float image (what the reference's ``run_denoising`` calls slice by slice).  Every elementwise operation is one rounding
+in the working precision, in the order written; the two energy sums are accumulated in float64 (skimage sums them in
+the image's precision, so on a float32 image its stop can fall one iteration away when ``|E_prev - E|`` lies within
+float32 rounding of the threshold).  Host code for tests and baselines: the product path is the HIP kernel."""
+from __future__ import annotations
+
+import numpy as np
+
+DEFAULT_WEIGHT, DEFAULT_EPS, DEFAULT_MAX_ITER = 0.1, 2e-4, 200
+
+
+def tv_problem(f, weight=DEFAULT_WEIGHT, eps=DEFAULT_EPS, max_iter=DEFAULT_MAX_ITER, dtype=np.float32):
+    """One problem: ``f`` is a 2-D slice or a 3-D volume, iterated in ``dtype``.  Returns ``(out, n_iter, E)`` with ``out``
+    in ``dtype``, ``n_iter`` the number of updates of p the result reflects and ``E`` the energy of the last iteration."""
+    T = np.dtype(dtype).type
+    f = np.asarray(f).astype(T)
+    n = f.ndim
+    if n not in (2, 3):
+        raise ValueError("a problem is a 2-D slice or a 3-D volume")
+    tau = T(1.0 / (2.0 * n))
+    tw = T((1.0 / (2.0 * n)) / float(weight))
+    one = T(1.0)
+    p = [np.zeros(f.shape, T) for _ in range(n)]
+    lo = [tuple(slice(1, None) if b == a else slice(None) for b in range(n)) for a in range(n)]   # x with x - e_a inside
+    hi = [tuple(slice(0, -1) if b == a else slice(None) for b in range(n)) for a in range(n)]    # x with x + e_a inside
+    e_init = e_prev = e = 0.0
+    out = f
+    n_iter = 0
+    with np.errstate(all="ignore"):
+        for i in range(int(max_iter)):
+            if i == 0:
+                d = np.zeros(f.shape, T)
+            else:
+                s = p[0] + p[1]
+                if n == 3:
+                    s = s + p[2]
+                d = -s
+                for a in range(n):
+                    d[lo[a]] = d[lo[a]] + p[a][hi[a]]
+            out = f + d
+            g = []
+            for a in range(n):
+                ga = np.zeros(f.shape, T)
+                ga[hi[a]] = out[lo[a]] - out[hi[a]]
+                g.append(ga)
+            sq = g[0] * g[0] + g[1] * g[1]
+            if n == 3:
+                sq = sq + g[2] * g[2]
+            nrm = np.sqrt(sq)
+            e = (float(np.sum((d * d).astype(np.float64))) + float(weight) * float(np.sum(nrm.astype(np.float64)))) / f.size
+            den = one + tw * nrm
+            p = [(p[a] - tau * g[a]) / den for a in range(n)]
+            n_iter = i
+            if i == 0:
+                e_init = e_prev = e
+            elif abs(e_prev - e) < eps * e_init:
+                break
+            else:
+                e_prev = e
+    return out, n_iter, e
+
+
+def denoise_tv(stack, weight=DEFAULT_WEIGHT, eps=DEFAULT_EPS, max_iter=DEFAULT_MAX_ITER, dims=2, precision="f32"):
+    """The whole call on the host: ``stack`` is ``(Z, Y, X)`` or ``(n, Z, Y, X)`` float32; ``dims=2`` takes every
+    ``(Y, X)`` slice as a problem, ``dims=3`` every volume.  Returns ``(out float32 like stack, n_iter int32 per problem,
+    energy float64 per problem)``, problems in memory order."""
+    a = np.ascontiguousarray(stack, dtype=np.float32)
+    if a.ndim not in (3, 4):
+        raise ValueError("stack must be (Z, Y, X) or (n, Z, Y, X)")
+    if dims not in (2, 3):
+        raise ValueError("dims must be 2 or 3")
+    dtype = {"f32": np.float32, "f64": np.float64}[precision]
+    v = a.reshape((-1,) + a.shape[-3:])
+    probs = v.reshape((-1,) + v.shape[-2:]) if dims == 2 else v
+    out = np.empty(probs.shape, np.float32)
+    n_iter = np.zeros(len(probs), np.int32)
+    energy = np.zeros(len(probs), np.float64)
+    for k, f in enumerate(probs):
+        o, n_iter[k], energy[k] = tv_problem(f, weight, eps, max_iter, dtype)
+        out[k] = o.astype(np.float32)
+    return out.reshape(a.shape), n_iter, energy

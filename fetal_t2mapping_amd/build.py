@@ -10,7 +10,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libt2fit_hip.so")
-SOURCES = [os.path.join(CSRC, "t2fit_kernels.hip"), os.path.join(CSRC, "t2fit_roi.hip"), os.path.join(CSRC, "t2fit_boot.hip")]
+SOURCES = [os.path.join(CSRC, "t2fit_kernels.hip"), os.path.join(CSRC, "t2fit_roi.hip"), os.path.join(CSRC, "t2fit_boot.hip"),
+           os.path.join(CSRC, "t2fit_denoise.hip")]
 ARCH = "gfx950"
 
 

@@ -4,6 +4,7 @@
         --in_vivo --gaussian --lf --sim 1 [--TEs 114 202 299] [--no_prior] [--solver lbfgsb|lm|loglin] [--gpus N]
         [--roi_stats ho:2 --roi_stats jhu:3 --roi_stats feta] [--roi_connectivity 3] [--roi_erosion 1]
         [--bootstrap 100 [--bootstrap_seed 0] [--bootstrap_alpha 0.05] [--bootstrap_noise background|sigma_map|<float>]]
+        [--denoise tv [--denoise_weight 0.1|<c>sigma] [--denoise_dims 2|3] [--denoise_eps 2e-4] [--denoise_iter 200]]
 
 --gpus N (N > 1) starts one process per GPU (torch.distributed.run, RCCL) before anything touches a GPU: with at
 least N subjects in the CSVs each rank streams its own subjects (dist.subjects_of_rank: nothing is exchanged,
@@ -21,6 +22,9 @@ utils/ada_utils.py:130-216 and :885-968 on the GPU (t2map.roi_table).
 --bootstrap R adds, after the maps, R replicas of the parametric bootstrap (t2map.bootstrap_volume): the T2 standard
 deviation, bias, percentile interval and replica count of every voxel as ..._T2stdmap / T2biasmap / T2cilomap /
 T2cihimap / T2nokmap_ada-<fit>.nii.gz beside the four maps.
+--denoise tv passes the decoded echo volumes through t2map.denoise_tv (TV-Chambolle as scikit-image defines it: the
+reference's run_denoising, utils/qmri_utils.py:393-405, the last step of its reconstruction stage) before the union mask
+and the fit; masks, geometry and output file names are unchanged.
 The convergence-study figures (:465-468) are written on request (--plots, convergence.py).  ``--csv prj-004``
 (prj-003, prj-002) stands for the session logs of that project of the reference's paper, as in
 utils/metadata_utils.py:19-85.
@@ -375,6 +379,54 @@ def save_bootstrap_maps(vols, mask, maps4, te_eff, fit, fit_params, prior, solve
 
 
 # ---- driver ------------------------------------------------------------------------------------
+def parse_denoise_weight(text: str):
+    """``--denoise_weight``: a number > 0 (intensity units), or ``<c>sigma`` = ``c`` times the background noise level of
+    the stack (``sigma`` alone is ``1sigma``).  Returns ``("abs", w)`` or ``("sigma", c)``."""
+    t = str(text).strip().lower()
+    kind = "abs"
+    if t.endswith("sigma"):
+        kind, t = "sigma", (t[:-5].strip() or "1")
+    try:
+        v = float(t)
+    except ValueError:
+        raise ValueError(f"--denoise_weight {text!r}: expected a number or <c>sigma (e.g. 1sigma, 0.5sigma)") from None
+    if not (v > 0.0 and np.isfinite(v)):
+        raise ValueError(f"--denoise_weight {text!r}: the weight must be a positive number")
+    return kind, v
+
+
+def denoise_subject(vols, masks, weight, dims=2, eps=2e-4, max_iter=200, device=0):
+    """``--denoise tv``: the decoded echo volumes through t2map.denoise_tv on the device (what the reference's
+    run_denoising does to them on the host before run_t2mapping.py reads the file), ahead of the union mask and the
+    fit.  ``weight``: parse_denoise_weight's pair; the ``sigma`` form measures the noise level on the voxels outside
+    the union mask, before denoising.  Masks and geometry are untouched.  Returns the denoised volumes (float32)."""
+    import torch
+
+    t0 = time.time()
+    dev = torch.device("cuda", device)
+    shape = tuple(np.asarray(vols[0]).shape)
+    if len(shape) != 3:
+        raise ValueError(f"--denoise tv needs 3-D echo volumes, got shape {shape}")
+    stack = torch.empty((len(vols),) + shape, dtype=torch.float32, device=dev)
+    for i, v in enumerate(vols):
+        stack[i] = torch.from_numpy(np.ascontiguousarray(v).astype(np.float32, copy=False)).to(dev)
+    kind, value = weight
+    note = ""
+    if kind == "sigma":
+        union = np.zeros(shape, bool)
+        for m in masks:
+            union |= np.asarray(m) != 0
+        sigma, count = t2map.estimate_background_sigma(stack, union.astype(np.uint8), device=device)
+        note = f" ({value:g} x background sigma {sigma:.4g} over {count} samples)"
+        value = value * sigma
+    out, info = t2map.denoise_tv(stack, value, eps=eps, max_iter=max_iter, dims=dims, out=stack, return_info=True)
+    n_iter = info["n_iter"].cpu().numpy()
+    host = out.cpu().numpy()
+    print(f"Denoising: TV-Chambolle {dims}-D, weight {value:.4g}{note}, {n_iter.size} problems, n_iter mean "
+          f"{float(n_iter.mean()):.1f} max {int(n_iter.max())}, {time.time() - t0:.3f} s")
+    return [host[i] for i in range(len(vols))]
+
+
 def _fit_subject(vols, masks, keep, te_eff, fit, fit_params, prior, norm, solver, precision, device, numpy_legacy=False):
     """One (sub, ses): union mask + flat indices on the device (bit-identical to
     run_t2mapping.py:383-384,412,421), fit, maps back to the host as (Z,Y,X) float32."""
@@ -513,11 +565,12 @@ def _one_block(vols):
 def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field, prior, fast, norm, sim,
                    solver="lbfgsb", precision="f64", device=0, plots=False, plot_seed=None, numpy_legacy=False,
                    roi_specs=(), roi_connectivity=3, roi_erosion=1, bootstrap=0, bootstrap_seed=0, bootstrap_alpha=0.05,
-                   bootstrap_noise="background"):
+                   bootstrap_noise="background", denoise=None):
     """run_t2mapping.py:333-479 with the voxel loop on the GPU.  ``plots``: also write the reference's
     convergence-study figures (:465-468) under <prj>/ada/convergence_analysis.  ``roi_specs``: (name, tissue) pairs
     of --roi_stats; each adds a per-region table after the maps (save_roi_csvs).  ``bootstrap`` > 0: that many
-    replicas of the parametric bootstrap after the maps (save_bootstrap_maps)."""
+    replicas of the parametric bootstrap after the maps (save_bootstrap_maps).  ``denoise``: None, or the keyword
+    arguments of denoise_subject (--denoise tv): the echoes are denoised after decoding, before the mask and the fit."""
     sitk = _sitk()
     tes_s = [x / 1000 for x in TEs]
     metadata = metadata[metadata["EchoTime"].isin(tes_s)]
@@ -526,6 +579,9 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
     rank, world, _ = _dist_env()
     subjects = [(prj, sub, ses) for prj, prj_md in metadata.groupby("prj") for (sub, ses), _ in prj_md.groupby(["sub", "ses"])]
     share_volumes = world > 1 and len(subjects) < world
+    if denoise and share_volumes:
+        raise ValueError("--denoise is not run on a volume that is shared by several ranks (each rank holds a part of the "
+                         "echoes): give at least as many subjects as ranks, or run on one GPU")
     mine = set(subjects if (world == 1 or share_volumes) else
                [subjects[i] for i in dist_subjects_of_rank(len(subjects), rank, world)])
     writer = (rank == 0) or not share_volumes
@@ -558,6 +614,8 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
             else:
                 vols, masks, label, recon_img = _read_subject(sitk, recon_paths, mask_paths, label_path)
                 keep = (label != 0) if (phantom and fast) else None  # :394-400
+                if denoise:
+                    vols = denoise_subject(vols, masks, device=device, **denoise)
                 t0 = time.time()
                 fitted = _fit_subject(vols, masks, keep, te_eff, fit, fit_params, prior, norm, solver, precision, device,
                                       **({"numpy_legacy": True} if numpy_legacy else {}))
@@ -680,7 +738,35 @@ def parse_arguments(argv=None):
     p.add_argument("--bootstrap_noise", default="background", metavar="{background,sigma_map,<float>}",
                    help="noise level of the replicas: measured on the voxels outside the mask (default), the fitted sigma of "
                         "every voxel (3-parameter fits only), or a number")
+    p.add_argument("--denoise", choices=["tv"], default=None,
+                   help="denoise the echo volumes on the GPU before the fit: tv = TV-Chambolle as scikit-image's "
+                        "denoise_tv_chambolle, the reference's run_denoising; off by default")
+    p.add_argument("--denoise_weight", default="0.1", metavar="{W,<c>sigma}",
+                   help="TV weight in intensity units (default 0.1, the reference's, which barely changes images with "
+                        "values in the hundreds), or <c>sigma: c times the background noise level measured outside the mask")
+    p.add_argument("--denoise_dims", type=int, choices=[2, 3], default=2,
+                   help="2: every slice on its own (default, the reference's); 3: every volume as a whole")
+    p.add_argument("--denoise_eps", type=float, default=2e-4, help="relative energy change that stops a problem (default 2e-4)")
+    p.add_argument("--denoise_iter", type=int, default=200, help="iteration limit of a problem (default 200)")
     args = p.parse_args(argv)
+    args.denoise_args = None
+    given = [f for f in ("--denoise_weight", "--denoise_dims", "--denoise_eps", "--denoise_iter")
+             if any(a == f or a.startswith(f + "=") for a in (argv if argv is not None else sys.argv[1:]))]
+    if given and not args.denoise:
+        p.error(f"{given[0]} has no effect without --denoise tv")
+    if args.denoise:
+        try:
+            weight = parse_denoise_weight(args.denoise_weight)
+        except ValueError as e:
+            p.error(str(e))
+        if not (args.denoise_eps >= 0.0 and np.isfinite(args.denoise_eps)):
+            p.error("--denoise_eps must be >= 0")
+        if args.denoise_iter < 1:
+            p.error("--denoise_iter must be >= 1")
+        if args.bootstrap:
+            p.error("--denoise cannot be combined with --bootstrap: the replicas would not pass through the denoiser, so "
+                    "their spread would not be that of the fitted maps")
+        args.denoise_args = {"weight": weight, "dims": args.denoise_dims, "eps": args.denoise_eps, "max_iter": args.denoise_iter}
     if args.bootstrap:
         try:
             args.bootstrap_noise = parse_bootstrap_noise(args.bootstrap_noise)
@@ -762,7 +848,7 @@ def main(argv=None):
                        plots=args.plots, plot_seed=args.plot_seed, numpy_legacy=args.numpy_legacy,
                        roi_specs=args.roi_specs, roi_connectivity=args.roi_connectivity, roi_erosion=args.roi_erosion,
                        bootstrap=args.bootstrap, bootstrap_seed=args.bootstrap_seed, bootstrap_alpha=args.bootstrap_alpha,
-                       bootstrap_noise=args.bootstrap_noise)
+                       bootstrap_noise=args.bootstrap_noise, **({"denoise": args.denoise_args} if args.denoise_args else {}))
     finally:
         if world > 1:
             import torch.distributed as dist

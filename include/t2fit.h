@@ -20,6 +20,7 @@
 #ifndef T2FIT_H
 #define T2FIT_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -314,6 +315,69 @@ int t2fit_bootstrap_dev(t2fit_context *ctx, const t2fit_config *cfg, const float
                         const float *sigma_dev, double noise_scalar, const float *noise_map_dev, int noise_kind,
                         const uint8_t *mask_dev, int64_t n_vox, int n_replicas, uint64_t seed, double alpha,
                         int which_params, const t2fit_boot_maps *out, int flags, void *stream);
+
+/* ---- Total-variation denoising of the echo stack, ahead of the fit ---------------------------------------------------
+ * The reference's reconstruction stage ends with run_denoising (utils/qmri_utils.py:393-405): every slice of every echo
+ * volume goes through skimage.restoration.denoise_tv_chambolle (scikit-image 0.22, its defaults) before run_t2mapping.py
+ * reads the file.  This is that function on the device for a float32 stack (n_vol, nz, ny, nx), x innermost.  Additive
+ * to ABI 5: three new symbols and one new struct (look the symbols up to detect them).
+ *
+ * One problem is one (ny, nx) slice (dims = 2: n_vol * nz problems) or one (nz, ny, nx) volume (dims = 3: n_vol
+ * problems); problems are independent.  For a problem f with n = dims axes (in memory order, x last) and N elements, in
+ * the working precision T, tau = 1 / (2 n):
+ *   p_a = 0 for every axis a
+ *   for i = 0 .. max_iter - 1:
+ *     d[x]   = 0 if i == 0, else ((-(p_0 + .. + p_{n-1})[x]) + p_0[x - e_0]) + p_1[x - e_1] ..   (axis order; a term is
+ *              dropped where x - e_a is outside)
+ *     out    = f + d
+ *     g_a[x] = out[x + e_a] - out[x]   (0 where x + e_a is outside)
+ *     nrm    = sqrt((g_0^2 + g_1^2) (+ g_2^2))
+ *     E      = (sum d^2 + weight * sum nrm) / N
+ *     p_a    = (p_a - T(tau) * g_a) / (1 + T(tau / weight) * nrm)
+ *     i == 0: E_init = E_prev = E;  else if |E_prev - E| < eps * E_init: stop;  else E_prev = E
+ *   result = out of the last iteration executed; n_iter = i at a stop, max_iter - 1 when the loop runs out
+ * Every elementwise operation is one correctly rounded operation in T, in the order written (no fused multiply-add).
+ * The squares d^2 and the norms are formed in T and summed in float64 in a fixed tree (E is float64: skimage sums in
+ * the image's precision, so on a float32 image its stop can fall one iteration away when |E_prev - E| lies within
+ * float32 rounding of the threshold); the stop iteration and every output byte are the same from call to call.
+ * precision = T2FIT_PREC_F32 iterates in float32 (skimage on a float32 image); T2FIT_PREC_F64 widens the input,
+ * iterates in float64 and rounds `out` to float32 once at the end (the reference: float64 reconstruction, the file is
+ * read back as float32).  eps = 0 never stops early.  fetal_t2mapping_amd/_tv.py restates the loop in numpy. */
+typedef struct t2fit_tv_params {
+  double weight;     /* > 0, in intensity units of the stack (skimage does not rescale a float image) */
+  double eps;        /* >= 0 */
+  int32_t max_iter;  /* >= 1 */
+  int32_t dims;      /* 2 or 3 */
+  int32_t precision; /* T2FIT_PREC_F32 or T2FIT_PREC_F64 */
+  int32_t flags;     /* reserved, must be 0 */
+} t2fit_tv_params;
+
+/* skimage's defaults, hence the reference's: weight 0.1, eps 2e-4, max_iter 200; dims 2, T2FIT_PREC_F32, flags 0 */
+int t2fit_tv_params_default(t2fit_tv_params *p);
+
+/* Bytes of the workspace a call needs; plain arithmetic, no device.  With e = 4 (F32) or 8 (F64) bytes, up(v) = v
+ * rounded up to a multiple of 256, problems as above and tiles of 32 x 64 (dims = 2: ceil(ny / 32) ceil(nx / 64) per
+ * problem) or 4 x 8 x 64 (dims = 3: ceil(nz / 4) ceil(ny / 8) ceil(nx / 64) per problem):
+ *   2 up(dims * n_vol * nz * ny * nx * e)  [the two halves of the p pair]  +  up(16 * tiles)  [partial energies]
+ *   +  up(32 * problems)  [E_init, E_prev, E, done flag, n_iter of every problem]
+ * Refuses what t2fit_tv_denoise_dev refuses in p and the sizes: a size < 1, more than 2^40 elements (the voxel index is
+ * 64-bit, the byte counts stay far inside size_t), more than 2^31-1 tiles (the launch index is 32-bit). */
+int t2fit_tv_workspace_bytes(const t2fit_tv_params *p, int n_vol, int nz, int ny, int nx, size_t *bytes);
+
+/* Denoise in_dev into out_dev (both device float32 [n_vol * nz * ny * nx]; out_dev == in_dev is allowed, a partial
+ * overlap is not).  workspace_dev: at least t2fit_tv_workspace_bytes bytes, aligned to 256; its contents on entry do not
+ * matter and it may be reused or freed once the stream has passed the call.  n_iter_dev (int32) / energy_dev (float64,
+ * E of the last iteration executed): one per problem in memory order, or NULL.  A 1-wide axis is legal (its difference
+ * is 0).  NaN / Inf in a problem stay in that problem (it runs max_iter iterations: no comparison with NaN stops it).
+ * Asynchronous on `stream`: 2 max_iter + 1 launches are queued, the stop rule runs on the device and the workgroups of a
+ * finished problem return at once; no allocation, free, copy or synchronisation inside.  Every argument is checked
+ * before HIP is touched (T2FIT_E_INVALID and a message): NULL p / in_dev / out_dev / workspace_dev, weight <= 0 or not
+ * finite, eps < 0 or not finite, max_iter < 1, dims not 2 / 3, unknown precision, flags != 0, a size < 1 or too large
+ * (above), a workspace that is too small or not aligned to 256 bytes, a stack pointer not aligned to 4 bytes.
+ * 128-bit accesses are used when nx % 4 == 0 and the stack pointers are 16-byte aligned; anything else takes
+ * element-wise accesses and gives the same bits. */
+int t2fit_tv_denoise_dev(const t2fit_tv_params *p, const float *in_dev, float *out_dev, int n_vol, int nz, int ny, int nx,
+                         void *workspace_dev, size_t workspace_bytes, int32_t *n_iter_dev, double *energy_dev, void *stream);
 
 /* Kernel timing for benchmarks (no reference counterpart).  With timing enabled (t2fit_set_timing(1)) every
  * t2fit_volume_dev call of this thread records HIP events around its fit kernel on the launch stream.
