@@ -8,10 +8,10 @@ Python host side that mirrors the reference's function surface.  There is no CPU
 from ._philox import philox4x32_10
 from .t2map import (BootMaps, BootStats, RoiStats, T2Maps, bootstrap_volume, compute_residuals, denoise_tv, dense_labels,
                     estimate_background_sigma, fit_table, fit_volume, fit_voxel, fit_voxels, fit_voxels_trace, label_stats,
-                    make_config, roi_erode, roi_frame, roi_stats, roi_table, set_fit_params, stack_mask_flatten,
-                    synth_replica, union_mask_dev)
+                    make_config, reconstruct_stacks, resample_volume, roi_erode, roi_frame, roi_stats, roi_table,
+                    set_fit_params, stack_mask_flatten, synth_replica, union_mask_dev)
 
 __all__ = ["BootMaps", "BootStats", "RoiStats", "T2Maps", "bootstrap_volume", "compute_residuals", "denoise_tv", "dense_labels",
            "estimate_background_sigma", "fit_table", "fit_volume", "fit_voxel", "fit_voxels", "fit_voxels_trace", "label_stats",
-           "make_config", "philox4x32_10", "roi_erode", "roi_frame", "roi_stats", "roi_table", "set_fit_params",
+           "make_config", "philox4x32_10", "reconstruct_stacks", "resample_volume", "roi_erode", "roi_frame", "roi_stats", "roi_table", "set_fit_params",
            "stack_mask_flatten", "synth_replica", "union_mask_dev"]

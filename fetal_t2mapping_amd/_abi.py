@@ -58,6 +58,11 @@ class T2FitTvParams(C.Structure):
                 ("precision", C.c_int32), ("flags", C.c_int32)]
 
 
+INTERP_LINEAR, INTERP_NEAREST = 0, 1
+INTERPS = {"linear": INTERP_LINEAR, "nearest": INTERP_NEAREST}
+RESAMPLE_F32, RESAMPLE_I32 = 0, 1
+RESAMPLE_INTEGER_CAST, RECON_CHAIN = 1, 2  # flags bits
+
 # every symbol include/t2fit.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -86,6 +91,12 @@ SYMBOLS = [
     ("t2fit_tv_workspace_bytes", C.c_int, [C.POINTER(T2FitTvParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     ("t2fit_tv_denoise_dev", C.c_int, [C.POINTER(T2FitTvParams), _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t,
                                        _P, _P, _P]),
+    ("t2fit_resample_dev", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _P, C.c_int, C.c_int, C.c_int,
+                                     C.c_int, C.c_int, C.c_double, C.c_int, _P]),
+    ("t2fit_reconstruct_workspace_bytes", C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
+                                                    C.POINTER(C.c_size_t)]),
+    ("t2fit_reconstruct_dev", C.c_int, [C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_double), _P, C.c_int, C.c_int, _P, C.c_size_t, _P]),
     ("t2fit_set_timing", C.c_int, [C.c_int]),
     ("t2fit_set_reserve_cus", C.c_int, [C.c_int]),
     ("t2fit_kernel_ms", C.c_double, [C.c_int]),
@@ -98,7 +109,8 @@ SYMBOLS = [
 
 # entry points added to ABI 5 after its first release: another build of the same ABI (T2FIT_LIB) may lack them
 ADDITIVE = ("t2fit_boot_background_dev", "t2fit_boot_synth_dev", "t2fit_bootstrap_dev",
-            "t2fit_tv_params_default", "t2fit_tv_workspace_bytes", "t2fit_tv_denoise_dev")
+            "t2fit_tv_params_default", "t2fit_tv_workspace_bytes", "t2fit_tv_denoise_dev",
+            "t2fit_resample_dev", "t2fit_reconstruct_workspace_bytes", "t2fit_reconstruct_dev")
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

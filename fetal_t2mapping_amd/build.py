@@ -11,7 +11,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libt2fit_hip.so")
 SOURCES = [os.path.join(CSRC, "t2fit_kernels.hip"), os.path.join(CSRC, "t2fit_roi.hip"), os.path.join(CSRC, "t2fit_boot.hip"),
-           os.path.join(CSRC, "t2fit_denoise.hip")]
+           os.path.join(CSRC, "t2fit_denoise.hip"), os.path.join(CSRC, "t2fit_resample.hip")]
 ARCH = "gfx950"
 
 

@@ -137,6 +137,15 @@ def _read_subject(sitk, recon_paths, mask_paths, label_path):
     return vols, masks, label, recon_img
 
 
+def _read_masks(sitk, mask_paths, label_path):
+    """The masks and the optional vial labels of one (sub, ses) when the echoes do not come from files (--reconstruct):
+    ``([], masks, label, None)``, the shape of _read_subject's result."""
+    DECODED["mask"] += len(mask_paths)
+    masks = [sitk.GetArrayFromImage(sitk.ReadImage(mp)) for mp in mask_paths]
+    label = sitk.GetArrayFromImage(sitk.ReadImage(label_path)) if label_path else None
+    return [], masks, label, None
+
+
 # ---- metadata / paths --------------------------------------------------------------------------
 def mk_bids_dir(bids_dir, *dirs):
     """utils/dcm_utils.py:189-195 (there: `if not exists: mkdir`; with --gpus N several ranks create the shared
@@ -565,12 +574,14 @@ def _one_block(vols):
 def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field, prior, fast, norm, sim,
                    solver="lbfgsb", precision="f64", device=0, plots=False, plot_seed=None, numpy_legacy=False,
                    roi_specs=(), roi_connectivity=3, roi_erosion=1, bootstrap=0, bootstrap_seed=0, bootstrap_alpha=0.05,
-                   bootstrap_noise="background", denoise=None):
+                   bootstrap_noise="background", denoise=None, reconstruct=None):
     """run_t2mapping.py:333-479 with the voxel loop on the GPU.  ``plots``: also write the reference's
     convergence-study figures (:465-468) under <prj>/ada/convergence_analysis.  ``roi_specs``: (name, tissue) pairs
     of --roi_stats; each adds a per-region table after the maps (save_roi_csvs).  ``bootstrap`` > 0: that many
     replicas of the parametric bootstrap after the maps (save_bootstrap_maps).  ``denoise``: None, or the keyword
-    arguments of denoise_subject (--denoise tv): the echoes are denoised after decoding, before the mask and the fit."""
+    arguments of denoise_subject (--denoise tv): the echoes are denoised after decoding, before the mask and the fit.
+    ``reconstruct``: None, or the keyword arguments of recon.reconstruct_subject (--reconstruct): the echoes are not read
+    from recon_1mm but reconstructed in memory from the acquired ax / cor / sag stacks, ahead of the denoiser."""
     sitk = _sitk()
     tes_s = [x / 1000 for x in TEs]
     metadata = metadata[metadata["EchoTime"].isin(tes_s)]
@@ -581,6 +592,9 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
     share_volumes = world > 1 and len(subjects) < world
     if denoise and share_volumes:
         raise ValueError("--denoise is not run on a volume that is shared by several ranks (each rank holds a part of the "
+                         "echoes): give at least as many subjects as ranks, or run on one GPU")
+    if reconstruct is not None and share_volumes:
+        raise ValueError("--reconstruct is not run on a volume that is shared by several ranks (each rank holds a part of the "
                          "echoes): give at least as many subjects as ranks, or run on one GPU")
     mine = set(subjects if (world == 1 or share_volumes) else
                [subjects[i] for i in dist_subjects_of_rank(len(subjects), rank, world)])
@@ -612,7 +626,17 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
                     precision, device, numpy_legacy)
                 vols = None
             else:
-                vols, masks, label, recon_img = _read_subject(sitk, recon_paths, mask_paths, label_path)
+                if reconstruct is not None:
+                    from . import recon
+
+                    vols, recon_img = recon.reconstruct_subject(sitk, bids_path, sub_md, sub, ses, device=device, **reconstruct)
+                    _, masks, label, _ = _read_masks(sitk, mask_paths, label_path)
+                    bad = [tuple(np.asarray(m).shape) for m in masks if tuple(np.asarray(m).shape) != vols[0].shape]
+                    if bad:
+                        raise ValueError(f"--reconstruct: the mask of {sub}_{ses} has shape {bad[0]}, the reconstructed grid "
+                                         f"has {vols[0].shape}: masks must be drawn on the reconstruction that is fitted")
+                else:
+                    vols, masks, label, recon_img = _read_subject(sitk, recon_paths, mask_paths, label_path)
                 keep = (label != 0) if (phantom and fast) else None  # :394-400
                 if denoise:
                     vols = denoise_subject(vols, masks, device=device, **denoise)
@@ -738,6 +762,15 @@ def parse_arguments(argv=None):
     p.add_argument("--bootstrap_noise", default="background", metavar="{background,sigma_map,<float>}",
                    help="noise level of the replicas: measured on the voxels outside the mask (default), the fitted sigma of "
                         "every voxel (3-parameter fits only), or a number")
+    p.add_argument("--reconstruct", action="store_true",
+                   help="do not read recon_1mm: reconstruct every echo in memory from the acquired ax / cor / sag stacks "
+                        "(resample to --recon_res mm, merge on the --recon_fixed grid; python -m fetal_t2mapping_amd.recon "
+                        "writes the same volumes), ahead of --denoise and the fit; off by default")
+    p.add_argument("--recon_fixed", choices=["ax", "cor", "sag"], default="ax", help="grid of the reconstruction (default ax)")
+    p.add_argument("--recon_res", type=float, default=1.0, help="isotropic resolution of the reconstruction [mm] (default 1)")
+    p.add_argument("--recon_transforms", default=None, metavar="DIR",
+                   help="rigid transforms <sub>_<ses>_<orientation>.txt of the moving stacks (4 x 4 text, fixed point -> "
+                        "moving point); a missing file is the identity")
     p.add_argument("--denoise", choices=["tv"], default=None,
                    help="denoise the echo volumes on the GPU before the fit: tv = TV-Chambolle as scikit-image's "
                         "denoise_tv_chambolle, the reference's run_denoising; off by default")
@@ -749,6 +782,17 @@ def parse_arguments(argv=None):
     p.add_argument("--denoise_eps", type=float, default=2e-4, help="relative energy change that stops a problem (default 2e-4)")
     p.add_argument("--denoise_iter", type=int, default=200, help="iteration limit of a problem (default 200)")
     args = p.parse_args(argv)
+    args.reconstruct_args = None
+    given = [f for f in ("--recon_fixed", "--recon_res", "--recon_transforms")
+             if any(a == f or a.startswith(f + "=") for a in (argv if argv is not None else sys.argv[1:]))]
+    if given and not args.reconstruct:
+        p.error(f"{given[0]} has no effect without --reconstruct")
+    if args.reconstruct:
+        if not (args.recon_res > 0.0 and np.isfinite(args.recon_res)):
+            p.error("--recon_res must be a positive number")
+        if args.recon_transforms is not None and not os.path.isdir(args.recon_transforms):
+            p.error(f"--recon_transforms {args.recon_transforms!r} is not a directory")
+        args.reconstruct_args = {"fixed": args.recon_fixed, "res": args.recon_res, "transforms_dir": args.recon_transforms}
     args.denoise_args = None
     given = [f for f in ("--denoise_weight", "--denoise_dims", "--denoise_eps", "--denoise_iter")
              if any(a == f or a.startswith(f + "=") for a in (argv if argv is not None else sys.argv[1:]))]
@@ -848,7 +892,8 @@ def main(argv=None):
                        plots=args.plots, plot_seed=args.plot_seed, numpy_legacy=args.numpy_legacy,
                        roi_specs=args.roi_specs, roi_connectivity=args.roi_connectivity, roi_erosion=args.roi_erosion,
                        bootstrap=args.bootstrap, bootstrap_seed=args.bootstrap_seed, bootstrap_alpha=args.bootstrap_alpha,
-                       bootstrap_noise=args.bootstrap_noise, **({"denoise": args.denoise_args} if args.denoise_args else {}))
+                       bootstrap_noise=args.bootstrap_noise, **({"denoise": args.denoise_args} if args.denoise_args else {}),
+                       **({"reconstruct": args.reconstruct_args} if args.reconstruct_args else {}))
     finally:
         if world > 1:
             import torch.distributed as dist

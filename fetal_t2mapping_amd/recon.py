@@ -1,0 +1,216 @@
+"""Steps 1 and 2 of the reference's run_qmri_reconstruction.py on the GPU: every acquired thick-slice stack is resampled
+to an isotropic grid (run_resample_volume, utils/qmri_utils.py:35-58), the cor and sag volumes of an echo are resampled
+onto the ax grid and the three are averaged (run_reconstruct_volume, :359-391), and the result is denoised
+(run_denoising, :393-405) and written under ``recon_1mm`` with the reference's file names, where cli.py reads it.
+
+    python -m fetal_t2mapping_amd.recon --path <qMRI root> --csv <log.csv ...> (--in_vivo | --in_vitro) (--lf | --hf)
+
+The registration of the reference (elastix, rigid) is not part of this package: ``--transforms DIR`` supplies rigid
+transforms as 4 x 4 text matrices (fixed point -> moving point, LPS millimetres) and a missing file is the identity,
+the reference's own reading of ``recon_1mm`` when nothing moved.  Each echo is reconstructed once: the reference runs
+its loop body for each of the three rows of an echo and writes the same file three times."""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+from . import _resample, t2map
+from .cli import _sitk, get_img_path, recon_dirname, set_metadata
+
+in_dirname = "anat"
+resamp_dirname = "resamp_1mm"
+
+
+def transform_path(transforms_dir, acq, orientation):
+    """``<DIR>/<sub>_<ses>_<orientation>.txt``: the rigid transform of moving stack `orientation` of this (sub, ses)."""
+    return os.path.join(transforms_dir, f"{acq['sub']}_{acq['ses']}_{orientation}.txt")
+
+
+def load_transforms(transforms_dir, acq, fixed):
+    """{moving orientation: 4 x 4} for the files that exist under `transforms_dir` (None: no directory given)."""
+    out = {}
+    if not transforms_dir:
+        return out
+    for o in _resample.moving_order(fixed):
+        path = transform_path(transforms_dir, acq, o)
+        if os.path.exists(path):
+            m = np.loadtxt(path, dtype=np.float64)
+            if m.shape != (4, 4) or not np.all(np.isfinite(m)):
+                raise ValueError(f"{path}: expected a finite 4 x 4 matrix")
+            out[o] = m
+    return out
+
+
+def echo_groups(metadata):
+    """[(prj, sub, ses, [(echo time [s], {orientation: row})])] in the reference's iteration order: (prj, sub, ses),
+    then EchoTime; an echo's rows are keyed by ImageOrientationPatientSTR (a later row of the same orientation replaces
+    an earlier one, as the reference's dict does)."""
+    out = []
+    for (prj, sub, ses), sub_md in metadata.groupby(["prj", "sub", "ses"]):
+        echoes = []
+        for echotime, te_md in sub_md.groupby("EchoTime"):
+            echoes.append((float(echotime), {acq["ImageOrientationPatientSTR"]: acq for _, acq in te_md.iterrows()}))
+        out.append((prj, sub, ses, echoes))
+    return out
+
+
+def _same_grid(a, b):
+    return (a.GetSize() == b.GetSize() and a.GetSpacing() == b.GetSpacing() and a.GetOrigin() == b.GetOrigin()
+            and a.GetDirection() == b.GetDirection())
+
+
+def _int16_on_disk(img, sitk):
+    arr = sitk.GetArrayFromImage(img)
+    return arr.dtype == np.int16
+
+
+def read_echoes(sitk, bids_path, echoes, sub, ses):
+    """The acquired stacks of the echoes that have the three orientations: [(echo time, rows, {orientation: image})]."""
+    ready = []
+    for echotime, rows in echoes:
+        if not all(o in rows for o in _resample.ORIENTATIONS) or len(rows) != 3:
+            print(f"Warning: TE {int(echotime * 1000):3} ms of {sub}_{ses} has orientations {sorted(rows)}. "
+                  "Reconstruction is skipped.")
+            continue
+        imgs = {o: sitk.ReadImage(get_img_path(bids_path, rows[o], in_dirname)) for o in _resample.ORIENTATIONS}
+        ready.append((echotime, rows, imgs))
+    return ready
+
+
+def batches_of(ready):
+    """Echoes whose three stacks lie on the same grids share a call."""
+    batches = []
+    for item in ready:
+        for batch in batches:
+            if all(_same_grid(_resample.as_geometry(item[2][o]), _resample.as_geometry(batch[0][2][o]))
+                   for o in _resample.ORIENTATIONS):
+                batch.append(item)
+                break
+        else:
+            batches.append([item])
+    return batches
+
+
+def batch_inputs(sitk, batch, integer_cast=None):
+    """``(stacks, geoms, cast)`` of a batch: float32 ``(n, Z, Y, X)`` per orientation, the first echo's images as
+    geometries, and whether the pixel type is kept (None: yes when every stack is int16 on disk, as the reference)."""
+    geoms = {o: batch[0][2][o] for o in _resample.ORIENTATIONS}
+    stacks = {o: np.stack([np.asarray(sitk.GetArrayFromImage(it[2][o]), np.float32) for it in batch])
+              for o in _resample.ORIENTATIONS}
+    cast = all(_int16_on_disk(it[2][o], sitk) for it in batch for o in _resample.ORIENTATIONS) \
+        if integer_cast is None else bool(integer_cast)
+    return stacks, geoms, cast
+
+
+def process_recon(metadata, bids_path, *, fixed="ax", res=1.0, transforms_dir=None, write_resamp=False, denoise=True,
+                  integer_cast=None, device=0):
+    """Reconstruct every echo of every (prj, sub, ses) of `metadata` that has the three orientations and write it.
+    The echoes of a subject whose stacks share their geometry per orientation go through one call.  ``integer_cast``:
+    None keeps the pixel type as the reference does (cast when the stacks are int16 on disk).  Returns the paths
+    written under ``recon_1mm``."""
+    import torch
+
+    sitk = _sitk()
+    written = []
+    for prj, sub, ses, echoes in echo_groups(metadata):
+        for batch in batches_of(read_echoes(sitk, bids_path, echoes, sub, ses)):
+            t0 = time.time()
+            stacks, geoms, cast = batch_inputs(sitk, batch, integer_cast)
+            transforms = load_transforms(transforms_dir, batch[0][1][fixed], fixed)
+            print(f"===== Reconstruction: {prj}_{sub}_{ses}, TE {[int(it[0] * 1000) for it in batch]} ms, fixed {fixed}, "
+                  f"transforms {sorted(transforms) or 'identity'} =====")
+            if write_resamp:  # the intermediate volumes of step 1, as run_resample_volume leaves them
+                for o in _resample.ORIENTATIONS:
+                    hi, g = t2map.resample_volume(stacks[o], geoms[o], res=res, integer_cast=cast, device=device)
+                    for it, vol in zip(batch, hi):
+                        img = sitk.GetImageFromArray(vol)
+                        img.SetSpacing(g.GetSpacing()), img.SetOrigin(g.GetOrigin()), img.SetDirection(g.GetDirection())
+                        path = get_img_path(bids_path, it[1][o], resamp_dirname)
+                        sitk.WriteImage(img, path)
+                        print(f"Image saved in : {path}")
+            merged, header = t2map.reconstruct_stacks(stacks, geoms, fixed=fixed, res=res, transforms=transforms,
+                                                      integer_cast=cast, device=device)
+            if denoise:
+                merged = t2map.denoise_tv(merged, out=merged)
+            torch.cuda.synchronize(merged.device)
+            host = merged.cpu().numpy()
+            for it, vol in zip(batch, host):
+                img = sitk.GetImageFromArray(vol)
+                img.SetSpacing(header.GetSpacing()), img.SetOrigin(header.GetOrigin()), img.SetDirection(header.GetDirection())
+                path = get_img_path(bids_path, it[1][fixed], recon_dirname)
+                sitk.WriteImage(img, path)
+                written.append(path)
+                print(f"Image saved in : {path}")
+            print(f"... done. Time to reconstruct: {round(time.time() - t0, 4)} sec")
+    return written
+
+
+def reconstruct_subject(sitk, bids_path, sub_md, sub, ses, *, fixed="ax", res=1.0, transforms_dir=None, integer_cast=None,
+                        device=0):
+    """cli.py --reconstruct: the echoes of one (sub, ses) (`sub_md`: its metadata rows) reconstructed in memory.  Every
+    echo must have the three orientations and the echoes must share their grids.  Returns ``(volumes: list of (Z, Y, X)
+    float32 arrays in EchoTime order, header)``."""
+    echoes = [(float(te), {acq["ImageOrientationPatientSTR"]: acq for _, acq in te_md.iterrows()})
+              for te, te_md in sub_md.groupby("EchoTime")]
+    ready = read_echoes(sitk, bids_path, echoes, sub, ses)
+    if len(ready) != len(echoes):
+        raise ValueError(f"--reconstruct: {sub}_{ses} lacks an orientation (ax, cor, sag) at one or more echo times")
+    batches = batches_of(ready)
+    if len(batches) != 1:
+        raise ValueError(f"--reconstruct: the stacks of {sub}_{ses} do not lie on the same grids at every echo time")
+    stacks, geoms, cast = batch_inputs(sitk, batches[0], integer_cast)
+    merged, header = t2map.reconstruct_stacks(stacks, geoms, fixed=fixed, res=res,
+                                              transforms=load_transforms(transforms_dir, ready[0][1][fixed], fixed),
+                                              integer_cast=cast, device=device)
+    host = merged.cpu().numpy()
+    return [host[i] for i in range(host.shape[0])], header
+
+
+def parse_arguments(argv=None):
+    """Flag set of run_qmri_reconstruction.py:93-112 plus what the registration-free reconstruction can be told."""
+    p = argparse.ArgumentParser(prog="fetal_t2mapping_amd.recon",
+                                description="resample three orthogonal stacks per echo to 1 mm and merge them on an MI355X")
+    p.add_argument("--path", required=True, help="root of the qMRI tree (contains projects/ and dicom/logs/)")
+    p.add_argument("--csv", nargs="+", required=True, help="metadata log CSV file name(s) under dicom/logs/, or prj-00X")
+    g = p.add_mutually_exclusive_group(required=True)
+    g.add_argument("--in_vivo", action="store_true", help="process in vivo data")
+    g.add_argument("--in_vitro", action="store_true", help="process NIST phantom data")
+    g = p.add_mutually_exclusive_group(required=True)
+    g.add_argument("--lf", action="store_true", help="low-field 0.55 T data")
+    g.add_argument("--hf", action="store_true", help="high-field 1.5 T data")
+    p.add_argument("--fixed", choices=list(_resample.ORIENTATIONS), default="ax",
+                   help="the orientation whose grid the result lies on (default ax, the reference's orient_fix_type)")
+    p.add_argument("--res", type=float, default=1.0, help="isotropic resolution [mm] (default 1, the reference's high_res)")
+    p.add_argument("--transforms", default=None, metavar="DIR",
+                   help="directory of rigid transforms <sub>_<ses>_<orientation>.txt (4 x 4 text, fixed point -> moving "
+                        "point); a missing file is the identity")
+    p.add_argument("--write_resamp", action="store_true", help="also write the 1 mm volume of every stack under resamp_1mm/")
+    p.add_argument("--no_denoise", action="store_true",
+                   help="skip the TV-Chambolle pass the reference applies to the merged volume (denoising=True)")
+    p.add_argument("--device", type=int, default=0, help="HIP device ordinal")
+    args = p.parse_args(argv)
+    if not (args.res > 0.0 and np.isfinite(args.res)):
+        p.error("--res must be a positive number")
+    if args.transforms is not None and not os.path.isdir(args.transforms):
+        p.error(f"--transforms {args.transforms!r} is not a directory")
+    return args
+
+
+def main(argv=None):
+    args = parse_arguments(argv)
+    if not os.path.exists(args.path):
+        print(f"Error: The specified path does not exist: {args.path}")
+        raise SystemExit(1)
+    bids_path = os.path.join(args.path, "projects/")
+    csv_path = os.path.join(args.path, "dicom/logs/")
+    metadata = set_metadata(csv_path, args.csv, bool(args.lf))
+    process_recon(metadata, bids_path, fixed=args.fixed, res=args.res, transforms_dir=args.transforms,
+                  write_resamp=args.write_resamp, denoise=not args.no_denoise, device=args.device)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

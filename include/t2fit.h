@@ -379,6 +379,70 @@ int t2fit_tv_workspace_bytes(const t2fit_tv_params *p, int n_vol, int nz, int ny
 int t2fit_tv_denoise_dev(const t2fit_tv_params *p, const float *in_dev, float *out_dev, int n_vol, int nz, int ny, int nx,
                          void *workspace_dev, size_t workspace_bytes, int32_t *n_iter_dev, double *energy_dev, void *stream);
 
+/* ---- Orthogonal-stack reconstruction: resample to an isotropic grid and merge -------------------------------------
+ * Steps 1 and 2 of the reference's run_qmri_reconstruction.py: every acquired thick-slice stack (ax / cor / sag, one per
+ * echo time) is resampled to a 1 mm grid with linear interpolation (utils/qmri_utils.py resample_volume, :62-80), the
+ * two moving ones are resampled onto the fixed one's grid after a rigid registration, and the three are averaged
+ * (reconstruct_vol_trilinear, :82-136).  The registration is not part of this library: rigid transforms enter through
+ * the affines below (identity = the reference's "no motion" reading).  fetal_t2mapping_amd/_resample.py restates
+ * everything here in numpy, geometry included; the device output is bit-identical to it and the same from call to call.
+ *
+ * Volumes are (nz, ny, nx) with x fastest.  Geometry stays on the host: a stage is described by 12 doubles A (row-major
+ * 3 x 4), the continuous source index of the integer output index (ix, iy, iz),
+ *   c_a = ((A[4a] ix + A[4a+1] iy) + A[4a+2] iz) + A[4a+3]      a = 0 (x), 1 (y), 2 (z), float64, no fused multiply-add.
+ * The voxel is inside iff -0.5 <= c_a < n_a - 0.5 on all three axes; otherwise the result is default_value.
+ * T2FIT_INTERP_LINEAR: b_a = clamp(floor(c_a), 0, n_a - 1), d_a = max(c_a - b_a, 0), upper neighbour min(b_a + 1, n_a - 1)
+ * (the half-voxel rim replicates the edge); interpolation along x, then y, then z in float64 as lo + d (hi - lo); where
+ * d_a == 0 the upper sample along a is not read and the result is lo (a resample onto the source's own nodes is the
+ * identity bit for bit, and an Inf next to a node does not become a NaN); one rounding to float32 at the end.  With
+ * T2FIT_RESAMPLE_INTEGER_CAST the float64 result is first truncated toward zero and clamped to [-32768, 32767] (a stack
+ * that is int16 on disk and keeps its pixel type through sitk.Resample).
+ * T2FIT_INTERP_NEAREST: the node floor(c_a + 0.5), clamped into the volume, is copied (float32 or int32 sources).
+ * Parity with ITK on the rim, on nearest-neighbour ties and on the integer cast is not pinned. */
+#define T2FIT_INTERP_LINEAR 0
+#define T2FIT_INTERP_NEAREST 1
+#define T2FIT_RESAMPLE_F32 0
+#define T2FIT_RESAMPLE_I32 1
+#define T2FIT_RESAMPLE_INTEGER_CAST 1 /* flags bit of t2fit_resample_dev and t2fit_reconstruct_dev */
+#define T2FIT_RECON_CHAIN 2           /* flags bit of t2fit_reconstruct_*: the chain of single stages, not the fused kernel */
+
+/* One stage: n_vol volumes of (nz, ny, nx) at src_dev (src_type T2FIT_RESAMPLE_F32, or T2FIT_RESAMPLE_I32 with
+ * T2FIT_INTERP_NEAREST), which share the geometry (the echoes of one orientation), into n_vol volumes of (oz, oy, ox) of
+ * the same type at out_dev.  default_value is rounded to the volume's type.  The workgroups walk their output bricks
+ * along the output axis with the largest |A[0..2]| (the one that follows the source's x), so that the reads are
+ * contiguous whichever way the stack is oriented; the result does not depend on it.  Asynchronous on `stream`: one
+ * launch, no allocation, copy or synchronisation.  Every argument is checked before HIP is touched (T2FIT_E_INVALID and
+ * a message): NULL src_dev / out_dev / A, out_dev == src_dev, pointers not aligned to 4 bytes, unknown src_type or
+ * interp, an int32 source with linear interpolation, flags other than T2FIT_RESAMPLE_INTEGER_CAST (which goes with
+ * linear only), n_vol or a size < 1, more than 2^40 elements in a stack, more than 2^31-1 bricks of 512 output voxels,
+ * a non-finite entry of A, a default_value outside int32 for an int32 source. */
+int t2fit_resample_dev(const void *src_dev, int src_type, int nz, int ny, int nx, const double *A, void *out_dev, int oz, int oy,
+                       int ox, int n_vol, int interp, double default_value, int flags, void *stream);
+
+/* The whole reconstruction of n_vol echoes.  Index 0 is the fixed orientation, 1 and 2 the moving ones in the order of
+ * ["ax", "cor", "sag"] without the fixed one.  lo_size[9] / hi_size[9]: (nz, ny, nx) of the three acquired stacks L_s and
+ * of their isotropic grids H_s; A1[36]: the three stage-1 affines (H_s index -> L_s index); A2[24]: the two stage-2
+ * affines (H_0 index -> H_m index, the rigid transform of moving stack m folded in).
+ *   stage 1  H_s = linear resample of L_s by A1[s]                          s = 0, 1, 2, default 0
+ *   stage 2  R_m = linear resample of H_m (float32) by A2[m - 1] onto H_0   m = 1, 2, default 0
+ *   merge    out = ((H_0 + R_1) + R_2) / 3 in float64, rounded to float32   (np.mean of the three, as the reference)
+ * T2FIT_RESAMPLE_INTEGER_CAST applies to both stages.  out_dev: float32 [n_vol][hi_size[0..2]], the layout
+ * t2fit_tv_denoise_dev and t2fit_volume_dev (te-major) take.
+ * flags = 0 runs one fused kernel: every stage-2 tap is a stage-1 sample formed on the spot and rounded to float32 as the
+ * stored intermediate would be; no workspace (workspace_dev may be NULL).  T2FIT_RECON_CHAIN runs three stage-1 and two
+ * stage-2 launches of the single-stage kernel plus a merge and needs
+ *   t2fit_reconstruct_workspace_bytes = up(4 n_vol |H_1|) + up(4 n_vol |H_2|) + 2 up(4 n_vol |H_0|),  up(v) = v rounded up
+ * to 256, aligned to 256 bytes.  Both forms give the same bytes; at 256^3 x 8 from three 1 x 1 x 4.5 mm stacks the chain
+ * measured 3.5 ms and the fused kernel 4.6 ms, so the Python mirror asks for the chain.  Asynchronous on `stream`; no allocation, copy or
+ * synchronisation.  Checked before HIP is touched: NULL stacks_dev (or an entry) / lo_size / hi_size / A1 / A2 / out_dev /
+ * bytes, a stack that is out_dev, pointers not aligned to 4 bytes, undefined flags, n_vol or a size < 1, too many
+ * elements or bricks (as above), non-finite affines, a workspace that is missing, too small or misaligned for the chain.
+ * t2fit_reconstruct_workspace_bytes is plain arithmetic and needs no device. */
+int t2fit_reconstruct_workspace_bytes(int n_vol, const int32_t *lo_size, const int32_t *hi_size, int flags, size_t *bytes);
+int t2fit_reconstruct_dev(const float *const *stacks_dev, const int32_t *lo_size, const double *A1, const int32_t *hi_size,
+                          const double *A2, float *out_dev, int n_vol, int flags, void *workspace_dev, size_t workspace_bytes,
+                          void *stream);
+
 /* Kernel timing for benchmarks (no reference counterpart).  With timing enabled (t2fit_set_timing(1)) every
  * t2fit_volume_dev call of this thread records HIP events around its fit kernel on the launch stream.
  * t2fit_kernel_ms(k): duration in milliseconds of the fit kernel launched k timed calls ago (0 = the most recent;
