@@ -23,10 +23,11 @@
 #include "t2fit_config.h"
 #include "t2fit_context.h"
 #include "t2fit_error.h"
+#include "t2fit_support.h"
 
 namespace {
 
-constexpr int kBlock = 256;
+using t2fit::kBlock;
 constexpr int kMaxIntervalReplicas = 512;  // R values of 64 voxels staged in LDS: 512 x 256 B = 128 KiB of the CU's 160 KiB
 
 // ---- the replica stream -----------------------------------------------------------------------------------------------
@@ -323,9 +324,8 @@ __global__ __launch_bounds__(kBlock) void boot_background_final_kernel(const dou
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
+using t2fit::aligned16;
 using t2fit::fail;
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // -DT2FIT_BOOT_PHASES (a diagnostic build, never the product): host-clock time of the phases of a bootstrap call on stderr
 #ifdef T2FIT_BOOT_PHASES

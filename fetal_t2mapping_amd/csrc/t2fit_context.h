@@ -1,5 +1,5 @@
 // t2fit_context.h -- the host seam's long-lived state ("t2fit_create/destroy for a context holding
-// streams ... and pinned staging").  Defined inline throughout: t2fit_kernels.hip owns the contexts, t2fit_boot.hip
+// streams ... and pinned staging").  Defined inline throughout: t2fit_host.hip owns the contexts, t2fit_boot.hip
 // borrows their streams.
 //
 // A numpy-in / numpy-out fit of one volume is three transfers around one kernel: pageable host memory -> HBM,

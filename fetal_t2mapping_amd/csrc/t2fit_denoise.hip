@@ -17,10 +17,11 @@
 #include <string>
 
 #include "t2fit_error.h"
+#include "t2fit_support.h"
 
 namespace {
 
-constexpr int kBlock = 256;
+using t2fit::align_up, t2fit::kBlock;
 constexpr int kWaves = kBlock / 64;
 // A workgroup owns a tile of kTZ x kTY x kTX voxels (x innermost; 2-D: 1 x 32 x 64, 3-D: 4 x 8 x 64), 512 quads of four
 // consecutive x: two per thread.  `out` of the tile and of its upper halo (the points x + e_a) is staged in LDS; the
@@ -406,8 +407,6 @@ __global__ __launch_bounds__(kBlock) void tv_finish_kernel(const TvArgs a, const
   }
 }
 
-size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
-
 struct TvPlan {
   int64_t n_problems, n_problem, n_total, tiles_per_problem, n_tiles;
   int pnz, tiles_x, tiles_y;
@@ -442,9 +441,9 @@ int tv_plan(const char* who, const t2fit_tv_params* p, int n_vol, int nz, int ny
   if (plan->tiles_per_problem > INT32_MAX || plan->n_tiles > INT32_MAX)
     return t2fit::fail(T2FIT_E_INVALID, w + ": the stack has more than 2^31-1 tiles (the launch index is 32-bit)");
   plan->elem = p->precision == T2FIT_PREC_F32 ? 4 : 8;
-  plan->field_bytes = align_up((size_t)p->dims * (size_t)n_total * plan->elem);
-  plan->partial_bytes = align_up((size_t)plan->n_tiles * 16);
-  plan->state_bytes = align_up((size_t)plan->n_problems * sizeof(TvState));
+  plan->field_bytes = align_up((size_t)p->dims * (size_t)n_total * plan->elem, kAlign);
+  plan->partial_bytes = align_up((size_t)plan->n_tiles * 16, kAlign);
+  plan->state_bytes = align_up((size_t)plan->n_problems * sizeof(TvState), kAlign);
   plan->total = 2 * plan->field_bytes + plan->partial_bytes + plan->state_bytes;
   return T2FIT_OK;
 }

@@ -1,5 +1,6 @@
 // t2fit_error.h -- error plumbing shared by the translation units of libt2fit_hip.so: the message
-// t2fit_last_error() returns is one thread-local string (owned by t2fit_kernels.hip) whichever unit failed.
+// t2fit_last_error() returns is one thread-local string whichever unit failed.  The string and the other basics of the
+// library (ABI version, default configuration, device count) live in t2fit_host.hip.
 #ifndef T2FIT_ERROR_H
 #define T2FIT_ERROR_H
 
@@ -11,7 +12,7 @@
 
 namespace t2fit {
 
-// records `msg` as the calling thread's last error and returns `code` (defined in t2fit_kernels.hip)
+// records `msg` as the calling thread's last error and returns `code` (defined in t2fit_host.hip)
 int fail(int code, const std::string& msg);
 
 }  // namespace t2fit

@@ -5,6 +5,10 @@
 // host-side lane simulator that tests/ uses to check solver logic where no GPU is present.  The
 // simulator is test infrastructure; the product library contains device code only.
 //
+// Rule: of the library's translation units, t2fit_kernels.hip alone includes the lane headers (this file,
+// t2fit_lbfgsb.h, t2fit_lm.h, t2fit_loglin.h, t2fit_dispatch.h).  The i0e tables below are device variables defined in
+// a header: a second unit that included it would define them again.
+//
 // Reference formulas: run_t2mapping.py:129-177 (models/objectives), utils/t2map_utils.py:62-89
 // (residual map).  T2, TE in milliseconds.
 #pragma once
@@ -15,6 +19,7 @@
 #include <type_traits>
 
 #include "../../include/t2fit.h"
+#include "t2fit_diag.h"
 
 #if defined(__HIPCC__)
 #define T2_HD __host__ __device__ __forceinline__
@@ -258,7 +263,9 @@ template <int J, int JN, class F> T2_HD void static_for(F&& f) {
 // operand of the recurrence's add -- and the recurrence is a real loop.  (Round 2 had them as literals in fully
 // unrolled code: every coefficient was re-materialised by two moves per use and the Rician-likelihood kernel for
 // eight echoes was 138 KB of instructions, twice the instruction cache two CUs share.)  Device side the tables are
-// __constant__ and NOT const, so the compiler cannot fold the loads back into literals.
+// __constant__ and NOT const, so the compiler cannot fold the loads back into literals.  They keep external linkage
+// although only t2fit_kernels.hip may include this header (see the rule at the top): with internal linkage the
+// compiler emits other instruction streams for the 22 Rician-likelihood kernels (compared symbol by symbol).
 #if defined(__HIPCC__)
 #define T2_TABLE __device__ __constant__
 #else
@@ -569,9 +576,7 @@ struct ObjCtx {
   double* trace = nullptr;  // optional: (k, T2, sigma, f) after each iteration, 4 doubles each
   int trace_cap = 0;
   int* trace_n = nullptr;
-#if defined(T2_PHASE_STAMPS)
-  unsigned long long* diag = nullptr;  // diagnostic build: this wave's block counters (t2fit_lbfgsb.h T2_BLK_END)
-#endif
+  T2_DIAG_COUNTERS  // diagnostic build (t2fit_diag.h): this wave's block counters
   T2_HD float sample(int i) const { return y[i]; }
 };
 

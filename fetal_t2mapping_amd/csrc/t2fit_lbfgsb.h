@@ -37,26 +37,6 @@
 
 #include "t2fit_lane.h"
 
-// Diagnostic build (-DT2_PHASE_STAMPS) only: wave-level cost of each block of the lane solver.  T2_BLK_END adds, for
-// block i, the shader cycles since the matching T2_BLK_T0, the number of lanes that were active in it and one
-// entry to three counters of the wave's own LDS block (c.diag); the kernel adds them up over the grid at exit.
-#if defined(T2_PHASE_STAMPS) && defined(__HIP_DEVICE_COMPILE__)
-#define T2_BLK_T0(name) const unsigned long long name = __builtin_amdgcn_s_memtime();
-#define T2_BLK_END(c, i, t0) t2_blk_end((c).diag, i, t0);
-__device__ __forceinline__ void t2_blk_end(unsigned long long* dg, int i, unsigned long long t0) {
-  const unsigned long long dt = __builtin_amdgcn_s_memtime() - t0;
-  const unsigned long long ex = __ballot(true);
-  if ((int)(threadIdx.x & 63) == __ffsll((long long)ex) - 1) {
-    dg[3 * i] += dt;
-    dg[3 * i + 1] += (unsigned long long)__popcll(ex);
-    dg[3 * i + 2] += 1ull;
-  }
-}
-#else
-#define T2_BLK_T0(name)
-#define T2_BLK_END(c, i, t0)
-#endif
-
 namespace t2fit {
 
 // ---- objective with numpy's summation order --------------------------------------------------
@@ -421,9 +401,7 @@ struct Lbfgsb {
     if constexpr (NTE > 0) return ys[i];
     else return c.sample(i);
   }
-#if defined(T2_PHASE_STAMPS)
-  unsigned long long* diag = nullptr;  // diagnostic build: the wave's block counters, for the const helpers
-#endif
+  T2_DIAG_COUNTERS  // diagnostic build (t2fit_diag.h): the wave's block counters, for the const helpers
 #if !defined(__HIPCC__)
   int n_reset = 0;  // host simulator only (debugging aid): how often the correction memory was dropped
 #define T2_COUNT_RESET() ++n_reset

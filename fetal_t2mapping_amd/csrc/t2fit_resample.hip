@@ -24,10 +24,11 @@
 #include <string>
 
 #include "t2fit_error.h"
+#include "t2fit_support.h"
 
 namespace {
 
-constexpr int kBlock = 256;
+using t2fit::align_up, t2fit::ceil_div, t2fit::kBlock;
 constexpr int kPerThread = 2;
 constexpr int kBrick = kBlock * kPerThread;  // voxels of a workgroup's output brick
 constexpr size_t kAlign = 256;
@@ -238,8 +239,6 @@ __global__ __launch_bounds__(kBlock) void reconstruct_kernel(const ReconArgs a) 
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------
-size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
-
 bool finite12(const double* A) {
   for (int i = 0; i < 12; ++i)
     if (!std::isfinite(A[i])) return false;
@@ -253,8 +252,6 @@ int64_t count_voxels(int n_vol, int nz, int ny, int nx) {
   if (slabs > ((int64_t)1 << 40) / plane) return -1;
   return slabs * plane;
 }
-
-int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // the output axis whose step moves the source's x index most (ties: the lower axis)
 int lane_axis(const double* A) {
@@ -332,7 +329,7 @@ int recon_plan(const std::string& w, int n_vol, const int32_t* lo_size, const in
     plan->n_hi[s] = count_voxels(n_vol, hi_size[3 * s], hi_size[3 * s + 1], hi_size[3 * s + 2]);
     if (plan->n_lo[s] < 0 || plan->n_hi[s] < 0)
       return t2fit::fail(T2FIT_E_INVALID, w + ": n_vol and the sizes must all be >= 1 and a stack at most 2^40 elements");
-    plan->h_bytes[s] = align_up((size_t)plan->n_hi[s] * 4);
+    plan->h_bytes[s] = align_up((size_t)plan->n_hi[s] * 4, kAlign);
   }
   plan->chain_total = plan->h_bytes[1] + plan->h_bytes[2] + 2 * plan->h_bytes[0];
   return T2FIT_OK;

@@ -18,10 +18,11 @@
 #include <vector>
 
 #include "t2fit_error.h"
+#include "t2fit_support.h"
 
 namespace {
 
-constexpr int kBlock = 256;
+using t2fit::kBlock;
 constexpr int kWaves = kBlock / 64;
 constexpr int kMaxRoiLabels = 256;  // one 8-bit digit: the classes 1..256 are the keys 0..255 of the counting sort
 
@@ -413,47 +414,10 @@ __global__ __launch_bounds__(kBlock) void roi_median_kernel(const float* __restr
   if (tid == 0) median_out[l] = 0.5 * ((double)roi_key_float(prefix[0]) + (double)roi_key_float(prefix[1]));
 }
 
-// ---- scratch buffers --------------------------------------------------------------------------------------------------
-// The erosion's second buffer and the sort's tables and segments are kept between calls: one buffer per (device, stream,
-// use), grown on demand.  Launches on one stream run one after the other, so they may share it; launches on different
-// streams may overlap and must not.  Buffers live as long as the process.
-struct Scratch { int device; hipStream_t stream; int use; char* p; size_t bytes; };
-std::mutex g_scratch_mutex;
-std::vector<Scratch> g_scratch;
-
-hipError_t scratch_get(hipStream_t st, int use, size_t bytes, char** out) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  std::lock_guard<std::mutex> g(g_scratch_mutex);
-  Scratch* r = nullptr;
-  for (Scratch& c : g_scratch)
-    if (c.device == dev && c.stream == st && c.use == use) r = &c;
-  if (!r) {
-    g_scratch.push_back(Scratch{dev, st, use, nullptr, 0});
-    r = &g_scratch.back();
-  }
-  if (r->bytes < bytes) {
-    if (r->p) {  // (a kernel queued earlier on this stream may still be using it)
-      if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-      (void)hipFree(r->p);
-      r->p = nullptr;
-      r->bytes = 0;
-    }
-    if ((e = hipMalloc((void**)&r->p, bytes)) != hipSuccess) return e;
-    r->bytes = bytes;
-  }
-  *out = r->p;
-  return hipSuccess;
-}
-
-constexpr int kUseErode = 0, kUseStats = 1;
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-size_t round16(size_t b) { return (b + 15u) & ~(size_t)15u; }
-
-using t2fit::fail;
+// ---- host side ----------------------------------------------------------------------------------------------------------
+// (the erosion's second buffer and the sort's tables and segments are kept between calls: the scratch cache of
+// t2fit_support.h)
+using namespace t2fit;
 
 }  // namespace
 
@@ -482,7 +446,7 @@ int t2fit_roi_erode_dev(const int32_t* label_dev, const int32_t* tissue_dev, int
   int32_t* tmp = nullptr;
   if (iterations > 1) {
     char* p = nullptr;
-    T2_HIP(scratch_get(st, kUseErode, (size_t)n_vox * sizeof(int32_t), &p));
+    T2_HIP(scratch_get(st, kScratchRoiErode, (size_t)n_vox * sizeof(int32_t), &p));
     tmp = reinterpret_cast<int32_t*>(p);
   }
   ErodeArgs a{};
@@ -521,10 +485,10 @@ int t2fit_roi_stats_dev(const float* map_dev, const int32_t* roi_dev, int64_t n_
   span = span < 8192 ? 8192 : (span + 63) / 64 * 64;
   const unsigned n_units = (unsigned)((n_vox + span - 1) / span);
   const unsigned n_blocks = (n_units + kWaves - 1) / kWaves;
-  const size_t part_b = round16((size_t)n_labels * n_units * sizeof(unsigned));
-  const size_t len_b = round16((size_t)(kMaxRoiLabels + 1) * sizeof(unsigned));
+  const size_t part_b = align_up((size_t)n_labels * n_units * sizeof(unsigned), 16);
+  const size_t len_b = align_up((size_t)(kMaxRoiLabels + 1) * sizeof(unsigned), 16);
   char* base = nullptr;
-  T2_HIP(scratch_get(st, kUseStats, 2 * part_b + 2 * len_b + (size_t)n_vox * sizeof(float), &base));
+  T2_HIP(scratch_get(st, kScratchRoiStats, 2 * part_b + 2 * len_b + (size_t)n_vox * sizeof(float), &base));
   unsigned* part_valid = reinterpret_cast<unsigned*>(base);
   unsigned* part_all = reinterpret_cast<unsigned*>(base + part_b);
   unsigned* seg_len = reinterpret_cast<unsigned*>(base + 2 * part_b);

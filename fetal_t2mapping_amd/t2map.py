@@ -154,9 +154,8 @@ def union_mask_dev(masks):
     idx = torch.empty(n, dtype=torch.int64, device=masks.device)
     cnt = torch.zeros(1, dtype=torch.int64, device=masks.device)
     with torch.cuda.device(masks.device):
-        st = torch.cuda.current_stream().cuda_stream
         check(lib.t2fit_union_mask_dev(masks.data_ptr(), masks.shape[0], n, mask.data_ptr(), idx.data_ptr(),
-                                       cnt.data_ptr(), C.c_void_p(st)))
+                                       cnt.data_ptr(), _current_stream()))
     return mask, idx, cnt
 
 
@@ -179,7 +178,7 @@ def label_stats(map_, label, n_labels: int, device: int = 0):
     cnt = torch.empty(n_labels, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         check(lib.t2fit_label_stats_dev(m.data_ptr(), lab.data_ptr(), m.numel(), int(n_labels), mean.data_ptr(),
-                                        std.data_ptr(), cnt.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                        std.data_ptr(), cnt.data_ptr(), _current_stream()))
     return mean.cpu().numpy(), std.cpu().numpy(), cnt.cpu().numpy()
 
 
@@ -285,7 +284,7 @@ def roi_erode(label, tissue=None, tissue_value=None, *, labels=None, connectivit
     nz, ny, nx = (int(v) for v in lab.shape)
     out = torch.empty_like(lab)
     with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        st = _current_stream()
         if n <= ROI_MAX_LABELS:
             check(lib.t2fit_roi_erode_dev(lab.data_ptr(), tis.data_ptr() if tis is not None else None,
                                           tv if tis is not None else 0, nz, ny, nx, n, int(connectivity), int(iterations),
@@ -329,7 +328,7 @@ def roi_stats(map_, roi, n_labels: int, *, median: bool = True, device: int = 0)
     cnt = torch.empty(n_labels, dtype=torch.int64, device=dev)
     val = torch.empty(n_labels, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        st = _current_stream()
         for lo in range(0, n_labels, ROI_MAX_LABELS):
             k = min(ROI_MAX_LABELS, n_labels - lo)
             rc = r if n_labels <= ROI_MAX_LABELS else torch.where((r > lo) & (r <= lo + k), r - lo, torch.zeros_like(r)).contiguous()
@@ -461,10 +460,9 @@ def fit_volume(echoes, mask, TEeffs, fit, fit_params, prior=True, norm=False, *,
                 raise ValueError(f"out.{name} is required")
             setattr(maps, name, None if t is None else t.data_ptr())
         with torch.cuda.device(dev):
-            st = torch.cuda.current_stream().cuda_stream
             check(lib.t2fit_volume_dev(C.byref(cfg), echoes.data_ptr(), lay,
                                        None if mask is None else mask.data_ptr(), n, C.byref(maps),
-                                       C.c_void_p(st)))
+                                       _current_stream()))
         return out
     e = np.ascontiguousarray(echoes, dtype=np.float32)
     m = None
@@ -621,9 +619,8 @@ def compute_residuals(reshaped_t2w, TEeffs, fit, norm, k_map, t2_map, sigma_map,
     sg = torch.from_numpy(np.ascontiguousarray(sigma_map, np.float32).reshape(-1)).to(dev)
     res = torch.empty(n, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        st = torch.cuda.current_stream().cuda_stream
         check(lib.t2fit_residuals_dev(C.byref(cfg), e.data_ptr(), _abi.LAYOUT_VOXEL_MAJOR, sel.data_ptr(), n,
-                                      t2.data_ptr(), k.data_ptr(), sg.data_ptr(), res.data_ptr(), C.c_void_p(st)))
+                                      t2.data_ptr(), k.data_ptr(), sg.data_ptr(), res.data_ptr(), _current_stream()))
     out = np.asarray(res_map, dtype=np.float32).reshape(-1).copy()
     r = res.cpu().numpy()
     mi = np.asarray(mask_indices, dtype=np.int64)
@@ -693,14 +690,32 @@ def _mask_dev(mask, dev, n):
     return m
 
 
-def _boot_lib():
-    """The library, with the bootstrap entry points (additive symbols of ABI 5: looked up, not assumed)."""
+_BOOT_SYMBOLS, _TV_SYMBOLS, _RECON_SYMBOLS = _abi.ADDITIVE[0:3], _abi.ADDITIVE[3:6], _abi.ADDITIVE[6:9]
+
+
+def _require(*symbols):
+    """The library, with these entry points (additive symbols of ABI 5: looked up, not assumed)."""
     lib = require_gpu()
-    missing = [name for name in _abi.ADDITIVE if "boot" in name and not hasattr(lib, name)]
+    missing = [name for name in symbols if not hasattr(lib, name)]
     if missing:
         raise RuntimeError(f"this build of libt2fit_hip.so lacks {', '.join(missing)}: rebuild it "
                            "(python -m fetal_t2mapping_amd.build)")
     return lib
+
+
+def _current_stream():
+    """The current device's current torch stream, as the C ABI takes one."""
+    import torch
+
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _workspace(nbytes, dev):
+    """A device workspace of nbytes for the library: the tensor that owns it and the pointer, 256-byte aligned."""
+    import torch
+
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+    return ws, (ws.data_ptr() + 255) // 256 * 256
 
 
 def _noise_kind(noise):
@@ -716,7 +731,7 @@ def estimate_background_sigma(echoes, mask, *, layout="te_major", device=0):
     Returns ``(sigma, M)``; a mask that covers everything raises ValueError."""
     import torch
 
-    lib = _boot_lib()
+    lib = _require(*_BOOT_SYMBOLS)
     if mask is None:
         raise ValueError("estimate_background_sigma needs a mask: the noise is measured outside it")
     n_te = int(echoes.shape[0] if layout in ("te_major", _abi.LAYOUT_TE_MAJOR) else echoes.shape[-1])
@@ -728,19 +743,8 @@ def estimate_background_sigma(echoes, mask, *, layout="te_major", device=0):
     sigma, count = C.c_double(0.0), C.c_int64(0)
     with torch.cuda.device(dev):
         check(lib.t2fit_boot_background_dev(e.data_ptr(), lay, m.data_ptr(), n_te, n, C.byref(sigma), C.byref(count),
-                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                            _current_stream()))
     return float(sigma.value), int(count.value)
-
-
-def _tv_lib():
-    """The library, with the denoiser's entry points (additive symbols of ABI 5: looked up, not assumed)."""
-    lib = require_gpu()
-    missing = [name for name in ("t2fit_tv_params_default", "t2fit_tv_workspace_bytes", "t2fit_tv_denoise_dev")
-               if not hasattr(lib, name)]
-    if missing:
-        raise RuntimeError(f"this build of libt2fit_hip.so lacks {', '.join(missing)}: rebuild it "
-                           "(python -m fetal_t2mapping_amd.build)")
-    return lib
 
 
 def tv_params(weight=0.1, eps=2e-4, max_iter=200, dims=2, precision="f32"):
@@ -767,7 +771,7 @@ def denoise_tv(echoes, weight=0.1, *, eps=2e-4, max_iter=200, dims=2, precision=
     :mod:`fetal_t2mapping_amd._tv` states the same loop in numpy."""
     import torch
 
-    lib = _tv_lib()
+    lib = _require(*_TV_SYMBOLS)
     if layout in ("voxel_major", _abi.LAYOUT_VOXEL_MAJOR):
         raise ValueError("denoise_tv takes the te-major stack (nTE, Z, Y, X): a slice must be contiguous.  Permute a "
                          "voxel-major (Z, Y, X, nTE) stack first: np.moveaxis(echoes, -1, 0) or echoes.permute(3, 0, 1, 2)")
@@ -802,9 +806,8 @@ def denoise_tv(echoes, weight=0.1, *, eps=2e-4, max_iter=200, dims=2, precision=
         while group > 1 and need.value > budget:
             group = (group + 1) // 2
             check(lib.t2fit_tv_workspace_bytes(C.byref(par), group, nz, ny, nx, C.byref(need)))
-        ws = torch.empty(need.value + 256, dtype=torch.uint8, device=dev)
-        ws_ptr = (ws.data_ptr() + 255) // 256 * 256
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        ws, ws_ptr = _workspace(need.value, dev)
+        stream = _current_stream()
         n_v = nz * ny * nx
         for v0 in range(0, n_vol, group):
             g = min(group, n_vol - v0)
@@ -821,17 +824,6 @@ def denoise_tv(echoes, weight=0.1, *, eps=2e-4, max_iter=200, dims=2, precision=
     if not is_t:
         info = {k: v.cpu().numpy() for k, v in info.items()}
     return res, info
-
-
-def _resample_lib():
-    """The library, with the reconstruction's entry points (additive symbols of ABI 5: looked up, not assumed)."""
-    lib = require_gpu()
-    missing = [name for name in ("t2fit_resample_dev", "t2fit_reconstruct_workspace_bytes", "t2fit_reconstruct_dev")
-               if not hasattr(lib, name)]
-    if missing:
-        raise RuntimeError(f"this build of libt2fit_hip.so lacks {', '.join(missing)}: rebuild it "
-                           "(python -m fetal_t2mapping_amd.build)")
-    return lib
 
 
 def _geometry_header(g):
@@ -856,7 +848,7 @@ def resample_volume(vol, geom, *, res=None, like=None, transform=None, interp="l
 
     from . import _resample
 
-    lib = _resample_lib()
+    lib = _require(*_RECON_SYMBOLS)
     if interp not in _abi.INTERPS:
         raise ValueError(f"interp must be 'linear' or 'nearest', got {interp!r}")
     if (res is None) == (like is None):
@@ -886,7 +878,7 @@ def resample_volume(vol, geom, *, res=None, like=None, transform=None, interp="l
         check(lib.t2fit_resample_dev(src.data_ptr(), _abi.RESAMPLE_I32 if as_int else _abi.RESAMPLE_F32, *shape[-3:],
                                      A.ctypes.data_as(C.POINTER(C.c_double)), out.data_ptr(), oz, oy, ox, n_vol,
                                      _abi.INTERPS[interp], float(default), _abi.RESAMPLE_INTEGER_CAST if integer_cast else 0,
-                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                     _current_stream()))
         src.record_stream(torch.cuda.current_stream())
     return (out if is_t else out.cpu().numpy()), dst_geom
 
@@ -910,7 +902,7 @@ def reconstruct_stacks(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, i
 
     from . import _resample
 
-    lib = _resample_lib()
+    lib = _require(*_RECON_SYMBOLS)
     if form not in RECON_FORMS:
         raise ValueError(f"form must be one of {RECON_FORMS}, got {form!r}")
     missing = [o for o in _resample.ORIENTATIONS if o not in stacks or o not in geoms]
@@ -936,11 +928,10 @@ def reconstruct_stacks(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, i
     check(lib.t2fit_reconstruct_workspace_bytes(n_vol, lo_size, hi_size, flags, C.byref(need)))
     out = torch.empty((n_vol,) + hi[0].shape, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        ws = torch.empty(need.value + 256, dtype=torch.uint8, device=dev) if need.value else None
-        ws_ptr = (ws.data_ptr() + 255) // 256 * 256 if ws is not None else None
+        ws, ws_ptr = _workspace(need.value, dev) if need.value else (None, None)
         ptrs = (C.c_void_p * 3)(*[t.data_ptr() for t in src])
         check(lib.t2fit_reconstruct_dev(ptrs, lo_size, A1, hi_size, A2, out.data_ptr(), n_vol, flags, ws_ptr, need.value,
-                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                        _current_stream()))
         for t in src + ([ws] if ws is not None else []):
             t.record_stream(torch.cuda.current_stream())
     return out, _geometry_header(hi[0])
@@ -961,7 +952,7 @@ def synth_replica(t2, k, TEeffs, noise_sigma, mask, *, seed, replica, noise="ric
     volume the stream refers to (a slab ``[z0:z1]`` with ``voxel_offset = z0 * Y * X`` equals those rows of the whole)."""
     import torch
 
-    lib = _boot_lib()
+    lib = _require(*_BOOT_SYMBOLS)
     cfg = _boot_config(TEeffs)
     spatial = tuple(t2.shape)
     n = int(np.prod(spatial)) if len(spatial) else 1
@@ -974,7 +965,7 @@ def synth_replica(t2, k, TEeffs, noise_sigma, mask, *, seed, replica, noise="ric
         check(lib.t2fit_boot_synth_dev(C.byref(cfg), t2_d.data_ptr(), k_d.data_ptr(), scalar,
                                        None if s_d is None else s_d.data_ptr(), None if m is None else m.data_ptr(), n,
                                        int(voxel_offset), int(seed) & (2 ** 64 - 1), int(replica), _noise_kind(noise),
-                                       out.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                       out.data_ptr(), _current_stream()))
     return out
 
 
@@ -996,7 +987,7 @@ def bootstrap_volume(echoes, mask, TEeffs, fit, fit_params, prior=True, *, n_rep
     depend on the arguments alone.  Normalised fits (``norm``) are not supported."""
     import torch
 
-    lib = _boot_lib()
+    lib = _require(*_BOOT_SYMBOLS)
     cfg = make_config(fit, fit_params, TEeffs, prior, False, solver, precision, numpy_legacy)
     params = tuple(params)
     if not params or any(p not in _abi.BOOT_PARAMS for p in params):
@@ -1062,7 +1053,7 @@ def bootstrap_volume(echoes, mask, TEeffs, fit, fit_params, prior=True, *, n_rep
                                       None if sg_d is None else sg_d.data_ptr(), scalar, None if s_d is None else s_d.data_ptr(),
                                       kind, m.data_ptr(), n, n_replicas, int(seed) & (2 ** 64 - 1), float(alpha), which,
                                       C.byref(out), 0,
-                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                      _current_stream()))
     host = (lambda t: t) if as_torch else (lambda t: None if t is None else t.cpu().numpy())
     if not as_torch:
         for p in stats:
