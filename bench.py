@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mvoxel/s of the per-voxel T2 fit on a synthetic 256^3 x 8 TE volume.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one pass of the hot path over the volume: the fit kernel over voxels x 8 echoes already resident in HBM
@@ -12,16 +12,22 @@ same share of every region of the mask, contiguous Z-slabs of the ellipsoid do n
 all-gather puts the four maps of the whole volume on every rank.  `--scaling weak`: every rank fits its own 256^3
 volume (round 1's mode).  `value` = dense voxels of the volume(s) / wall time (max over ranks) in Mvoxel/s.
 
+A plain run does what the headline needs and no more: set-up, warm-up, the K timed steps, the dump if asked for, the JSON
+line.  `--full` adds every secondary measurement and check, each after the timed region (the CPU baselines before the
+process opens the GPU), none of them part of `value`: cpu_baseline / cpu_baseline_native, steps_over_two_streams, the
+also_* configurations (`--no-also` and `--cpu-seconds 0` still switch those off one by one) and, for N > 1,
+reserve_cus_ab and gathered_maps_equal_single_gpu_fit.
+
 The JSON line also carries
   roofline     : achieved algorithmic HBM GB/s of the dominant kernel, the fit (45 B/voxel at 8 TE: 4*nTE samples + 1
                  mask byte + the three float32 parameter maps it writes) over its mean launch duration on rank 0,
                  measured with HIP events on the launch stream inside the library, against 8 TB/s; `epilogue` beside it
                  is the streaming pass that follows every fit and writes the fourth map, `res` (49 B/voxel: samples,
                  mask, the three maps read back, res written).  SURVEY.md 8d's 49 B/voxel is the two together.
-  cpu_baseline : the CPU oracle (oracle/t2fit_oracle.py: the reference's scipy L-BFGS-B loop restated) timed on this
+  cpu_baseline : (--full) the CPU oracle (oracle/t2fit_oracle.py: the reference's scipy L-BFGS-B loop restated) timed on this
                  host's cores over a bounded sample of the same masked voxels; on the same basis as `value` (dense
                  voxels/s at the bench volume's mask fill), with the fitted-voxel rates of both beside it.
-  cpu_baseline_native : SURVEY.md 8d (ii): the build's own lane solver (the headers the kernels are compiled from, built
+  cpu_baseline_native : (--full) SURVEY.md 8d (ii): the build's own lane solver (the headers the kernels are compiled from, built
                  by g++ into tests/hostsim: test infrastructure, never loaded by the product) on all host cores.
 
 `--dump-outputs DIR` writes what the LAST timed step left in the buffers a caller of the step reads, the four float32 maps
@@ -68,6 +74,9 @@ VEC_F64_PEAK_TFLOPS = 256 * 4 * 16 * 2 * 2.4e9 / 1e12  # vector (non-MFMA) float
 DUMP_NAMES = ("t2", "k", "sigma", "res")  # rows of the packed output of a step
 DUMP_MAX_VOXELS = 1 << 21  # four float32 maps of 2^21 voxels: 32 MiB per dump
 DUMP_SEED = 20250103
+# fields of the JSON line that only a --full run has (each needs runs of its own beside the timed steps)
+FULL_ONLY_KEYS = ("cpu_baseline", "cpu_baseline_native", "steps_over_two_streams", "reserve_cus_ab", "also_rician", "also_noprior",
+                  "also", "also_lm_f64", "also_loglin")
 
 
 def dump_index(n):
@@ -132,8 +141,12 @@ def parse():
     p.add_argument("--precision", default="f64", choices=["f64", "f32"])
     p.add_argument("--no-prior", action="store_true")
     p.add_argument("--no-gather", action="store_true", help="skip the all-gather of the maps (N > 1)")
-    p.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline duration (0 = skip)")
-    p.add_argument("--no-also", action="store_true", help="skip the secondary (converged LM float32) measurement")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also run every secondary measurement and check (CPU baselines, the steps over two "
+                        "streams, the also_* configurations; N > 1: the other --reserve-cus setting and the comparison of the "
+                        "gathered maps with a single-GPU fit).  Off by default: a plain run times the steps and prints the line")
+    p.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: target CPU-baseline duration (0 = skip)")
+    p.add_argument("--no-also", action="store_true", help="--full: skip the secondary solver / configuration measurements")
     p.add_argument("--reserve-cus", type=int, default=0,
                    help="N > 1 with the all-gather: CUs the persistent fit kernel leaves free for RCCL's kernels in the timed "
                         "steps (0 = none, the default).  Whether that pays cannot be measured on one GPU "
@@ -234,7 +247,7 @@ def main():
             raise SystemExit("launch N>1 with: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N")
         a.gpus = world
     cpu = cpu_native = None
-    if world == 1 and a.cpu_seconds > 0:
+    if a.full and world == 1 and a.cpu_seconds > 0:
         # timed BEFORE this process touches the GPU (the worker pool forks); a thin slab of the
         # same synthetic distribution: same TE vector, k/T2/noise ranges and mask shape
         ev, mv, te_c = synth.brain_volume((6, a.shape[1], a.shape[2]), a.n_te, synth.SEED_BASE + 3)
@@ -299,7 +312,7 @@ def main():
     do_gather = world > 1 and not a.no_gather
     pipelined = a.pipeline == "on" or (a.pipeline == "auto" and world > 1)
     n_streams = max(2, a.pipeline_streams) if (pipelined and not do_gather) else 2
-    side_pipeline = world == 1 and not pipelined and a.solver == "lbfgsb" and not a.no_also
+    side_pipeline = a.full and world == 1 and not pipelined and a.solver == "lbfgsb" and not a.no_also
     n_buf = n_streams if pipelined else (2 if (do_gather or side_pipeline) else 1)
     packed = [torch.empty((4, n_vox), dtype=torch.float32, device=dev) for _ in range(n_buf)]
     gathered = [torch.empty((world, 4, n_vox), dtype=torch.float32, device=dev) for _ in range(2)] if do_gather else None
@@ -425,7 +438,7 @@ def main():
         step_no[0] = 0
     # the other reserve-CUs setting, same steps, after the timed region (N > 1 only): reported, never `value`
     reserve_ab = None
-    if can_reserve and a.reserve_cus_ab != reserved and a.reserve_cus_ab >= 0:
+    if a.full and can_reserve and a.reserve_cus_ab != reserved and a.reserve_cus_ab >= 0:
         lib.t2fit_set_reserve_cus(a.reserve_cus_ab)
         step(False)
         drain()
@@ -448,7 +461,7 @@ def main():
     # strong scaling self-check (outside the timed region): the maps every rank now holds for the whole volume are,
     # bit for bit, the maps of a single-GPU fit of that volume (rank 0 fits it alone and compares)
     verified = None
-    if strong and do_gather and rank == 0:
+    if a.full and strong and do_gather and rank == 0:
         e_all, m_all, _ = synth.brain_volume_torch((z, y, x), a.n_te, synth.SEED_BASE + 3, dev)
         alone = torch.empty((4, n_vol), dtype=torch.float32, device=dev)
         ma = _abi.T2FitMaps()
@@ -494,7 +507,7 @@ def main():
                                        / HBM_PEAK_GBS, 6)}
 
     also = also_f64 = also_loglin = also_rician = also_noprior = None
-    if a.solver == "lbfgsb" and a.fit != "rician" and not a.no_also:
+    if a.full and a.solver == "lbfgsb" and a.fit != "rician" and not a.no_also:
         # the reference's other configurations on the same stack, so that a regression there is visible in this line:
         # the Rician-likelihood objective (--rician) and the paper's bounds (--no_prior)
         cfg_r = t2.make_config("rician", t2.fit_table("rician", True), te, prior=not a.no_prior, norm=False, solver="lbfgsb")
@@ -540,7 +553,7 @@ def main():
         part = "one volume" if world == 1 else (f"one volume in {a.partition} shares x{world}" if strong else f"one volume per rank x{world}")
         out = {
             "metric": "Mvoxel/s T2 fit, 256\u00b3\u00d78TE 3-param LM, 1/2/4/8 GPU; % HBM roofline",  # BASELINE.json's metric, verbatim
-            "value": round(value, 3), "unit": "Mvoxel/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "value": round(value, 3), "unit": "Mvoxel/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "full": a.full,
             "ms_per_step": round(ms_per_step, 4),
             "ms_per_step_median": round(float(np.median(step_ms)), 4) if step_ms else None,
             "higher_is_better": True, "scaling": a.scaling, "vs_baseline": None,
@@ -559,7 +572,7 @@ def main():
                        "steps_pipelined_over_two_streams": pipelined,
                        "metric_note": "BASELINE.json words the metric '3-param LM'; the reference's solver is scipy L-BFGS-B "
                                       "(SURVEY.md F1) and `value` is the solver that reproduces the reference's maps; the "
-                                      "converged LM kernel north_star describes is measured in the same run under `also` "
+                                      "converged LM kernel north_star describes is measured by a --full run under `also` "
                                       "(float32) and `also_lm_f64` (the reference's precision)"},
             "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,

@@ -47,9 +47,19 @@ def test_dump_outputs_writes_the_sampled_rows_as_float32(tmp_path, monkeypatch):
         assert np.array_equal(part, maps4[j].numpy()[idx], equal_nan=True)
 
 
+def test_full_is_an_option_that_is_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and (a.gpus, a.steps, a.warmup) == (1, 4, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full is True and a.cpu_seconds > 0 and not a.no_also  # --full alone runs every secondary measurement
+    assert "cpu_baseline" in bench.FULL_ONLY_KEYS and "also" in bench.FULL_ONLY_KEYS and "value" not in bench.FULL_ONLY_KEYS
+
+
 @pytest.mark.gpu
 def test_bench_dump_is_the_fit_of_the_seeded_volume(tmp_path):
-    """bench.py in a process of its own (3 timed steps, a volume larger than a dump holds), then the same seeded volume
+    """A plain bench.py run in a process of its own (3 timed steps, a volume larger than a dump holds), then the same seeded volume
     through fit_volume here: the dumped maps are that fit's maps at the dump's voxels, bit for bit."""
     import torch
 
@@ -60,11 +70,14 @@ def test_bench_dump_is_the_fit_of_the_seeded_volume(tmp_path):
     n = shape[0] * shape[1] * shape[2]
     out = tmp_path / "dump"
     run = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--shape", *map(str, shape), "--cpu-seconds", "0", "--no-also", "--dump-outputs", str(out)],
+                          "--shape", *map(str, shape), "--dump-outputs", str(out)],
                          capture_output=True, text=True, cwd=str(tmp_path))
     assert run.returncode == 0, run.stderr[-2000:]
     line = json.loads([ln for ln in run.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["steps"] == 3 and line["outputs_dumped"]["voxels"] == n
+    # a plain run: the headline fields, nothing of what --full measures or checks besides
+    assert line["full"] is False and line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "Mvoxel/s"
+    assert not set(line) & set(bench.FULL_ONLY_KEYS) and line["gathered_maps_equal_single_gpu_fit"] is None
     assert line["outputs_dumped"]["voxels_written"] == bench.DUMP_MAX_VOXELS < n
     echoes, mask, te = synth.brain_volume_torch(shape, 8, synth.SEED_BASE + 3, torch.device("cuda", 0))
     maps = t2.fit_volume(echoes.reshape((8,) + shape), mask, te, "gaussian_rician", t2.fit_table("gaussian_rician", True))

@@ -1248,8 +1248,8 @@ def test_cli_shared_volume_path_on_device(t2, tmp_path):
 def test_bench_strong_scaling_control_flow_two_ranks_one_gpu(t2, partition):
     """bench.py's N > 1 path rehearsed on the one GPU of this box (two ranks on cuda:0, gather staged through gloo;
     the timing means nothing): one volume cut in two shares, each rank fits its share, all-gather, back into voxel
-    order -- and bench.py's own check that the result equals a single-GPU fit of the whole volume bit for bit.  The
-    ragged size (a volume that is not a whole number of chunks) exercises the padding."""
+    order -- and bench.py's own check (a --full run makes it) that the result equals a single-GPU fit of the whole volume
+    bit for bit.  The ragged size (a volume that is not a whole number of chunks) exercises the padding."""
     import json
     import socket
     import subprocess
@@ -1263,13 +1263,13 @@ def test_bench_strong_scaling_control_flow_two_ranks_one_gpu(t2, partition):
     env = dict(os.environ, T2FIT_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--shape", "37", "96", "100", "--no-also", "--cpu-seconds", "0", "--partition", partition]
+           "--shape", "37", "96", "100", "--full", "--no-also", "--cpu-seconds", "0", "--partition", partition]
     out = subprocess.run(cmd, check=True, capture_output=True, text=True, env=env, timeout=600, cwd=repo)
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["gathered_maps_equal_single_gpu_fit"] is True
     assert d["config"]["voxels_total"] == 37 * 96 * 100 and d["value"] > 0 and d["fitted_value"] < d["value"]
-    # the all-gather steps are timed with no CU held back for RCCL and, after the timed region, with 8 held back
+    # the all-gather steps are timed with no CU held back for RCCL and, after the timed region of a --full run, with 8 held back
     assert d["config"]["cus_left_free_for_rccl"] == 0 and d["reserve_cus_ab"]["cus_left_free_for_rccl"] == 8
     assert d["reserve_cus_ab"]["value"] > 0
 

@@ -1,5 +1,5 @@
-"""Turn the per-kernel PMC summaries of a profile round (gpurun_out/pmc_<tag>_{lbfgsb,lmf32,loglin}.txt, written by
-tools/profile_r02.sh) into profiles/traffic.json (HBM bytes per launch) and profiles/instr_mix.json (VALU instruction
+"""Turn the per-kernel PMC summaries of a profile round ($T2FIT_PROFILE_OUT/pmc_<tag>_{lbfgsb,lmf32,loglin}.txt, by
+default under profile_out/, written by tools/profile_r02.sh) into profiles/traffic.json (HBM bytes per launch) and profiles/instr_mix.json (VALU instruction
 counts per launch), which bench.py reads for `roofline.traffic` and the `alu` view.
 
     python tools/make_profile_json.py <tag>
@@ -9,6 +9,7 @@ import os
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("T2FIT_PROFILE_OUT") or os.path.join(REPO, "profile_out")  # where the profile scripts write
 tag = sys.argv[1]
 KEYS = {"lbfgsb": "gaussian_rician/lbfgsb/f64/256x256x256x8", "rician": "rician/lbfgsb/f64/180x256x256x6", "lmf32": "gaussian_rician/lm/f32/256x256x256x8",
         "lmf64": "gaussian_rician/lm/f64/256x256x256x8", "loglin": "gaussian/loglin/f64/256x256x256x8"}
@@ -16,7 +17,7 @@ KEYS = {"lbfgsb": "gaussian_rician/lbfgsb/f64/256x256x256x8", "rician": "rician/
 
 def read(name):
     out = {}
-    for line in open(os.path.join(REPO, "gpurun_out", f"pmc_{tag}_{name}.txt")):
+    for line in open(os.path.join(OUT, f"pmc_{tag}_{name}.txt")):
         parts = line.split()
         c = [p for p in parts if p.startswith(("SQ", "FETCH", "WRITE", "TCC"))]
         m = [p for p in parts if p.startswith("mean=")]
@@ -39,7 +40,7 @@ traffic = {"_comment": "HBM bytes per launch of the dominant kernel, 1 x MI355X,
 mix = {"_comment": "VALU wave-instructions per launch by class (rocprofv3 --pmc, own passes), 256^3 x 8 TE, mask fill 0.44; "
                    "lanes_active = SQ_THREAD_CYCLES_VALU / (64 * SQ_ACTIVE_INST_VALU)."}
 for name, key in KEYS.items():
-    if not os.path.exists(os.path.join(REPO, "gpurun_out", f"pmc_{tag}_{name}.txt")):
+    if not os.path.exists(os.path.join(OUT, f"pmc_{tag}_{name}.txt")):
         continue
     c = read(name)
     if name == "loglin":  # echo planes read 16 B per lane (reported 1/2), the mask 4 B per lane
