@@ -63,6 +63,11 @@ INTERPS = {"linear": INTERP_LINEAR, "nearest": INTERP_NEAREST}
 RESAMPLE_F32, RESAMPLE_I32 = 0, 1
 RESAMPLE_INTEGER_CAST, RECON_CHAIN = 1, 2  # flags bits
 
+MORPH_DILATE, MORPH_ERODE, MORPH_CLOSE, MORPH_OPEN = 0, 1, 2, 3
+MORPH_OPS = {"dilate": MORPH_DILATE, "erode": MORPH_ERODE, "close": MORPH_CLOSE, "open": MORPH_OPEN}
+MORPH_UNBOUNDED = 1  # flags bit
+MORPH_F32, MORPH_I32, MORPH_U8 = 0, 1, 2
+
 # every symbol include/t2fit.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -97,6 +102,14 @@ SYMBOLS = [
                                                     C.POINTER(C.c_size_t)]),
     ("t2fit_reconstruct_dev", C.c_int, [C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_double), _P, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    ("t2fit_morph_workspace_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    ("t2fit_binary_threshold_dev", C.c_int, [_P, C.c_int, C.c_int64, C.c_double, C.c_double, _P, _P]),
+    ("t2fit_binary_morph_dev", C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         _P, C.c_size_t, _P]),
+    ("t2fit_fill_holes_dev", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(C.c_int32), _P]),
+    ("t2fit_seed_labels_dev", C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_size_t,
+                                        _P]),
+    ("t2fit_relabel_dev", C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P]),
     ("t2fit_set_timing", C.c_int, [C.c_int]),
     ("t2fit_set_reserve_cus", C.c_int, [C.c_int]),
     ("t2fit_kernel_ms", C.c_double, [C.c_int]),
@@ -110,7 +123,9 @@ SYMBOLS = [
 # entry points added to ABI 5 after its first release: another build of the same ABI (T2FIT_LIB) may lack them
 ADDITIVE = ("t2fit_boot_background_dev", "t2fit_boot_synth_dev", "t2fit_bootstrap_dev",
             "t2fit_tv_params_default", "t2fit_tv_workspace_bytes", "t2fit_tv_denoise_dev",
-            "t2fit_resample_dev", "t2fit_reconstruct_workspace_bytes", "t2fit_reconstruct_dev")
+            "t2fit_resample_dev", "t2fit_reconstruct_workspace_bytes", "t2fit_reconstruct_dev",
+            "t2fit_morph_workspace_bytes", "t2fit_binary_threshold_dev", "t2fit_binary_morph_dev", "t2fit_fill_holes_dev",
+            "t2fit_seed_labels_dev", "t2fit_relabel_dev")
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

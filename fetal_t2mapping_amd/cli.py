@@ -146,6 +146,41 @@ def _read_masks(sitk, mask_paths, label_path):
     return [], masks, label, None
 
 
+def _read_echoes(sitk, recon_paths):
+    """The echo volumes of one (sub, ses) alone (--build_mask: no mask or label file is read): ``(vols, last image)``."""
+    DECODED["echo"] += len(recon_paths)
+    vols, recon_img = [], None
+    for rp in recon_paths:
+        recon_img = sitk.ReadImage(rp)
+        vols.append(sitk.GetArrayFromImage(recon_img))
+    return vols, recon_img
+
+
+# ---- phantom masks and labels built on the device (--build_mask phantom) -------------------------
+def load_seeds(path):
+    """``--phantom_seeds FILE``: a JSON list of ``[x, y, z]`` voxel indices, one per vial in label order (the `seeds`
+    list of the reference's run_qmri_reconstruction.py)."""
+    import json
+
+    with open(path) as f:
+        seeds = json.load(f)
+    if (not isinstance(seeds, list) or not seeds
+            or not all(isinstance(s, list) and len(s) == 3 and all(isinstance(v, int) for v in s) for s in seeds)):
+        raise ValueError(f"{path}: expected a JSON list of [x, y, z] integer triples")
+    if len(seeds) > 255:
+        raise ValueError(f"{path}: at most 255 seeds fit the uint8 label image")
+    return seeds
+
+
+def build_phantom_subject(vols, seeds, threshold=100, close_radius=15, dilate_radius=10, label_radius=6, device=0):
+    """The masks of every echo volume (build_phantom_masks, utils/qmri_utils.py:591-623) and the vial labels
+    (build_phantom_labels_v2, :868-933) of one (sub, ses) on the device: ``(masks: list of uint8 arrays, label: uint8
+    array)``, what the recon_1mm_mask / recon_1mm_label files would hold."""
+    masks = [t2map.phantom_mask(np.asarray(v, np.float32), threshold, close_radius, dilate_radius, device=device) for v in vols]
+    label = t2map.phantom_labels(np.asarray(vols[0]).shape, seeds, label_radius, device=device)
+    return [m.cpu().numpy() for m in masks], label.cpu().numpy()
+
+
 # ---- metadata / paths --------------------------------------------------------------------------
 def mk_bids_dir(bids_dir, *dirs):
     """utils/dcm_utils.py:189-195 (there: `if not exists: mkdir`; with --gpus N several ranks create the shared
@@ -574,14 +609,17 @@ def _one_block(vols):
 def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field, prior, fast, norm, sim,
                    solver="lbfgsb", precision="f64", device=0, plots=False, plot_seed=None, numpy_legacy=False,
                    roi_specs=(), roi_connectivity=3, roi_erosion=1, bootstrap=0, bootstrap_seed=0, bootstrap_alpha=0.05,
-                   bootstrap_noise="background", denoise=None, reconstruct=None):
+                   bootstrap_noise="background", denoise=None, reconstruct=None, build_mask=None):
     """run_t2mapping.py:333-479 with the voxel loop on the GPU.  ``plots``: also write the reference's
     convergence-study figures (:465-468) under <prj>/ada/convergence_analysis.  ``roi_specs``: (name, tissue) pairs
     of --roi_stats; each adds a per-region table after the maps (save_roi_csvs).  ``bootstrap`` > 0: that many
     replicas of the parametric bootstrap after the maps (save_bootstrap_maps).  ``denoise``: None, or the keyword
     arguments of denoise_subject (--denoise tv): the echoes are denoised after decoding, before the mask and the fit.
     ``reconstruct``: None, or the keyword arguments of recon.reconstruct_subject (--reconstruct): the echoes are not read
-    from recon_1mm but reconstructed in memory from the acquired ax / cor / sag stacks, ahead of the denoiser."""
+    from recon_1mm but reconstructed in memory from the acquired ax / cor / sag stacks, ahead of the denoiser.
+    ``build_mask``: None, or the keyword arguments of build_phantom_subject (--build_mask phantom): the masks of every
+    echo and the vial labels are built on the device from the volumes about to be fitted (after the reconstruction, if
+    any) and used in place of the recon_1mm_mask / recon_1mm_label files."""
     sitk = _sitk()
     tes_s = [x / 1000 for x in TEs]
     metadata = metadata[metadata["EchoTime"].isin(tes_s)]
@@ -596,6 +634,11 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
     if reconstruct is not None and share_volumes:
         raise ValueError("--reconstruct is not run on a volume that is shared by several ranks (each rank holds a part of the "
                          "echoes): give at least as many subjects as ranks, or run on one GPU")
+    if build_mask is not None and share_volumes:
+        raise ValueError("--build_mask is not run on a volume that is shared by several ranks (each rank holds a part of the "
+                         "echoes): give at least as many subjects as ranks, or run on one GPU")
+    if build_mask is not None and not phantom:
+        raise ValueError("--build_mask phantom goes with --in_vitro / --in_vitro_fast")
     mine = set(subjects if (world == 1 or share_volumes) else
                [subjects[i] for i in dist_subjects_of_rank(len(subjects), rank, world)])
     writer = (rank == 0) or not share_volumes
@@ -630,11 +673,17 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
                     from . import recon
 
                     vols, recon_img = recon.reconstruct_subject(sitk, bids_path, sub_md, sub, ses, device=device, **reconstruct)
-                    _, masks, label, _ = _read_masks(sitk, mask_paths, label_path)
+                    if build_mask is not None:
+                        masks, label = build_phantom_subject(vols, device=device, **build_mask)
+                    else:
+                        _, masks, label, _ = _read_masks(sitk, mask_paths, label_path)
                     bad = [tuple(np.asarray(m).shape) for m in masks if tuple(np.asarray(m).shape) != vols[0].shape]
                     if bad:
                         raise ValueError(f"--reconstruct: the mask of {sub}_{ses} has shape {bad[0]}, the reconstructed grid "
                                          f"has {vols[0].shape}: masks must be drawn on the reconstruction that is fitted")
+                elif build_mask is not None:
+                    vols, recon_img = _read_echoes(sitk, recon_paths)
+                    masks, label = build_phantom_subject(vols, device=device, **build_mask)
                 else:
                     vols, masks, label, recon_img = _read_subject(sitk, recon_paths, mask_paths, label_path)
                 keep = (label != 0) if (phantom and fast) else None  # :394-400
@@ -771,6 +820,12 @@ def parse_arguments(argv=None):
     p.add_argument("--recon_transforms", default=None, metavar="DIR",
                    help="rigid transforms <sub>_<ses>_<orientation>.txt of the moving stacks (4 x 4 text, fixed point -> "
                         "moving point); a missing file is the identity")
+    p.add_argument("--build_mask", choices=["phantom"], default=None,
+                   help="build the masks of every echo and the vial labels on the GPU from the volumes about to be fitted "
+                        "(after --reconstruct if given) instead of reading recon_1mm_mask / recon_1mm_label: phantom = the "
+                        "reference's build_phantom_masks and build_phantom_labels_v2; needs --phantom_seeds; off by default")
+    p.add_argument("--phantom_seeds", default=None, metavar="FILE",
+                   help="JSON list of [x, y, z] voxel indices, one per vial in label order")
     p.add_argument("--denoise", choices=["tv"], default=None,
                    help="denoise the echo volumes on the GPU before the fit: tv = TV-Chambolle as scikit-image's "
                         "denoise_tv_chambolle, the reference's run_denoising; off by default")
@@ -793,6 +848,18 @@ def parse_arguments(argv=None):
         if args.recon_transforms is not None and not os.path.isdir(args.recon_transforms):
             p.error(f"--recon_transforms {args.recon_transforms!r} is not a directory")
         args.reconstruct_args = {"fixed": args.recon_fixed, "res": args.recon_res, "transforms_dir": args.recon_transforms}
+    args.build_mask_args = None
+    if args.phantom_seeds is not None and not args.build_mask:
+        p.error("--phantom_seeds has no effect without --build_mask phantom")
+    if args.build_mask:
+        if not (args.in_vitro or args.in_vitro_fast):
+            p.error("--build_mask phantom goes with --in_vitro / --in_vitro_fast")
+        if args.phantom_seeds is None:
+            p.error("--build_mask phantom needs --phantom_seeds FILE (the vial labels are painted at the seeds)")
+        try:
+            args.build_mask_args = {"seeds": load_seeds(args.phantom_seeds)}
+        except (OSError, ValueError) as e:
+            p.error(str(e))
     args.denoise_args = None
     given = [f for f in ("--denoise_weight", "--denoise_dims", "--denoise_eps", "--denoise_iter")
              if any(a == f or a.startswith(f + "=") for a in (argv if argv is not None else sys.argv[1:]))]
@@ -893,7 +960,8 @@ def main(argv=None):
                        roi_specs=args.roi_specs, roi_connectivity=args.roi_connectivity, roi_erosion=args.roi_erosion,
                        bootstrap=args.bootstrap, bootstrap_seed=args.bootstrap_seed, bootstrap_alpha=args.bootstrap_alpha,
                        bootstrap_noise=args.bootstrap_noise, **({"denoise": args.denoise_args} if args.denoise_args else {}),
-                       **({"reconstruct": args.reconstruct_args} if args.reconstruct_args else {}))
+                       **({"reconstruct": args.reconstruct_args} if args.reconstruct_args else {}),
+                       **({"build_mask": args.build_mask_args} if args.build_mask_args else {}))
     finally:
         if world > 1:
             import torch.distributed as dist

@@ -19,7 +19,8 @@ import time
 import numpy as np
 
 from . import _resample, t2map
-from .cli import _sitk, get_img_path, recon_dirname, set_metadata
+from .cli import (_sitk, build_phantom_subject, get_img_path, load_seeds, mask_dirname, phantom_labels_dirname, recon_dirname,
+                  set_metadata)
 
 in_dirname = "anat"
 resamp_dirname = "resamp_1mm"
@@ -149,6 +150,45 @@ def process_recon(metadata, bids_path, *, fixed="ax", res=1.0, transforms_dir=No
     return written
 
 
+def label_file_name(recon_name):
+    """The reference names a label file ``recon_name.replace("T2w", "T2w_labels")``.  A recon_1mm name has no "T2w", which
+    leaves the label under the volume's own name where the fit (``…_recon_1mm_label``) does not look for it; such a name
+    gets the suffix the fit reads."""
+    name = recon_name.replace("T2w", "T2w_labels")
+    return name if name != recon_name else recon_name.replace(recon_dirname, phantom_labels_dirname)
+
+
+def process_phantom_masks(metadata, bids_path, *, seeds=None, fixed="ax", threshold=100, close_radius=15, dilate_radius=10,
+                          label_radius=6, device=0):
+    """``--phantom_masks``: for every reconstructed echo volume under recon_1mm, the phantom mask (build_phantom_masks,
+    utils/qmri_utils.py:591-623) under recon_1mm_mask and, with ``seeds``, the vial labels (build_phantom_labels_v2,
+    :868-933) under recon_1mm_label, uint8, built on the device.  Returns the paths written."""
+    sitk = _sitk()
+    written = []
+
+    def write(arr, like, path):
+        img = sitk.GetImageFromArray(arr)
+        img.SetSpacing(like.GetSpacing()), img.SetOrigin(like.GetOrigin()), img.SetDirection(like.GetDirection())
+        sitk.WriteImage(img, path)
+        written.append(path)
+        print(f"Image saved in : {path}")
+
+    for prj, sub, ses, echoes in echo_groups(metadata):
+        for echotime, rows in echoes:
+            acq = rows[fixed] if fixed in rows else next(iter(rows.values()))
+            recon_path = get_img_path(bids_path, acq, recon_dirname).replace(" ", "")
+            img = sitk.ReadImage(recon_path)
+            masks, label = build_phantom_subject([sitk.GetArrayFromImage(img)], seeds or [[0, 0, 0]], threshold, close_radius,
+                                                 dilate_radius, label_radius, device=device)
+            name = os.path.basename(recon_path)
+            mask_dir = os.path.dirname(get_img_path(bids_path, acq, mask_dirname))
+            write(masks[0], img, os.path.join(mask_dir, name.replace(recon_dirname, recon_dirname + "_mask")))
+            if seeds:
+                label_dir = os.path.dirname(get_img_path(bids_path, acq, phantom_labels_dirname))
+                write(label, img, os.path.join(label_dir, label_file_name(name)))
+    return written
+
+
 def reconstruct_subject(sitk, bids_path, sub_md, sub, ses, *, fixed="ax", res=1.0, transforms_dir=None, integer_cast=None,
                         device=0):
     """cli.py --reconstruct: the echoes of one (sub, ses) (`sub_md`: its metadata rows) reconstructed in memory.  Every
@@ -191,8 +231,24 @@ def parse_arguments(argv=None):
     p.add_argument("--write_resamp", action="store_true", help="also write the 1 mm volume of every stack under resamp_1mm/")
     p.add_argument("--no_denoise", action="store_true",
                    help="skip the TV-Chambolle pass the reference applies to the merged volume (denoising=True)")
+    p.add_argument("--phantom_masks", action="store_true",
+                   help="--in_vitro: after the reconstruction, build the phantom mask of every echo on the GPU and write it "
+                        "under recon_1mm_mask/ (the reference's build_phantom_masks); off by default")
+    p.add_argument("--phantom_seeds", default=None, metavar="FILE",
+                   help="with --phantom_masks: JSON list of [x, y, z] voxel indices, one per vial; the vial labels are written "
+                        "under recon_1mm_label/ (the reference's build_phantom_labels_v2)")
     p.add_argument("--device", type=int, default=0, help="HIP device ordinal")
     args = p.parse_args(argv)
+    if args.phantom_masks and not args.in_vitro:
+        p.error("--phantom_masks goes with --in_vitro")
+    if args.phantom_seeds is not None and not args.phantom_masks:
+        p.error("--phantom_seeds has no effect without --phantom_masks")
+    args.seeds = None
+    if args.phantom_seeds is not None:
+        try:
+            args.seeds = load_seeds(args.phantom_seeds)
+        except (OSError, ValueError) as e:
+            p.error(str(e))
     if not (args.res > 0.0 and np.isfinite(args.res)):
         p.error("--res must be a positive number")
     if args.transforms is not None and not os.path.isdir(args.transforms):
@@ -210,6 +266,8 @@ def main(argv=None):
     metadata = set_metadata(csv_path, args.csv, bool(args.lf))
     process_recon(metadata, bids_path, fixed=args.fixed, res=args.res, transforms_dir=args.transforms,
                   write_resamp=args.write_resamp, denoise=not args.no_denoise, device=args.device)
+    if args.phantom_masks:
+        process_phantom_masks(metadata, bids_path, seeds=args.seeds, fixed=args.fixed, device=args.device)
 
 
 if __name__ == "__main__":

@@ -443,6 +443,86 @@ int t2fit_reconstruct_dev(const float *const *stacks_dev, const int32_t *lo_size
                           const double *A2, float *out_dev, int n_vol, int flags, void *workspace_dev, size_t workspace_bytes,
                           void *stream);
 
+/* ---- Masks and phantom labels: binary morphology, hole filling, seed labels, relabelling ------------------------------
+ * What the reference builds on the host before a fit can start (utils/qmri_utils.py): build_mask (:223-252),
+ * build_phantom_masks (:591-623), build_phantom_labels_v2 (:868-933), build_mask_from_labels (:935-951) and the lookup of
+ * convert_synthseg_to_feta (:976-1009).  Additive to ABI 5: six new symbols (look them up to detect them).
+ * fetal_t2mapping_amd/_morph.py restates every definition in numpy; the device results equal it, and
+ * scipy.ndimage, bit for bit.  Parity with ITK's ball voxelisation is not pinned.
+ *
+ * Volumes are (nz, ny, nx) with x fastest; masks are uint8 (0 / not 0 in, 0 / 1 out).  Inside, a mask is bit-packed in the
+ * workspace, 64 x voxels per word.  A structuring element is its footprint's sizes size[3] = (sz, sy, sx), each odd and
+ * at most 65 (radius 32; the origin is the centre), and a run list of n_runs (1..16900) rows of four int32
+ * (dz, dy, x0, x1): "the offsets (dz, dy, x), x0 <= x <= x1, belong to the element"; several runs per (dz, dy) row are
+ * allowed, every run lies inside the footprint.  `size` and `runs` are HOST pointers.
+ *   dilate  out[v] = OR  over s in S of in[v - s]     a voxel outside the volume reads as border_value
+ *   erode   out[v] = AND over s in S of in[v + s]     (the exact dual: complement, reflected S, complemented border)
+ *   close   `iterations` dilations, then as many erosions;  open: erosions, then dilations  (each with border_value:
+ *           scipy's binary_closing / binary_opening)
+ *   T2FIT_MORPH_UNBOUNDED (close / open, border_value 0): the operation on the unbounded domain -- the volume is extended
+ *           by zeros as far as the element reaches (radius * iterations), what the dilation spills outside is kept for
+ *           the erosion, and the result is cropped: ITK's safe border. */
+#define T2FIT_MORPH_DILATE 0
+#define T2FIT_MORPH_ERODE 1
+#define T2FIT_MORPH_CLOSE 2
+#define T2FIT_MORPH_OPEN 3
+#define T2FIT_MORPH_UNBOUNDED 1 /* flags bit of t2fit_binary_morph_dev */
+#define T2FIT_MORPH_F32 0       /* element types of t2fit_binary_threshold_dev / t2fit_seed_labels_dev */
+#define T2FIT_MORPH_I32 1
+#define T2FIT_MORPH_U8 2
+
+/* Bytes of the workspace the calls below need for an (nz, ny, nx) volume; plain arithmetic, no device.  `reach`: 0, or
+ * for T2FIT_MORPH_UNBOUNDED the largest radius * iterations that will be asked for (0..256).  With up(v) = v rounded up
+ * to 256, P = up(8 (nz + 2 reach)(ny + 2 reach) ceil((nx + 2 reach) / 64)) the bytes of a packed grid:
+ *   up(16 * 16900) [runs] + up(16 * 65 * 65) [element bitmap] + up(16 * 4096) [seeds] + 256 [flags] + 3 P
+ * Refuses a size < 1 and a packed grid of 2^31 words or more. */
+int t2fit_morph_workspace_bytes(int nz, int ny, int nx, int reach, size_t *bytes);
+
+/* out[v] = (lo <= src[v] <= hi) as uint8 0 / 1; src_type T2FIT_MORPH_F32 or T2FIT_MORPH_I32; the comparison is made in
+ * float64 (exact for both), a NaN gives 0; lo = -inf / hi = +inf leave a side open.  n_vox in 1..2^39-1.  Asynchronous on
+ * `stream`; NULL pointers, a bad type or size, a NaN bound are T2FIT_E_INVALID before HIP is touched. */
+int t2fit_binary_threshold_dev(const void *src_dev, int src_type, int64_t n_vox, double lo, double hi, uint8_t *out_dev,
+                               void *stream);
+
+/* op in T2FIT_MORPH_DILATE / ERODE / CLOSE / OPEN on in_dev into out_dev (device uint8 [nz ny nx]; out_dev == in_dev is
+ * allowed: the input is packed before anything is written).  iterations in 1..8.  workspace_dev: at least
+ * t2fit_morph_workspace_bytes bytes, aligned to 256.  The run list is copied to the device and the call returns when it
+ * has been read (it waits for `stream` once, before its kernels are queued); the kernels are asynchronous on `stream`.
+ * Checked before HIP is touched (T2FIT_E_INVALID and a message): NULL in_dev / out_dev / size / runs / workspace_dev, an
+ * unknown op, a size < 1, an even or too large footprint (radius > 32), n_runs outside 1..16900, a run that is empty or
+ * leaves the footprint, iterations outside 1..8, border_value not 0 / 1, undefined flags, T2FIT_MORPH_UNBOUNDED with
+ * dilate / erode or border_value 1, a workspace that is too small or misaligned. */
+int t2fit_binary_morph_dev(int op, const uint8_t *in_dev, uint8_t *out_dev, int nz, int ny, int nx, const int32_t *size,
+                           const int32_t *runs, int n_runs, int iterations, int border_value, int flags, void *workspace_dev,
+                           size_t workspace_bytes, void *stream);
+
+/* out = in plus its holes: the background is flooded from the volume's border through faces (scipy's default structure,
+ * ITK's fullyConnected = false) and the output is the complement of what was reached.  slice_axis = -1: one 3-D problem;
+ * 0, 1, 2: every plane perpendicular to that axis of the (z, y, x) array is its own 2-D problem whose border is the
+ * plane's rim (build_mask: 2, planes of (z, y)).  Tiles of 8 x 8 x 256 voxels are grown to their fixed point on chip and
+ * swept until a sweep changes nothing; the reached set only grows and its fixed point is unique, so the result -- and
+ * the sweep count -- is a function of the input alone and there is no iteration cap.
+ * THIS CALL SYNCHRONISES `stream`: the host reads the sweeps' flags back from pinned memory every four sweeps.  Only the
+ * final unpack is still in flight on return.  *n_sweeps_out (HOST pointer, or NULL): sweeps run, the last of which
+ * changed nothing.  out_dev == in_dev is allowed.  Checked before HIP is touched: NULL in_dev / out_dev / workspace_dev,
+ * a size < 1, slice_axis outside -1..2, a workspace that is too small or misaligned. */
+int t2fit_fill_holes_dev(const uint8_t *in_dev, uint8_t *out_dev, int nz, int ny, int nx, int slice_axis, void *workspace_dev,
+                         size_t workspace_bytes, int32_t *n_sweeps_out, void *stream);
+
+/* out[v] = max over the seeds s of labels[s] * [v - seed_s in S], 0 where no seed reaches: a ball painted at every seed,
+ * merged with a maximum (build_phantom_labels_v2).  seeds: HOST int32 [n_seeds][3] = (x, y, z) indices as the reference
+ * indexes an image (a seed may lie outside the volume; what leaves the volume is clipped); labels: HOST int32 [n_seeds],
+ * >= 0 and <= 255 for a uint8 output; n_seeds in 1..4096.  out_type T2FIT_MORPH_U8 or T2FIT_MORPH_I32.  The seeds and the
+ * element are copied to the workspace and the call returns when they have been read (it waits for `stream` once); the
+ * kernel is asynchronous.  Checked before HIP is touched, as t2fit_binary_morph_dev. */
+int t2fit_seed_labels_dev(const int32_t *seeds, const int32_t *labels, int n_seeds, const int32_t *size, const int32_t *runs,
+                          int n_runs, int nz, int ny, int nx, void *out_dev, int out_type, void *workspace_dev,
+                          size_t workspace_bytes, void *stream);
+
+/* out[v] = lut[in[v]] where 0 <= in[v] < n_lut, else 0 (int32 -> int32, all device pointers; out_dev == in_dev is
+ * allowed).  n_vox in 1..2^39-1.  Asynchronous on `stream`. */
+int t2fit_relabel_dev(const int32_t *in_dev, int64_t n_vox, const int32_t *lut_dev, int n_lut, int32_t *out_dev, void *stream);
+
 /* Kernel timing for benchmarks (no reference counterpart).  With timing enabled (t2fit_set_timing(1)) every
  * t2fit_volume_dev call of this thread records HIP events around its fit kernel on the launch stream.
  * t2fit_kernel_ms(k): duration in milliseconds of the fit kernel launched k timed calls ago (0 = the most recent;
