@@ -33,9 +33,9 @@ extern "C" int hostsim_config_default(t2fit_config* cfg, int model, int low_fiel
   return config_default_impl(cfg, model, low_field);
 }
 
-// rows: (n, nTE) voxel-major float32
+// rows: (n, nTE) voxel-major float32; maps (optional): the epilogue's float32 map values k, T2, sigma, fun per row
 extern "C" int hostsim_fit_rows(const t2fit_config* cfg, const float* rows, int64_t n, double* x,
-                                double* fun, int32_t* nit, uint8_t* status, float* res, float* r2) {
+                                double* fun, int32_t* nit, uint8_t* status, float* res, float* r2, float* maps) {
   const char* why;
   int rc = config_check(cfg, &why);
   if (rc != T2FIT_OK) return rc;
@@ -57,6 +57,7 @@ extern "C" int hostsim_fit_rows(const t2fit_config* cfg, const float* rows, int6
     if (getenv("T2_HOSTSIM_NFEV")) nit[v] = r.nfev;  // debugging aid: report evaluations instead of iterations
     if (res) res[v] = o.res;
     if (r2) r2[v] = o.r2;
+    if (maps) { maps[4 * v] = o.k; maps[4 * v + 1] = o.t2; maps[4 * v + 2] = o.sigma; maps[4 * v + 3] = o.fun; }
   }
   return 0;
 }

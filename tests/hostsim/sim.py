@@ -32,7 +32,7 @@ def lib():
     if _lib is None:
         _lib = C.CDLL(build())
         _lib.hostsim_config_default.argtypes = [C.POINTER(_abi.T2FitConfig), C.c_int, C.c_int]
-        _lib.hostsim_fit_rows.argtypes = [C.POINTER(_abi.T2FitConfig), C.c_void_p, C.c_int64] + [C.c_void_p] * 6
+        _lib.hostsim_fit_rows.argtypes = [C.POINTER(_abi.T2FitConfig), C.c_void_p, C.c_int64] + [C.c_void_p] * 7
     return _lib
 
 
@@ -62,11 +62,12 @@ def fit_rows(cfg, rows):
     st = np.zeros(n, np.uint8)
     res = np.zeros(n, np.float32)
     r2 = np.zeros(n, np.float32)
+    maps = np.zeros((n, 4), np.float32)  # the epilogue's float32 map values: k, T2, sigma, fun
     rc = lib().hostsim_fit_rows(C.byref(cfg), rows.ctypes.data, n, x.ctypes.data, fun.ctypes.data,
-                                nit.ctypes.data, st.ctypes.data, res.ctypes.data, r2.ctypes.data)
+                                nit.ctypes.data, st.ctypes.data, res.ctypes.data, r2.ctypes.data, maps.ctypes.data)
     if rc != 0:
         raise RuntimeError(f"hostsim_fit_rows rc={rc}")
-    return {"x": x, "fun": fun, "nit": nit, "status": st, "res": res, "r2": r2}
+    return {"x": x, "fun": fun, "nit": nit, "status": st, "res": res, "r2": r2, "maps": maps}
 
 
 def trace_row(cfg, row, cap=200):
