@@ -120,17 +120,18 @@ SYMBOLS = [
 ]
 
 
-# entry points added to ABI 5 after its first release: another build of the same ABI (T2FIT_LIB) may lack them
-ADDITIVE = ("t2fit_boot_background_dev", "t2fit_boot_synth_dev", "t2fit_bootstrap_dev",
-            "t2fit_tv_params_default", "t2fit_tv_workspace_bytes", "t2fit_tv_denoise_dev",
-            "t2fit_resample_dev", "t2fit_reconstruct_workspace_bytes", "t2fit_reconstruct_dev",
-            "t2fit_morph_workspace_bytes", "t2fit_binary_threshold_dev", "t2fit_binary_morph_dev", "t2fit_fill_holes_dev",
-            "t2fit_seed_labels_dev", "t2fit_relabel_dev")
+# entry points added to ABI 5 after its first release, by stage: another build of the same ABI (T2FIT_LIB) may lack them
+BOOT_SYMBOLS = ("t2fit_boot_background_dev", "t2fit_boot_synth_dev", "t2fit_bootstrap_dev")
+TV_SYMBOLS = ("t2fit_tv_params_default", "t2fit_tv_workspace_bytes", "t2fit_tv_denoise_dev")
+RECON_SYMBOLS = ("t2fit_resample_dev", "t2fit_reconstruct_workspace_bytes", "t2fit_reconstruct_dev")
+MORPH_SYMBOLS = ("t2fit_morph_workspace_bytes", "t2fit_binary_threshold_dev", "t2fit_binary_morph_dev", "t2fit_fill_holes_dev",
+                 "t2fit_seed_labels_dev", "t2fit_relabel_dev")
+ADDITIVE = BOOT_SYMBOLS + TV_SYMBOLS + RECON_SYMBOLS + MORPH_SYMBOLS
 
 
 def bind(lib: C.CDLL) -> C.CDLL:
     """Attach prototypes; raises AttributeError if the library lacks a declared symbol (the ADDITIVE ones are looked
-    up: a library without them binds, and t2map raises when one is called)."""
+    up: a library without them binds, and the stage that needs one raises when it is called)."""
     for name, res, args in SYMBOLS:
         if name in ADDITIVE and not hasattr(lib, name):
             continue

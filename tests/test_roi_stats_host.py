@@ -38,7 +38,7 @@ def test_roi_table_runs_erosion_once_and_statistics_per_map(monkeypatch):
     assembles the answers."""
     import torch
 
-    from fetal_t2mapping_amd import t2map
+    from fetal_t2mapping_amd import _gpu_roi, t2map
 
     calls = {"erode": [], "stats": []}
     label = np.zeros((2, 3, 4), np.int16)
@@ -56,8 +56,8 @@ def test_roi_table_runs_erosion_once_and_statistics_per_map(monkeypatch):
         mean = np.array([np.mean(np.asarray(m)[r == i + 1]) if cnt[i] else np.nan for i in range(n_labels)])
         return t2map.RoiStats(mean, mean * 0, mean, cnt, cnt)
 
-    monkeypatch.setattr(t2map, "roi_erode", fake_erode)
-    monkeypatch.setattr(t2map, "roi_stats", fake_stats)
+    monkeypatch.setattr(_gpu_roi, "roi_erode", fake_erode)
+    monkeypatch.setattr(_gpu_roi, "roi_stats", fake_stats)
     maps = {"t2": np.full(label.shape, 80.1, np.float32), "sigma": np.full(label.shape, 3.0, np.float32)}
     f = t2map.roi_table(maps, label, label, 12, labels=[47, 12, 5], names=["a", "b", "c"], connectivity=2, iterations=3)
     assert calls == {"erode": [(12, [47, 12, 5], 2, 3)], "stats": [3, 3]}
@@ -72,7 +72,7 @@ def test_roi_table_runs_erosion_once_and_statistics_per_map(monkeypatch):
 def test_dense_labels_remaps_sparse_ids_on_cpu_tensors():
     import torch
 
-    from fetal_t2mapping_amd import t2map
+    from fetal_t2mapping_amd import _gpu, t2map
 
     lab = torch.tensor([[[0, 1003, 17, 17], [2035, 4, 99, -1]]], dtype=torch.int64)
     out = t2map.dense_labels(lab, [1003, 17, 2035, 4])
@@ -92,7 +92,7 @@ def test_dense_labels_remaps_sparse_ids_on_cpu_tensors():
     with pytest.raises(ValueError):
         t2map.dense_labels(lab, [4, 17, 4])
     with pytest.raises(ValueError):
-        t2map._int_tensor(np.zeros((2, 2, 2), np.float32))
+        _gpu.int_labels(np.zeros((2, 2, 2), np.float32))
 
 
 def test_cli_roi_flags_and_csv_path(tmp_path):
