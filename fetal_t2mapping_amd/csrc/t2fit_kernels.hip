@@ -331,11 +331,14 @@ constexpr int kChunkSmall = 64;   // small volumes (phantoms): more, smaller chu
 constexpr int kQueueCap = 64 + kChunkLarge;
 
 // what the persistent kernel needs to know about a resumable lane solver
-template <int MODEL, int NTE = 0, bool GSPLIT = false> struct LbfgsbLane {
-  using Solver = Lbfgsb<MODEL, NTE, GSPLIT>;
-  // the one-wave-workgroup kernels keep one number of each pair in global memory (three parameters: eight waves per CU)
-  using WaveWg = LbfgsbLane<MODEL, NTE, MODEL != T2FIT_MODEL_GAUSSIAN>;
-  static constexpr bool kGlobalPart = Solver::kSplit;
+template <int MODEL, int NTE = 0, int HOME = PAIRS_LDS> struct LbfgsbLane {
+  using Solver = Lbfgsb<MODEL, NTE, HOME>;
+  // the one-wave-workgroup kernels keep one number of each pair outside LDS (three parameters: eight waves per CU): in
+  // the lane's registers where it has 20 to spare (least squares: 221 -> 241 of 256), in global memory where it has
+  // not (the Rician likelihood fills all 256 as it is)
+  using WaveWg = LbfgsbLane<MODEL, NTE, MODEL == T2FIT_MODEL_GAUSSIAN ? PAIRS_LDS
+                                         : MODEL == T2FIT_MODEL_RICIAN ? PAIRS_GLOBAL : PAIRS_REG>;
+  static constexpr bool kGlobalPart = Solver::kPairGlobal;
   static constexpr int NP = Solver::N;
   static constexpr int kNte = NTE;  // > 0: the echo count is a compile-time constant (the refill loops flatten too)
   static constexpr int kHistDoubles = Solver::M * Solver::PAIR_L;  // correction pairs, per lane, in LDS
@@ -764,13 +767,16 @@ hipError_t launch_persistent(const LaunchArgs& a) {
     // One-wave workgroups.  The lane's correction pairs (400 B with three parameters, 240 B with two: s is kept as a
     // direction, t2fit_lbfgsb.h load_s) cap a CU's 160 KiB of LDS at 409 lanes: four waves as one 256-lane workgroup,
     // six as one-wave workgroups (round 2), and EIGHT -- two on every SIMD, what the lane's 256 registers allow -- once
-    // one of a pair's five numbers lives in global memory instead (A::WaveWg, Lbfgsb<.., GSPLIT>: 320 B per lane, 16 of
-    // a CU's 128 LDS pieces per wave; the 10 MiB of the global part stay in L2).  Measured on one box, maps identical
-    // bit for bit: 256^3 x 8 TE 13.62 -> 12.02 ms; with the split ring but capped at six waves 14.05 (the global
-    // accesses cost 3 %), at seven 12.96 (profiles/r03_exp3_eight_waves.txt).  Nothing but the pairs is in LDS: the
-    // samples are in registers (echo-count specialisation), the voxel queue too.
+    // one of a pair's five numbers lives elsewhere (A::WaveWg: 320 B per lane, 16 of a CU's 128 LDS pieces per wave).
+    // Elsewhere is the lane's own registers for the least-squares lanes (Lbfgsb<.., PAIRS_REG>: ten doubles, 221 -> 241
+    // registers at 8 echoes, nothing spilled to memory; no allocation, no traffic), and global memory for the Rician
+    // likelihood, which fills its 256 registers as it is (PAIRS_GLOBAL: M x 64 doubles per wave, 10 MiB for the whole
+    // chip, read back from L2).  Measured on one box with the global part, maps identical bit for bit: 256^3 x 8 TE
+    // 13.62 -> 12.02 ms; with the split ring but capped at six waves 14.05 (the global accesses cost 3 %), at seven
+    // 12.96 (profiles/r03_exp3_eight_waves.txt); global part against registers: profiles/r10_pair_registers_ab.txt.
+    // Nothing but the pairs is in LDS: the samples are in registers (echo-count specialisation), the voxel queue too.
     if (tune.wave_wg) {
-      using AW = typename A::WaveWg;  // three parameters: one number of every pair in global memory, 320 B of LDS per lane
+      using AW = typename A::WaveWg;  // three parameters: one number of every pair outside LDS, 320 B of LDS per lane
       constexpr int kHint = AW::kWaveWgHint;  // waves per SIMD the register allocator is held to
       auto k64 = extras ? fit_persistent_kernel<AW, kChunkSmall, false, kHint, true, 64, true>
                         : fit_persistent_kernel<AW, kChunkSmall, false, kHint, false, 64, true>;
@@ -796,7 +802,7 @@ hipError_t launch_persistent(const LaunchArgs& a) {
       // every wave that fits is resident; more would only start to leave
       const unsigned n_wg = std::min<unsigned>(a.grid, (unsigned)cus) * per_cu;
       double* ghist = nullptr;
-      if constexpr (AW::kGlobalPart) {  // M x 64 doubles per wave (5 KiB; 10 MiB for the whole chip: it lives in L2),
+      if constexpr (AW::kGlobalPart) {  // Rician likelihood only: M x 64 doubles per wave (5 KiB; 10 MiB for the whole chip),
         // kept between launches (t2fit_support.h): the kernel keeps live solver state in it
         e = scratch_get(a.st, kScratchRing, (size_t)n_wg * (wg / 64) * AW::Solver::M * 64 * sizeof(double), &ghist);
         if (e != hipSuccess) return e;

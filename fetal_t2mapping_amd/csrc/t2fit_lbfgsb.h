@@ -365,17 +365,29 @@ template <int NTE> struct RowSums4 {
 // NTE > 0 fixes the number of echoes at compile time (the kernels instantiate the common train lengths): the
 // evaluation then is one straight-line block -- no per-echo `i < n` tests between the echoes, so their
 // exp / sqrt chains interleave -- and only the summation order that numpy uses for that length is carried.
-// GSPLIT (three parameters only): the last ratio of every pair's s lives in a second array (`ghist`, global memory in
-// the kernels) instead of the ring in LDS.  Four instead of five doubles per pair are then in LDS, 320 instead of 400
-// bytes per lane, and 160 KiB hold the rings of EIGHT one-wave workgroups instead of six: every SIMD of a CU
-// interleaves two waves.  Where a number is kept does not change it: results are the same bit for bit.
-template <int MODEL, int NTE = 0, bool GSPLIT = false>
-struct Lbfgsb {
+// HOME (three parameters only): where the last ratio of every pair's s lives.  PAIRS_LDS: in the ring with the other
+// four numbers.  Otherwise four instead of five doubles per pair are in LDS, 320 instead of 400 bytes per lane, and
+// 160 KiB hold the rings of EIGHT one-wave workgroups instead of six: every SIMD of a CU interleaves two waves.
+// Where a number is kept does not change it: results are the same bit for bit.
+//   PAIRS_REG: in M members of the solver (`hr`: registers in the kernels).  A register file cannot be indexed by the
+//     ring slot, so `hr` is kept "newest last" and every access is static: storing a pair shifts the members down by
+//     one and puts the new ratio into hr[M - 1]; pair number p (0 = oldest) of a lane with `col` pairs is
+//     hr[M - col + p], and build_b() walks the index i = 0 .. M-1 with the guard i >= M - col.  Dropping the memory
+//     (col = 0) needs no work on them: what the guard excludes is never read.
+//   PAIRS_GLOBAL: in a second array (`ghist`, global memory in the kernels), for the lane that has no registers to
+//     spare (the Rician likelihood: DESIGN.md section 5).
+enum { PAIRS_LDS = 0, PAIRS_REG = 1, PAIRS_GLOBAL = 2 };
+// the members of PAIRS_REG; no other form has them
+template <bool ON, int M> struct PairRegs { double hr[M]; };
+template <int M> struct PairRegs<false, M> {};
+template <int MODEL, int NTE = 0, int HOME = PAIRS_LDS>
+struct Lbfgsb : PairRegs<HOME == PAIRS_REG && MODEL != T2FIT_MODEL_GAUSSIAN, 10> {
   static constexpr int N = MODEL == T2FIT_MODEL_GAUSSIAN ? 2 : 3;
   static constexpr int kNte = NTE;
   static constexpr int M = 10;
   static constexpr int PAIR = 2 * N - 1;  // doubles per correction pair (see load_s / store_s)
-  static constexpr bool kSplit = GSPLIT && N == 3;
+  static constexpr bool kSplit = HOME != PAIRS_LDS && N == 3;  // one of a pair's numbers is not in the ring
+  static constexpr bool kPairRegs = kSplit && HOME == PAIRS_REG, kPairGlobal = kSplit && HOME == PAIRS_GLOBAL;
   static constexpr int PAIR_L = kSplit ? PAIR - 1 : PAIR;  // of which in the ring `hist`
 
   double lb[N], ub[N];              // box
@@ -387,7 +399,7 @@ struct Lbfgsb {
   // y / sqrt(y's): see store_s), element e of slot q at hist[(q*PAIR + e) * hstride].  In the kernel that is LDS (one
   // column per lane, 400 B per lane for n = 3), which is what keeps the solver state within the VGPR budget.
   double* hist;
-  double* ghist;  // kSplit: element q * gstride holds the last ratio of the pair in ring slot q
+  double* ghist;  // kPairGlobal: element q * gstride holds the last ratio of the pair in ring slot q
   int hstride, gstride, head;
   int iwhere[N];
   int col, nit, nfev, ifun;
@@ -608,17 +620,24 @@ struct Lbfgsb {
   // +-2^-400 max|s_i|: the direction moves by 2^-400, the ratios stay below 2^400 and their squares times B finite.
   T2_HD int slot_of(int p) const { return (head + p) % M; }
   T2_HD double& hratio(int q, int e) const {
-    if constexpr (kSplit) {
+    if constexpr (kPairGlobal) {
       if (e == N - 2) return ghist[q * gstride];
     }
-    return hist[(q * PAIR_L + e) * hstride];
+    return hist[(q * PAIR_L + e) * hstride];  // (kPairRegs: e < N - 2 only)
   }
   T2_HD double& hy(int q, int i) const { return hist[(q * PAIR_L + (kSplit ? N - 2 : N - 1) + i) * hstride]; }
   T2_HD void load_s(int q, double* sv) const {  // as a vector (tests; build_b() reads the ratios directly)
     sv[0] = 1.0;
     T2_UNROLL
-    for (int i = 1; i < N; ++i) sv[i] = hratio(q, i - 1);
+    for (int i = 1; i < (kPairRegs ? N - 1 : N); ++i) sv[i] = hratio(q, i - 1);
+    if constexpr (kPairRegs) {  // slot q holds pair number (q - head) mod M: a chain of selects over the constant indices
+      const int at = M - col + (q - head + M) % M;
+      double v = this->hr[0];
+      static_for<1, M>([&](auto IC) { v = at == decltype(IC)::value ? this->hr[decltype(IC)::value] : v; });
+      sv[N - 1] = v;
+    }
   }
+  // kPairRegs: slot q must be the one after the newest pair (what digest() passes); `hr` keeps no slot numbers
   T2_HD void store_s(int q, const double* sv) {
     double big = lb_abs(sv[0]);
     T2_UNROLL
@@ -627,7 +646,12 @@ struct Lbfgsb {
     const double p0 = lb_abs(sv[0]) < least ? (sv[0] < 0.0 ? -least : least) : sv[0];
     const double r = t2_rcp_for_div(p0);
     T2_UNROLL
-    for (int i = 1; i < N; ++i) hratio(q, i - 1) = t2_div_by_rcp(sv[i], p0, r);
+    for (int i = 1; i < (kPairRegs ? N - 1 : N); ++i) hratio(q, i - 1) = t2_div_by_rcp(sv[i], p0, r);
+    if constexpr (kPairRegs) {
+      T2_UNROLL
+      for (int i = 0; i + 1 < M; ++i) this->hr[i] = this->hr[i + 1];
+      this->hr[M - 1] = t2_div_by_rcp(sv[N - 1], p0, r);
+    }
   }
 
   // B = theta*I updated by the stored pairs, oldest first (BFGS recursion; B stays symmetric, so
@@ -649,50 +673,97 @@ struct Lbfgsb {
     double rp[2][N], yp[2][N];
     T2_UNROLL
     for (int i = 0; i < N; ++i) { rp[0][i] = 0.0; yp[0][i] = 0.0; rp[1][i] = 0.0; yp[1][i] = 0.0; }
-    int q = head;  // ring slot of pair p, stepped along instead of (head + p) % M per pair
-    if (col > 0) {
-      T2_UNROLL
-      for (int i = 1; i < N; ++i) rp[0][i] = hratio(q, i - 1);
-      T2_UNROLL
-      for (int i = 0; i < N; ++i) yp[0][i] = hy(q, i);
-    }
-    static_for<0, M>([&](auto PC) {
-      constexpr int p = decltype(PC)::value, cur = p & 1, nxt = cur ^ 1;
-      if (p < col) {
-        // (with the whole ring in LDS the slot is stepped past the last pair too: that fetch reads a slot nobody uses and
-        // nobody uses what it returns, two instructions less per pair; with a global part it would pull a line that was
-        // never written all the way from HBM, and the next pair's wait for it costs the 2.4 % the register sets bring:
-        // profiles/r03_exp21_step_and_digest.txt)
-        const int step = q + 1 == M ? 0 : q + 1;
-        const int qn = (!kSplit || p + 1 < col) ? step : q;
-        q = qn;
+    if constexpr (kPairRegs) {
+      // The trips are the indices of `hr`: trip t works on pair number t - (M - col), lanes with fewer than M pairs sit
+      // out the FIRST trips.  Pair number p is in ring slot (head + p) mod M, so trip t reads slot (head + col + t) mod M
+      // whether the lane takes part in it or not: the slot is stepped and the next one fetched by every lane at every
+      // trip (a slot nobody uses, where the trip is not the lane's: it is LDS, and nobody uses what it returns), and
+      // the register set of a trip is its parity for every lane -- no copy, no select on where a lane's pairs start.
+      auto fetch = [&](int qs, int set) {
         T2_UNROLL
-        for (int i = 1; i < N; ++i) rp[nxt][i] = hratio(qn, i - 1);
+        for (int i = 1; i < N - 1; ++i) rp[set][i] = hratio(qs, i - 1);
         T2_UNROLL
-        for (int i = 0; i < N; ++i) yp[nxt][i] = hy(qn, i);
-        // B s for s = (1, rp[1], rp[2]): the first column of B plus the ratios times the others
-        double bs[N];
-        T2_UNROLL
-        for (int i = 0; i < N; ++i) {
-          double a = U[0][i];  // = U[i][0] (symmetric; only j >= i is kept)
-          T2_UNROLL
-          for (int j = 1; j < N; ++j) a = fma(j >= i ? U[i][j] : U[j][i], rp[cur][j], a);
-          bs[i] = a;
+        for (int i = 0; i < N; ++i) yp[set][i] = hy(qs, i);
+      };
+      int q = head + col;
+      q = q >= M ? q - M : q;
+      fetch(q, 0);
+      static_for<0, M>([&](auto IC) {
+        constexpr int t = decltype(IC)::value, cur = t & 1, nxt = cur ^ 1;
+        if constexpr (t + 1 < M) {
+          q = q + 1 == M ? 0 : q + 1;
+          fetch(q, nxt);
         }
-        double sbs = bs[0];
-        T2_UNROLL
-        for (int i = 1; i < N; ++i) sbs = fma(rp[cur][i], bs[i], sbs);
-        const double rsbs = t2_fast_rcp(sbs);
-        double tb[N];
-        T2_UNROLL
-        for (int i = 0; i < N; ++i) tb[i] = bs[i] * rsbs;
-        // (the ring holds y / sqrt(y's): the rank-one term y y' / (y's) needs no scaling here -- digest())
-        T2_UNROLL
-        for (int i = 0; i < N; ++i)
+        if (t >= M - col) {
+          rp[cur][N - 1] = this->hr[t];
+          // B s for s = (1, rp[1], rp[2]), the scaling and the update: as in the other forms below
+          double bs[N];
           T2_UNROLL
-          for (int j = i; j < N; ++j) U[i][j] = fma(yp[cur][i], yp[cur][j], fma(-bs[i], tb[j], U[i][j]));
+          for (int i = 0; i < N; ++i) {
+            double a = U[0][i];
+            T2_UNROLL
+            for (int j = 1; j < N; ++j) a = fma(j >= i ? U[i][j] : U[j][i], rp[cur][j], a);
+            bs[i] = a;
+          }
+          double sbs = bs[0];
+          T2_UNROLL
+          for (int i = 1; i < N; ++i) sbs = fma(rp[cur][i], bs[i], sbs);
+          const double rsbs = t2_fast_rcp(sbs);
+          double tb[N];
+          T2_UNROLL
+          for (int i = 0; i < N; ++i) tb[i] = bs[i] * rsbs;
+          T2_UNROLL
+          for (int i = 0; i < N; ++i)
+            T2_UNROLL
+            for (int j = i; j < N; ++j) U[i][j] = fma(yp[cur][i], yp[cur][j], fma(-bs[i], tb[j], U[i][j]));
+        }
+      });
+    } else {
+      int q = head;  // ring slot of pair p, stepped along instead of (head + p) % M per pair
+      if (col > 0) {
+        T2_UNROLL
+        for (int i = 1; i < N; ++i) rp[0][i] = hratio(q, i - 1);
+        T2_UNROLL
+        for (int i = 0; i < N; ++i) yp[0][i] = hy(q, i);
       }
-    });
+      static_for<0, M>([&](auto PC) {
+        constexpr int p = decltype(PC)::value, cur = p & 1, nxt = cur ^ 1;
+        if (p < col) {
+          // (with the whole ring in LDS the slot is stepped past the last pair too: that fetch reads a slot nobody uses and
+          // nobody uses what it returns, two instructions less per pair; with a global part it would pull a line that was
+          // never written all the way from HBM, and the next pair's wait for it costs the 2.4 % the register sets bring:
+          // profiles/r03_exp21_step_and_digest.txt)
+          const int step = q + 1 == M ? 0 : q + 1;
+          const int qn = (!kPairGlobal || p + 1 < col) ? step : q;
+          q = qn;
+          T2_UNROLL
+          for (int i = 1; i < N; ++i) rp[nxt][i] = hratio(qn, i - 1);
+          T2_UNROLL
+          for (int i = 0; i < N; ++i) yp[nxt][i] = hy(qn, i);
+          // B s for s = (1, rp[1], rp[2]): the first column of B plus the ratios times the others
+          double bs[N];
+          T2_UNROLL
+          for (int i = 0; i < N; ++i) {
+            double a = U[0][i];  // = U[i][0] (symmetric; only j >= i is kept)
+            T2_UNROLL
+            for (int j = 1; j < N; ++j) a = fma(j >= i ? U[i][j] : U[j][i], rp[cur][j], a);
+            bs[i] = a;
+          }
+          double sbs = bs[0];
+          T2_UNROLL
+          for (int i = 1; i < N; ++i) sbs = fma(rp[cur][i], bs[i], sbs);
+          const double rsbs = t2_fast_rcp(sbs);
+          double tb[N];
+          T2_UNROLL
+          for (int i = 0; i < N; ++i) tb[i] = bs[i] * rsbs;
+          // (the ring holds y / sqrt(y's): the rank-one term y y' / (y's) needs no scaling here -- digest())
+          T2_UNROLL
+          for (int i = 0; i < N; ++i)
+            T2_UNROLL
+            for (int j = i; j < N; ++j) U[i][j] = fma(yp[cur][i], yp[cur][j], fma(-bs[i], tb[j], U[i][j]));
+        }
+      });
+    }
     T2_UNROLL
     for (int i = 0; i < N; ++i)
       T2_UNROLL
@@ -907,7 +978,7 @@ struct Lbfgsb {
   }
 
   // Start a fit: x = x0 clipped into the box (scipy), empty memory.  Next: eval(), then advance().
-  // `hist_` must hold M * PAIR_L doubles at stride `hstride_` (kSplit: and `ghist_` M doubles at stride `gstride_`).
+  // `hist_` must hold M * PAIR_L doubles at stride `hstride_` (kPairGlobal: and `ghist_` M doubles at stride `gstride_`).
   T2_HD void init(const double* x0_, const double* lb_, const double* ub_, double* hist_, int hstride_,
                   double* ghist_ = nullptr, int gstride_ = 0) {
     hist = hist_;

@@ -23,7 +23,7 @@ template <class T> constexpr T ceil_div(T a, T b) { return (a + b - 1) / b; }
 // live state in it).  t2fit_destroy gives back the buffers of its context's streams (scratch_release_stream); buffers of
 // caller-owned streams live as long as the process.
 enum ScratchUse : int {
-  kScratchRing,      // fit: global part of the correction-pair ring (one-wave-workgroup kernels)
+  kScratchRing,      // fit: global part of the correction-pair ring (one-wave-workgroup kernels, Rician likelihood)
   kScratchRoiErode,  // ROI statistics: the erosion's second buffer
   kScratchRoiStats,  // ROI statistics: the sort's tables and segments
 };
