@@ -68,6 +68,8 @@ MORPH_OPS = {"dilate": MORPH_DILATE, "erode": MORPH_ERODE, "close": MORPH_CLOSE,
 MORPH_UNBOUNDED = 1  # flags bit
 MORPH_F32, MORPH_I32, MORPH_U8 = 0, 1, 2
 
+REGISTER_SUMS = 43
+
 # every symbol include/t2fit.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -110,6 +112,11 @@ SYMBOLS = [
     ("t2fit_seed_labels_dev", C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_size_t,
                                         _P]),
     ("t2fit_relabel_dev", C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P]),
+    ("t2fit_register_workspace_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    ("t2fit_register_sums_dev", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(C.c_double), _P, _P, C.c_size_t, _P]),
+    ("t2fit_shrink_dev", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    ("t2fit_shrink_mask_dev", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     ("t2fit_set_timing", C.c_int, [C.c_int]),
     ("t2fit_set_reserve_cus", C.c_int, [C.c_int]),
     ("t2fit_kernel_ms", C.c_double, [C.c_int]),
@@ -127,13 +134,15 @@ RECON_SYMBOLS = ("t2fit_resample_dev", "t2fit_reconstruct_workspace_bytes", "t2f
 MORPH_SYMBOLS = ("t2fit_morph_workspace_bytes", "t2fit_binary_threshold_dev", "t2fit_binary_morph_dev", "t2fit_fill_holes_dev",
                  "t2fit_seed_labels_dev", "t2fit_relabel_dev")
 ADDITIVE = BOOT_SYMBOLS + TV_SYMBOLS + RECON_SYMBOLS + MORPH_SYMBOLS
+REGISTER_SYMBOLS = ("t2fit_register_workspace_bytes", "t2fit_register_sums_dev", "t2fit_shrink_dev", "t2fit_shrink_mask_dev")
+LOOKED_UP = ADDITIVE + REGISTER_SYMBOLS
 
 
 def bind(lib: C.CDLL) -> C.CDLL:
-    """Attach prototypes; raises AttributeError if the library lacks a declared symbol (the ADDITIVE ones are looked
+    """Attach prototypes; raises AttributeError if the library lacks a declared symbol (the LOOKED_UP ones are looked
     up: a library without them binds, and the stage that needs one raises when it is called)."""
     for name, res, args in SYMBOLS:
-        if name in ADDITIVE and not hasattr(lib, name):
+        if name in LOOKED_UP and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         fn.restype = res

@@ -1,0 +1,391 @@
+"""Rigid registration of one volume onto another, restated in numpy: the executable statement of the definition in
+include/t2fit.h (t2fit_register_sums_dev, t2fit_shrink_dev, t2fit_shrink_mask_dev) and the optimizer both the statement
+and the device path run.  It builds the explicit recipe of the reference's ``registration_itk``
+(utils/qmri_utils.py:167-221): correlation metric, fixed and moving masks from ``build_mask``, linear interpolator,
+Euler 3-D transform, regular-step gradient descent (learning rate 1, 100 iterations, minimum step 1e-6, gradient
+tolerance 1e-6), scales from the physical shift, and the 4 / 2 / 1 pyramid it has commented out -- deterministic where
+ITK samples at random.  Parity with elastix (``registration_elastix``, what the reference actually calls) is unpinned.
+
+Arrays are ``(Z, Y, X)``, x fastest; geometry is :class:`_resample.Geometry`'s.  Host code for tests and baselines, and
+the host half (metric arithmetic, optimizer) of the product path; the sums over the voxels are the HIP kernel's there.
+
+**The 43 sums.**  ``A`` is the index affine of :func:`_resample.index_affine` (fixed index -> continuous moving index).
+A fixed voxel ``i = (ix, iy, iz)`` counts iff ``fixed_mask[i] != 0``, ``c = A (ix, iy, iz, 1)`` passes the inside test of
+the resampler, and the moving mask at the nearest node ``floor(c + 0.5)`` (clamped) is not 0.  For a voxel that counts,
+``f`` is the fixed sample, ``m`` the float64 trilinear interpolant of the moving volume (lower node clamped, upper node
+replicated on the rim, x then y then z as ``lo + d (hi - lo)``, a zero weight returns ``lo``), and ``g_a = dm / dc_a`` the
+difference of the two neighbours along axis ``a`` interpolated along the other two axes with the same weights; ``g_a`` is
+0 where the interpolant is flat along ``a``: the upper neighbour is the clamped lower one, or ``c_a < 0`` (the lower
+rim).  The sums, in this order::
+
+    [0] N   [1] sum f   [2] sum m   [3] sum f f   [4] sum m m   [5] sum f m
+    [6 + 4 (3 w + a) + j]  sum (w g_a) u_j      w in (1, f, m), a in (x, y, z), u = (ix, iy, iz, 1)
+    [42] reserved, +0.0 (the count, 5 moments and 36 gradient sums are 42 numbers; the array has 43 slots)
+
+Every product rounds once (``w g_a`` first, then ``u_j``; ``u_3 = 1`` is no multiplication); a voxel that does not
+count contributes +0.0.  The volumes must be finite.
+
+**The summation tree** (a function of the fixed volume's sizes alone).  The fixed volume is cut into bricks of
+``BX x BY x BZ = 64 x 4 x 8`` voxels, padded with zeros.  In a brick, column ``(x, y)`` adds its 8 voxels in z order
+starting from 0.0; the 64 columns of a row are added by halving (``v[:32] + v[32:]``, then 16, .. 1); the 4 rows by
+halving.  That is the brick's slab.  The slabs, in ``(bz, by, bx)`` order, are reduced in passes: groups of 256
+consecutive values (the last group padded with zeros) are each added by halving; passes repeat until one value is left
+(at least one pass)."""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _morph, _resample
+
+BX, BY, BZ = 64, 4, 8
+FAN = 256
+N_SUMS = 43
+MIN_STEP, GRAD_TOL, RELAX, LEARNING_RATE = 1e-6, 1e-6, 0.5, 1.0
+MIN_LEVEL_SIZE = 4  # a pyramid level keeps at least this many voxels per axis
+
+
+def _halve(a):
+    """Halving adds over the last axis (a power of two)."""
+    while a.shape[-1] > 1:
+        h = a.shape[-1] // 2
+        a = a[..., :h] + a[..., h:]
+    return a[..., 0]
+
+
+def brick_counts(shape):
+    """(bricks_z, bricks_y, bricks_x) of a fixed volume of ``shape`` (Z, Y, X)."""
+    fz, fy, fx = (int(v) for v in shape)
+    return -(-fz // BZ), -(-fy // BY), -(-fx // BX)
+
+
+def pass_sizes(n_slabs):
+    """Values per sum that enter each pass of the reduction: [n_slabs, ceil(n_slabs / 256), ..] down to the pass whose
+    output is one value."""
+    out = [int(n_slabs)]
+    while out[-1] > FAN:
+        out.append(-(-out[-1] // FAN))
+    return out
+
+
+def workspace_bytes(shape):
+    """What t2fit_register_workspace_bytes returns: every pass's input, each rounded up to 256 bytes."""
+    bz, by, bx = brick_counts(shape)
+    return sum((N_SUMS * 8 * n + 255) // 256 * 256 for n in pass_sizes(bz * by * bx))
+
+
+def _terms(fixed, fmask, moving, mmask, a, z0, nzc):
+    """float64 ``(43, nzc, fy, fx)``: what every voxel of the fixed planes ``z0 .. z0 + nzc`` adds to the sums."""
+    _, fy, fx = fixed.shape
+    n = moving.shape[::-1]
+    shape = (nzc, fy, fx)
+    c = _resample._coords(a, shape, (0, 0, z0))
+    counted = fmask[z0:z0 + nzc] != 0
+    for k in range(3):
+        counted = counted & (c[k] >= -0.5) & (c[k] < n[k] - 0.5)
+    near = [np.clip(np.floor(c[k] + 0.5), 0, n[k] - 1).astype(np.int64) for k in range(3)]
+    counted = counted & (mmask[near[2], near[1], near[0]] != 0)
+    b = [np.clip(np.floor(c[k]), 0, n[k] - 1) for k in range(3)]
+    d = [np.maximum(c[k] - b[k], 0.0) for k in range(3)]
+    lo = [b[k].astype(np.int64) for k in range(3)]
+    hi = [np.minimum(lo[k] + 1, n[k] - 1) for k in range(3)]
+    flat = [(hi[k] == lo[k]) | (c[k] < 0.0) for k in range(3)]
+    v = moving.astype(np.float64)
+
+    def lerp(p, q, w):
+        return np.where(w == 0.0, p, p + w * (q - p))
+
+    tap = {(z, y, x): v[(lo, hi)[z][2], (lo, hi)[y][1], (lo, hi)[x][0]] for z in (0, 1) for y in (0, 1) for x in (0, 1)}
+    row = {(z, y): lerp(tap[z, y, 0], tap[z, y, 1], d[0]) for z in (0, 1) for y in (0, 1)}
+    plane = [lerp(row[z, 0], row[z, 1], d[1]) for z in (0, 1)]
+    m = lerp(plane[0], plane[1], d[2])
+    gx = lerp(lerp(tap[0, 0, 1] - tap[0, 0, 0], tap[0, 1, 1] - tap[0, 1, 0], d[1]),
+              lerp(tap[1, 0, 1] - tap[1, 0, 0], tap[1, 1, 1] - tap[1, 1, 0], d[1]), d[2])
+    gy = lerp(row[0, 1] - row[0, 0], row[1, 1] - row[1, 0], d[2])
+    gz = plane[1] - plane[0]
+    g = [np.where(flat[k], 0.0, gk) for k, gk in enumerate((gx, gy, gz))]
+    f = fixed[z0:z0 + nzc].astype(np.float64)
+    u = [np.broadcast_to(np.arange(fx, dtype=np.float64)[None, None, :], shape),
+         np.broadcast_to(np.arange(fy, dtype=np.float64)[None, :, None], shape),
+         np.broadcast_to(np.arange(z0, z0 + nzc, dtype=np.float64)[:, None, None], shape)]
+    out = np.zeros((N_SUMS,) + shape, np.float64)
+    out[0], out[1], out[2], out[3], out[4], out[5] = 1.0, f, m, f * f, m * m, f * m
+    for w, wv in enumerate((None, f, m)):
+        for k in range(3):
+            wg = g[k] if wv is None else wv * g[k]
+            for j in range(4):
+                out[6 + 4 * (3 * w + k) + j] = wg * u[j] if j < 3 else wg
+    return np.where(counted[None], out, 0.0)
+
+
+def _volumes(fixed, fixed_mask, moving, moving_mask):
+    fixed, moving = np.asarray(fixed, np.float32), np.asarray(moving, np.float32)
+    if fixed.ndim != 3 or moving.ndim != 3:
+        raise ValueError("fixed and moving must be (Z, Y, X) volumes")
+    fmask = np.ones(fixed.shape, np.uint8) if fixed_mask is None else (np.asarray(fixed_mask) != 0).astype(np.uint8)
+    mmask = np.ones(moving.shape, np.uint8) if moving_mask is None else (np.asarray(moving_mask) != 0).astype(np.uint8)
+    if fmask.shape != fixed.shape or mmask.shape != moving.shape:
+        raise ValueError("a mask has the shape of its volume")
+    return fixed, fmask, moving, mmask
+
+
+def slabs(fixed, fixed_mask, moving, moving_mask, A):
+    """float64 ``(43, n_slabs)``: the slab of every brick of the fixed volume, bricks in ``(bz, by, bx)`` order."""
+    fixed, fmask, moving, mmask = _volumes(fixed, fixed_mask, moving, moving_mask)
+    a = np.asarray(A, np.float64).reshape(3, 4)
+    fz, fy, fx = fixed.shape
+    nbz, nby, nbx = brick_counts(fixed.shape)
+    out = np.zeros((N_SUMS, nbz, nby, nbx), np.float64)
+    with np.errstate(all="ignore"):
+        for bz in range(nbz):
+            z0 = bz * BZ
+            nzc = min(BZ, fz - z0)
+            pad = np.zeros((N_SUMS, BZ, nby * BY, nbx * BX), np.float64)
+            pad[:, :nzc, :fy, :fx] = _terms(fixed, fmask, moving, mmask, a, z0, nzc)
+            acc = np.zeros(pad.shape[:1] + pad.shape[2:], np.float64)
+            for k in range(BZ):
+                acc = acc + pad[:, k]
+            acc = _halve(acc.reshape(N_SUMS, nby, BY, nbx, BX))       # the 64 columns of a row
+            out[:, bz] = _halve(np.moveaxis(acc, 2, -1))              # the 4 rows
+    return out.reshape(N_SUMS, -1)
+
+
+def reduce_slabs(v):
+    """The passes of the tree over ``(43, n)`` values."""
+    v = np.asarray(v, np.float64)
+    while True:
+        groups = -(-v.shape[1] // FAN)
+        pad = np.zeros((v.shape[0], groups * FAN), np.float64)
+        pad[:, :v.shape[1]] = v
+        with np.errstate(all="ignore"):
+            v = _halve(pad.reshape(v.shape[0], groups, FAN))
+        if groups == 1:
+            return v[:, 0]
+
+
+def registration_sums(fixed, moving, A, fixed_mask=None, moving_mask=None):
+    """The 43 float64 sums (module docstring) of ``moving`` sampled at ``A`` against ``fixed``; masks None: all ones."""
+    return reduce_slabs(slabs(fixed, fixed_mask, moving, moving_mask, A))
+
+
+# ---- metric: host arithmetic, shared by the statement and the device path --------------------------------------------
+def metric(sums):
+    """``(C, dC/dA [3, 4])`` from the 43 sums: ``C = -sfm^2 / (sff smm)`` with ``sfm = sum fm - sum f sum m / N`` (ITK's
+    correlation metric), the derivative by the chain rule with N held constant.  ValueError when no voxel counts or a
+    variance vanishes (no overlap, a constant volume): there is no metric there, and no transform is made up."""
+    s = np.asarray(sums, np.float64)
+    n = s[0]
+    if not n >= 1.0:
+        raise ValueError("the registration has no voxel to compare: the masks do not overlap under this transform")
+    sf, sm, sff_, smm_, sfm_ = s[1:6]
+    sfm, sff, smm = sfm_ - sf * sm / n, sff_ - sf * sf / n, smm_ - sm * sm / n
+    if not (sff > 0.0 and smm > 0.0):
+        raise ValueError("the registration metric is undefined: the fixed or the moving samples are constant")
+    d1, df, dm = (s[6 + 12 * w:18 + 12 * w].reshape(3, 4) for w in range(3))
+    dsfm = df - (sf / n) * d1
+    dsmm = 2.0 * dm - 2.0 * (sm / n) * d1
+    c = -(sfm * sfm) / (sff * smm)
+    dc = -2.0 * sfm * dsfm / (sff * smm) + (sfm * sfm) * dsmm / (sff * smm * smm)
+    return float(c), dc
+
+
+# ---- transform: Euler angles about a centre ----------------------------------------------------------------------------
+def _rotations(p):
+    """R = Rz Rx Ry (ITK's Euler3DTransform order) and its derivatives with respect to (rx, ry, rz)."""
+    cx, sx, cy, sy, cz, sz = np.cos(p[0]), np.sin(p[0]), np.cos(p[1]), np.sin(p[1]), np.cos(p[2]), np.sin(p[2])
+    rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]], np.float64)
+    ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]], np.float64)
+    rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]], np.float64)
+    dx = np.array([[0, 0, 0], [0, -sx, -cx], [0, cx, -sx]], np.float64)
+    dy = np.array([[-sy, 0, cy], [0, 0, 0], [-cy, 0, -sy]], np.float64)
+    dz = np.array([[-sz, -cz, 0], [cz, -sz, 0], [0, 0, 0]], np.float64)
+    return rz @ rx @ ry, (rz @ dx @ ry, rz @ rx @ dy, dz @ rx @ ry)
+
+
+def compose(p, centre):
+    """4 x 4 (fixed point -> moving point, LPS millimetres) of ``p = (rx, ry, rz [rad], tx, ty, tz [mm])``:
+    ``x' = R (x - centre) + centre + t``."""
+    p, centre = np.asarray(p, np.float64), np.asarray(centre, np.float64)
+    r, _ = _rotations(p)
+    t = np.eye(4)
+    t[:3, :3] = r
+    t[:3, 3] = centre - r @ centre + p[3:]
+    return t
+
+
+def parameter_gradient(dc_da, p, centre, fixed_geom, moving_geom):
+    """dC/dp from dC/dA: ``A = Mm^-1 [R Mf | R of + (centre - R centre + t) - om]`` is linear in R and t."""
+    mf, of = _resample._index_to_point(fixed_geom)
+    mm, _ = _resample._index_to_point(moving_geom)
+    h = np.linalg.inv(mm).T @ np.asarray(dc_da, np.float64)
+    d_r = h[:, :3] @ mf.T + np.outer(h[:, 3], of - np.asarray(centre, np.float64))
+    _, dr = _rotations(np.asarray(p, np.float64))
+    return np.array([np.sum(d_r * dr[0]), np.sum(d_r * dr[1]), np.sum(d_r * dr[2]), h[0, 3], h[1, 3], h[2, 3]])
+
+
+def mask_centre_and_scales(fixed_mask, fixed_geom):
+    """The rotation centre -- the centroid of the fixed mask, a physical point -- and the parameter scales: 1 for the
+    translations; for the rotations the mean squared distance [mm^2] of the mask's voxels from the centre, which is what
+    ITK's scales from the physical shift amount to for a rigid transform (a unit rotation shifts a voxel by its distance
+    from the axis, a unit translation by 1; the scale is the mean squared shift)."""
+    idx = np.argwhere(np.asarray(fixed_mask) != 0)[:, ::-1].astype(np.float64)  # (x, y, z)
+    if len(idx) == 0:
+        raise ValueError("the fixed mask is empty")
+    m, o = _resample._index_to_point(fixed_geom)
+    pts = idx @ m.T + o
+    centre = pts.mean(axis=0)
+    r2 = float(np.mean(np.sum((pts - centre) ** 2, axis=1)))
+    return centre, np.array([r2, r2, r2, 1.0, 1.0, 1.0]) if r2 > 0.0 else np.ones(6)
+
+
+# ---- pyramid ---------------------------------------------------------------------------------------------------------
+def level_shape(shape, s):
+    """(Z, Y, X) of a level of shrink factor ``s``: whole blocks only, the ragged edge is dropped."""
+    return tuple(int(v) // int(s) for v in shape)
+
+
+def level_geometry(geom, s, shape=None):
+    """The grid of the block means: spacing ``s`` times as large, the origin at the centre of the first block."""
+    g = _resample.as_geometry(geom, shape)
+    m, o = _resample._index_to_point(g)
+    origin = o + m @ np.full(3, (s - 1) / 2.0)
+    return _resample.Geometry([v // s for v in g.GetSize()], [v * s for v in g.GetSpacing()], origin, g.GetDirection())
+
+
+def shrink(vol, s):
+    """Mean of the ``s^3`` blocks: a float64 sum in (dz, dy, dx) order from 0.0, divided by ``s^3``, one rounding to
+    float32."""
+    v = np.asarray(vol, np.float32).astype(np.float64)
+    nz, ny, nx = level_shape(v.shape, s)
+    acc = np.zeros((nz, ny, nx), np.float64)
+    for dz in range(s):
+        for dy in range(s):
+            for dx in range(s):
+                acc = acc + v[dz:nz * s:s, dy:ny * s:s, dx:nx * s:s]
+    return (acc / float(s ** 3)).astype(np.float32)
+
+
+def shrink_mask(mask, s):
+    """1 where any voxel of the block is set."""
+    m = np.asarray(mask) != 0
+    nz, ny, nx = level_shape(m.shape, s)
+    return m[:nz * s, :ny * s, :nx * s].reshape(nz, s, ny, s, nx, s).any(axis=(1, 3, 5)).astype(np.uint8)
+
+
+def build_mask(vol, threshold=1.0, slice_axis=2, size=5):
+    """The reference's ``build_mask`` (utils/qmri_utils.py:223-252) with :mod:`_morph`, as ``_gpu_morph.build_mask``."""
+    fp = [size, size, size]
+    fp[slice_axis] = 1
+    square = np.ones(fp, bool)
+    m = _morph.fill_holes(np.asarray(vol, np.float32) > np.float32(threshold), slice_axis=slice_axis)
+    return _morph.erode(_morph.dilate(m, square), square).astype(np.uint8)
+
+
+def check_levels(levels, fixed_shape, moving_shape):
+    levels = tuple(int(s) for s in levels)
+    if not levels or any(s < 1 or s > 32 for s in levels):
+        raise ValueError(f"levels are shrink factors in 1..32, got {levels!r}")
+    for s in levels:
+        if min(level_shape(fixed_shape, s) + level_shape(moving_shape, s)) < MIN_LEVEL_SIZE:
+            raise ValueError(f"shrink factor {s} leaves fewer than {MIN_LEVEL_SIZE} voxels along an axis of "
+                             f"{tuple(fixed_shape)} / {tuple(moving_shape)}")
+    return levels
+
+
+class HostPyramid:
+    """The volumes and masks of every level, and their sums, in numpy.  The device path has the same two methods."""
+
+    def __init__(self, fixed, fixed_mask, moving, moving_mask):
+        self.full = _volumes(fixed, fixed_mask, moving, moving_mask)
+
+    def level(self, s):
+        fixed, fmask, moving, mmask = self.full
+        if s == 1:
+            return self.full
+        return shrink(fixed, s), shrink_mask(fmask, s), shrink(moving, s), shrink_mask(mmask, s)
+
+    def sums(self, level, A):
+        fixed, fmask, moving, mmask = level
+        return registration_sums(fixed, moving, A, fmask, mmask)
+
+
+# ---- optimizer -------------------------------------------------------------------------------------------------------
+class Registration:
+    """``transform`` 4 x 4 (fixed point -> moving point, LPS millimetres: what ``recon.py --transforms`` reads),
+    ``parameters`` (rx, ry, rz, tx, ty, tz) about ``centre``, ``metric`` at the returned parameters, ``iterations`` per
+    level, ``stop``: why the last level ended ('gradient', 'step' or 'iterations'), ``stops``: every level's."""
+
+    def __init__(self, transform, parameters, centre, metric, iterations, stops):  # noqa: A002
+        self.transform, self.parameters, self.centre, self.metric = transform, parameters, centre, metric
+        self.iterations, self.stops, self.stop = tuple(iterations), tuple(stops), stops[-1]
+
+    def __repr__(self):
+        return (f"Registration(parameters={np.array2string(self.parameters, precision=5)}, metric={self.metric:.6f}, "
+                f"iterations={self.iterations}, stop={self.stop!r})")
+
+
+def initial_step(s):
+    """The first step [mm in scaled parameter space] of a level of shrink factor ``s``: ``registration_itk``'s learning
+    rate 1 at full resolution, ``s`` times as long on a grid ``s`` times as coarse (a step of one voxel at every level)."""
+    return LEARNING_RATE * float(s)
+
+
+def optimize(pyramid, fixed_geom, moving_geom, centre, scales, *, levels=(4, 2, 1), max_iter=100, init=None):
+    """Regular-step gradient descent over the levels.  Per iteration: the sums at ``A(p)``, ``C`` and ``dC/dp``, the scaled
+    gradient ``g_i = (dC/dp_i) / scale_i``; stop when ``|g| < 1e-6`` ('gradient'); halve the step when ``g`` and the
+    previous ``g`` have a negative scalar product; stop when the step is below 1e-6 ('step'); move
+    ``p -= step g / |g|``; stop after ``max_iter`` moves ('iterations').  The parameters carry from level to level."""
+    p = np.zeros(6) if init is None else np.array(init, np.float64)
+    if p.shape != (6,) or not np.all(np.isfinite(p)):
+        raise ValueError("init is (rx, ry, rz [rad], tx, ty, tz [mm]), finite")
+    iterations, stops = [], []
+    for s in levels:
+        level = pyramid.level(s)
+        fg, mg = level_geometry(fixed_geom, s), level_geometry(moving_geom, s)
+
+        def evaluate(q):
+            a = _resample.index_affine(fg, mg, compose(q, centre))
+            c, dc = metric(pyramid.sums(level, a))
+            return c, parameter_gradient(dc, q, centre, fg, mg) / scales
+
+        step, prev, n_it, stop = initial_step(s), None, 0, "iterations"
+        while True:
+            c, g = evaluate(p)
+            norm = float(np.sqrt(np.sum(g * g)))
+            if norm < GRAD_TOL:
+                stop = "gradient"
+                break
+            if prev is not None and float(np.sum(g * prev)) < 0.0:
+                step *= RELAX
+            if step < MIN_STEP:
+                stop = "step"
+                break
+            if n_it >= max_iter:
+                break
+            p = p - (step / norm) * g
+            prev, n_it = g, n_it + 1
+        iterations.append(n_it)
+        stops.append(stop)
+    return Registration(compose(p, centre), p, np.asarray(centre, np.float64), c, iterations, stops)
+
+
+def register_rigid(fixed, moving, fixed_geom, moving_geom, *, fixed_mask=None, moving_mask=None, levels=(4, 2, 1),
+                   max_iter=100, init=None):
+    """Register ``moving`` onto ``fixed`` (float32 ``(Z, Y, X)`` with their geometries); masks None: ``build_mask`` of
+    the volume.  Returns a :class:`Registration`.  The statement of ``t2map.register.register_rigid``."""
+    fixed, moving = np.asarray(fixed, np.float32), np.asarray(moving, np.float32)
+    fmask = build_mask(fixed) if fixed_mask is None else fixed_mask
+    mmask = build_mask(moving) if moving_mask is None else moving_mask
+    pyramid = HostPyramid(fixed, fmask, moving, mmask)
+    fg, mg = _resample.as_geometry(fixed_geom, fixed.shape), _resample.as_geometry(moving_geom, moving.shape)
+    levels = check_levels(levels, fixed.shape, moving.shape)
+    centre, scales = mask_centre_and_scales(pyramid.full[1], fg)
+    return optimize(pyramid, fg, mg, centre, scales, levels=levels, max_iter=max_iter, init=init)
+
+
+def target_registration_error(found, true, mask, geom):
+    """The largest distance [mm] between the images of the mask's voxels under two 4 x 4 transforms."""
+    idx = np.argwhere(np.asarray(mask) != 0)[:, ::-1].astype(np.float64)
+    m, o = _resample._index_to_point(_resample.as_geometry(geom, np.asarray(mask).shape))
+    pts = idx @ m.T + o
+    d = pts @ (np.asarray(found)[:3, :3] - np.asarray(true)[:3, :3]).T + (np.asarray(found)[:3, 3] - np.asarray(true)[:3, 3])
+    return float(np.sqrt(np.max(np.sum(d * d, axis=1))))

@@ -820,6 +820,10 @@ def parse_arguments(argv=None):
     p.add_argument("--recon_transforms", default=None, metavar="DIR",
                    help="rigid transforms <sub>_<ses>_<orientation>.txt of the moving stacks (4 x 4 text, fixed point -> "
                         "moving point); a missing file is the identity")
+    p.add_argument("--recon_register", action="store_true",
+                   help="with --reconstruct: find the transforms of the moving stacks on the GPU (recon.py --register)")
+    p.add_argument("--recon_register_echoes", action="store_true",
+                   help="with --reconstruct: register every merged echo onto the first one (recon.py --register_echoes)")
     p.add_argument("--build_mask", choices=["phantom"], default=None,
                    help="build the masks of every echo and the vial labels on the GPU from the volumes about to be fitted "
                         "(after --reconstruct if given) instead of reading recon_1mm_mask / recon_1mm_label: phantom = the "
@@ -838,7 +842,7 @@ def parse_arguments(argv=None):
     p.add_argument("--denoise_iter", type=int, default=200, help="iteration limit of a problem (default 200)")
     args = p.parse_args(argv)
     args.reconstruct_args = None
-    given = [f for f in ("--recon_fixed", "--recon_res", "--recon_transforms")
+    given = [f for f in ("--recon_fixed", "--recon_res", "--recon_transforms", "--recon_register", "--recon_register_echoes")
              if any(a == f or a.startswith(f + "=") for a in (argv if argv is not None else sys.argv[1:]))]
     if given and not args.reconstruct:
         p.error(f"{given[0]} has no effect without --reconstruct")
@@ -847,7 +851,13 @@ def parse_arguments(argv=None):
             p.error("--recon_res must be a positive number")
         if args.recon_transforms is not None and not os.path.isdir(args.recon_transforms):
             p.error(f"--recon_transforms {args.recon_transforms!r} is not a directory")
+        if args.recon_transforms is not None and (args.recon_register or args.recon_register_echoes):
+            p.error("--recon_transforms supplies the transforms: it does not go with --recon_register / --recon_register_echoes")
         args.reconstruct_args = {"fixed": args.recon_fixed, "res": args.recon_res, "transforms_dir": args.recon_transforms}
+        if args.recon_register:
+            args.reconstruct_args["register"] = True
+        if args.recon_register_echoes:
+            args.reconstruct_args["register_echoes"] = True
     args.build_mask_args = None
     if args.phantom_seeds is not None and not args.build_mask:
         p.error("--phantom_seeds has no effect without --build_mask phantom")

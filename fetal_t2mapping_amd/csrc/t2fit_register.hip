@@ -1,0 +1,306 @@
+// t2fit_register.hip -- gfx950 kernels and C ABI of the rigid registration's device half (include/t2fit.h:
+// t2fit_register_workspace_bytes, t2fit_register_sums_dev, t2fit_shrink_dev, t2fit_shrink_mask_dev).  Stands for the
+// metric evaluation inside the reference's registration_itk (utils/qmri_utils.py:167-221: correlation metric, masks,
+// linear interpolator); the optimizer stays on the host (fetal_t2mapping_amd/_register.py, which also states every
+// kernel here in numpy).
+//
+//   register_sums_kernel    a workgroup owns a brick of 64 x 4 x 8 fixed voxels: lanes along x (coalesced fixed and mask
+//                           reads; the eight moving taps of neighbouring lanes are neighbours along the image of the
+//                           fixed x axis), a wave per y, every lane walks its 8 voxels in z.  43 float64 accumulators
+//                           per lane; the wave adds them with a fixed xor butterfly (32, 16, .. 1: lane 0 holds the
+//                           halving tree), the four waves meet in LDS, and 43 lanes store the brick's slab.
+//   register_reduce_kernel  one pass of the tree over the slabs: a workgroup adds 256 consecutive values of one sum by
+//                           halving in LDS.  Passes repeat until one value per sum is left.
+//   shrink kernels          a pyramid level: the mean (the "any") of s^3 blocks, one thread per output voxel.
+// The order of every addition is a function of the sizes alone; there is no atomic anywhere.  Compiled with
+// -ffp-contract=off: every multiply and add rounds once, as numpy's do.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "t2fit_affine.h"
+#include "t2fit_error.h"
+#include "t2fit_support.h"
+
+namespace {
+
+using t2fit::align_up, t2fit::ceil_div, t2fit::kBlock;
+using t2fit::Affine, t2fit::Dims, t2fit::coord, t2fit::inside_axis, t2fit::clamp_index;
+
+constexpr int kBX = 64, kBY = 4, kBZ = 8;  // the brick; kBX lanes of a wave, kBY waves
+constexpr int kSums = T2FIT_REGISTER_SUMS;
+constexpr int kFan = 256;                  // values a workgroup of the reduction adds
+constexpr size_t kAlign = 256;
+static_assert(kBX == 64 && kBX * kBY == kBlock, "a wave per row of the brick");
+static_assert(kFan == kBlock, "a value per thread");
+
+struct SumsArgs {
+  const float* fixed;
+  const uint8_t* fixed_mask;
+  const float* moving;
+  const uint8_t* moving_mask;
+  Dims f, m;
+  Affine A;
+  int bricks_x, bricks_y;
+  int64_t n_bricks;
+  double* slabs;  // [kSums][n_bricks]
+};
+
+__device__ inline double lerp(double p, double q, double w) { return w == 0.0 ? p : p + w * (q - p); }
+
+__device__ inline double wave_butterfly(double v) {
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_xor(v, s, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(kBlock) void register_sums_kernel(const SumsArgs a) {
+  __shared__ double rows[kBY][kSums];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int t = blockIdx.x;
+  const int bx = t % a.bricks_x;
+  t /= a.bricks_x;
+  const int by = t % a.bricks_y, bz = t / a.bricks_y;
+  const int x = bx * kBX + lane, y = by * kBY + wave;
+  const bool column = x < a.f.nx && y < a.f.ny;
+  const Dims n = a.m;
+  double acc[kSums];
+#pragma unroll
+  for (int q = 0; q < kSums; ++q) acc[q] = 0.0;
+#pragma unroll 1
+  for (int k = 0; k < kBZ; ++k) {
+    const int z = bz * kBZ + k;
+    if (!column || z >= a.f.nz) continue;
+    const int64_t at = ((int64_t)z * a.f.ny + y) * a.f.nx + x;
+    if (a.fixed_mask[at] == 0) continue;
+    const double cx = coord(a.A, 0, x, y, z), cy = coord(a.A, 1, x, y, z), cz = coord(a.A, 2, x, y, z);
+    if (!(inside_axis(cx, n.nx) && inside_axis(cy, n.ny) && inside_axis(cz, n.nz))) continue;
+    const int qx = clamp_index(floor(cx + 0.5), n.nx), qy = clamp_index(floor(cy + 0.5), n.ny), qz = clamp_index(floor(cz + 0.5), n.nz);
+    if (a.moving_mask[((int64_t)qz * n.ny + qy) * n.nx + qx] == 0) continue;
+    const int x0 = clamp_index(floor(cx), n.nx), y0 = clamp_index(floor(cy), n.ny), z0 = clamp_index(floor(cz), n.nz);
+    double dx = cx - (double)x0, dy = cy - (double)y0, dz = cz - (double)z0;
+    dx = dx < 0.0 ? 0.0 : dx;
+    dy = dy < 0.0 ? 0.0 : dy;
+    dz = dz < 0.0 ? 0.0 : dz;
+    const int x1 = x0 + 1 < n.nx ? x0 + 1 : n.nx - 1, y1 = y0 + 1 < n.ny ? y0 + 1 : n.ny - 1, z1 = z0 + 1 < n.nz ? z0 + 1 : n.nz - 1;
+    const float* r00 = a.moving + ((int64_t)z0 * n.ny + y0) * n.nx;
+    const float* r01 = a.moving + ((int64_t)z0 * n.ny + y1) * n.nx;
+    const float* r10 = a.moving + ((int64_t)z1 * n.ny + y0) * n.nx;
+    const float* r11 = a.moving + ((int64_t)z1 * n.ny + y1) * n.nx;
+    const double v000 = r00[x0], v001 = r00[x1], v010 = r01[x0], v011 = r01[x1];
+    const double v100 = r10[x0], v101 = r10[x1], v110 = r11[x0], v111 = r11[x1];
+    const double l00 = lerp(v000, v001, dx), l01 = lerp(v010, v011, dx), l10 = lerp(v100, v101, dx), l11 = lerp(v110, v111, dx);
+    const double p0 = lerp(l00, l01, dy), p1 = lerp(l10, l11, dy);
+    const double m = lerp(p0, p1, dz);
+    double g[3];
+    g[0] = lerp(lerp(v001 - v000, v011 - v010, dy), lerp(v101 - v100, v111 - v110, dy), dz);
+    g[1] = lerp(l01 - l00, l11 - l10, dz);
+    g[2] = p1 - p0;
+    if (x1 == x0 || cx < 0.0) g[0] = 0.0;
+    if (y1 == y0 || cy < 0.0) g[1] = 0.0;
+    if (z1 == z0 || cz < 0.0) g[2] = 0.0;
+    const double f = (double)a.fixed[at];
+    const double u[3] = {(double)x, (double)y, (double)z};
+    acc[0] = acc[0] + 1.0;
+    acc[1] = acc[1] + f;
+    acc[2] = acc[2] + m;
+    acc[3] = acc[3] + f * f;
+    acc[4] = acc[4] + m * m;
+    acc[5] = acc[5] + f * m;
+#pragma unroll
+    for (int w = 0; w < 3; ++w) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const double wg = w == 0 ? g[c] : (w == 1 ? f * g[c] : m * g[c]);
+        const int q = 6 + 4 * (3 * w + c);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) acc[q + j] = acc[q + j] + wg * u[j];
+        acc[q + 3] = acc[q + 3] + wg;
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < kSums; ++q) {
+    const double s = wave_butterfly(acc[q]);
+    if (lane == 0) rows[wave][q] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < kSums) {
+    const int q = threadIdx.x;
+    a.slabs[(int64_t)q * a.n_bricks + blockIdx.x] = (rows[0][q] + rows[2][q]) + (rows[1][q] + rows[3][q]);
+  }
+}
+
+// out[q][b] = the halving sum of in[q][256 b .. 256 b + 255] (zeros beyond n); grid (n_out, kSums)
+__global__ __launch_bounds__(kBlock) void register_reduce_kernel(const double* __restrict__ in, int64_t n, double* __restrict__ out,
+                                                                 int64_t n_out) {
+  __shared__ double s[kFan];
+  const int tid = threadIdx.x;
+  const int64_t q = blockIdx.y, i = (int64_t)blockIdx.x * kFan + tid;
+  s[tid] = i < n ? in[q * n + i] : 0.0;
+  __syncthreads();
+#pragma unroll
+  for (int h = kFan / 2; h >= 1; h >>= 1) {
+    if (tid < h) s[tid] = s[tid] + s[tid + h];
+    __syncthreads();
+  }
+  if (tid == 0) out[q * n_out + blockIdx.x] = s[0];
+}
+
+__global__ __launch_bounds__(kBlock) void shrink_kernel(const float* __restrict__ src, Dims n, int s, Dims o, float* __restrict__ out) {
+  const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (v >= (int64_t)o.nz * o.ny * o.nx) return;
+  const int x = (int)(v % o.nx);
+  const int64_t r = v / o.nx;
+  const int y = (int)(r % o.ny), z = (int)(r / o.ny);
+  double acc = 0.0;
+  for (int dz = 0; dz < s; ++dz)
+    for (int dy = 0; dy < s; ++dy) {
+      const float* row = src + ((int64_t)(z * s + dz) * n.ny + (y * s + dy)) * n.nx + (int64_t)x * s;
+      for (int dx = 0; dx < s; ++dx) acc = acc + (double)row[dx];
+    }
+  out[v] = (float)(acc / (double)(s * s * s));
+}
+
+__global__ __launch_bounds__(kBlock) void shrink_mask_kernel(const uint8_t* __restrict__ src, Dims n, int s, Dims o,
+                                                             uint8_t* __restrict__ out) {
+  const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (v >= (int64_t)o.nz * o.ny * o.nx) return;
+  const int x = (int)(v % o.nx);
+  const int64_t r = v / o.nx;
+  const int y = (int)(r % o.ny), z = (int)(r / o.ny);
+  uint8_t any = 0;
+  for (int dz = 0; dz < s; ++dz)
+    for (int dy = 0; dy < s; ++dy) {
+      const uint8_t* row = src + ((int64_t)(z * s + dz) * n.ny + (y * s + dy)) * n.nx + (int64_t)x * s;
+      for (int dx = 0; dx < s; ++dx) any |= row[dx] != 0;
+    }
+  out[v] = any;
+}
+
+// ---- host --------------------------------------------------------------------------------------------------------
+constexpr int kMaxPasses = 8;
+constexpr int kMaxShrink = 32;
+
+struct Plan {
+  int bricks_x, bricks_y, bricks_z;
+  int n_pass;
+  int64_t pass_n[kMaxPasses];   // values per sum that enter pass p; pass_n[0] = the slabs
+  size_t pass_at[kMaxPasses];   // where they lie in the workspace
+  size_t total;
+};
+
+int sums_plan(const std::string& w, int fz, int fy, int fx, Plan* plan) {
+  if (t2fit::count_voxels(1, fz, fy, fx) < 0)
+    return t2fit::fail(T2FIT_E_INVALID, w + ": the fixed sizes must all be >= 1 and the volume at most 2^40 elements");
+  plan->bricks_x = ceil_div(fx, kBX), plan->bricks_y = ceil_div(fy, kBY), plan->bricks_z = ceil_div(fz, kBZ);
+  const int64_t bricks = (int64_t)plan->bricks_x * plan->bricks_y * plan->bricks_z;
+  if (bricks > INT32_MAX) return t2fit::fail(T2FIT_E_INVALID, w + ": the fixed volume has more than 2^31-1 bricks (the launch index is 32-bit)");
+  plan->n_pass = 0;
+  plan->total = 0;
+  for (int64_t n = bricks;; n = ceil_div(n, (int64_t)kFan)) {
+    plan->pass_n[plan->n_pass] = n;
+    plan->pass_at[plan->n_pass] = plan->total;
+    plan->total += align_up((size_t)n * kSums * sizeof(double), kAlign);
+    ++plan->n_pass;
+    if (n <= kFan) break;
+  }
+  return T2FIT_OK;
+}
+
+int shrink_check(const std::string& w, const void* src, const void* out, int nz, int ny, int nx, int s, Dims* o) {
+  if (!src || !out) return t2fit::fail(T2FIT_E_INVALID, w + ": src_dev / out_dev is NULL");
+  if (src == out) return t2fit::fail(T2FIT_E_INVALID, w + ": out_dev must not be src_dev");
+  if (t2fit::count_voxels(1, nz, ny, nx) < 0)
+    return t2fit::fail(T2FIT_E_INVALID, w + ": the sizes must all be >= 1 and the volume at most 2^40 elements");
+  if (s < 1 || s > kMaxShrink) return t2fit::fail(T2FIT_E_INVALID, w + ": the shrink factor s is outside 1..32");
+  if (nz / s < 1 || ny / s < 1 || nx / s < 1) return t2fit::fail(T2FIT_E_INVALID, w + ": s is larger than a size: the level would be empty");
+  *o = Dims{nz / s, ny / s, nx / s};
+  if (ceil_div((int64_t)o->nz * o->ny * o->nx, (int64_t)kBlock) > INT32_MAX)
+    return t2fit::fail(T2FIT_E_INVALID, w + ": the level has more than 2^39 elements");
+  return T2FIT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int t2fit_register_workspace_bytes(int fz, int fy, int fx, size_t* bytes) {
+  if (!bytes) return t2fit::fail(T2FIT_E_INVALID, "t2fit_register_workspace_bytes: bytes is NULL");
+  Plan plan;
+  const int rc = sums_plan("t2fit_register_workspace_bytes", fz, fy, fx, &plan);
+  if (rc != T2FIT_OK) return rc;
+  *bytes = plan.total;
+  return T2FIT_OK;
+}
+
+int t2fit_register_sums_dev(const float* fixed_dev, const uint8_t* fixed_mask_dev, int fz, int fy, int fx, const float* moving_dev,
+                            const uint8_t* moving_mask_dev, int mz, int my, int mx, const double* A, double* sums_dev,
+                            void* workspace_dev, size_t workspace_bytes, void* stream) {
+  const std::string w("t2fit_register_sums_dev");
+  if (!fixed_dev || !fixed_mask_dev || !moving_dev || !moving_mask_dev || !A || !sums_dev || !workspace_dev)
+    return t2fit::fail(T2FIT_E_INVALID, w + ": fixed_dev / fixed_mask_dev / moving_dev / moving_mask_dev / A / sums_dev / workspace_dev is NULL");
+  Plan plan;
+  const int rc = sums_plan(w, fz, fy, fx, &plan);
+  if (rc != T2FIT_OK) return rc;
+  if (t2fit::count_voxels(1, mz, my, mx) < 0)
+    return t2fit::fail(T2FIT_E_INVALID, w + ": the moving sizes must all be >= 1 and the volume at most 2^40 elements");
+  if (!t2fit::finite12(A)) return t2fit::fail(T2FIT_E_INVALID, w + ": A has a non-finite entry");
+  if ((reinterpret_cast<uintptr_t>(fixed_dev) & 3) || (reinterpret_cast<uintptr_t>(moving_dev) & 3))
+    return t2fit::fail(T2FIT_E_INVALID, w + ": fixed_dev / moving_dev is not aligned to 4 bytes");
+  if (reinterpret_cast<uintptr_t>(sums_dev) & 7) return t2fit::fail(T2FIT_E_INVALID, w + ": sums_dev is not aligned to 8 bytes");
+  if (reinterpret_cast<uintptr_t>(workspace_dev) & (kAlign - 1))
+    return t2fit::fail(T2FIT_E_INVALID, w + ": workspace_dev is not aligned to 256 bytes");
+  if (workspace_bytes < plan.total)
+    return t2fit::fail(T2FIT_E_INVALID, w + ": workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " +
+                                            std::to_string(plan.total) + " needed (t2fit_register_workspace_bytes)");
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace_dev);
+  SumsArgs a;
+  a.fixed = fixed_dev, a.fixed_mask = fixed_mask_dev, a.moving = moving_dev, a.moving_mask = moving_mask_dev;
+  a.f = Dims{fz, fy, fx}, a.m = Dims{mz, my, mx};
+  for (int i = 0; i < 12; ++i) a.A.m[i] = A[i];
+  a.bricks_x = plan.bricks_x, a.bricks_y = plan.bricks_y;
+  a.n_bricks = plan.pass_n[0];
+  a.slabs = reinterpret_cast<double*>(ws + plan.pass_at[0]);
+  hipLaunchKernelGGL(register_sums_kernel, dim3((unsigned)a.n_bricks), dim3(kBlock), 0, st, a);
+  for (int p = 0; p < plan.n_pass; ++p) {
+    const bool last = p + 1 == plan.n_pass;
+    const int64_t n_out = last ? 1 : plan.pass_n[p + 1];
+    double* out = last ? sums_dev : reinterpret_cast<double*>(ws + plan.pass_at[p + 1]);
+    hipLaunchKernelGGL(register_reduce_kernel, dim3((unsigned)n_out, kSums), dim3(kBlock), 0, st,
+                       (const double*)(ws + plan.pass_at[p]), plan.pass_n[p], out, n_out);
+  }
+  T2_HIP(hipGetLastError());
+  return T2FIT_OK;
+}
+
+int t2fit_shrink_dev(const float* src_dev, int nz, int ny, int nx, int s, float* out_dev, void* stream) {
+  const std::string w("t2fit_shrink_dev");
+  Dims o;
+  const int rc = shrink_check(w, src_dev, out_dev, nz, ny, nx, s, &o);
+  if (rc != T2FIT_OK) return rc;
+  if ((reinterpret_cast<uintptr_t>(src_dev) & 3) || (reinterpret_cast<uintptr_t>(out_dev) & 3))
+    return t2fit::fail(T2FIT_E_INVALID, w + ": src_dev / out_dev is not aligned to 4 bytes");
+  const int64_t n_out = (int64_t)o.nz * o.ny * o.nx;
+  hipLaunchKernelGGL(shrink_kernel, dim3((unsigned)ceil_div(n_out, (int64_t)kBlock)), dim3(kBlock), 0, (hipStream_t)stream, src_dev,
+                     Dims{nz, ny, nx}, s, o, out_dev);
+  T2_HIP(hipGetLastError());
+  return T2FIT_OK;
+}
+
+int t2fit_shrink_mask_dev(const uint8_t* src_dev, int nz, int ny, int nx, int s, uint8_t* out_dev, void* stream) {
+  const std::string w("t2fit_shrink_mask_dev");
+  Dims o;
+  const int rc = shrink_check(w, src_dev, out_dev, nz, ny, nx, s, &o);
+  if (rc != T2FIT_OK) return rc;
+  const int64_t n_out = (int64_t)o.nz * o.ny * o.nx;
+  hipLaunchKernelGGL(shrink_mask_kernel, dim3((unsigned)ceil_div(n_out, (int64_t)kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
+                     src_dev, Dims{nz, ny, nx}, s, o, out_dev);
+  T2_HIP(hipGetLastError());
+  return T2FIT_OK;
+}
+
+}  // extern "C"

@@ -23,36 +23,18 @@
 #include <cstdint>
 #include <string>
 
+#include "t2fit_affine.h"
 #include "t2fit_error.h"
 #include "t2fit_support.h"
 
 namespace {
 
 using t2fit::align_up, t2fit::ceil_div, t2fit::kBlock;
+using t2fit::Affine, t2fit::Dims, t2fit::coord, t2fit::inside_axis, t2fit::clamp_index, t2fit::finite12,
+    t2fit::count_voxels;
 constexpr int kPerThread = 2;
 constexpr int kBrick = kBlock * kPerThread;  // voxels of a workgroup's output brick
 constexpr size_t kAlign = 256;
-
-struct Affine {  // c_a = ((m[4a] ix + m[4a+1] iy) + m[4a+2] iz) + m[4a+3], a = 0 is x
-  double m[12];
-};
-
-struct Dims {
-  int nz, ny, nx;
-};
-
-__device__ inline double coord(const Affine& A, int a, int ix, int iy, int iz) {
-  return ((A.m[4 * a] * (double)ix + A.m[4 * a + 1] * (double)iy) + A.m[4 * a + 2] * (double)iz) + A.m[4 * a + 3];
-}
-
-__device__ inline bool inside_axis(double c, int n) { return c >= -0.5 && c < (double)n - 0.5; }
-
-__device__ inline int clamp_index(double f, int n) {
-  const double hi = (double)(n - 1);
-  f = f < 0.0 ? 0.0 : f;
-  f = f > hi ? hi : f;
-  return (int)f;
-}
 
 __device__ inline float integer_cast(double r) {  // an int16 pixel type: toward zero, saturating; NaN stays NaN
   r = trunc(r);
@@ -239,20 +221,6 @@ __global__ __launch_bounds__(kBlock) void reconstruct_kernel(const ReconArgs a) 
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------
-bool finite12(const double* A) {
-  for (int i = 0; i < 12; ++i)
-    if (!std::isfinite(A[i])) return false;
-  return true;
-}
-
-// voxels of n_vol volumes of (nz, ny, nx), or -1 when a size is < 1 or the count exceeds 2^40
-int64_t count_voxels(int n_vol, int nz, int ny, int nx) {
-  if (n_vol < 1 || nz < 1 || ny < 1 || nx < 1) return -1;
-  const int64_t plane = (int64_t)ny * nx, slabs = (int64_t)n_vol * nz;
-  if (slabs > ((int64_t)1 << 40) / plane) return -1;
-  return slabs * plane;
-}
-
 // the output axis whose step moves the source's x index most (ties: the lower axis)
 int lane_axis(const double* A) {
   int best = 0;

@@ -5,10 +5,14 @@ onto the ax grid and the three are averaged (run_reconstruct_volume, :359-391), 
 
     python -m fetal_t2mapping_amd.recon --path <qMRI root> --csv <log.csv ...> (--in_vivo | --in_vitro) (--lf | --hf)
 
-The registration of the reference (elastix, rigid) is not part of this package: ``--transforms DIR`` supplies rigid
-transforms as 4 x 4 text matrices (fixed point -> moving point, LPS millimetres) and a missing file is the identity,
-the reference's own reading of ``recon_1mm`` when nothing moved.  Each echo is reconstructed once: the reference runs
-its loop body for each of the three rows of an echo and writes the same file three times."""
+Rigid transforms of the moving stacks come from one of two places.  ``--transforms DIR`` supplies them as 4 x 4 text
+matrices (fixed point -> moving point, LPS millimetres); a missing file is the identity, the reference's own reading of
+``recon_1mm`` when nothing moved.  ``--register`` finds them on the GPU (``t2map.register.register_rigid``: the recipe of the
+reference's registration_itk, not elastix, which the reference calls; parity unpinned): per echo, each moving 1 mm
+volume onto the fixed one (utils/qmri_utils.py:82-136), and ``--write_transforms DIR`` saves them where
+``--transforms`` reads them.  ``--register_echoes`` registers every merged echo onto the first one and resamples it
+(:376-383).  Each echo is reconstructed once: the reference runs its loop body for each of the three rows of an echo and
+writes the same file three times."""
 from __future__ import annotations
 
 import argparse
@@ -26,24 +30,100 @@ in_dirname = "anat"
 resamp_dirname = "resamp_1mm"
 
 
-def transform_path(transforms_dir, acq, orientation):
-    """``<DIR>/<sub>_<ses>_<orientation>.txt``: the rigid transform of moving stack `orientation` of this (sub, ses)."""
-    return os.path.join(transforms_dir, f"{acq['sub']}_{acq['ses']}_{orientation}.txt")
+def transform_path(transforms_dir, acq, orientation, echo=False):
+    """``<DIR>/<sub>_<ses>_<orientation>.txt``: the rigid transform of moving stack `orientation` of this (sub, ses);
+    with ``echo`` ``<DIR>/<sub>_<ses>_te-<ms>_<orientation>.txt``: that of this echo alone."""
+    te = f"te-{int(round(acq['EchoTime'] * 1000))}_" if echo else ""
+    return os.path.join(transforms_dir, f"{acq['sub']}_{acq['ses']}_{te}{orientation}.txt")
 
 
 def load_transforms(transforms_dir, acq, fixed):
-    """{moving orientation: 4 x 4} for the files that exist under `transforms_dir` (None: no directory given)."""
+    """{moving orientation: 4 x 4} for the files that exist under `transforms_dir` (None: no directory given); the file
+    of the echo of `acq`, if there is one, goes before the file of the (sub, ses)."""
     out = {}
     if not transforms_dir:
         return out
     for o in _resample.moving_order(fixed):
-        path = transform_path(transforms_dir, acq, o)
-        if os.path.exists(path):
-            m = np.loadtxt(path, dtype=np.float64)
-            if m.shape != (4, 4) or not np.all(np.isfinite(m)):
-                raise ValueError(f"{path}: expected a finite 4 x 4 matrix")
-            out[o] = m
+        own = [transform_path(transforms_dir, acq, o, echo=True)] if "EchoTime" in acq else []
+        for path in own + [transform_path(transforms_dir, acq, o)]:
+            if os.path.exists(path):
+                m = np.loadtxt(path, dtype=np.float64)
+                if m.shape != (4, 4) or not np.all(np.isfinite(m)):
+                    raise ValueError(f"{path}: expected a finite 4 x 4 matrix")
+                out[o] = m
+                break
     return out
+
+
+def save_transforms(transforms_dir, acq, transforms):
+    """Write {orientation: 4 x 4} of the echo of `acq` where :func:`load_transforms` reads it, digits enough for the
+    float64 to come back bit for bit.  Returns the paths."""
+    os.makedirs(transforms_dir, exist_ok=True)
+    paths = []
+    for o, m in transforms.items():
+        paths.append(transform_path(transforms_dir, acq, o, echo=True))
+        np.savetxt(paths[-1], np.asarray(m, np.float64), fmt="%.17g")
+    return paths
+
+
+def register_stacks(stacks, geoms, *, fixed="ax", res=1.0, integer_cast=False, device=0, **register_args):
+    """{moving orientation: 4 x 4} of one echo: every stack ``(Z, Y, X)`` is resampled to its own ``res`` mm grid (stage 1)
+    and each moving volume ``H_m`` is registered onto the fixed one ``H_0`` (``t2map.register.register_rigid``)."""
+    order = [fixed] + _resample.moving_order(fixed)
+    hi = {o: t2map.resample_volume(stacks[o], geoms[o], res=res, integer_cast=integer_cast, device=device) for o in order}
+    return {o: t2map.register.register_rigid(hi[fixed][0], hi[o][0], hi[fixed][1], hi[o][1], device=device, **register_args).transform
+            for o in order[1:]}
+
+
+def _same_transforms(a, b):
+    return sorted(a) == sorted(b) and all(np.array_equal(a[o], b[o]) for o in a)
+
+
+def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False, transforms_dir=None, register=False,
+                 write_transforms=None, register_echoes=False, device=0):
+    """Stages 1 and 2 and the merge of the echoes of one batch (`acqs`: the fixed orientation's metadata row of every
+    echo).  The transforms of an echo are read (``transforms_dir``) or found (``register``); echoes with the same
+    transforms share a call, so without either the batch is one call.  ``register_echoes``: every merged echo but the
+    first is registered onto the first and resampled onto it by one more single stage.  Returns ``(float32 CUDA tensor
+    (n, Z, Y, X), header, transforms per echo)``."""
+    import torch
+
+    n = len(acqs)
+    dev = torch.device("cuda", device)
+    if register:
+        stacks = {o: torch.from_numpy(np.ascontiguousarray(stacks[o], np.float32)).to(dev) for o in stacks}
+        per_echo = [register_stacks({o: stacks[o][i] for o in stacks}, geoms, fixed=fixed, res=res, integer_cast=integer_cast,
+                                    device=device) for i in range(n)]
+        if write_transforms:
+            for acq, t in zip(acqs, per_echo):
+                save_transforms(write_transforms, acq, t)
+    else:
+        per_echo = [load_transforms(transforms_dir, acq, fixed) for acq in acqs]
+    groups = []
+    for i in range(n):
+        for g in groups:
+            if _same_transforms(per_echo[g[0]], per_echo[i]):
+                g.append(i)
+                break
+        else:
+            groups.append([i])
+    merged = None
+    for g in groups:
+        part = stacks if len(g) == n else {o: stacks[o][g] for o in stacks}
+        out, header = t2map.reconstruct_stacks(part, geoms, fixed=fixed, res=res, transforms=per_echo[g[0]],
+                                               integer_cast=integer_cast, device=device)
+        if len(g) == n:
+            merged = out
+        else:
+            merged = torch.empty((n,) + tuple(out.shape[1:]), dtype=out.dtype, device=out.device) if merged is None else merged
+            merged[g] = out
+    if register_echoes:
+        grid = _resample.as_geometry(header, tuple(merged.shape[1:]))
+        for i in range(1, n):
+            found = t2map.register.register_rigid(merged[0], merged[i], grid, grid, device=device)
+            merged[i] = t2map.resample_volume(merged[i], grid, like=grid, transform=found.transform,
+                                              integer_cast=integer_cast, device=device)[0]
+    return merged, header, per_echo
 
 
 def echo_groups(metadata):
@@ -108,11 +188,12 @@ def batch_inputs(sitk, batch, integer_cast=None):
 
 
 def process_recon(metadata, bids_path, *, fixed="ax", res=1.0, transforms_dir=None, write_resamp=False, denoise=True,
-                  integer_cast=None, device=0):
+                  integer_cast=None, register=False, write_transforms=None, register_echoes=False, device=0):
     """Reconstruct every echo of every (prj, sub, ses) of `metadata` that has the three orientations and write it.
     The echoes of a subject whose stacks share their geometry per orientation go through one call.  ``integer_cast``:
-    None keeps the pixel type as the reference does (cast when the stacks are int16 on disk).  Returns the paths
-    written under ``recon_1mm``."""
+    None keeps the pixel type as the reference does (cast when the stacks are int16 on disk).  ``register`` /
+    ``write_transforms`` / ``register_echoes``: see :func:`merge_echoes`.  Returns the paths written under
+    ``recon_1mm``."""
     import torch
 
     sitk = _sitk()
@@ -121,9 +202,8 @@ def process_recon(metadata, bids_path, *, fixed="ax", res=1.0, transforms_dir=No
         for batch in batches_of(read_echoes(sitk, bids_path, echoes, sub, ses)):
             t0 = time.time()
             stacks, geoms, cast = batch_inputs(sitk, batch, integer_cast)
-            transforms = load_transforms(transforms_dir, batch[0][1][fixed], fixed)
             print(f"===== Reconstruction: {prj}_{sub}_{ses}, TE {[int(it[0] * 1000) for it in batch]} ms, fixed {fixed}, "
-                  f"transforms {sorted(transforms) or 'identity'} =====")
+                  f"transforms {'registered' if register else (transforms_dir or 'identity')} =====")
             if write_resamp:  # the intermediate volumes of step 1, as run_resample_volume leaves them
                 for o in _resample.ORIENTATIONS:
                     hi, g = t2map.resample_volume(stacks[o], geoms[o], res=res, integer_cast=cast, device=device)
@@ -133,8 +213,9 @@ def process_recon(metadata, bids_path, *, fixed="ax", res=1.0, transforms_dir=No
                         path = get_img_path(bids_path, it[1][o], resamp_dirname)
                         sitk.WriteImage(img, path)
                         print(f"Image saved in : {path}")
-            merged, header = t2map.reconstruct_stacks(stacks, geoms, fixed=fixed, res=res, transforms=transforms,
-                                                      integer_cast=cast, device=device)
+            merged, header, _ = merge_echoes(stacks, geoms, [it[1][fixed] for it in batch], fixed=fixed, res=res,
+                                             integer_cast=cast, transforms_dir=transforms_dir, register=register,
+                                             write_transforms=write_transforms, register_echoes=register_echoes, device=device)
             if denoise:
                 merged = t2map.denoise_tv(merged, out=merged)
             torch.cuda.synchronize(merged.device)
@@ -190,7 +271,7 @@ def process_phantom_masks(metadata, bids_path, *, seeds=None, fixed="ax", thresh
 
 
 def reconstruct_subject(sitk, bids_path, sub_md, sub, ses, *, fixed="ax", res=1.0, transforms_dir=None, integer_cast=None,
-                        device=0):
+                        register=False, register_echoes=False, device=0):
     """cli.py --reconstruct: the echoes of one (sub, ses) (`sub_md`: its metadata rows) reconstructed in memory.  Every
     echo must have the three orientations and the echoes must share their grids.  Returns ``(volumes: list of (Z, Y, X)
     float32 arrays in EchoTime order, header)``."""
@@ -203,15 +284,15 @@ def reconstruct_subject(sitk, bids_path, sub_md, sub, ses, *, fixed="ax", res=1.
     if len(batches) != 1:
         raise ValueError(f"--reconstruct: the stacks of {sub}_{ses} do not lie on the same grids at every echo time")
     stacks, geoms, cast = batch_inputs(sitk, batches[0], integer_cast)
-    merged, header = t2map.reconstruct_stacks(stacks, geoms, fixed=fixed, res=res,
-                                              transforms=load_transforms(transforms_dir, ready[0][1][fixed], fixed),
-                                              integer_cast=cast, device=device)
+    merged, header, _ = merge_echoes(stacks, geoms, [it[1][fixed] for it in ready], fixed=fixed, res=res, integer_cast=cast,
+                                     transforms_dir=transforms_dir, register=register, register_echoes=register_echoes,
+                                     device=device)
     host = merged.cpu().numpy()
     return [host[i] for i in range(host.shape[0])], header
 
 
 def parse_arguments(argv=None):
-    """Flag set of run_qmri_reconstruction.py:93-112 plus what the registration-free reconstruction can be told."""
+    """Flag set of run_qmri_reconstruction.py:93-112 plus what this reconstruction can be told."""
     p = argparse.ArgumentParser(prog="fetal_t2mapping_amd.recon",
                                 description="resample three orthogonal stacks per echo to 1 mm and merge them on an MI355X")
     p.add_argument("--path", required=True, help="root of the qMRI tree (contains projects/ and dicom/logs/)")
@@ -228,6 +309,13 @@ def parse_arguments(argv=None):
     p.add_argument("--transforms", default=None, metavar="DIR",
                    help="directory of rigid transforms <sub>_<ses>_<orientation>.txt (4 x 4 text, fixed point -> moving "
                         "point); a missing file is the identity")
+    p.add_argument("--register", action="store_true",
+                   help="find the rigid transforms on the GPU: per echo, each moving 1 mm volume is registered onto the fixed "
+                        "one (correlation metric, masks from build_mask, 4/2/1 pyramid; not elastix); off by default")
+    p.add_argument("--write_transforms", default=None, metavar="DIR",
+                   help="with --register: save the transforms as <sub>_<ses>_te-<ms>_<orientation>.txt, which --transforms reads")
+    p.add_argument("--register_echoes", action="store_true",
+                   help="after the merge, register every echo onto the first one and resample it; off by default")
     p.add_argument("--write_resamp", action="store_true", help="also write the 1 mm volume of every stack under resamp_1mm/")
     p.add_argument("--no_denoise", action="store_true",
                    help="skip the TV-Chambolle pass the reference applies to the merged volume (denoising=True)")
@@ -253,6 +341,10 @@ def parse_arguments(argv=None):
         p.error("--res must be a positive number")
     if args.transforms is not None and not os.path.isdir(args.transforms):
         p.error(f"--transforms {args.transforms!r} is not a directory")
+    if args.transforms is not None and (args.register or args.register_echoes):
+        p.error("--transforms supplies the transforms: it does not go with --register / --register_echoes, which find them")
+    if args.write_transforms is not None and not args.register:
+        p.error("--write_transforms has no effect without --register")
     return args
 
 
@@ -265,7 +357,8 @@ def main(argv=None):
     csv_path = os.path.join(args.path, "dicom/logs/")
     metadata = set_metadata(csv_path, args.csv, bool(args.lf))
     process_recon(metadata, bids_path, fixed=args.fixed, res=args.res, transforms_dir=args.transforms,
-                  write_resamp=args.write_resamp, denoise=not args.no_denoise, device=args.device)
+                  write_resamp=args.write_resamp, denoise=not args.no_denoise, register=args.register,
+                  write_transforms=args.write_transforms, register_echoes=args.register_echoes, device=args.device)
     if args.phantom_masks:
         process_phantom_masks(metadata, bids_path, seeds=args.seeds, fixed=args.fixed, device=args.device)
 

@@ -383,8 +383,8 @@ int t2fit_tv_denoise_dev(const t2fit_tv_params *p, const float *in_dev, float *o
  * Steps 1 and 2 of the reference's run_qmri_reconstruction.py: every acquired thick-slice stack (ax / cor / sag, one per
  * echo time) is resampled to a 1 mm grid with linear interpolation (utils/qmri_utils.py resample_volume, :62-80), the
  * two moving ones are resampled onto the fixed one's grid after a rigid registration, and the three are averaged
- * (reconstruct_vol_trilinear, :82-136).  The registration is not part of this library: rigid transforms enter through
- * the affines below (identity = the reference's "no motion" reading).  fetal_t2mapping_amd/_resample.py restates
+ * (reconstruct_vol_trilinear, :82-136).  Rigid transforms enter through the affines below (identity = the reference's
+ * "no motion" reading); the registration that finds them is further down (t2fit_register_sums_dev).  fetal_t2mapping_amd/_resample.py restates
  * everything here in numpy, geometry included; the device output is bit-identical to it and the same from call to call.
  *
  * Volumes are (nz, ny, nx) with x fastest.  Geometry stays on the host: a stage is described by 12 doubles A (row-major
@@ -522,6 +522,62 @@ int t2fit_seed_labels_dev(const int32_t *seeds, const int32_t *labels, int n_see
 /* out[v] = lut[in[v]] where 0 <= in[v] < n_lut, else 0 (int32 -> int32, all device pointers; out_dev == in_dev is
  * allowed).  n_vox in 1..2^39-1.  Asynchronous on `stream`. */
 int t2fit_relabel_dev(const int32_t *in_dev, int64_t n_vox, const int32_t *lut_dev, int n_lut, int32_t *out_dev, void *stream);
+
+/* ---- Rigid registration: the correlation metric's sums and the pyramid levels -------------------------------------------
+ * The device half of a rigid registration built from the ingredients of the reference's registration_itk
+ * (utils/qmri_utils.py:167-221): correlation metric, fixed and moving masks, linear interpolator.  The metric's
+ * arithmetic, the Euler transform and the regular-step gradient descent are host code
+ * (fetal_t2mapping_amd/_register.py, which also restates everything here in numpy; the device results equal it bit for
+ * bit).  Parity with elastix, which the reference calls, is not pinned.  Additive to ABI 5: four new
+ * symbols (look them up to detect them).
+ *
+ * A is the index affine of t2fit_resample_dev: 12 doubles, fixed index (ix, iy, iz) -> continuous moving index c, in the
+ * order of evaluation written there.  A fixed voxel COUNTS iff fixed_mask != 0, c passes the inside test
+ * (-0.5 <= c_a < n_a - 0.5 on all axes) and the moving mask at the nearest node floor(c_a + 0.5), clamped, is != 0.  For
+ * a voxel that counts: f = the fixed sample; m = the float64 interpolant of T2FIT_INTERP_LINEAR (clamped lower node,
+ * replicated upper node on the rim, x then y then z as lo + d (hi - lo), a zero weight returns lo), not rounded to
+ * float32; g_a = dm/dc_a = the difference of the two neighbours along a, interpolated along the other two axes with the
+ * same weights and rule, and 0 where m is flat along a (the upper neighbour is the clamped lower one, or c_a < 0).
+ * sums[43], float64:
+ *   [0] N  [1] sum f  [2] sum m  [3] sum f f  [4] sum m m  [5] sum f m
+ *   [6 + 4 (3 w + a) + j] sum (w g_a) u_j     w in (1, f, m), a in (x, y, z), u = (ix, iy, iz, 1)
+ *   [42] reserved: +0.0 (N, the 5 moments and the 36 gradient sums are 42 numbers; the array keeps 43 slots)
+ * Every product rounds once (w g_a first, then u_j; u_3 = 1 is no multiplication), no fused multiply-add; a voxel that
+ * does not count adds +0.0.  N = 0 leaves 43 zeros (the caller decides what that means).  The volumes must be finite.
+ *
+ * THE SUMMATION TREE is part of the definition and a function of (fz, fy, fx) alone -- not of the data, the device or
+ * the launch.  The fixed volume is cut into bricks of 64 (x) x 4 (y) x 8 (z) voxels, padded with zeros.  In a brick,
+ * column (x, y) adds its 8 voxels in z order starting from 0.0; the 64 columns of a row are added by halving
+ * (v[i] + v[i + 32] for i < 32, then 16, .. 1); the 4 rows by halving ((r0 + r2) + (r1 + r3)): the brick's slab.  The
+ * slabs, in (bz, by, bx) order, bx fastest, are reduced in passes: each group of 256 consecutive values, the last one
+ * padded with zeros, is added by halving (128, 64, .. 1); passes repeat until one value is left (at least one pass).
+ * No floating-point atomics.
+ *
+ * t2fit_register_workspace_bytes: with n_0 = ceil(fx / 64) ceil(fy / 4) ceil(fz / 8) slabs and n_{p+1} = ceil(n_p / 256)
+ * while n_p > 256, the sum over the passes of up(43 * 8 * n_p), up(v) = v rounded up to 256.  Plain arithmetic, no
+ * device. */
+#define T2FIT_REGISTER_SUMS 43
+int t2fit_register_workspace_bytes(int fz, int fy, int fx, size_t *bytes);
+
+/* fixed_dev: float32 [fz fy fx]; fixed_mask_dev: uint8, same shape; moving_dev / moving_mask_dev likewise [mz my mx];
+ * A: HOST pointer, read before the call returns; sums_dev: device float64 [43]; workspace_dev: at least
+ * t2fit_register_workspace_bytes bytes, aligned to 256 (the slabs and the passes' values live there).  One launch for
+ * the slabs and one per pass.  Asynchronous on `stream`; no allocation, copy or synchronisation.  Checked before HIP is
+ * touched (T2FIT_E_INVALID and a message): a NULL pointer, a size < 1, more than 2^40 elements in a volume, more than
+ * 2^31-1 bricks, a non-finite entry of A, volumes not aligned to 4 bytes, sums_dev not aligned to 8, a workspace that is
+ * misaligned or too small. */
+int t2fit_register_sums_dev(const float *fixed_dev, const uint8_t *fixed_mask_dev, int fz, int fy, int fx,
+                            const float *moving_dev, const uint8_t *moving_mask_dev, int mz, int my, int mx, const double *A,
+                            double *sums_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* A pyramid level of integer shrink factor s (1..32): out is [nz / s][ny / s][nx / s] (integer division: whole blocks
+ * only, the ragged edge is dropped).  t2fit_shrink_dev: the mean of each s^3 block -- a float64 sum in (dz, dy, dx)
+ * order from 0.0, divided by s^3, one rounding to float32.  t2fit_shrink_mask_dev: 1 where any voxel of the block is
+ * != 0, else 0.  The level's grid has s times the spacing and its origin at the centre of the first block.
+ * Asynchronous on `stream`.  Checked before HIP is touched: NULL or equal pointers, a size < 1, s outside 1..32 or
+ * larger than a size, float pointers not aligned to 4 bytes. */
+int t2fit_shrink_dev(const float *src_dev, int nz, int ny, int nx, int s, float *out_dev, void *stream);
+int t2fit_shrink_mask_dev(const uint8_t *src_dev, int nz, int ny, int nx, int s, uint8_t *out_dev, void *stream);
 
 /* Kernel timing for benchmarks (no reference counterpart).  With timing enabled (t2fit_set_timing(1)) every
  * t2fit_volume_dev call of this thread records HIP events around its fit kernel on the launch stream.
