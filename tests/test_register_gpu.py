@@ -1,7 +1,9 @@
 """The rigid registration's device half (csrc/t2fit_register.hip) against its numpy statement
 (fetal_t2mapping_amd/_register.py), bit for bit: the 43 sums over sizes prime to the brick, several bricks, emptied
-bricks, a volume pushed outside and nothing at all; the pyramid levels; the whole registration against the statement's;
-raw calls on a caller's stream; recon.py --register on files.  tests/test_register_host.py covers what needs no device."""
+bricks, a volume pushed outside and nothing at all, two reduction passes with a ragged last group, degenerate and edge
+geometry, unaligned pointers; and against the sums restated from their definition (register_cases.reference_sums), which
+is all that holds the three-pass case; the pyramid levels; the whole registration against the statement's; raw calls on
+a caller's stream; recon.py --register on files.  tests/test_register_host.py covers what needs no device."""
 import ctypes as C
 import os
 
@@ -26,21 +28,56 @@ def t2():
     return t2
 
 
-def _case(name):
-    """(fixed, moving, A, fixed mask, moving mask) of a named case."""
-    rng = np.random.default_rng(31)
-    fshape, mshape = ((40, 48, 70), (37, 50, 66)) if name == "bricks" else ((19, 23, 37), (21, 18, 41))
-    fg = R.Geometry(fshape[::-1], (1.0, 1.1, 1.2), tuple(-0.5 * np.array(fshape[::-1])), K.OBLIQUE.ravel())
-    mg = R.Geometry(mshape[::-1], (1.1, 1.0, 0.9), tuple(-0.5 * np.array(mshape[::-1])), (K.rot(1, 4.0) @ K.OBLIQUE).ravel())
-    shift = {"outside": (14.0, -9.0, 6.0), "nothing": (400.0, 0.0, 0.0)}.get(name, (0.4, -0.7, 0.3))
-    a = R.index_affine(fg, mg, K.rigid((3.0, -2.0, 4.0), shift))
-    fixed = rng.normal(400, 120, fshape).astype(np.float32)
-    moving = rng.normal(400, 120, mshape).astype(np.float32)
-    fmask = (rng.random(fshape) < 0.8).astype(np.uint8)
-    mmask = (rng.random(mshape) < 0.9).astype(np.uint8)
-    if name == "empty_bricks":  # whole bricks of 64 x 4 x 8 without a voxel, and a mask that ends inside a brick
-        fmask[:8], fmask[:, 4:13], fmask[9:, :, 30:] = 0, 0, 0
-    return fixed, moving, a, fmask, mmask
+_case = K.case
+
+
+def _place(t, offset):
+    """A copy of the numpy array ``t`` in device memory that starts ``offset`` bytes past a 256-byte boundary:
+    ``(keep-alive tensor, pointer)``."""
+    import torch
+
+    raw = np.ascontiguousarray(t).view(np.uint8).ravel()
+    buf = torch.empty(raw.size + 512, dtype=torch.uint8, device="cuda")
+    start = (-buf.data_ptr()) % 256 + offset
+    buf[start:start + raw.size].copy_(torch.from_numpy(raw.copy()))
+    assert (buf.data_ptr() + start) % 256 == offset % 256
+    return buf, buf.data_ptr() + start
+
+
+def _raw_sums(name, offsets=(0, 0, 0, 0)):
+    """t2fit_register_sums_dev on a caller's stream and buffers; the workspace is exactly t2fit_register_workspace_bytes
+    long and filled with NaN bytes, so a pass that reads a value no kernel wrote shows.  ``offsets``: bytes past a
+    256-byte boundary of the fixed, fixed-mask, moving and moving-mask pointers."""
+    import torch
+
+    from fetal_t2mapping_amd._lib import load
+
+    lib = load()
+    fixed, moving, a, fmask, mmask = K.case(name)
+    need = C.c_size_t(0)
+    assert lib.t2fit_register_workspace_bytes(*fixed.shape, C.byref(need)) == 0 and need.value == G.workspace_bytes(fixed.shape)
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        keep = [_place(v, o) for v, o in zip((fixed, fmask, moving, mmask), offsets)]
+        ws = torch.full((need.value + 256,), 0xFF, dtype=torch.uint8, device="cuda")
+        ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+        ws = ws[:ws_ptr - ws.data_ptr() + need.value]
+        sums = torch.full((43,), np.nan, dtype=torch.float64, device="cuda")
+        A = (C.c_double * 12)(*np.asarray(a).ravel())
+        assert lib.t2fit_register_sums_dev(keep[0][1], keep[1][1], *fixed.shape, keep[2][1], keep[3][1], *moving.shape, A,
+                                           sums.data_ptr(), ws_ptr, need.value, C.c_void_p(stream.cuda_stream)) == 0
+    stream.synchronize()
+    return sums.cpu().numpy()
+
+
+def _device_sums(t2, name):
+    fixed, moving, a, fmask, mmask = K.case(name)
+    return t2.register.registration_sums(fixed, moving, a, fixed_mask=fmask, moving_mask=mmask)
+
+
+def _assert_bits(got, want, name):
+    diff = np.flatnonzero(K.bits(got) != K.bits(want))
+    assert diff.size == 0, (name, diff, got[diff], want[diff])
 
 
 @pytest.mark.parametrize("name", ["prime", "bricks", "empty_bricks", "outside", "nothing"])
@@ -53,6 +90,8 @@ def test_sums_are_bit_equal_to_the_statement_and_repeat(t2, name):
     diff = np.flatnonzero(K.bits(got) != K.bits(want))
     assert diff.size == 0, (name, diff, got[diff], want[diff])
     assert got.tobytes() == again.tobytes()
+    if name != "nothing":
+        K.assert_within_reference(got, name)  # independent of the statement: how far the kernel may ever drift
     n_all = fmask.sum()
     if name == "nothing":  # N = 0: zeros from the raw call, an error -- not a NaN transform -- from the registration
         assert got.tobytes() == np.zeros(43).tobytes()
@@ -71,6 +110,113 @@ def test_masks_default_to_all_ones_and_tensors_are_taken(t2):
     want = G.registration_sums(fixed, moving, a)
     got = t2.register.registration_sums(torch.from_numpy(fixed).cuda(), torch.from_numpy(moving).cuda(), a)
     assert np.array_equal(K.bits(got), K.bits(want))
+
+
+@pytest.mark.parametrize("name", K.TWO_PASS)
+def test_two_reduction_passes_with_a_ragged_last_group(t2, name):
+    """774 slabs reduce as [774, 4] (the last group of the first pass holds 6 values), 257 as [257, 2] (one value): the
+    second pass, its workspace offset, the stride of an intermediate pass and the zero fill beyond n all run."""
+    fixed, _, _, fmask, _ = K.case(name)
+    slabs = int(np.prod(G.brick_counts(fixed.shape)))
+    passes = G.pass_sizes(slabs)
+    print(f"{name}: fixed {fixed.shape}, {slabs} slabs, passes {passes}")
+    assert passes == {"tail774": [774, 4], "tail257": [257, 2]}[name]
+    assert np.all(K.counted_per_slab(name)[slabs // 256 * 256:] > 0)  # the ragged group is not a group of zeros
+    want = K.statement_sums(name)
+    got, again, raw = _device_sums(t2, name), _device_sums(t2, name), _raw_sums(name)
+    _assert_bits(got, want, name)
+    assert got.tobytes() == again.tobytes()
+    _assert_bits(raw, want, name)  # on a caller's stream, the workspace NaN before the call
+    K.assert_within_reference(got, name)
+    assert 1000 < got[0] < 0.6 * fmask.sum() and np.all(got[1:42] != 0) and got[42] == 0
+
+
+def test_three_reduction_passes_against_the_reference(t2):
+    """(2035, 1034, 3): 255 x 259 x 1 = 66045 slabs, passes [66045, 258, 2].  The numpy statement pads every brick to 64
+    lanes and is too slow here, so no bit-equality is claimed: the device is held to the reference under the tolerance
+    of the statement.  The fixed mask is sparse, but every group of 256 slabs of the first pass, and so every value of
+    the second and the third, has voxels that count."""
+    name = "three_pass"
+    fixed = K.case(name)[0]
+    slabs = int(np.prod(G.brick_counts(fixed.shape)))
+    assert G.brick_counts(fixed.shape) == (255, 259, 1) and G.pass_sizes(slabs) == [66045, 258, 2]
+    per_slab = K.counted_per_slab(name)
+    groups = np.add.reduceat(per_slab, np.arange(0, slabs, 256))
+    assert per_slab[0] > 0 and per_slab[-1] > 0 and groups.size == 258 and np.all(groups > 0)
+    got = _raw_sums(name)
+    print(f"{name}: {slabs} slabs, passes {G.pass_sizes(slabs)}, {per_slab.sum()} voxels count, at least {groups.min()} per group")
+    K.assert_within_reference(got, name)
+    assert got[0] == per_slab.sum() > 10000 and np.all(got[1:42] != 0) and got[42] == 0
+    assert _raw_sums(name).tobytes() == got.tobytes()
+
+
+@pytest.mark.parametrize("name", K.DEGENERATE + ("integer_eps",))
+def test_edge_geometry_is_bit_equal_to_the_statement(t2, name):
+    """A moving axis of one voxel, fixed volumes smaller than a brick down to one voxel, a second x-brick of one lane,
+    one exact brick, whole-voxel translations next to Inf and NaN, coordinates exactly on the rim."""
+    want = K.statement_sums(name)
+    got = _device_sums(t2, name)
+    if name == "integer_eps":  # off the nodes by 2^-40 the non-finite nodes have a weight: the same sums are lost
+        assert np.array_equal(np.isfinite(got), np.isfinite(want)) and not np.all(np.isfinite(got))
+        _assert_bits(got[np.isfinite(got)], want[np.isfinite(want)], name)
+        return
+    _assert_bits(got, want, name)
+    assert np.all(np.isfinite(got)) and got[0] == K.counted_per_slab(name).sum()
+    K.assert_within_reference(got, name)
+    _assert_bits(_raw_sums(name), want, name)
+    if name.startswith("moving_"):
+        assert got[0] > 5000
+
+
+def test_unaligned_volumes_and_masks(t2):
+    """Volumes 4 bytes past a 256-byte boundary and masks at odd addresses (all the ABI asks of them): byte for byte the
+    result of the aligned call."""
+    for name in ("prime", "fixed_9x6x65"):
+        aligned = _raw_sums(name)
+        _assert_bits(aligned, K.statement_sums(name), name)
+        assert _raw_sums(name, offsets=(4, 1, 260, 3)).tobytes() == aligned.tobytes()
+        assert _raw_sums(name, offsets=(252, 255, 4, 129)).tobytes() == aligned.tobytes()
+
+
+@pytest.mark.parametrize("s", K.PYRAMID_FACTORS)
+def test_pyramid_levels_at_odd_factors_and_the_limits(t2, s):
+    """s = 3 and 5 divide by 27 and 125, which rounds; s = 1 copies; s = 32 is the largest the ABI takes.  Raw calls and
+    DevicePyramid.level against the statement bit for bit, and -- independently of it -- against the exactly summed block
+    means: at most 1 float32 ulp from the correctly rounded mean (tests/test_register_host.py derives the bound)."""
+    import torch
+
+    from fetal_t2mapping_amd._gpu_register import DevicePyramid
+    from fetal_t2mapping_amd._lib import load
+
+    lib = load()
+    v, m = K.pyramid_case(s)
+    shape = G.level_shape(v.shape, s)
+    tv, tm = torch.from_numpy(v).cuda(), torch.from_numpy(m).cuda()
+    ov = torch.full(shape, np.nan, dtype=torch.float32, device="cuda")
+    om = torch.full(shape, 7, dtype=torch.uint8, device="cuda")
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert lib.t2fit_shrink_dev(tv.data_ptr(), *v.shape, s, ov.data_ptr(), st) == 0
+    assert lib.t2fit_shrink_mask_dev(tm.data_ptr(), *m.shape, s, om.data_ptr(), st) == 0
+    lv, lm = DevicePyramid(v, m, v, m, torch.device("cuda", 0)).level(s)[:2]
+    want_v, want_m = G.shrink(v, s), G.shrink_mask(m, s)
+    for got_v, got_m in ((ov, om), (lv, lm)):
+        assert tuple(got_v.shape) == tuple(got_m.shape) == shape
+        assert np.array_equal(got_v.cpu().numpy().view(np.uint32), want_v.view(np.uint32))
+        assert np.array_equal(got_m.cpu().numpy(), want_m)
+    ulps = np.abs(K.ordered(ov.cpu().numpy()) - K.ordered(K.block_means(s)))
+    print(f"s = {s}: level {shape}, {np.count_nonzero(ulps)} of {ulps.size} block means are not the correctly rounded one")
+    assert ulps.max() <= 1
+    assert 0 < int(om.sum().item()) < om.numel() and set(np.unique(om.cpu().numpy())) == {0, 1}
+
+
+def test_registration_with_an_odd_level_equals_the_statement(t2):
+    fixed, moving, g, fmask, mmask = K.recovery_pair()
+    kw = dict(fixed_mask=fmask, moving_mask=mmask, levels=(3, 1), max_iter=25)
+    want = G.register_rigid(fixed, moving, g, g, **kw)
+    got = t2.register.register_rigid(fixed, moving, g, g, **kw)
+    assert got.parameters.tobytes() == want.parameters.tobytes() and got.transform.tobytes() == want.transform.tobytes()
+    assert got.iterations == want.iterations and got.stops == want.stops and got.metric == want.metric
+    assert got.iterations[0] > 0 and got.iterations[1] > 0
 
 
 @pytest.mark.parametrize("s", [2, 4])

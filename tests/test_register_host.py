@@ -1,6 +1,7 @@
 """The rigid registration's numpy statement (fetal_t2mapping_amd/_register.py) and what needs no device: the gradient of
 the metric against differences of the metric, the identity, two recoveries of a known transform, counting / masks / rim
-by hand, pyramid shapes, the summation tree, the ABI's refusals, the driver's flags and the transform files.
+by hand, the 43 sums against their restatement in extended precision (register_cases.reference_sums), pyramid shapes and
+block means, the summation tree, the ABI's refusals, the driver's flags and the transform files.
 tests/test_register_gpu.py holds the device path against this statement."""
 import ctypes as C
 import math
@@ -176,6 +177,78 @@ def test_the_summation_tree_adds_every_term_once():
         assert abs(s[q] - exact) <= 1e-12 * scale, q
     # more than one pass: 300 slabs of ones
     assert np.array_equal(G.reduce_slabs(np.ones((43, 300))), np.full(43, 300.0))
+    # two passes whose first ends in a ragged group, on real slabs: against the sums restated from the definition
+    for name, bricks, passes in (("tail774", (3, 258, 1), [774, 4]), ("tail257", (1, 257, 1), [257, 2])):
+        shape = K.case(name)[0].shape
+        assert G.brick_counts(shape) == bricks and G.pass_sizes(int(np.prod(bricks))) == passes
+        assert np.all(K.counted_per_slab(name)[passes[0] // 256 * 256:] > 0)  # every slab of the ragged group is something
+        K.assert_within_reference(K.statement_sums(name), name)
+
+
+@pytest.mark.parametrize("name", K.REFERENCE_CASES)
+def test_the_statement_equals_the_sums_restated_from_the_definition(name):
+    """register_cases.reference_sums shares the float64 coordinates with the statement and nothing else: eight-tap weight
+    products in extended precision on a padded volume instead of nested float64 lerps, the counted voxels gathered, every
+    sum exact.  ``|s - ref| <= TOL * scale`` per sum (scale: the sum of the absolute terms) and the count exactly.
+
+    Measured, the statement's largest ``|s - ref| / scale`` per case: prime 2.2e-16, bricks 1.9e-16, empty_bricks
+    1.8e-16, outside 1.7e-16, tail774 3.7e-18, tail257 2.2e-16, moving_x1 2.2e-16, moving_y1 1.5e-16, moving_z1 1.8e-16,
+    fixed_1x1x1 4.6e-16 (one voxel: a single term's roundings), fixed_3x2x5 1.7e-16, fixed_9x6x65 2.1e-16, fixed_8x4x64
+    2.4e-17, integer 1.9e-16, half_rim 1.4e-16.  The largest is 4.6e-16; TOL is 16 times it, 7.4e-15.  The largest N is
+    57 340, so TOL * N < 1e-9: a voxel dropped or counted twice changes sum 0 by 1 and the others by about 1 / N of their
+    scale, far above the bar."""
+    fixed, _, _, fmask, _ = K.case(name)
+    s = K.statement_sums(name)
+    assert K.TOL == 16 * 4.6e-16
+    K.assert_within_reference(s, name)
+    if name in ("prime", "bricks", "empty_bricks", "outside") + K.TWO_PASS:  # the non-trivial cases of the device tests
+        assert 1000 < s[0] < 0.6 * fmask.sum() and np.all(s[1:42] != 0) and s[42] == 0
+
+
+def test_the_rim_and_degenerate_cases_are_what_they_claim():
+    # a moving axis of one voxel: thousands count, the interpolant is flat along it (its 12 gradient sums are exactly 0)
+    for axis, name in enumerate(("moving_x1", "moving_y1", "moving_z1")):
+        s = K.statement_sums(name)
+        assert K.case(name)[1].shape[2 - axis] == 1 and s[0] > 5000
+        flat = [6 + 4 * (3 * w + axis) + j for w in range(3) for j in range(4)]
+        assert np.all(s[flat] == 0) and np.all(np.delete(s[1:42], np.array(flat) - 1) != 0)
+    assert K.statement_sums("fixed_1x1x1")[0] == 1 and K.statement_sums("fixed_3x2x5")[0] == 30
+    # half_rim: c = i - 0.5; the voxels on c = -0.5 count, those on c = n - 0.5 do not
+    fixed, moving, a, fmask, mmask = K.case("half_rim")
+    iz, iy, ix, c = K.counted_voxels(fixed.shape, moving.shape, a, fmask, mmask)
+    assert (ix == 0).any() and (iy == 0).any() and (iz == 0).any()
+    assert ix.max() == moving.shape[2] - 1 and iy.max() == moving.shape[1] - 1 and iz.max() == moving.shape[0] - 1
+    assert fmask[-1].any() and fmask[:, -1].any() and fmask[:, :, -1].any()  # they were there to be refused
+    # integer: the non-finite nodes are masked, their lower edge and corner neighbours and upper neighbours count, and
+    # nothing non-finite reaches a sum; off the nodes by 2^-40 it does, in the statement as in the reference
+    fixed, moving, a, fmask, mmask = K.case("integer")
+    iz, iy, ix, c = K.counted_voxels(fixed.shape, moving.shape, a, fmask, mmask)
+    at = set(zip((iz + int(a[2, 3])).tolist(), (iy + int(a[1, 3])).tolist(), (ix + int(a[0, 3])).tolist()))  # moving nodes hit
+    touched = 0
+    for z, y, x, v in K.NON_FINITE_NODES:
+        assert not np.isfinite(moving[z, y, x]) and mmask[z, y, x] == 0 and (z, y, x) not in at
+        lower = [(z - dz, y - dy, x - dx) for dz in (0, 1) for dy in (0, 1) for dx in (0, 1) if dz + dy + dx >= 2]
+        touched += sum(p in at for p in lower)
+    assert touched >= 8  # voxels that count and have a non-finite node among their eight taps, at weight 0
+    assert np.all(np.isfinite(K.statement_sums("integer"))) and K.statement_sums("integer")[0] == len(iz)
+    off, (ref, _) = K.statement_sums("integer_eps"), K.reference("integer_eps")
+    assert off[0] == ref[0] == len(iz) and np.array_equal(np.isfinite(off), np.isfinite(ref)) and not np.all(np.isfinite(off))
+
+
+@pytest.mark.parametrize("s", K.PYRAMID_FACTORS)
+def test_block_means_are_the_correctly_rounded_ones(s):
+    """The statement adds a block's float32 values in float64 in a fixed order and divides: at most s^3 + 1 roundings of
+    2^-53 each, 4e-12 relative at s = 32, against half a float32 ulp of 6e-8.  The float32 result is therefore one of the
+    two float32 neighbours of the exact mean: the correctly rounded one, or -- when the exact mean lies within 4e-12
+    relative of a tie -- the one next to it.  The bar is 1 ulp; measured: 0 of 16169, 504, 84 and 2 values differ."""
+    v, m = K.pyramid_case(s)
+    got, want = G.shrink(v, s), K.block_means(s)
+    assert got.shape == want.shape == G.level_shape(v.shape, s) and all(n % s for n in v.shape) == (s > 1)
+    ulps = np.abs(K.ordered(got) - K.ordered(want))
+    print(f"s = {s}: {np.count_nonzero(ulps)} of {ulps.size} block means are not the correctly rounded one")
+    assert ulps.max() <= 1
+    lm = G.shrink_mask(m, s)
+    assert 0 < lm.sum() < lm.size
 
 
 # ---- the ABI, without a device ---------------------------------------------------------------------------------------
@@ -198,11 +271,13 @@ def test_symbols_workspace_arithmetic_and_refusals_without_a_device(lib):
     assert lib.t2fit_abi_version() == 5 and all(hasattr(lib, n) for n in _abi.REGISTER_SYMBOLS)
     need = C.c_size_t(0)
     up = lambda v: (v + 255) // 256 * 256
-    for shape, slabs in (((19, 23, 37), 3 * 6 * 1), ((40, 48, 70), 5 * 12 * 2), ((256, 256, 256), 32 * 64 * 4)):
+    for shape, slabs in (((19, 23, 37), 3 * 6 * 1), ((40, 48, 70), 5 * 12 * 2), ((256, 256, 256), 32 * 64 * 4),
+                         ((19, 1030, 5), 774), ((5, 1027, 7), 257), ((2035, 1034, 3), 66045)):
         assert lib.t2fit_register_workspace_bytes(*shape, C.byref(need)) == 0
         passes = G.pass_sizes(slabs)
         assert need.value == sum(up(43 * 8 * n) for n in passes) == G.workspace_bytes(shape), shape
     assert G.pass_sizes(32 * 64 * 4) == [8192, 32]
+    assert G.pass_sizes(774) == [774, 4] and G.pass_sizes(257) == [257, 2] and G.pass_sizes(66045) == [66045, 258, 2]
     assert lib.t2fit_register_workspace_bytes(4, 4, 4, None) == _abi.E_INVALID
     assert lib.t2fit_register_workspace_bytes(4, 0, 4, C.byref(need)) == _abi.E_INVALID and ">= 1" in _err(lib)
 
