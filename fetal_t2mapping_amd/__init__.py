@@ -10,7 +10,8 @@ from .t2map import (BootMaps, BootStats, RoiStats, T2Maps, bootstrap_volume, com
                     estimate_background_sigma, fit_table, fit_volume, fit_voxel, fit_voxels, fit_voxels_trace, label_stats,
                     make_config, reconstruct_stacks, resample_volume, roi_erode, roi_frame, roi_stats, roi_table,
                     set_fit_params, stack_mask_flatten, synth_replica, union_mask_dev)
-from .t2map import register  # the rigid registration: register.register_rigid, register.registration_sums
+from .t2map import register  # the registrations: register.register_rigid, register.register_affine, register.registration_sums
+from .t2map import atlas  # the atlas-label stage: atlas.atlas_labels, atlas.extract_brain
 from .t2map import (binary_close, binary_dilate, binary_erode, binary_open, binary_threshold, build_mask, fill_holes,
                     mask_from_labels, phantom_labels, phantom_mask, relabel, seed_labels, synthseg_to_feta)
 
@@ -19,4 +20,5 @@ __all__ = ["BootMaps", "BootStats", "RoiStats", "T2Maps", "bootstrap_volume", "c
            "make_config", "philox4x32_10", "reconstruct_stacks", "resample_volume", "roi_erode", "roi_frame", "roi_stats", "roi_table", "set_fit_params",
            "stack_mask_flatten", "synth_replica", "union_mask_dev",
            "binary_close", "binary_dilate", "binary_erode", "binary_open", "binary_threshold", "build_mask", "fill_holes",
-           "mask_from_labels", "phantom_labels", "phantom_mask", "relabel", "seed_labels", "synthseg_to_feta", "register"]
+           "mask_from_labels", "phantom_labels", "phantom_mask", "relabel", "seed_labels", "synthseg_to_feta", "register",
+           "atlas"]

@@ -69,6 +69,7 @@ MORPH_UNBOUNDED = 1  # flags bit
 MORPH_F32, MORPH_I32, MORPH_U8 = 0, 1, 2
 
 REGISTER_SUMS = 43
+REGISTER_MAX_BINS = 64
 
 # every symbol include/t2fit.h declares: (name, restype, argtypes)
 _P = C.c_void_p
@@ -117,6 +118,12 @@ SYMBOLS = [
                                           C.POINTER(C.c_double), _P, _P, C.c_size_t, _P]),
     ("t2fit_shrink_dev", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     ("t2fit_shrink_mask_dev", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    ("t2fit_register_bin_dev", C.c_int, [_P, C.c_int64, C.c_double, C.c_double, C.c_int, _P, _P]),
+    ("t2fit_register_binned_workspace_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    ("t2fit_register_binned_sums_dev", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
+                                                 C.POINTER(C.c_double), C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    ("t2fit_register_sums_lut_dev", C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
+                                              C.POINTER(C.c_double), _P, _P, C.c_size_t, _P]),
     ("t2fit_set_timing", C.c_int, [C.c_int]),
     ("t2fit_set_reserve_cus", C.c_int, [C.c_int]),
     ("t2fit_kernel_ms", C.c_double, [C.c_int]),
@@ -135,7 +142,9 @@ MORPH_SYMBOLS = ("t2fit_morph_workspace_bytes", "t2fit_binary_threshold_dev", "t
                  "t2fit_seed_labels_dev", "t2fit_relabel_dev")
 ADDITIVE = BOOT_SYMBOLS + TV_SYMBOLS + RECON_SYMBOLS + MORPH_SYMBOLS
 REGISTER_SYMBOLS = ("t2fit_register_workspace_bytes", "t2fit_register_sums_dev", "t2fit_shrink_dev", "t2fit_shrink_mask_dev")
-LOOKED_UP = ADDITIVE + REGISTER_SYMBOLS
+ATLAS_SYMBOLS = ("t2fit_register_bin_dev", "t2fit_register_binned_workspace_bytes", "t2fit_register_binned_sums_dev",
+                 "t2fit_register_sums_lut_dev")
+LOOKED_UP = ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

@@ -1,0 +1,51 @@
+"""Atlas labels on a subject's grid with the registration's sums and the resampling on the GPU;
+:mod:`fetal_t2mapping_amd._atlas` states the stage in numpy."""
+import numpy as np
+
+from . import _atlas, _gpu_register, _resample
+from ._gpu import is_tensor, pick_device, volume
+from ._gpu_morph import build_mask
+from ._gpu_resample import resample_volume
+
+
+def extract_brain(vol, mask, *, device=0):
+    """``sitk.Mask`` (the reference's ``extract_brain``, utils/qmri_utils.py:953-974): ``vol`` where ``mask`` is not 0, zero
+    elsewhere, float32.  numpy in, numpy out; a CUDA tensor in, a tensor out.  A selection, no arithmetic."""
+    import torch
+
+    if not (is_tensor(vol) or is_tensor(mask)):
+        return _atlas.extract_brain(vol, mask)
+    dev = pick_device((vol, mask), device)
+    v, m = volume(vol, torch.float32, dev, "vol"), volume(mask, torch.uint8, dev, "mask")
+    if v.shape != m.shape:
+        raise ValueError("extract_brain takes a (Z, Y, X) volume and a mask of its shape")
+    return torch.where(m != 0, v, torch.zeros((), dtype=torch.float32, device=dev))
+
+
+def atlas_labels(subject, subject_geom, template, template_geom, atlases, *, mask=None, bins=32, dof=12, levels=(4, 2, 1),
+                 max_iter=100, init="centroids", device=0):
+    """The reference's ``build_jhu_ho_labels`` (utils/qmri_utils.py:1011-1037) without FSL: ``subject`` (float32
+    ``(Z, Y, X)``, e.g. the first-echo reconstruction) is brain-extracted with ``mask`` (None: :func:`build_mask`), the
+    ``template`` (e.g. MNI152 T1; its mask is ``template > 0``) is registered onto it by
+    ``register.register_affine(metric='cr')`` with ``dof`` degrees of freedom and ``bins`` bins, and the found transform
+    resamples the template (linear) and every volume of ``atlases`` ({name: integer labels on the template's grid}) with
+    nearest-neighbour interpolation (t2fit_resample_dev, int32, 0 outside) onto the subject's grid.  Returns ``(warped
+    template float32, {name: int32 labels}, Registration)`` as numpy arrays; ``Registration.transform`` is the 4 x 4
+    (subject point -> template point, LPS mm -- not FSL's convention).  Equal to :func:`_atlas.atlas_labels`.  Parity with
+    flirt is not pinned: the cost and the transform model are its, the optimizer and the (absent) search are not."""
+    import torch
+
+    dev = pick_device((subject, template, mask), device)
+    template_host = template.cpu().numpy() if is_tensor(template) else np.asarray(template, np.float32)
+    atlases = _atlas.check_atlases({n: (a.cpu().numpy() if is_tensor(a) else a) for n, a in dict(atlases).items()}, template_host.shape)
+    s, t = volume(subject, torch.float32, dev, "subject"), volume(template, torch.float32, dev, "template")
+    fmask = build_mask(s, device=dev.index) if mask is None else volume(mask, torch.uint8, dev, "mask")
+    brain = extract_brain(s, fmask)
+    sg, tg = _resample.as_geometry(subject_geom, tuple(s.shape)), _resample.as_geometry(template_geom, tuple(t.shape))
+    found = _gpu_register.register_affine(brain, t, sg, tg, metric="cr", bins=bins, dof=dof, fixed_mask=fmask,
+                                          moving_mask=(t > 0).to(torch.uint8), levels=levels, max_iter=max_iter, init=init,
+                                          device=dev.index)
+    warped = resample_volume(t, tg, like=sg, transform=found.transform)[0].cpu().numpy()
+    labels = {n: resample_volume(torch.from_numpy(lab).to(dev), tg, like=sg, transform=found.transform, interp="nearest",
+                                 default=0)[0].cpu().numpy() for n, lab in atlases.items()}
+    return warped, labels, found

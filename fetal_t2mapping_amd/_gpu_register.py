@@ -1,5 +1,5 @@
-"""Rigid registration with the metric's sums on the GPU; :mod:`fetal_t2mapping_amd._register` states the sums and the
-pyramid in numpy and holds the metric arithmetic and the optimizer, which run here unchanged."""
+"""Rigid and affine registration with the metric's sums on the GPU; :mod:`fetal_t2mapping_amd._register` states the sums
+and the pyramid in numpy and holds the metric arithmetic and the optimizers, which run here unchanged."""
 import ctypes as C
 
 import numpy as np
@@ -60,6 +60,73 @@ class DevicePyramid:
             return self.out.cpu().numpy()  # (waits: the workspace and the tensors of the level are no longer in use)
 
 
+def _bin_dev(lib, vol, lo, scale, n_bins, dev):
+    import torch
+
+    out = torch.empty(tuple(vol.shape), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.t2fit_register_bin_dev(vol.data_ptr(), vol.numel(), float(lo), float(scale), int(n_bins), out.data_ptr(),
+                                         current_stream()))
+    return out
+
+
+def _bins_tensor(bins, dev):
+    """A uint8 bin volume (values kept, unlike a mask) on ``dev``."""
+    import torch
+
+    if not (torch.is_tensor(bins) and bins.dtype == torch.uint8) and not (isinstance(bins, np.ndarray) and bins.dtype == np.uint8):
+        raise ValueError("bins is a uint8 (Z, Y, X) volume")
+    return volume(bins, torch.uint8, dev, "bins")
+
+
+class DeviceAffinePyramid(DevicePyramid):
+    """:class:`DevicePyramid` and the correlation ratio's steps, the methods of :class:`_register.HostAffinePyramid`.
+    ``bins`` keeps a level's uint8 bin volume on the device (t2fit_register_bin_dev, once per level; the level's range
+    inside its mask is read on the host, one copy of the level per level).  ``cr_sums`` queues
+    t2fit_register_binned_sums_dev (N_b, S_b and the table) and t2fit_register_sums_lut_dev on the current stream -- no
+    host step in between -- and copies ``2 n_bins + 43`` doubles back, which waits for the stream."""
+
+    def __init__(self, fixed, fixed_mask, moving, moving_mask, dev):
+        super().__init__(fixed, fixed_mask, moving, moving_mask, dev)
+        self.lib = require(*(_abi.REGISTER_SYMBOLS + _abi.ATLAS_SYMBOLS))
+        self._bufs = {}
+
+    def bins(self, level, n_bins):
+        lo, scale = _register.bin_range(level[0].cpu().numpy(), level[1].cpu().numpy(), n_bins)
+        return _bin_dev(self.lib, level[0], lo, scale, n_bins, self.dev)
+
+    def _buffers(self, shape, n_bins):
+        """(results [2 B + B + 43] float64, binned workspace tensor, pointer, bytes) of a fixed shape and bin count."""
+        import torch
+
+        key = (tuple(shape), int(n_bins))
+        if key not in self._bufs:
+            need = C.c_size_t(0)
+            check(self.lib.t2fit_register_binned_workspace_bytes(shape[0], shape[1], shape[2], int(n_bins), C.byref(need)))
+            self._bufs = {key: (torch.empty(3 * n_bins + _abi.REGISTER_SUMS, dtype=torch.float64, device=self.dev),)
+                          + workspace(need.value, self.dev) + (need.value,)}
+        return self._bufs[key]
+
+    def cr_sums(self, level, bins, n_bins, A):
+        import torch
+
+        _, fmask, moving, mmask, _, ptr, nbytes = level
+        n_bins = int(n_bins)
+        a = np.ascontiguousarray(A, np.float64).reshape(12)
+        a_ptr = a.ctypes.data_as(C.POINTER(C.c_double))
+        with torch.cuda.device(self.dev):
+            out, _, bptr, bbytes = self._buffers(fmask.shape, n_bins)
+            binned, lut, sums = out.data_ptr(), out.data_ptr() + 16 * n_bins, out.data_ptr() + 24 * n_bins
+            st = current_stream()
+            check(self.lib.t2fit_register_binned_sums_dev(bins.data_ptr(), fmask.data_ptr(), *fmask.shape, moving.data_ptr(),
+                                                          mmask.data_ptr(), *moving.shape, a_ptr, n_bins, binned, lut, bptr, bbytes, st))
+            check(self.lib.t2fit_register_sums_lut_dev(bins.data_ptr(), lut, n_bins, fmask.data_ptr(), *fmask.shape, moving.data_ptr(),
+                                                       mmask.data_ptr(), *moving.shape, a_ptr, sums, ptr, nbytes, st))
+            host = out.cpu().numpy()  # (waits)
+        self.lut = host[2 * n_bins:3 * n_bins]
+        return host[:2 * n_bins], host[3 * n_bins:]
+
+
 def _ones_like(t):
     import torch
 
@@ -105,3 +172,78 @@ def register_rigid(fixed, moving, fixed_geom, moving_geom, *, fixed_mask=None, m
     levels = _register.check_levels(levels, tuple(f.shape), tuple(m.shape))
     centre, scales = _register.mask_centre_and_scales(pyramid.full[1].cpu().numpy(), fg)  # one mask to the host, once
     return _register.optimize(pyramid, fg, mg, centre, scales, levels=levels, max_iter=max_iter, init=init)
+
+
+def _affine_pyramid(fixed, moving, fixed_mask, moving_mask, device):
+    import torch
+
+    dev = pick_device((fixed, moving, fixed_mask, moving_mask), device)
+    f, m = volume(fixed, torch.float32, dev, "fixed"), volume(moving, torch.float32, dev, "moving")
+    return DeviceAffinePyramid(f, _ones_like(f) if fixed_mask is None else fixed_mask, m,
+                               _ones_like(m) if moving_mask is None else moving_mask, dev)
+
+
+def bin_volume(vol, lo, scale, n_bins, *, device=0):
+    """uint8 CUDA tensor ``clamp(floor((float64(vol) - lo) * scale), 0, n_bins - 1)``, NaN -> 0 (t2fit_register_bin_dev):
+    bit-identical to :func:`_register.bin_volume`."""
+    import torch
+
+    dev = pick_device((vol,), device)
+    return _bin_dev(require(*_abi.ATLAS_SYMBOLS), volume(vol, torch.float32, dev, "vol"), lo, scale, n_bins, dev)
+
+
+def binned_sums(bins, moving, A, n_bins, *, fixed_mask=None, moving_mask=None, device=0, return_lut=False):
+    """``N_b`` then ``S_b`` (float64 ``[2 n_bins]``, numpy) of ``moving`` sampled at ``A`` over the uint8 ``bins`` volume
+    of the fixed grid; with ``return_lut`` also ``lut[b] = S_b / N_b``.  Bit-identical to :func:`_register.binned_sums`
+    and :func:`_register.lut_from_binned`, and the same from call to call.  Waits for the stream."""
+    import torch
+
+    dev = pick_device((bins, moving, fixed_mask, moving_mask), device)
+    b = _bins_tensor(bins, dev)
+    pyramid = _affine_pyramid(torch.zeros(tuple(b.shape), dtype=torch.float32, device=dev), moving, fixed_mask, moving_mask, device)
+    binned, _ = pyramid.cr_sums(pyramid.level(1), b, n_bins, A)
+    return (binned, pyramid.lut) if return_lut else binned
+
+
+def registration_sums_lut(bins, lut, moving, A, *, fixed_mask=None, moving_mask=None, device=0):
+    """The 43 sums with ``f = lut[bins]`` (float64, not rounded to float32; t2fit_register_sums_lut_dev): bit-identical
+    to :func:`_register.registration_sums_lut`.  Waits for the stream."""
+    import torch
+
+    dev = pick_device((bins, moving, fixed_mask, moving_mask), device)
+    b = _bins_tensor(bins, dev)
+    table = torch.from_numpy(np.ascontiguousarray(lut, np.float64).ravel()).to(dev)
+    pyramid = _affine_pyramid(torch.zeros(tuple(b.shape), dtype=torch.float32, device=dev), moving, fixed_mask, moving_mask, device)
+    _, fmask, m, mmask, _, ptr, nbytes = pyramid.level(1)
+    a = np.ascontiguousarray(A, np.float64).reshape(12)
+    with torch.cuda.device(dev):
+        check(pyramid.lib.t2fit_register_sums_lut_dev(b.data_ptr(), table.data_ptr(), table.numel(), fmask.data_ptr(), *fmask.shape,
+                                                      m.data_ptr(), mmask.data_ptr(), *m.shape, a.ctypes.data_as(C.POINTER(C.c_double)),
+                                                      pyramid.out.data_ptr(), ptr, nbytes, current_stream()))
+        return pyramid.out.cpu().numpy()
+
+
+def register_affine(fixed, moving, fixed_geom, moving_geom, *, metric="cr", bins=32, dof=12, fixed_mask=None, moving_mask=None,  # noqa: A002
+                    levels=(4, 2, 1), max_iter=100, init=None, device=0):
+    """Register ``moving`` onto ``fixed`` with ``dof`` in (6, 7, 9, 12) degrees of freedom: ``x' = R K (x - centre) +
+    centre + t`` (:func:`_register.compose_affine`: Euler angles, translation, log scales, shears) by the regular-step
+    descent of :func:`register_rigid`.  ``metric='cr'``: the correlation ratio of the moving samples given the fixed
+    volume binned into ``bins`` (1..64) bins -- what the reference asks of FSL's flirt for the T1 template onto a T2w
+    volume; each level's bins span that level's fixed samples inside its mask.  ``'ncc'``: the squared correlation of
+    :func:`register_rigid`.  ``init``: None, 12 parameters, or 'centroids' (start at the translation between the masks'
+    centroids: a template and a subject do not share a frame).  Masks None: :func:`build_mask` on the device.  Returns a
+    :class:`_register.Registration` with 12 parameters; they, the iteration counts and the stops equal
+    :func:`_register.register_affine`'s.  Parity with flirt (another optimizer, another search) is not pinned."""
+    import torch
+
+    dev = pick_device((fixed, moving, fixed_mask, moving_mask), device)
+    f, m = volume(fixed, torch.float32, dev, "fixed"), volume(moving, torch.float32, dev, "moving")
+    pyramid = DeviceAffinePyramid(f, build_mask(f, device=dev.index) if fixed_mask is None else fixed_mask,
+                                  m, build_mask(m, device=dev.index) if moving_mask is None else moving_mask, dev)
+    fg, mg = _resample.as_geometry(fixed_geom, tuple(f.shape)), _resample.as_geometry(moving_geom, tuple(m.shape))
+    levels = _register.check_levels(levels, tuple(f.shape), tuple(m.shape))
+    fmask_host = pyramid.full[1].cpu().numpy()
+    centre, scales = _register.affine_centre_and_scales(fmask_host, fg)
+    p0 = _register.affine_init(init, fmask_host, fg, pyramid.full[3].cpu().numpy() if isinstance(init, str) else None, mg)
+    return _register.optimize_affine(pyramid, fg, mg, centre, scales, metric=metric, bins=bins, dof=dof, levels=levels,
+                                     max_iter=max_iter, init=p0)

@@ -30,7 +30,11 @@ count contributes +0.0.  The volumes must be finite.
 starting from 0.0; the 64 columns of a row are added by halving (``v[:32] + v[32:]``, then 16, .. 1); the 4 rows by
 halving.  That is the brick's slab.  The slabs, in ``(bz, by, bx)`` order, are reduced in passes: groups of 256
 consecutive values (the last group padded with zeros) are each added by halving; passes repeat until one value is left
-(at least one pass)."""
+(at least one pass).
+
+**The affine registration across contrasts** (``register_affine``: the correlation ratio over a binned fixed volume, 6 to
+12 degrees of freedom; what the atlas-label stage of :mod:`_atlas` runs) is the last part of this module and builds on
+everything above without changing it."""
 from __future__ import annotations
 
 import numpy as np
@@ -389,3 +393,291 @@ def target_registration_error(found, true, mask, geom):
     pts = idx @ m.T + o
     d = pts @ (np.asarray(found)[:3, :3] - np.asarray(true)[:3, :3]).T + (np.asarray(found)[:3, 3] - np.asarray(true)[:3, 3])
     return float(np.sqrt(np.max(np.sum(d * d, axis=1))))
+
+
+# ---- correlation ratio: the cross-contrast metric of the affine registration ---------------------------------------------
+# The statement of include/t2fit.h's t2fit_register_bin_dev, t2fit_register_binned_sums_dev and
+# t2fit_register_sums_lut_dev.  The fixed volume is binned once per level; N_b and S_b are the count and the sum of the
+# interpolated moving samples over the counted voxels of bin b, by the tree of the 43 sums; lut[b] = S_b / N_b; the 43
+# sums with f = lut[bin] give, through metric(), C = CR - 1 and dC/dA with the voxel set held fixed (lut maximises the
+# correlation over the functions constant on each bin, so its own derivative drops out).
+MAX_BINS = 64
+_correlation = metric  # (register_affine has a ``metric`` argument)
+
+
+def _check_bins(n_bins):
+    n_bins = int(n_bins)
+    if not 1 <= n_bins <= MAX_BINS:
+        raise ValueError(f"n_bins is in 1..{MAX_BINS}, got {n_bins}")
+    return n_bins
+
+
+def bin_range(fixed, fixed_mask, n_bins):
+    """``(lo, scale)`` of a level: ``lo`` / ``hi`` the smallest / largest fixed sample inside the mask,
+    ``scale = n_bins / (hi - lo)`` in float64, 0 when ``hi == lo``.  ValueError on an empty mask."""
+    inside = np.asarray(fixed, np.float32)[np.asarray(fixed_mask) != 0]
+    if inside.size == 0:
+        raise ValueError("the fixed mask is empty")
+    lo, hi = float(inside.min()), float(inside.max())
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError("the fixed volume is not finite inside its mask")
+    return lo, (float(_check_bins(n_bins)) / (hi - lo) if hi > lo else 0.0)
+
+
+def bin_volume(vol, lo, scale, n_bins):
+    """uint8 ``clamp(floor((float64(vol) - lo) * scale), 0, n_bins - 1)``, each operation rounding once; NaN gives 0."""
+    n_bins = _check_bins(n_bins)
+    with np.errstate(all="ignore"):
+        b = np.floor((np.asarray(vol, np.float32).astype(np.float64) - float(lo)) * float(scale))
+        return np.where(b > 0.0, np.minimum(b, float(n_bins - 1)), 0.0).astype(np.uint8)
+
+
+def _bins_and_masks(bins, fixed_mask, moving, moving_mask, n_bins):
+    bins = np.minimum(np.asarray(bins, np.uint8), np.uint8(_check_bins(n_bins) - 1))
+    if bins.ndim != 3:
+        raise ValueError("bins is a (Z, Y, X) uint8 volume")
+    _, fmask, moving, mmask = _volumes(np.zeros(bins.shape, np.float32), fixed_mask, moving, moving_mask)
+    return bins, fmask, moving, mmask
+
+
+def _tree(shape, n_rows, terms):
+    """The summation tree over ``n_rows`` kinds of terms of a fixed volume of ``shape``; ``terms(z0, nzc)`` gives the
+    float64 ``(n_rows, nzc, fy, fx)`` of the planes ``z0 .. z0 + nzc``."""
+    fz, fy, fx = shape
+    nbz, nby, nbx = brick_counts(shape)
+    out = np.zeros((n_rows, nbz, nby, nbx), np.float64)
+    with np.errstate(all="ignore"):
+        for bz in range(nbz):
+            z0 = bz * BZ
+            nzc = min(BZ, fz - z0)
+            t = terms(z0, nzc)
+            for r0 in range(0, n_rows, 16):  # (rows in groups: the padded copy of a thin, long volume is large)
+                r = min(16, n_rows - r0)
+                pad = np.zeros((r, BZ, nby * BY, nbx * BX), np.float64)
+                pad[:, :nzc, :fy, :fx] = t[r0:r0 + r]
+                acc = np.zeros(pad.shape[:1] + pad.shape[2:], np.float64)
+                for k in range(BZ):
+                    acc = acc + pad[:, k]
+                acc = _halve(acc.reshape(r, nby, BY, nbx, BX))
+                out[r0:r0 + r, bz] = _halve(np.moveaxis(acc, 2, -1))
+    return reduce_slabs(out.reshape(n_rows, -1))
+
+
+def binned_sums(bins, moving, A, n_bins, fixed_mask=None, moving_mask=None):
+    """float64 ``[2 n_bins]``: ``N_b`` then ``S_b``.  A counted voxel adds ``(1.0, m)`` to its own bin and +0.0 to every
+    other; counting rule, ``m`` and tree as for the 43 sums.  A bin byte above ``n_bins - 1`` counts as ``n_bins - 1``."""
+    bins, fmask, moving, mmask = _bins_and_masks(bins, fixed_mask, moving, moving_mask, n_bins)
+    a = np.asarray(A, np.float64).reshape(3, 4)
+    zero = np.zeros(bins.shape, np.float32)
+    which = np.arange(n_bins, dtype=np.uint8)[:, None, None, None]
+
+    def terms(z0, nzc):
+        t = _terms(zero, fmask, moving, mmask, a, z0, nzc)
+        own = bins[None, z0:z0 + nzc] == which
+        return np.concatenate([np.where(own, t[0][None], 0.0), np.where(own, t[2][None], 0.0)])
+
+    return _tree(bins.shape, 2 * n_bins, terms)
+
+
+def lut_from_binned(binned):
+    """``lut[b] = S_b / N_b`` where ``N_b > 0``, else 0.0."""
+    b = np.asarray(binned, np.float64)
+    n, s = b[:b.size // 2], b[b.size // 2:]
+    with np.errstate(all="ignore"):
+        return np.where(n > 0.0, s / np.where(n > 0.0, n, 1.0), 0.0)
+
+
+def registration_sums_lut(bins, lut, moving, A, fixed_mask=None, moving_mask=None):
+    """The 43 sums with ``f = lut[bins]``, a float64 that is not rounded to float32: the tree of
+    :func:`registration_sums` over the same terms."""
+    lut = np.asarray(lut, np.float64).ravel()
+    bins, fmask, moving, mmask = _bins_and_masks(bins, fixed_mask, moving, moving_mask, lut.size)
+    a = np.asarray(A, np.float64).reshape(3, 4)
+    f = lut[bins]
+    return _tree(bins.shape, N_SUMS, lambda z0, nzc: _terms(f, fmask, moving, mmask, a, z0, nzc))
+
+
+def cr_metric(binned, sums_lut):
+    """``(CR, dC/dA [3, 4])``: the correlation ratio ``1 + C`` of the moving samples given the binned fixed ones, and
+    the derivative with the voxel set held fixed -- :func:`metric` of the 43 sums with ``f = lut[bin]``.  ``binned`` must
+    be the ``N_b, S_b`` those sums' table came from (their counts must add up to the sums' N)."""
+    b = np.asarray(binned, np.float64)
+    if b.ndim != 1 or b.size % 2 or float(np.sum(b[:b.size // 2])) != float(np.asarray(sums_lut)[0]):
+        raise ValueError("binned is [2 n_bins] and its counts add up to the N of sums_lut")
+    c, dc = metric(sums_lut)
+    return 1.0 + c, dc
+
+
+# ---- affine transform: rotation, translation, log scales, shears ---------------------------------------------------------
+N_AFFINE = 12
+DOFS = (6, 7, 9, 12)
+
+
+def _stretch(p):
+    """K = [[e^s0, h01, h02], [0, e^s1, h12], [0, 0, e^s2]] and its derivatives with respect to p[6:12]."""
+    e = np.exp(p[6:9])
+    k = np.array([[e[0], p[9], p[10]], [0.0, e[1], p[11]], [0.0, 0.0, e[2]]], np.float64)
+    dk = []
+    for i in range(3):
+        d = np.zeros((3, 3))
+        d[i, i] = e[i]
+        dk.append(d)
+    for i, j in ((0, 1), (0, 2), (1, 2)):
+        d = np.zeros((3, 3))
+        d[i, j] = 1.0
+        dk.append(d)
+    return k, dk
+
+
+def compose_affine(p, centre):
+    """4 x 4 (fixed point -> moving point, LPS millimetres) of ``p = (rx, ry, rz, tx, ty, tz, s0, s1, s2, h01, h02,
+    h12)``: ``x' = R K (x - centre) + centre + t`` with R of :func:`compose` and K upper triangular, ``e^s`` on its
+    diagonal."""
+    p, centre = np.asarray(p, np.float64), np.asarray(centre, np.float64)
+    r, _ = _rotations(p)
+    k, _ = _stretch(p)
+    t = np.eye(4)
+    t[:3, :3] = r @ k
+    t[:3, 3] = centre - t[:3, :3] @ centre + p[3:6]
+    return t
+
+
+def affine_parameter_gradient(dc_da, p, centre, fixed_geom, moving_geom):
+    """dC/dp [12] from dC/dA: ``A = Mm^-1 [L Mf | L (of - centre) + centre + t - om]`` is linear in ``L = R K`` and t."""
+    p = np.asarray(p, np.float64)
+    mf, of = _resample._index_to_point(fixed_geom)
+    mm, _ = _resample._index_to_point(moving_geom)
+    h = np.linalg.inv(mm).T @ np.asarray(dc_da, np.float64)
+    d_l = h[:, :3] @ mf.T + np.outer(h[:, 3], of - np.asarray(centre, np.float64))
+    r, dr = _rotations(p)
+    k, dk = _stretch(p)
+    return np.array([np.sum(d_l * (d @ k)) for d in dr] + [h[0, 3], h[1, 3], h[2, 3]] + [np.sum(d_l * (r @ d)) for d in dk])
+
+
+def affine_centre_and_scales(fixed_mask, fixed_geom):
+    """The centre and the rotation / translation scales of :func:`mask_centre_and_scales`, and by the same rule (the mean
+    squared shift of a mask point under a unit change) for ``s_a`` the mean square of component ``a`` of (mask point -
+    centre), for ``h_ij`` that of component ``j``.  A vanishing scale is 1."""
+    centre, rigid = mask_centre_and_scales(fixed_mask, fixed_geom)
+    idx = np.argwhere(np.asarray(fixed_mask) != 0)[:, ::-1].astype(np.float64)
+    m, o = _resample._index_to_point(fixed_geom)
+    ms = np.mean((idx @ m.T + o - centre) ** 2, axis=0)
+    scales = np.concatenate([rigid, ms, [ms[1], ms[2], ms[2]]])
+    return centre, np.where(scales > 0.0, scales, 1.0)
+
+
+def dof_basis(dof):
+    """``[12, dof]``: the parameters are ``p = E q``.  6: rigid; 7: one scale, the three ``s`` tied; 9: three scales; 12."""
+    if dof not in DOFS:
+        raise ValueError(f"dof is one of {DOFS}, got {dof!r}")
+    e = np.zeros((N_AFFINE, dof))
+    e[:6, :6] = np.eye(6)
+    if dof == 7:
+        e[6:9, 6] = 1.0
+    else:
+        e[6:dof, 6:dof] = np.eye(dof - 6)
+    return e
+
+
+class HostAffinePyramid(HostPyramid):
+    """:class:`HostPyramid` and the correlation ratio's two steps; the device path has the same methods."""
+
+    def bins(self, level, n_bins):
+        fixed, fmask = level[0], level[1]
+        lo, scale = bin_range(fixed, fmask, n_bins)
+        return bin_volume(fixed, lo, scale, n_bins)
+
+    def cr_sums(self, level, bins, n_bins, A):
+        _, fmask, moving, mmask = level[:4]
+        binned = binned_sums(bins, moving, A, n_bins, fmask, mmask)
+        return binned, registration_sums_lut(bins, lut_from_binned(binned), moving, A, fmask, mmask)
+
+
+def optimize_affine(pyramid, fixed_geom, moving_geom, centre, scales, *, metric="cr", bins=32, dof=12, levels=(4, 2, 1),  # noqa: A002
+                    max_iter=100, init=None):
+    """The regular-step descent of :func:`optimize` over ``q`` with ``p = E q`` (:func:`dof_basis`): the gradient is
+    ``E^T dC/dp``, a tied parameter's scale the sum of its members'.  ``metric``: 'cr' (each level's bins come from that
+    level's fixed volume inside its mask) or 'ncc' (the 43 sums as they are).  ``init``: 12 parameters."""
+    if metric not in ("cr", "ncc"):
+        raise ValueError(f"metric is 'cr' or 'ncc', got {metric!r}")
+    n_bins = _check_bins(bins)
+    e = dof_basis(dof)
+    p0 = np.zeros(N_AFFINE) if init is None else np.array(init, np.float64)
+    if p0.shape != (N_AFFINE,) or not np.all(np.isfinite(p0)):
+        raise ValueError("init is (rx, ry, rz, tx, ty, tz, s0, s1, s2, h01, h02, h12), finite")
+    q_scales = e.T @ np.asarray(scales, np.float64)
+    q = np.zeros(dof)
+    iterations, stops = [], []
+    for s in levels:
+        level = pyramid.level(s)
+        fg, mg = level_geometry(fixed_geom, s), level_geometry(moving_geom, s)
+        level_bins = pyramid.bins(level, n_bins) if metric == "cr" else None
+
+        def evaluate(q):
+            p = p0 + e @ q
+            a = _resample.index_affine(fg, mg, compose_affine(p, centre))
+            c, dc = cr_metric(*pyramid.cr_sums(level, level_bins, n_bins, a)) if metric == "cr" else _correlation(
+                pyramid.sums(level, a))
+            return c, (e.T @ affine_parameter_gradient(dc, p, centre, fg, mg)) / q_scales
+
+        step, prev, n_it, stop = initial_step(s), None, 0, "iterations"
+        while True:
+            c, g = evaluate(q)
+            norm = float(np.sqrt(np.sum(g * g)))
+            if norm < GRAD_TOL:
+                stop = "gradient"
+                break
+            if prev is not None and float(np.sum(g * prev)) < 0.0:
+                step *= RELAX
+            if step < MIN_STEP:
+                stop = "step"
+                break
+            if n_it >= max_iter:
+                break
+            q = q - (step / norm) * g
+            prev, n_it = g, n_it + 1
+        iterations.append(n_it)
+        stops.append(stop)
+    p = p0 + e @ q
+    return Registration(compose_affine(p, centre), p, np.asarray(centre, np.float64), c, iterations, stops)
+
+
+def mask_centroid(mask, geom):
+    """The physical centroid of a mask's voxels."""
+    idx = np.argwhere(np.asarray(mask) != 0)[:, ::-1].astype(np.float64)
+    if len(idx) == 0:
+        raise ValueError("the mask is empty")
+    m, o = _resample._index_to_point(geom)
+    return (idx @ m.T + o).mean(axis=0)
+
+
+def affine_init(init, fixed_mask, fixed_geom, moving_mask, moving_geom):
+    """None: zeros; 'centroids': the translation that takes the fixed mask's centroid onto the moving mask's (a template
+    and a subject do not share a frame); else 12 parameters."""
+    if init is None:
+        return np.zeros(N_AFFINE)
+    if isinstance(init, str):
+        if init != "centroids":
+            raise ValueError(f"init is None, 'centroids' or 12 parameters, got {init!r}")
+        p = np.zeros(N_AFFINE)
+        p[3:6] = mask_centroid(moving_mask, moving_geom) - mask_centroid(fixed_mask, fixed_geom)
+        return p
+    return np.array(init, np.float64)
+
+
+def register_affine(fixed, moving, fixed_geom, moving_geom, *, metric="cr", bins=32, dof=12, fixed_mask=None,  # noqa: A002
+                    moving_mask=None, levels=(4, 2, 1), max_iter=100, init=None):
+    """Register ``moving`` onto ``fixed`` with up to 12 degrees of freedom and the correlation ratio ('cr', for volumes
+    of different contrast) or the squared correlation ('ncc').  Masks None: ``build_mask`` of the volume.  Returns a
+    :class:`Registration` whose ``parameters`` are the 12 of :func:`compose_affine`.  The statement of
+    ``t2map.register.register_affine``."""
+    fixed, moving = np.asarray(fixed, np.float32), np.asarray(moving, np.float32)
+    fmask = build_mask(fixed) if fixed_mask is None else fixed_mask
+    mmask = build_mask(moving) if moving_mask is None else moving_mask
+    pyramid = HostAffinePyramid(fixed, fmask, moving, mmask)
+    fg, mg = _resample.as_geometry(fixed_geom, fixed.shape), _resample.as_geometry(moving_geom, moving.shape)
+    levels = check_levels(levels, fixed.shape, moving.shape)
+    centre, scales = affine_centre_and_scales(pyramid.full[1], fg)
+    p0 = affine_init(init, pyramid.full[1], fg, pyramid.full[3], mg)
+    return optimize_affine(pyramid, fg, mg, centre, scales, metric=metric, bins=bins, dof=dof, levels=levels,
+                           max_iter=max_iter, init=p0)

@@ -2,13 +2,19 @@
 // t2fit_register_workspace_bytes, t2fit_register_sums_dev, t2fit_shrink_dev, t2fit_shrink_mask_dev).  Stands for the
 // metric evaluation inside the reference's registration_itk (utils/qmri_utils.py:167-221: correlation metric, masks,
 // linear interpolator); the optimizer stays on the host (fetal_t2mapping_amd/_register.py, which also states every
-// kernel here in numpy).
+// kernel here in numpy).  The correlation-ratio half of the affine registration (t2fit_register_bin_dev,
+// t2fit_register_binned_sums_dev, t2fit_register_sums_lut_dev) lives here too: same bricks, same tree.
 //
 //   register_sums_kernel    a workgroup owns a brick of 64 x 4 x 8 fixed voxels: lanes along x (coalesced fixed and mask
 //                           reads; the eight moving taps of neighbouring lanes are neighbours along the image of the
 //                           fixed x axis), a wave per y, every lane walks its 8 voxels in z.  43 float64 accumulators
 //                           per lane; the wave adds them with a fixed xor butterfly (32, 16, .. 1: lane 0 holds the
 //                           halving tree), the four waves meet in LDS, and 43 lanes store the brick's slab.
+//                           <true>: f is lut[bin] of a uint8 bin volume instead of the fixed sample, nothing else differs.
+//   register_binned_kernel  the same brick; a lane keeps the (bin, m) of its 8 voxels in registers.  The bins present in a
+//                           wave are one 64-bit word (an OR butterfly of 1 << bin); only those run the sum's butterfly --
+//                           an absent bin's column values are all +0.0 and so is their tree.  The counts are whole
+//                           numbers below 2^53, exact in any order: popcounts of ballots stand for their tree.
 //   register_reduce_kernel  one pass of the tree over the slabs: a workgroup adds 256 consecutive values of one sum by
 //                           halving in LDS.  Passes repeat until one value per sum is left.
 //   shrink kernels          a pyramid level: the mean (the "any") of s^3 blocks, one thread per output voxel.
@@ -36,8 +42,13 @@ constexpr size_t kAlign = 256;
 static_assert(kBX == 64 && kBX * kBY == kBlock, "a wave per row of the brick");
 static_assert(kFan == kBlock, "a value per thread");
 
+constexpr int kMaxBins = 64;  // the bins of a wave fit one 64-bit presence word
+
 struct SumsArgs {
-  const float* fixed;
+  const float* fixed;        // <false>
+  const uint8_t* bins;       // <true>: f = lut[bins[at]]
+  const double* lut;
+  int n_bins;
   const uint8_t* fixed_mask;
   const float* moving;
   const uint8_t* moving_mask;
@@ -45,8 +56,11 @@ struct SumsArgs {
   Affine A;
   int bricks_x, bricks_y;
   int64_t n_bricks;
-  double* slabs;  // [kSums][n_bricks]
+  double* slabs;  // [kSums][n_bricks], the binned kernel: [2 n_bins][n_bricks]
 };
+
+// a bin byte above n_bins - 1 counts as n_bins - 1 (t2fit_register_bin_dev writes none)
+__device__ inline int bin_of(uint8_t b, int n_bins) { return (int)b < n_bins ? (int)b : n_bins - 1; }
 
 __device__ inline double lerp(double p, double q, double w) { return w == 0.0 ? p : p + w * (q - p); }
 
@@ -56,6 +70,40 @@ __device__ inline double wave_butterfly(double v) {
   return v;
 }
 
+// whether the fixed voxel (x, y, z), whose mask byte is set, counts; if so its interpolant m and, <true>, dm/dc
+template <bool kGrad>
+__device__ inline bool sample(const float* moving, const uint8_t* moving_mask, const Dims n, const Affine& A, int x, int y, int z,
+                              double& m, double* g) {
+  const double cx = coord(A, 0, x, y, z), cy = coord(A, 1, x, y, z), cz = coord(A, 2, x, y, z);
+  if (!(inside_axis(cx, n.nx) && inside_axis(cy, n.ny) && inside_axis(cz, n.nz))) return false;
+  const int qx = clamp_index(floor(cx + 0.5), n.nx), qy = clamp_index(floor(cy + 0.5), n.ny), qz = clamp_index(floor(cz + 0.5), n.nz);
+  if (moving_mask[((int64_t)qz * n.ny + qy) * n.nx + qx] == 0) return false;
+  const int x0 = clamp_index(floor(cx), n.nx), y0 = clamp_index(floor(cy), n.ny), z0 = clamp_index(floor(cz), n.nz);
+  double dx = cx - (double)x0, dy = cy - (double)y0, dz = cz - (double)z0;
+  dx = dx < 0.0 ? 0.0 : dx;
+  dy = dy < 0.0 ? 0.0 : dy;
+  dz = dz < 0.0 ? 0.0 : dz;
+  const int x1 = x0 + 1 < n.nx ? x0 + 1 : n.nx - 1, y1 = y0 + 1 < n.ny ? y0 + 1 : n.ny - 1, z1 = z0 + 1 < n.nz ? z0 + 1 : n.nz - 1;
+  const float* r00 = moving + ((int64_t)z0 * n.ny + y0) * n.nx;
+  const float* r01 = moving + ((int64_t)z0 * n.ny + y1) * n.nx;
+  const float* r10 = moving + ((int64_t)z1 * n.ny + y0) * n.nx;
+  const float* r11 = moving + ((int64_t)z1 * n.ny + y1) * n.nx;
+  const double v000 = r00[x0], v001 = r00[x1], v010 = r01[x0], v011 = r01[x1];
+  const double v100 = r10[x0], v101 = r10[x1], v110 = r11[x0], v111 = r11[x1];
+  const double l00 = lerp(v000, v001, dx), l01 = lerp(v010, v011, dx), l10 = lerp(v100, v101, dx), l11 = lerp(v110, v111, dx);
+  const double p0 = lerp(l00, l01, dy), p1 = lerp(l10, l11, dy);
+  m = lerp(p0, p1, dz);
+  if (!kGrad) return true;
+  g[0] = lerp(lerp(v001 - v000, v011 - v010, dy), lerp(v101 - v100, v111 - v110, dy), dz);
+  g[1] = lerp(l01 - l00, l11 - l10, dz);
+  g[2] = p1 - p0;
+  if (x1 == x0 || cx < 0.0) g[0] = 0.0;
+  if (y1 == y0 || cy < 0.0) g[1] = 0.0;
+  if (z1 == z0 || cz < 0.0) g[2] = 0.0;
+  return true;
+}
+
+template <bool kLut>
 __global__ __launch_bounds__(kBlock) void register_sums_kernel(const SumsArgs a) {
   __shared__ double rows[kBY][kSums];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -75,33 +123,9 @@ __global__ __launch_bounds__(kBlock) void register_sums_kernel(const SumsArgs a)
     if (!column || z >= a.f.nz) continue;
     const int64_t at = ((int64_t)z * a.f.ny + y) * a.f.nx + x;
     if (a.fixed_mask[at] == 0) continue;
-    const double cx = coord(a.A, 0, x, y, z), cy = coord(a.A, 1, x, y, z), cz = coord(a.A, 2, x, y, z);
-    if (!(inside_axis(cx, n.nx) && inside_axis(cy, n.ny) && inside_axis(cz, n.nz))) continue;
-    const int qx = clamp_index(floor(cx + 0.5), n.nx), qy = clamp_index(floor(cy + 0.5), n.ny), qz = clamp_index(floor(cz + 0.5), n.nz);
-    if (a.moving_mask[((int64_t)qz * n.ny + qy) * n.nx + qx] == 0) continue;
-    const int x0 = clamp_index(floor(cx), n.nx), y0 = clamp_index(floor(cy), n.ny), z0 = clamp_index(floor(cz), n.nz);
-    double dx = cx - (double)x0, dy = cy - (double)y0, dz = cz - (double)z0;
-    dx = dx < 0.0 ? 0.0 : dx;
-    dy = dy < 0.0 ? 0.0 : dy;
-    dz = dz < 0.0 ? 0.0 : dz;
-    const int x1 = x0 + 1 < n.nx ? x0 + 1 : n.nx - 1, y1 = y0 + 1 < n.ny ? y0 + 1 : n.ny - 1, z1 = z0 + 1 < n.nz ? z0 + 1 : n.nz - 1;
-    const float* r00 = a.moving + ((int64_t)z0 * n.ny + y0) * n.nx;
-    const float* r01 = a.moving + ((int64_t)z0 * n.ny + y1) * n.nx;
-    const float* r10 = a.moving + ((int64_t)z1 * n.ny + y0) * n.nx;
-    const float* r11 = a.moving + ((int64_t)z1 * n.ny + y1) * n.nx;
-    const double v000 = r00[x0], v001 = r00[x1], v010 = r01[x0], v011 = r01[x1];
-    const double v100 = r10[x0], v101 = r10[x1], v110 = r11[x0], v111 = r11[x1];
-    const double l00 = lerp(v000, v001, dx), l01 = lerp(v010, v011, dx), l10 = lerp(v100, v101, dx), l11 = lerp(v110, v111, dx);
-    const double p0 = lerp(l00, l01, dy), p1 = lerp(l10, l11, dy);
-    const double m = lerp(p0, p1, dz);
-    double g[3];
-    g[0] = lerp(lerp(v001 - v000, v011 - v010, dy), lerp(v101 - v100, v111 - v110, dy), dz);
-    g[1] = lerp(l01 - l00, l11 - l10, dz);
-    g[2] = p1 - p0;
-    if (x1 == x0 || cx < 0.0) g[0] = 0.0;
-    if (y1 == y0 || cy < 0.0) g[1] = 0.0;
-    if (z1 == z0 || cz < 0.0) g[2] = 0.0;
-    const double f = (double)a.fixed[at];
+    double m, g[3];
+    if (!sample<true>(a.moving, a.moving_mask, n, a.A, x, y, z, m, g)) continue;
+    const double f = kLut ? a.lut[bin_of(a.bins[at], a.n_bins)] : (double)a.fixed[at];
     const double u[3] = {(double)x, (double)y, (double)z};
     acc[0] = acc[0] + 1.0;
     acc[1] = acc[1] + f;
@@ -133,7 +157,81 @@ __global__ __launch_bounds__(kBlock) void register_sums_kernel(const SumsArgs a)
   }
 }
 
-// out[q][b] = the halving sum of in[q][256 b .. 256 b + 255] (zeros beyond n); grid (n_out, kSums)
+// slabs[b] = N_b and slabs[n_bins + b] = S_b of the brick, by the tree of the 43 sums
+__global__ __launch_bounds__(kBlock) void register_binned_kernel(const SumsArgs a) {
+  __shared__ double rows[kBY][2 * kMaxBins];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int t = blockIdx.x;
+  const int bx = t % a.bricks_x;
+  t /= a.bricks_x;
+  const int by = t % a.bricks_y, bz = t / a.bricks_y;
+  const int x = bx * kBX + lane, y = by * kBY + wave;
+  const bool column = x < a.f.nx && y < a.f.ny;
+  double mk[kBZ];
+  int bk[kBZ];  // -1: the voxel does not count
+  uint32_t lo = 0, hi = 0;
+#pragma unroll
+  for (int k = 0; k < kBZ; ++k) {
+    const int z = bz * kBZ + k;
+    mk[k] = 0.0;
+    bk[k] = -1;
+    if (column && z < a.f.nz) {
+      const int64_t at = ((int64_t)z * a.f.ny + y) * a.f.nx + x;
+      double m;
+      if (a.fixed_mask[at] != 0 && sample<false>(a.moving, a.moving_mask, a.m, a.A, x, y, z, m, nullptr)) {
+        const int b = bin_of(a.bins[at], a.n_bins);
+        mk[k] = m;
+        bk[k] = b;
+        if (b < 32) lo |= 1u << b; else hi |= 1u << (b - 32);
+      }
+    }
+  }
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) {
+    lo |= (uint32_t)__shfl_xor((int)lo, s, 64);
+    hi |= (uint32_t)__shfl_xor((int)hi, s, 64);
+  }
+  uint64_t present = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)hi) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
+  double my_n = 0.0, my_s = 0.0;  // lane b keeps bin b's row values
+  while (present) {
+    const int b = __ffsll((unsigned long long)present) - 1;
+    present &= present - 1;
+    double s = 0.0;
+    int count = 0;
+#pragma unroll
+    for (int k = 0; k < kBZ; ++k) {
+      const bool mine = bk[k] == b;
+      if (mine) s = s + mk[k];
+      count += __popcll(__ballot(mine));
+    }
+    s = wave_butterfly(s);
+    if (lane == b) my_n = (double)count, my_s = s;
+  }
+  rows[wave][lane] = my_n;
+  rows[wave][kMaxBins + lane] = my_s;
+  __syncthreads();
+  if (threadIdx.x < 2 * kMaxBins) {
+    const int q = threadIdx.x, b = q & (kMaxBins - 1), which = q / kMaxBins;
+    if (b < a.n_bins)
+      a.slabs[(int64_t)(which * a.n_bins + b) * a.n_bricks + blockIdx.x] = (rows[0][q] + rows[2][q]) + (rows[1][q] + rows[3][q]);
+  }
+}
+
+// bin = clamp(floor(((double)f - lo) * scale), 0, n_bins - 1); NaN: 0
+__global__ __launch_bounds__(kBlock) void register_bin_kernel(const float* __restrict__ src, int64_t n, double lo, double scale, int n_bins,
+                                                              uint8_t* __restrict__ out) {
+  const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (v >= n) return;
+  const double b = floor(((double)src[v] - lo) * scale), top = (double)(n_bins - 1);
+  out[v] = (uint8_t)(b > 0.0 ? (b > top ? top : b) : 0.0);
+}
+
+__global__ void register_lut_kernel(const double* __restrict__ binned, int n_bins, double* __restrict__ lut) {
+  const int b = threadIdx.x;
+  if (b < n_bins) lut[b] = binned[b] > 0.0 ? binned[n_bins + b] / binned[b] : 0.0;
+}
+
+// out[q][b] = the halving sum of in[q][256 b .. 256 b + 255] (zeros beyond n); grid (n_out, the number of sums)
 __global__ __launch_bounds__(kBlock) void register_reduce_kernel(const double* __restrict__ in, int64_t n, double* __restrict__ out,
                                                                  int64_t n_out) {
   __shared__ double s[kFan];
@@ -192,7 +290,7 @@ struct Plan {
   size_t total;
 };
 
-int sums_plan(const std::string& w, int fz, int fy, int fx, Plan* plan) {
+int sums_plan(const std::string& w, int fz, int fy, int fx, Plan* plan, int n_sums = kSums) {
   if (t2fit::count_voxels(1, fz, fy, fx) < 0)
     return t2fit::fail(T2FIT_E_INVALID, w + ": the fixed sizes must all be >= 1 and the volume at most 2^40 elements");
   plan->bricks_x = ceil_div(fx, kBX), plan->bricks_y = ceil_div(fy, kBY), plan->bricks_z = ceil_div(fz, kBZ);
@@ -203,11 +301,51 @@ int sums_plan(const std::string& w, int fz, int fy, int fx, Plan* plan) {
   for (int64_t n = bricks;; n = ceil_div(n, (int64_t)kFan)) {
     plan->pass_n[plan->n_pass] = n;
     plan->pass_at[plan->n_pass] = plan->total;
-    plan->total += align_up((size_t)n * kSums * sizeof(double), kAlign);
+    plan->total += align_up((size_t)n * n_sums * sizeof(double), kAlign);
     ++plan->n_pass;
     if (n <= kFan) break;
   }
   return T2FIT_OK;
+}
+
+// the checks the three entry points that sample the moving volume share, after the NULL checks and the plan
+int sums_check(const std::string& w, const float* moving_dev, int mz, int my, int mx, const double* A, const void* workspace_dev,
+               size_t workspace_bytes, const Plan& plan, const char* bytes_fn) {
+  if (t2fit::count_voxels(1, mz, my, mx) < 0)
+    return t2fit::fail(T2FIT_E_INVALID, w + ": the moving sizes must all be >= 1 and the volume at most 2^40 elements");
+  if (!t2fit::finite12(A)) return t2fit::fail(T2FIT_E_INVALID, w + ": A has a non-finite entry");
+  if (reinterpret_cast<uintptr_t>(moving_dev) & 3) return t2fit::fail(T2FIT_E_INVALID, w + ": moving_dev is not aligned to 4 bytes");
+  if (reinterpret_cast<uintptr_t>(workspace_dev) & (kAlign - 1))
+    return t2fit::fail(T2FIT_E_INVALID, w + ": workspace_dev is not aligned to 256 bytes");
+  if (workspace_bytes < plan.total)
+    return t2fit::fail(T2FIT_E_INVALID, w + ": workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " +
+                                            std::to_string(plan.total) + " needed (" + bytes_fn + ")");
+  return T2FIT_OK;
+}
+
+SumsArgs sums_args(const uint8_t* fixed_mask_dev, int fz, int fy, int fx, const float* moving_dev, const uint8_t* moving_mask_dev, int mz,
+                   int my, int mx, const double* A, const Plan& plan, void* workspace_dev) {
+  SumsArgs a;
+  a.fixed = nullptr, a.bins = nullptr, a.lut = nullptr, a.n_bins = 1;
+  a.fixed_mask = fixed_mask_dev, a.moving = moving_dev, a.moving_mask = moving_mask_dev;
+  a.f = Dims{fz, fy, fx}, a.m = Dims{mz, my, mx};
+  for (int i = 0; i < 12; ++i) a.A.m[i] = A[i];
+  a.bricks_x = plan.bricks_x, a.bricks_y = plan.bricks_y;
+  a.n_bricks = plan.pass_n[0];
+  a.slabs = reinterpret_cast<double*>(static_cast<char*>(workspace_dev) + plan.pass_at[0]);
+  return a;
+}
+
+// the passes of the tree over the n_sums rows of slabs, the last one into out_dev
+void reduce_passes(const Plan& plan, int n_sums, void* workspace_dev, double* out_dev, hipStream_t st) {
+  char* ws = static_cast<char*>(workspace_dev);
+  for (int p = 0; p < plan.n_pass; ++p) {
+    const bool last = p + 1 == plan.n_pass;
+    const int64_t n_out = last ? 1 : plan.pass_n[p + 1];
+    double* out = last ? out_dev : reinterpret_cast<double*>(ws + plan.pass_at[p + 1]);
+    hipLaunchKernelGGL(register_reduce_kernel, dim3((unsigned)n_out, n_sums), dim3(kBlock), 0, st, (const double*)(ws + plan.pass_at[p]),
+                       plan.pass_n[p], out, n_out);
+  }
 }
 
 int shrink_check(const std::string& w, const void* src, const void* out, int nz, int ny, int nx, int s, Dims* o) {
@@ -256,23 +394,81 @@ int t2fit_register_sums_dev(const float* fixed_dev, const uint8_t* fixed_mask_de
   if (workspace_bytes < plan.total)
     return t2fit::fail(T2FIT_E_INVALID, w + ": workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " +
                                             std::to_string(plan.total) + " needed (t2fit_register_workspace_bytes)");
+  SumsArgs a = sums_args(fixed_mask_dev, fz, fy, fx, moving_dev, moving_mask_dev, mz, my, mx, A, plan, workspace_dev);
+  a.fixed = fixed_dev;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(register_sums_kernel<false>), dim3((unsigned)a.n_bricks), dim3(kBlock), 0, (hipStream_t)stream, a);
+  reduce_passes(plan, kSums, workspace_dev, sums_dev, (hipStream_t)stream);
+  T2_HIP(hipGetLastError());
+  return T2FIT_OK;
+}
+
+int t2fit_register_bin_dev(const float* src_dev, int64_t n_vox, double lo, double scale, int n_bins, uint8_t* out_dev, void* stream) {
+  const std::string w("t2fit_register_bin_dev");
+  if (!src_dev || !out_dev) return t2fit::fail(T2FIT_E_INVALID, w + ": src_dev / out_dev is NULL");
+  if (n_vox < 1 || n_vox >= ((int64_t)1 << 39)) return t2fit::fail(T2FIT_E_INVALID, w + ": n_vox is outside 1..2^39-1");
+  if (n_bins < 1 || n_bins > kMaxBins) return t2fit::fail(T2FIT_E_INVALID, w + ": n_bins is outside 1..64");
+  if (!std::isfinite(lo) || !std::isfinite(scale)) return t2fit::fail(T2FIT_E_INVALID, w + ": lo / scale is not finite");
+  if (reinterpret_cast<uintptr_t>(src_dev) & 3) return t2fit::fail(T2FIT_E_INVALID, w + ": src_dev is not aligned to 4 bytes");
+  hipLaunchKernelGGL(register_bin_kernel, dim3((unsigned)ceil_div(n_vox, (int64_t)kBlock)), dim3(kBlock), 0, (hipStream_t)stream, src_dev,
+                     n_vox, lo, scale, n_bins, out_dev);
+  T2_HIP(hipGetLastError());
+  return T2FIT_OK;
+}
+
+int t2fit_register_binned_workspace_bytes(int fz, int fy, int fx, int n_bins, size_t* bytes) {
+  const std::string w("t2fit_register_binned_workspace_bytes");
+  if (!bytes) return t2fit::fail(T2FIT_E_INVALID, w + ": bytes is NULL");
+  if (n_bins < 1 || n_bins > kMaxBins) return t2fit::fail(T2FIT_E_INVALID, w + ": n_bins is outside 1..64");
+  Plan plan;
+  const int rc = sums_plan(w, fz, fy, fx, &plan, 2 * n_bins);
+  if (rc != T2FIT_OK) return rc;
+  *bytes = plan.total;
+  return T2FIT_OK;
+}
+
+int t2fit_register_binned_sums_dev(const uint8_t* bins_dev, const uint8_t* fixed_mask_dev, int fz, int fy, int fx, const float* moving_dev,
+                                   const uint8_t* moving_mask_dev, int mz, int my, int mx, const double* A, int n_bins,
+                                   double* binned_dev, double* lut_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  const std::string w("t2fit_register_binned_sums_dev");
+  if (!bins_dev || !fixed_mask_dev || !moving_dev || !moving_mask_dev || !A || !binned_dev || !workspace_dev)
+    return t2fit::fail(T2FIT_E_INVALID, w + ": bins_dev / fixed_mask_dev / moving_dev / moving_mask_dev / A / binned_dev / workspace_dev is NULL");
+  if (n_bins < 1 || n_bins > kMaxBins) return t2fit::fail(T2FIT_E_INVALID, w + ": n_bins is outside 1..64");
+  Plan plan;
+  int rc = sums_plan(w, fz, fy, fx, &plan, 2 * n_bins);
+  if (rc != T2FIT_OK) return rc;
+  if ((rc = sums_check(w, moving_dev, mz, my, mx, A, workspace_dev, workspace_bytes, plan, "t2fit_register_binned_workspace_bytes")) != T2FIT_OK)
+    return rc;
+  if ((reinterpret_cast<uintptr_t>(binned_dev) & 7) || (reinterpret_cast<uintptr_t>(lut_dev) & 7))
+    return t2fit::fail(T2FIT_E_INVALID, w + ": binned_dev / lut_dev is not aligned to 8 bytes");
   hipStream_t st = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace_dev);
-  SumsArgs a;
-  a.fixed = fixed_dev, a.fixed_mask = fixed_mask_dev, a.moving = moving_dev, a.moving_mask = moving_mask_dev;
-  a.f = Dims{fz, fy, fx}, a.m = Dims{mz, my, mx};
-  for (int i = 0; i < 12; ++i) a.A.m[i] = A[i];
-  a.bricks_x = plan.bricks_x, a.bricks_y = plan.bricks_y;
-  a.n_bricks = plan.pass_n[0];
-  a.slabs = reinterpret_cast<double*>(ws + plan.pass_at[0]);
-  hipLaunchKernelGGL(register_sums_kernel, dim3((unsigned)a.n_bricks), dim3(kBlock), 0, st, a);
-  for (int p = 0; p < plan.n_pass; ++p) {
-    const bool last = p + 1 == plan.n_pass;
-    const int64_t n_out = last ? 1 : plan.pass_n[p + 1];
-    double* out = last ? sums_dev : reinterpret_cast<double*>(ws + plan.pass_at[p + 1]);
-    hipLaunchKernelGGL(register_reduce_kernel, dim3((unsigned)n_out, kSums), dim3(kBlock), 0, st,
-                       (const double*)(ws + plan.pass_at[p]), plan.pass_n[p], out, n_out);
-  }
+  SumsArgs a = sums_args(fixed_mask_dev, fz, fy, fx, moving_dev, moving_mask_dev, mz, my, mx, A, plan, workspace_dev);
+  a.bins = bins_dev, a.n_bins = n_bins;
+  hipLaunchKernelGGL(register_binned_kernel, dim3((unsigned)a.n_bricks), dim3(kBlock), 0, st, a);
+  reduce_passes(plan, 2 * n_bins, workspace_dev, binned_dev, st);
+  if (lut_dev) hipLaunchKernelGGL(register_lut_kernel, dim3(1), dim3(kMaxBins), 0, st, (const double*)binned_dev, n_bins, lut_dev);
+  T2_HIP(hipGetLastError());
+  return T2FIT_OK;
+}
+
+int t2fit_register_sums_lut_dev(const uint8_t* bins_dev, const double* lut_dev, int n_bins, const uint8_t* fixed_mask_dev, int fz, int fy,
+                                int fx, const float* moving_dev, const uint8_t* moving_mask_dev, int mz, int my, int mx, const double* A,
+                                double* sums_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  const std::string w("t2fit_register_sums_lut_dev");
+  if (!bins_dev || !lut_dev || !fixed_mask_dev || !moving_dev || !moving_mask_dev || !A || !sums_dev || !workspace_dev)
+    return t2fit::fail(T2FIT_E_INVALID,
+                       w + ": bins_dev / lut_dev / fixed_mask_dev / moving_dev / moving_mask_dev / A / sums_dev / workspace_dev is NULL");
+  if (n_bins < 1 || n_bins > kMaxBins) return t2fit::fail(T2FIT_E_INVALID, w + ": n_bins is outside 1..64");
+  Plan plan;
+  int rc = sums_plan(w, fz, fy, fx, &plan);
+  if (rc != T2FIT_OK) return rc;
+  if ((rc = sums_check(w, moving_dev, mz, my, mx, A, workspace_dev, workspace_bytes, plan, "t2fit_register_workspace_bytes")) != T2FIT_OK)
+    return rc;
+  if ((reinterpret_cast<uintptr_t>(sums_dev) & 7) || (reinterpret_cast<uintptr_t>(lut_dev) & 7))
+    return t2fit::fail(T2FIT_E_INVALID, w + ": sums_dev / lut_dev is not aligned to 8 bytes");
+  SumsArgs a = sums_args(fixed_mask_dev, fz, fy, fx, moving_dev, moving_mask_dev, mz, my, mx, A, plan, workspace_dev);
+  a.bins = bins_dev, a.lut = lut_dev, a.n_bins = n_bins;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(register_sums_kernel<true>), dim3((unsigned)a.n_bricks), dim3(kBlock), 0, (hipStream_t)stream, a);
+  reduce_passes(plan, kSums, workspace_dev, sums_dev, (hipStream_t)stream);
   T2_HIP(hipGetLastError());
   return T2FIT_OK;
 }

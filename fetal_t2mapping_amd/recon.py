@@ -12,7 +12,13 @@ reference's registration_itk, not elastix, which the reference calls; parity unp
 volume onto the fixed one (utils/qmri_utils.py:82-136), and ``--write_transforms DIR`` saves them where
 ``--transforms`` reads them.  ``--register_echoes`` registers every merged echo onto the first one and resamples it
 (:376-383).  Each echo is reconstructed once: the reference runs its loop body for each of the three rows of an echo and
-writes the same file three times."""
+writes the same file three times.
+
+``--atlas_labels --atlas_template FILE --atlas NAME=FILE ...`` stands for the reference's extract_brain and
+build_jhu_ho_labels (utils/qmri_utils.py:953-974, :1011-1037) without FSL: per (sub, ses) the first echo's recon_1mm
+volume is masked by its recon_1mm_mask (``recon_1mm_bet``), the template is registered onto it on the GPU
+(``t2map.atlas.atlas_labels``: 12 degrees of freedom, correlation ratio; not flirt, parity unpinned) and written on the subject's
+grid as ``recon_1mm_mni152``, every atlas as ``recon_1mm_<NAME>`` -- the name ``cli.py --roi_stats NAME`` opens."""
 from __future__ import annotations
 
 import argparse
@@ -270,6 +276,71 @@ def process_phantom_masks(metadata, bids_path, *, seeds=None, fixed="ax", thresh
     return written
 
 
+atlas_bet_dirname = recon_dirname + "_bet"
+atlas_template_dirname = recon_dirname + "_mni152"
+
+
+def parse_atlas_spec(spec):
+    """``--atlas NAME=FILE`` -> ``(NAME, FILE)``; NAME becomes part of ``recon_1mm_<NAME>`` and is held to the letters,
+    digits and '-' that ``--roi_stats NAME`` takes."""
+    name, sep, path = str(spec).partition("=")
+    if not sep or not path:
+        raise ValueError(f"--atlas {spec!r}: expected NAME=FILE")
+    if not name or not all(ch.isalnum() or ch == "-" for ch in name):
+        raise ValueError(f"--atlas {spec!r}: NAME must be made of letters, digits and '-'")
+    if name in ("bet", "mni152", "mask", "label", "feta"):
+        raise ValueError(f"--atlas {spec!r}: recon_1mm_{name} is another image's name")
+    return name, path
+
+
+def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fixed="ax", dof=12, bins=32, device=0):
+    """``--atlas_labels``: for every (sub, ses), from the first echo's recon_1mm volume and recon_1mm_mask: the masked volume
+    under recon_1mm_bet, the registered template under recon_1mm_mni152 with the 4 x 4 transform beside it (``.txt``:
+    subject point -> template point, LPS millimetres, the text form of --write_transforms; not FSL's convention), and
+    every atlas (int32, nearest neighbour) under recon_1mm_<NAME>.  Returns the paths written."""
+    sitk = _sitk()
+    template_img = sitk.ReadImage(template_path)
+    template = np.asarray(sitk.GetArrayFromImage(template_img), np.float32)
+    atlases = {}
+    for name, path in atlas_specs:
+        img = sitk.ReadImage(path)
+        arr = np.asarray(sitk.GetArrayFromImage(img))
+        if arr.shape != template.shape or any(getattr(img, get)() != getattr(template_img, get)()
+                                              for get in ("GetSpacing", "GetOrigin", "GetDirection")):
+            raise ValueError(f"--atlas {name}={path}: the atlas does not lie on the template's grid")
+        atlases[name] = (arr if arr.dtype.kind in "iu" else np.rint(arr)).astype(np.int32)
+    written = []
+
+    def write(arr, like, path):
+        img = sitk.GetImageFromArray(arr)
+        img.SetSpacing(like.GetSpacing()), img.SetOrigin(like.GetOrigin()), img.SetDirection(like.GetDirection())
+        sitk.WriteImage(img, path)
+        written.append(path)
+        print(f"Image saved in : {path}")
+
+    for prj, sub, ses, echoes in echo_groups(metadata):
+        rows = echoes[0][1]
+        acq = rows[fixed] if fixed in rows else next(iter(rows.values()))
+        recon_path = get_img_path(bids_path, acq, recon_dirname).replace(" ", "")
+        mask_path = get_img_path(bids_path, acq, mask_dirname).replace(" ", "")
+        img = sitk.ReadImage(recon_path)
+        mask = np.asarray(sitk.GetArrayFromImage(sitk.ReadImage(mask_path)))
+        t0 = time.time()
+        subject = np.asarray(sitk.GetArrayFromImage(img), np.float32)
+        warped, labels, found = t2map.atlas.atlas_labels(subject, img, template, template_img, atlases, mask=mask, dof=dof, bins=bins,
+                                                   device=device)
+        write(t2map.atlas.extract_brain(subject, mask), img, get_img_path(bids_path, acq, atlas_bet_dirname).replace(" ", ""))
+        template_out = get_img_path(bids_path, acq, atlas_template_dirname).replace(" ", "")
+        write(warped, img, template_out)
+        np.savetxt(template_out.replace(".nii.gz", ".txt"), found.transform, fmt="%.17g")
+        written.append(template_out.replace(".nii.gz", ".txt"))
+        for name, lab in labels.items():
+            write(lab, img, get_img_path(bids_path, acq, recon_dirname + "_" + name).replace(" ", ""))
+        print(f"... atlas labels of {sub}_{ses}: CR {found.metric:.4f}, iterations {found.iterations}, "
+              f"{round(time.time() - t0, 4)} sec")
+    return written
+
+
 def reconstruct_subject(sitk, bids_path, sub_md, sub, ses, *, fixed="ax", res=1.0, transforms_dir=None, integer_cast=None,
                         register=False, register_echoes=False, device=0):
     """cli.py --reconstruct: the echoes of one (sub, ses) (`sub_md`: its metadata rows) reconstructed in memory.  Every
@@ -325,8 +396,37 @@ def parse_arguments(argv=None):
     p.add_argument("--phantom_seeds", default=None, metavar="FILE",
                    help="with --phantom_masks: JSON list of [x, y, z] voxel indices, one per vial; the vial labels are written "
                         "under recon_1mm_label/ (the reference's build_phantom_labels_v2)")
+    p.add_argument("--atlas_labels", action="store_true",
+                   help="after the reconstruction: register --atlas_template onto the first echo's recon_1mm volume masked by "
+                        "recon_1mm_mask (affine, correlation ratio, on the GPU; stands for the reference's flirt call, parity "
+                        "unpinned) and write recon_1mm_bet, recon_1mm_mni152 and one recon_1mm_<NAME> per --atlas, which "
+                        "cli.py --roi_stats NAME reads; the 4 x 4 transform is written beside recon_1mm_mni152 as text: "
+                        "subject point -> template point in LPS millimetres, not FSL's convention; off by default")
+    p.add_argument("--atlas_template", default=None, metavar="FILE", help="with --atlas_labels: the template image (MNI152 T1)")
+    p.add_argument("--atlas", action="append", default=[], metavar="NAME=FILE",
+                   help="with --atlas_labels: a label image on the template's grid, repeatable (ho=..., jhu=...)")
+    p.add_argument("--atlas_dof", type=int, choices=[6, 7, 9, 12], default=12, help="degrees of freedom (default 12, as flirt's)")
+    p.add_argument("--atlas_bins", type=int, default=32, help="bins of the correlation ratio, 1..64 (default 32)")
     p.add_argument("--device", type=int, default=0, help="HIP device ordinal")
     args = p.parse_args(argv)
+    if args.atlas_labels:
+        if args.atlas_template is None or not os.path.isfile(args.atlas_template):
+            p.error(f"--atlas_labels needs --atlas_template FILE, an existing image (got {args.atlas_template!r})")
+        if not args.atlas:
+            p.error("--atlas_labels needs at least one --atlas NAME=FILE")
+        if not 1 <= args.atlas_bins <= 64:
+            p.error("--atlas_bins is in 1..64")
+        try:
+            args.atlas_specs = [parse_atlas_spec(spec) for spec in args.atlas]
+        except ValueError as e:
+            p.error(str(e))
+        if len({n for n, _ in args.atlas_specs}) != len(args.atlas_specs):
+            p.error("--atlas: a NAME is given twice")
+        for _, path in args.atlas_specs:
+            if not os.path.isfile(path):
+                p.error(f"--atlas: {path!r} does not exist")
+    elif args.atlas_template is not None or args.atlas:
+        p.error("--atlas_template / --atlas have no effect without --atlas_labels")
     if args.phantom_masks and not args.in_vitro:
         p.error("--phantom_masks goes with --in_vitro")
     if args.phantom_seeds is not None and not args.phantom_masks:
@@ -361,6 +461,9 @@ def main(argv=None):
                   write_transforms=args.write_transforms, register_echoes=args.register_echoes, device=args.device)
     if args.phantom_masks:
         process_phantom_masks(metadata, bids_path, seeds=args.seeds, fixed=args.fixed, device=args.device)
+    if args.atlas_labels:
+        process_atlas_labels(metadata, bids_path, args.atlas_template, args.atlas_specs, fixed=args.fixed, dof=args.atlas_dof,
+                             bins=args.atlas_bins, device=args.device)
 
 
 if __name__ == "__main__":

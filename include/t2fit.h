@@ -579,6 +579,53 @@ int t2fit_register_sums_dev(const float *fixed_dev, const uint8_t *fixed_mask_de
 int t2fit_shrink_dev(const float *src_dev, int nz, int ny, int nx, int s, float *out_dev, void *stream);
 int t2fit_shrink_mask_dev(const uint8_t *src_dev, int nz, int ny, int nx, int s, uint8_t *out_dev, void *stream);
 
+/* ---- Affine registration across contrasts: the correlation ratio's sums -------------------------------------------------
+ * The device half of the T1-template-onto-T2 registration behind the atlas labels (the reference runs FSL's flirt with
+ * 12 degrees of freedom and the correlation-ratio cost: utils/qmri_utils.py:1011-1037).  The FIXED volume's intensities
+ * are binned once per pyramid level; with N_b and S_b the count and the sum of the interpolated moving samples m over
+ * the counted voxels of bin b, mu_b = S_b / N_b and phi(i) = mu_bin(i), the correlation ratio of m given the binned f is
+ *   CR = 1 - (sum_b S_b^2 / N_b - (sum m)^2 / N) / (sum m^2 - (sum m)^2 / N) = 1 + C,
+ * C being the correlation metric of the 43 sums with f replaced by phi; phi maximises that correlation over the functions
+ * constant on each bin, so dCR/dA with the voxel set held fixed is the dC/dA of those same sums.  One evaluation is
+ * t2fit_register_binned_sums_dev (N_b, S_b and the table mu) followed by t2fit_register_sums_lut_dev (the 43 sums with
+ * f = mu[bin]), on one stream without a host round trip.  Metric arithmetic, the 12-parameter transform and the descent
+ * are host code (fetal_t2mapping_amd/_register.py, which restates everything here in numpy; the device results equal it
+ * bit for bit).  Parity with flirt is not pinned.  Additive to ABI 5: four new symbols (look them up).
+ *
+ * The counting rule, the interpolant m and THE SUMMATION TREE are those written above for the 43 sums.  A bin byte above
+ * n_bins - 1 counts as n_bins - 1.  Checked before HIP is touched by all of them (T2FIT_E_INVALID and a message): a NULL
+ * pointer (lut_dev of t2fit_register_binned_sums_dev alone may be NULL), n_bins outside 1..64, a size < 1, a non-finite
+ * entry of A, lo or scale, float32 volumes not aligned to 4 bytes, float64 arrays not aligned to 8, a workspace that is
+ * not aligned to 256 bytes or too small.
+ *
+ * t2fit_register_bin_dev: out[v] = clamp(floor(((double)src[v] - lo) * scale), 0, n_bins - 1) as uint8, every operation
+ * rounding once in float64; a NaN gives 0, so scale = 0 gives all zeros.  n_vox in 1..2^39-1.  The host chooses lo = the
+ * smallest and hi = the largest sample inside the fixed mask and scale = n_bins / (hi - lo), 0 when hi == lo; a sample
+ * equal to hi clamps to n_bins - 1. */
+int t2fit_register_bin_dev(const float *src_dev, int64_t n_vox, double lo, double scale, int n_bins, uint8_t *out_dev,
+                           void *stream);
+
+/* As t2fit_register_workspace_bytes with 2 n_bins values per slab in place of 43. */
+int t2fit_register_binned_workspace_bytes(int fz, int fy, int fx, int n_bins, size_t *bytes);
+
+/* binned_dev: device float64 [2 n_bins] = N_0 .. N_{B-1}, S_0 .. S_{B-1}.  A voxel that counts adds (1.0, m) to its own
+ * bin and +0.0 to every other, all through the tree; no floating-point atomics; the order of every addition is a
+ * function of (fz, fy, fx) and n_bins alone.  lut_dev: NULL, or device float64 [n_bins] that a last small kernel fills
+ * with lut[b] = N_b > 0 ? S_b / N_b : 0.0.  N = 0 leaves zeros.  bins_dev: uint8 [fz fy fx]; the other arguments as for
+ * t2fit_register_sums_dev; workspace_dev: at least t2fit_register_binned_workspace_bytes bytes, aligned to 256.  One
+ * launch for the slabs, one per pass, one for the table.  Asynchronous on `stream`. */
+int t2fit_register_binned_sums_dev(const uint8_t *bins_dev, const uint8_t *fixed_mask_dev, int fz, int fy, int fx,
+                                   const float *moving_dev, const uint8_t *moving_mask_dev, int mz, int my, int mx,
+                                   const double *A, int n_bins, double *binned_dev, double *lut_dev, void *workspace_dev,
+                                   size_t workspace_bytes, void *stream);
+
+/* The 43 sums of t2fit_register_sums_dev with f = lut_dev[bins_dev[i]], a float64 that is not rounded to float32 (the
+ * same kernel body).  workspace_dev: at least t2fit_register_workspace_bytes bytes.  Asynchronous on `stream`. */
+int t2fit_register_sums_lut_dev(const uint8_t *bins_dev, const double *lut_dev, int n_bins, const uint8_t *fixed_mask_dev,
+                                int fz, int fy, int fx, const float *moving_dev, const uint8_t *moving_mask_dev, int mz,
+                                int my, int mx, const double *A, double *sums_dev, void *workspace_dev,
+                                size_t workspace_bytes, void *stream);
+
 /* Kernel timing for benchmarks (no reference counterpart).  With timing enabled (t2fit_set_timing(1)) every
  * t2fit_volume_dev call of this thread records HIP events around its fit kernel on the launch stream.
  * t2fit_kernel_ms(k): duration in milliseconds of the fit kernel launched k timed calls ago (0 = the most recent;
