@@ -12,6 +12,7 @@ from .t2map import (BootMaps, BootStats, RoiStats, T2Maps, bootstrap_volume, com
                     set_fit_params, stack_mask_flatten, synth_replica, union_mask_dev)
 from .t2map import register  # the registrations: register.register_rigid, register.register_affine, register.registration_sums
 from .t2map import atlas  # the atlas-label stage: atlas.atlas_labels, atlas.extract_brain
+from .t2map import bias  # the N4 bias-field correction: bias.n4_correct, bias.apply_field
 from .t2map import (binary_close, binary_dilate, binary_erode, binary_open, binary_threshold, build_mask, fill_holes,
                     mask_from_labels, phantom_labels, phantom_mask, relabel, seed_labels, synthseg_to_feta)
 
@@ -21,4 +22,4 @@ __all__ = ["BootMaps", "BootStats", "RoiStats", "T2Maps", "bootstrap_volume", "c
            "stack_mask_flatten", "synth_replica", "union_mask_dev",
            "binary_close", "binary_dilate", "binary_erode", "binary_open", "binary_threshold", "build_mask", "fill_holes",
            "mask_from_labels", "phantom_labels", "phantom_mask", "relabel", "seed_labels", "synthseg_to_feta", "register",
-           "atlas"]
+           "atlas", "bias"]

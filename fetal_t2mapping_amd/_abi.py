@@ -124,6 +124,15 @@ SYMBOLS = [
                                                  C.POINTER(C.c_double), C.c_int, _P, _P, _P, C.c_size_t, _P]),
     ("t2fit_register_sums_lut_dev", C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
                                               C.POINTER(C.c_double), _P, _P, C.c_size_t, _P]),
+    ("t2fit_n4_workspace_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    ("t2fit_n4_log_dev", C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
+    ("t2fit_n4_minmax_dev", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
+    ("t2fit_n4_histogram_dev", C.c_int, [_P, _P, C.c_int64, C.c_double, C.c_double, C.c_int, _P, _P]),
+    ("t2fit_n4_weights_dev", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    ("t2fit_n4_fit_dev", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_double, C.c_double, C.c_int, C.c_int, _P, _P, _P, _P,
+                                   C.c_size_t, _P]),
+    ("t2fit_n4_field_dev", C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    ("t2fit_n4_apply_dev", C.c_int, [_P, _P, C.c_int64, C.c_double, _P, _P]),
     ("t2fit_set_timing", C.c_int, [C.c_int]),
     ("t2fit_set_reserve_cus", C.c_int, [C.c_int]),
     ("t2fit_kernel_ms", C.c_double, [C.c_int]),
@@ -144,7 +153,9 @@ ADDITIVE = BOOT_SYMBOLS + TV_SYMBOLS + RECON_SYMBOLS + MORPH_SYMBOLS
 REGISTER_SYMBOLS = ("t2fit_register_workspace_bytes", "t2fit_register_sums_dev", "t2fit_shrink_dev", "t2fit_shrink_mask_dev")
 ATLAS_SYMBOLS = ("t2fit_register_bin_dev", "t2fit_register_binned_workspace_bytes", "t2fit_register_binned_sums_dev",
                  "t2fit_register_sums_lut_dev")
-LOOKED_UP = ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS
+N4_SYMBOLS = ("t2fit_n4_workspace_bytes", "t2fit_n4_log_dev", "t2fit_n4_minmax_dev", "t2fit_n4_histogram_dev", "t2fit_n4_weights_dev",
+              "t2fit_n4_fit_dev", "t2fit_n4_field_dev", "t2fit_n4_apply_dev")
+LOOKED_UP = ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

@@ -822,6 +822,9 @@ def parse_arguments(argv=None):
                         "moving point); a missing file is the identity")
     p.add_argument("--recon_register", action="store_true",
                    help="with --reconstruct: find the transforms of the moving stacks on the GPU (recon.py --register)")
+    p.add_argument("--recon_n4", action="store_true",
+                   help="with --reconstruct: N4 bias-field correction of the acquired stacks on the GPU first (recon.py --n4 "
+                        "with its defaults)")
     p.add_argument("--recon_register_echoes", action="store_true",
                    help="with --reconstruct: register every merged echo onto the first one (recon.py --register_echoes)")
     p.add_argument("--build_mask", choices=["phantom"], default=None,
@@ -842,7 +845,8 @@ def parse_arguments(argv=None):
     p.add_argument("--denoise_iter", type=int, default=200, help="iteration limit of a problem (default 200)")
     args = p.parse_args(argv)
     args.reconstruct_args = None
-    given = [f for f in ("--recon_fixed", "--recon_res", "--recon_transforms", "--recon_register", "--recon_register_echoes")
+    given = [f for f in ("--recon_fixed", "--recon_res", "--recon_transforms", "--recon_register", "--recon_register_echoes",
+                         "--recon_n4")
              if any(a == f or a.startswith(f + "=") for a in (argv if argv is not None else sys.argv[1:]))]
     if given and not args.reconstruct:
         p.error(f"{given[0]} has no effect without --reconstruct")
@@ -858,6 +862,10 @@ def parse_arguments(argv=None):
             args.reconstruct_args["register"] = True
         if args.recon_register_echoes:
             args.reconstruct_args["register_echoes"] = True
+        if args.recon_n4:
+            from .recon import N4_DEFAULTS
+
+            args.reconstruct_args["n4"] = dict(N4_DEFAULTS)
     args.build_mask_args = None
     if args.phantom_seeds is not None and not args.build_mask:
         p.error("--phantom_seeds has no effect without --build_mask phantom")

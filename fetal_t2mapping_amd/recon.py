@@ -18,7 +18,16 @@ writes the same file three times.
 build_jhu_ho_labels (utils/qmri_utils.py:953-974, :1011-1037) without FSL: per (sub, ses) the first echo's recon_1mm
 volume is masked by its recon_1mm_mask (``recon_1mm_bet``), the template is registered onto it on the GPU
 (``t2map.atlas.atlas_labels``: 12 degrees of freedom, correlation ratio; not flirt, parity unpinned) and written on the subject's
-grid as ``recon_1mm_mni152``, every atlas as ``recon_1mm_<NAME>`` -- the name ``cli.py --roi_stats NAME`` opens."""
+grid as ``recon_1mm_mni152``, every atlas as ``recon_1mm_<NAME>`` -- the name ``cli.py --roi_stats NAME`` opens.
+
+``--n4`` stands for the reference's run_biasfield_correction2 (utils/qmri_utils.py:296-357) without SimpleITK's N4 filter:
+per (sub, ses) and orientation one log bias field is estimated on the raw stack of one echo (``--n4_echo MS``; default the
+255 ms echo when present, else the first) on the GPU (``t2map.bias.n4_correct``; full width 0.25 for cor, 0.5 for ax and sag
+as the reference sets them; parity with ITK unpinned), inside the stack's ``<run>_T2w_mask`` file under the derivative
+directory ``mask`` when it exists, else inside ``build_mask`` of the stack, and every echo's stack of that orientation is
+divided by that one field before step 1 -- the decay curve keeps its shape.  ``--write_n4`` writes the corrected stacks under
+the derivative directory ``n4``.  The reference takes both directory names as arguments and never fixes them: ``mask`` and
+``n4`` are this driver's choice."""
 from __future__ import annotations
 
 import argparse
@@ -34,6 +43,10 @@ from .cli import (_sitk, build_phantom_subject, get_img_path, load_seeds, mask_d
 
 in_dirname = "anat"
 resamp_dirname = "resamp_1mm"
+n4_dirname = "n4"             # --write_n4: the corrected stacks (a choice: the reference passes the name in)
+stack_mask_dirname = "mask"   # --n4: <sub>_<ses>_<run>_T2w_mask.nii.gz of an acquired stack, when there is one
+N4_DEFAULTS = {"fwhm_cor": 0.25, "fwhm": 0.5, "echo": None, "scale": 1.0}
+N4_ECHO_MS = 255
 
 
 def transform_path(transforms_dir, acq, orientation, echo=False):
@@ -193,13 +206,61 @@ def batch_inputs(sitk, batch, integer_cast=None):
     return stacks, geoms, cast
 
 
+def n4_echo_index(echo_ms, echo=None):
+    """The echo the field is estimated on: ``echo`` [ms] when given, else the 255 ms echo when present, else the first."""
+    echo_ms = [int(round(float(t))) for t in echo_ms]
+    if echo is not None:
+        if int(echo) not in echo_ms:
+            raise ValueError(f"--n4_echo {int(echo)}: the echo times are {echo_ms} ms")
+        return echo_ms.index(int(echo))
+    return echo_ms.index(N4_ECHO_MS) if N4_ECHO_MS in echo_ms else 0
+
+
+def correct_stacks(stacks, masks, echo_ms, *, fwhm_cor=0.25, fwhm=0.5, echo=None, scale=1.0, device=0):
+    """run_biasfield_correction2 on the stacks of a batch: ``stacks`` {orientation: float32 ``(n, Z, Y, X)``}, ``masks``
+    {orientation: mask or None (``build_mask``)}.  Per orientation ONE log field, estimated on the echo of
+    :func:`n4_echo_index`, divides every echo.  Returns ``(corrected stacks, {orientation: log field})``."""
+    at = n4_echo_index(echo_ms, echo)
+    out, fields = {}, {}
+    for o in _resample.ORIENTATIONS:
+        found = t2map.bias.n4_correct(stacks[o][at], masks.get(o), fwhm=fwhm_cor if o == "cor" else fwhm, device=device)
+        fields[o] = np.asarray(found.log_field, np.float32)
+        out[o] = np.stack([np.asarray(t2map.bias.apply_field(v, fields[o], scale, device=device), np.float32) for v in stacks[o]])
+        print(f"N4 bias field correction: {o.upper()}, TE {int(round(float(echo_ms[at])))} ms, iterations {found.iterations}")
+    return out, fields
+
+
+def read_stack_masks(sitk, bids_path, rows, shapes):
+    """{orientation: the ``_T2w_mask`` array of the stack of `rows`, or None when there is no such file}."""
+    masks = {}
+    for o in _resample.ORIENTATIONS:
+        path = get_img_path(bids_path, rows[o], stack_mask_dirname)
+        masks[o] = None
+        if os.path.isfile(path):
+            masks[o] = np.asarray(sitk.GetArrayFromImage(sitk.ReadImage(path)))
+            if masks[o].shape != tuple(shapes[o]):
+                raise ValueError(f"--n4: {path} has shape {masks[o].shape}, the stack has {tuple(shapes[o])}")
+    return masks
+
+
+def n4_batch(sitk, bids_path, batch, stacks, n4, device=0):
+    """The stacks of a batch after ``--n4`` (`n4`: the keyword arguments of :func:`correct_stacks`)."""
+    echo_ms = [it[0] * 1000.0 for it in batch]
+    at = n4_echo_index(echo_ms, n4.get("echo"))
+    masks = read_stack_masks(sitk, bids_path, batch[at][1], {o: stacks[o].shape[1:] for o in _resample.ORIENTATIONS})
+    return correct_stacks(stacks, masks, echo_ms, device=device, **n4)[0]
+
+
 def process_recon(metadata, bids_path, *, fixed="ax", res=1.0, transforms_dir=None, write_resamp=False, denoise=True,
-                  integer_cast=None, register=False, write_transforms=None, register_echoes=False, device=0):
+                  integer_cast=None, register=False, write_transforms=None, register_echoes=False, n4=None, write_n4=False,
+                  device=0):
     """Reconstruct every echo of every (prj, sub, ses) of `metadata` that has the three orientations and write it.
     The echoes of a subject whose stacks share their geometry per orientation go through one call.  ``integer_cast``:
     None keeps the pixel type as the reference does (cast when the stacks are int16 on disk).  ``register`` /
-    ``write_transforms`` / ``register_echoes``: see :func:`merge_echoes`.  Returns the paths written under
-    ``recon_1mm``."""
+    ``write_transforms`` / ``register_echoes``: see :func:`merge_echoes`.  ``n4``: None, or the keyword arguments of
+    :func:`correct_stacks` (``--n4``): the stacks are bias-corrected before step 1 and are no longer integers, so the
+    pixel type is not kept unless ``integer_cast`` says so; ``write_n4`` writes them under ``n4``.  Returns the paths
+    written under ``recon_1mm``."""
     import torch
 
     sitk = _sitk()
@@ -208,6 +269,17 @@ def process_recon(metadata, bids_path, *, fixed="ax", res=1.0, transforms_dir=No
         for batch in batches_of(read_echoes(sitk, bids_path, echoes, sub, ses)):
             t0 = time.time()
             stacks, geoms, cast = batch_inputs(sitk, batch, integer_cast)
+            if n4 is not None:
+                stacks, cast = n4_batch(sitk, bids_path, batch, stacks, n4, device), bool(integer_cast)
+                if write_n4:
+                    for o in _resample.ORIENTATIONS:
+                        for it, vol in zip(batch, stacks[o]):
+                            img = sitk.GetImageFromArray(vol)
+                            g = geoms[o]
+                            img.SetSpacing(g.GetSpacing()), img.SetOrigin(g.GetOrigin()), img.SetDirection(g.GetDirection())
+                            path = get_img_path(bids_path, it[1][o], n4_dirname)
+                            sitk.WriteImage(img, path)
+                            print(f"Image saved in : {path}")
             print(f"===== Reconstruction: {prj}_{sub}_{ses}, TE {[int(it[0] * 1000) for it in batch]} ms, fixed {fixed}, "
                   f"transforms {'registered' if register else (transforms_dir or 'identity')} =====")
             if write_resamp:  # the intermediate volumes of step 1, as run_resample_volume leaves them
@@ -342,10 +414,10 @@ def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fix
 
 
 def reconstruct_subject(sitk, bids_path, sub_md, sub, ses, *, fixed="ax", res=1.0, transforms_dir=None, integer_cast=None,
-                        register=False, register_echoes=False, device=0):
+                        register=False, register_echoes=False, n4=None, device=0):
     """cli.py --reconstruct: the echoes of one (sub, ses) (`sub_md`: its metadata rows) reconstructed in memory.  Every
-    echo must have the three orientations and the echoes must share their grids.  Returns ``(volumes: list of (Z, Y, X)
-    float32 arrays in EchoTime order, header)``."""
+    echo must have the three orientations and the echoes must share their grids.  ``n4``: as :func:`process_recon`.
+    Returns ``(volumes: list of (Z, Y, X) float32 arrays in EchoTime order, header)``."""
     echoes = [(float(te), {acq["ImageOrientationPatientSTR"]: acq for _, acq in te_md.iterrows()})
               for te, te_md in sub_md.groupby("EchoTime")]
     ready = read_echoes(sitk, bids_path, echoes, sub, ses)
@@ -355,6 +427,8 @@ def reconstruct_subject(sitk, bids_path, sub_md, sub, ses, *, fixed="ax", res=1.
     if len(batches) != 1:
         raise ValueError(f"--reconstruct: the stacks of {sub}_{ses} do not lie on the same grids at every echo time")
     stacks, geoms, cast = batch_inputs(sitk, batches[0], integer_cast)
+    if n4 is not None:
+        stacks, cast = n4_batch(sitk, bids_path, batches[0], stacks, n4, device), bool(integer_cast)
     merged, header, _ = merge_echoes(stacks, geoms, [it[1][fixed] for it in ready], fixed=fixed, res=res, integer_cast=cast,
                                      transforms_dir=transforms_dir, register=register, register_echoes=register_echoes,
                                      device=device)
@@ -407,8 +481,30 @@ def parse_arguments(argv=None):
                    help="with --atlas_labels: a label image on the template's grid, repeatable (ho=..., jhu=...)")
     p.add_argument("--atlas_dof", type=int, choices=[6, 7, 9, 12], default=12, help="degrees of freedom (default 12, as flirt's)")
     p.add_argument("--atlas_bins", type=int, default=32, help="bins of the correlation ratio, 1..64 (default 32)")
+    p.add_argument("--n4", action="store_true",
+                   help="N4 bias-field correction of the acquired stacks on the GPU before step 1 (the reference's "
+                        "run_biasfield_correction2; parity with ITK unpinned): per orientation one log field, estimated on one "
+                        "echo inside the stack's <run>_T2w_mask file under derivatives/mask (else build_mask), divides every "
+                        "echo; off by default")
+    p.add_argument("--n4_fwhm_cor", type=float, default=N4_DEFAULTS["fwhm_cor"],
+                   help="with --n4: full width at half maximum of the deconvolution for the cor stack (default 0.25)")
+    p.add_argument("--n4_fwhm", type=float, default=N4_DEFAULTS["fwhm"], help="with --n4: for the ax and sag stacks (default 0.5)")
+    p.add_argument("--n4_echo", type=int, default=None, metavar="MS",
+                   help="with --n4: the echo [ms] the field is estimated on (default 255 when present, else the first)")
+    p.add_argument("--n4_scale", type=float, default=N4_DEFAULTS["scale"],
+                   help="with --n4: factor on the corrected stacks (default 1; run_biasfield_correction's 0.25 is --n4_scale 0.25)")
+    p.add_argument("--write_n4", action="store_true", help="with --n4: also write the corrected stacks under derivatives/n4/")
     p.add_argument("--device", type=int, default=0, help="HIP device ordinal")
     args = p.parse_args(argv)
+    given = [f for f in ("--n4_fwhm_cor", "--n4_fwhm", "--n4_echo", "--n4_scale", "--write_n4")
+             if any(a == f or a.startswith(f + "=") for a in (argv if argv is not None else sys.argv[1:]))]
+    if given and not args.n4:
+        p.error(f"{given[0]} has no effect without --n4")
+    args.n4_args = None
+    if args.n4:
+        if not (args.n4_fwhm_cor > 0.0 and args.n4_fwhm > 0.0 and np.isfinite(args.n4_fwhm_cor + args.n4_fwhm + args.n4_scale)):
+            p.error("--n4_fwhm_cor and --n4_fwhm must be positive numbers and --n4_scale finite")
+        args.n4_args = {"fwhm_cor": args.n4_fwhm_cor, "fwhm": args.n4_fwhm, "echo": args.n4_echo, "scale": args.n4_scale}
     if args.atlas_labels:
         if args.atlas_template is None or not os.path.isfile(args.atlas_template):
             p.error(f"--atlas_labels needs --atlas_template FILE, an existing image (got {args.atlas_template!r})")
@@ -458,7 +554,8 @@ def main(argv=None):
     metadata = set_metadata(csv_path, args.csv, bool(args.lf))
     process_recon(metadata, bids_path, fixed=args.fixed, res=args.res, transforms_dir=args.transforms,
                   write_resamp=args.write_resamp, denoise=not args.no_denoise, register=args.register,
-                  write_transforms=args.write_transforms, register_echoes=args.register_echoes, device=args.device)
+                  write_transforms=args.write_transforms, register_echoes=args.register_echoes, n4=args.n4_args,
+                  write_n4=args.write_n4, device=args.device)
     if args.phantom_masks:
         process_phantom_masks(metadata, bids_path, seeds=args.seeds, fixed=args.fixed, device=args.device)
     if args.atlas_labels:

@@ -27,6 +27,7 @@ resampling, merge      ``_gpu_resample``   ``_resample``
 masks, phantom labels  ``_gpu_morph``      ``_morph``
 rigid registration     ``_gpu_register``   ``_register`` (and the optimizer, which is host code); here as ``register``
 atlas labels           ``_gpu_atlas``      ``_atlas`` (affine registration by the correlation ratio: ``register``); here as ``atlas``
+N4 bias field          ``_gpu_bias``       ``_bias`` (and the sharpening table, the refinement and the loop, which are host code); here as ``bias``
 =====================  ==================  ===========================================================
 
 Python only marshals buffers (``_gpu``: conversions, ``out=`` checks, stream, workspace); all arithmetic happens in
@@ -38,6 +39,7 @@ from ._gpu_fit import (T2Maps, compute_residuals, fit_table, fit_volume, fit_vox
 from ._gpu_morph import (binary_close, binary_dilate, binary_erode, binary_open, binary_threshold, build_mask,  # noqa: F401
                          fill_holes, mask_from_labels, phantom_labels, phantom_mask, relabel, seed_labels, synthseg_to_feta)
 from . import _gpu_atlas as atlas  # noqa: F401  (a namespace: atlas.atlas_labels, atlas.extract_brain)
+from . import _gpu_bias as bias  # noqa: F401  (a namespace: bias.n4_correct, bias.apply_field, the step functions)
 from . import _gpu_register as register  # noqa: F401  (a namespace: register.register_rigid, .register_affine, ..)
 from ._gpu_resample import RECON_FORMS, reconstruct_stacks, resample_volume  # noqa: F401
 from ._gpu_roi import ROI_MAX_LABELS, RoiStats, dense_labels, roi_erode, roi_frame, roi_stats, roi_table  # noqa: F401

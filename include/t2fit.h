@@ -626,6 +626,93 @@ int t2fit_register_sums_lut_dev(const uint8_t *bins_dev, const double *lut_dev, 
                                 int my, int mx, const double *A, double *sums_dev, void *workspace_dev,
                                 size_t workspace_bytes, void *stream);
 
+/* ---- N4 bias-field correction: log image, sharpening histogram, B-spline fit, field -------------------------------------
+ * The device half of the reference's run_biasfield_correction / run_biasfield_correction2 (utils/qmri_utils.py:254-357),
+ * which call sitk.N4BiasFieldCorrectionImageFilter.  The definition is written from the N4 paper (Tustison 2010), the
+ * multilevel B-spline paper (Lee, Wolberg and Shin 1997) and ITK's documentation; PARITY WITH ITK IS UNPINNED (DESIGN.md
+ * 8h).  The sharpening table, the lattice refinement, the convergence figure and the loop are host code
+ * (fetal_t2mapping_amd/_bias.py, which also restates everything here in numpy; the device results equal it bit for bit
+ * wherever no transcendental is involved).  Additive to ABI 5: eight new symbols (look them up).
+ *
+ * Every per-voxel volume is float32 [nz ny nx] in memory; all arithmetic is float64, every multiply and add rounding once
+ * (no fused multiply-add), one rounding at a float32 store.  Inputs must be finite.
+ *
+ * 1. LOG IMAGE.  M = mask != 0 and in > 0 (mask NULL: in > 0); u0 = (float)log((double)in) in M, +0.0 elsewhere.  The
+ *    loop starts from u = u0, field = 0 and a lattice L of zeros of side 4.
+ * 2. SHARPENING.  lo, hi = min, max of u over M; slope = (hi - lo) / (B - 1), B bins (200).  The bin coordinate of a
+ *    voxel: c = clamp(((double)u - lo) / slope, 0, B - 1), i = min(floor(c), B - 2), t = c - i.  The histogram is fixed
+ *    point: w = floor(t 2^24 + 0.5), H[i] += 2^24 - w, H[i + 1] += w in uint64 -- integer adds, exact in any order (a
+ *    stated departure from ITK's float histogram: 6e-8 of a voxel).  From H the host makes the table E[B] (the histogram
+ *    deconvolved by a Gaussian of full width fwhm with a Wiener filter, then the expected true value per bin).  The
+ *    sharpened value of a voxel is E[i] (1 - t) + E[i + 1] t and its residual r = (double)u - that, in M.
+ * 3. FIT, one level of multilevel B-spline approximation on a lattice of side c (4, 5, 7, 11, 19 by level).  Along an
+ *    axis of n voxels: s = c - 3, p = (i s) / (n - 1), k = floor(p), tau = p - k; for i = n - 1: k = s - 1, tau = 1; for
+ *    n = 1: k = 0, tau = 0.  The uniform cubic B-spline weights at nodes k .. k + 3, every other weight 0:
+ *      b0 = ((1 - tau)^2 (1 - tau)) / 6        b1 = ((3 tau^3 - 6 tau^2) + 4) / 6
+ *      b2 = (((-3 tau^3 + 3 tau^2) + 3 tau) + 1) / 6        b3 = tau^3 / 6        (tau^2 = tau tau, tau^3 = tau^2 tau)
+ *    q = b b, S = ((q0 + q1) + q2) + q3, a = (q b) / S.  Over the voxels of M,
+ *      delta[cz][cy][cx] = sum az ay ax r        omega[cz][cy][cx] = sum qz qy qx
+ *    contracted x first, then y, then z; the lattice increment is delta / omega, 0 where omega = 0: L += delta / omega.
+ *    THE ORDER OF SUMMATION is part of the definition.  The x contraction of a row (z, y) and node cx takes the terms
+ *    ax r (q for omega) in x order, zero-padded to a multiple of 64: lane l adds terms l, l + 64, .. in order from +0.0,
+ *    then the 64 lanes halve (v[i] + v[i + 32] for i < 32, then 16, .. 1).  The y and the z contraction add weight times
+ *    partial sum in index order from +0.0.  omega depends on M and the level only.
+ * 4. FIELD, at every voxel: T1[z][cy][cx] = ((bz0 L[kz] + bz1 L[kz + 1]) + bz2 L[kz + 2]) + bz3 L[kz + 3], T2[z][y][cx]
+ *    likewise from T1 along y, field = (float)(likewise from T2 along x).
+ * 5. CONVERGENCE.  d = expm1((double)field_new - (double)field_old) over M; sum d and sum d d per row by the lanes and
+ *    the halving of step 3, the rows in (z, y) order by passes of 256-to-1 halving groups (the last group padded with
+ *    zeros, at least one pass: the tree of t2fit_register_sums_dev).  Then u = (float)((double)u0 - (double)field_new)
+ *    in M, +0.0 elsewhere.  The host forms conv = sqrt((sum dd - (sum d)^2 / N) / (N - 1)) / (1 + sum d / N).
+ * 6. NEXT LEVEL: the host refines L by cubic subdivision (side c -> 2 c - 3; the field is unchanged).
+ * 7. OUTPUT: out = (float)(((double)in / exp((double)field)) scale) at every voxel.
+ * No floating-point atomics anywhere.  log, expm1 and exp are the device library's: results that pass through one may
+ * differ from another library's in the last bit.
+ *
+ * All pointers but `bytes` are device pointers.  Every entry point is asynchronous on `stream`, allocates and copies
+ * nothing, and checks every argument before HIP is touched (T2FIT_E_INVALID and a message): a NULL pointer (mask_dev of
+ * t2fit_n4_log_dev and table_dev of t2fit_n4_fit_dev alone may be NULL), a size < 1, more than 2^31-1 rows (nz ny) or
+ * 2^40 elements, n_vox outside 1..2^39-1, a lattice side that is not 4, 5, 7, 11 or 19, bins outside 2..1024, lo, slope
+ * or scale not finite, slope <= 0, float32 arrays not aligned to 4 bytes, float64 and uint64 arrays not aligned to 8,
+ * arrays that must differ being the same, a workspace that is NULL, not aligned to 256 bytes or too small.
+ *
+ * t2fit_n4_workspace_bytes: one workspace serves every entry point below for a volume and a side (the axis tables, the
+ * row sums of the x contraction [nz ny][c], the y contraction [nz][c][c], the rows' minima and maxima and the passes of
+ * the tree, each part rounded up to 256 bytes; never less than 8192).  Plain arithmetic, no device.  The entry points keep
+ * nothing in it between calls: it may hold anything, NaN included, when a call starts. */
+int t2fit_n4_workspace_bytes(int nz, int ny, int nx, int side, size_t *bytes);
+
+/* Step 1.  u0_dev: float32 [n_vox], m_dev: uint8 [n_vox] (0 / 1); u0_dev must not be in_dev. */
+int t2fit_n4_log_dev(const float *in_dev, const uint8_t *mask_dev, int64_t n_vox, float *u0_dev, uint8_t *m_dev, void *stream);
+
+/* range_dev: float32 [2] = min, max of u over M (+inf, -inf when M is empty).  workspace_dev: at least 8192 bytes. */
+int t2fit_n4_minmax_dev(const float *u_dev, const uint8_t *m_dev, int64_t n_vox, float *range_dev, void *workspace_dev,
+                        size_t workspace_bytes, void *stream);
+
+/* Step 2's histogram: hist_dev uint64 [bins], zeroed and filled by the call (a per-workgroup histogram in LDS, then
+ * integer atomics).  The sum of hist_dev is 2^24 times the voxels of M. */
+int t2fit_n4_histogram_dev(const float *u_dev, const uint8_t *m_dev, int64_t n_vox, double lo, double slope, int bins,
+                           uint64_t *hist_dev, void *stream);
+
+/* Step 3's omega: omega_dev float64 [side^3]. */
+int t2fit_n4_weights_dev(const uint8_t *m_dev, int nz, int ny, int nx, int side, double *omega_dev, void *workspace_dev,
+                         size_t workspace_bytes, void *stream);
+
+/* Step 3: delta_dev float64 [side^3] is written, lattice_dev float64 [side^3] is updated in place with omega_dev (of
+ * t2fit_n4_weights_dev for the same M and side).  table_dev: float64 [bins], the table E; NULL: r = u (lo, slope and
+ * bins are then ignored), which fits u itself. */
+int t2fit_n4_fit_dev(const float *u_dev, const uint8_t *m_dev, int nz, int ny, int nx, const double *table_dev, double lo,
+                     double slope, int bins, int side, const double *omega_dev, double *lattice_dev, double *delta_dev,
+                     void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* Steps 4 and 5: field_dev holds the old field and receives the new one; u_dev receives the new u; sums_dev float64 [2]
+ * = sum d, sum d d; range_dev float32 [2] = min, max of the new u over M, so the next iteration needs no range pass. */
+int t2fit_n4_field_dev(const double *lattice_dev, int side, const float *u0_dev, const uint8_t *m_dev, int nz, int ny, int nx,
+                       float *field_dev, float *u_dev, double *sums_dev, float *range_dev, void *workspace_dev,
+                       size_t workspace_bytes, void *stream);
+
+/* Step 7; out_dev may be in_dev, not field_dev. */
+int t2fit_n4_apply_dev(const float *in_dev, const float *field_dev, int64_t n_vox, double scale, float *out_dev, void *stream);
+
 /* Kernel timing for benchmarks (no reference counterpart).  With timing enabled (t2fit_set_timing(1)) every
  * t2fit_volume_dev call of this thread records HIP events around its fit kernel on the launch stream.
  * t2fit_kernel_ms(k): duration in milliseconds of the fit kernel launched k timed calls ago (0 = the most recent;
