@@ -9,6 +9,36 @@ from ._gpu import current_stream, flat, is_tensor, pick_device, release, require
 from ._lib import check
 
 
+_INT32_RANGE = (-2 ** 31, 2 ** 31 - 1)
+
+
+def _labels_fit_int32(vol, is_t):
+    """Refuse an integer volume whose ids do not fit the int32 the kernel copies (a cast would wrap them silently), with
+    their range in the message.  Returns the volume to convert: itself, or for torch's unsigned 32- and 64-bit types
+    (which torch neither reduces nor converts everywhere) the same bits as the signed type, equal in value once they
+    fit.  A tensor is reduced once where it lives and two numbers are read back: one synchronisation for a CUDA tensor."""
+    import torch
+
+    if (vol.numel() if is_t else vol.size) == 0:
+        return vol
+    wrap = 0
+    if not is_t:
+        lo, hi = int(vol.min()), int(vol.max())
+    else:
+        if vol.dtype in (torch.uint32, torch.uint64):
+            wrap = 2 ** (8 * vol.dtype.itemsize)
+            vol = vol.contiguous().view(torch.int32 if vol.dtype == torch.uint32 else torch.int64)
+        lo, hi = (int(v) for v in torch.stack(torch.aminmax(vol)).tolist())
+        if wrap and lo < 0:  # negative as signed is the upper half as unsigned; the refusal may take its time
+            neg, pos = vol[vol < 0], vol[vol >= 0]
+            hi = int(neg.max()) + wrap
+            lo = int(pos.min()) if pos.numel() else int(neg.min()) + wrap
+    if lo < _INT32_RANGE[0] or hi > _INT32_RANGE[1]:
+        raise ValueError(f"the label volume ({'u' if wrap else ''}{str(vol.dtype).split('.')[-1]}) holds values in [{lo}, {hi}], which do "
+                         f"not fit int32 [{_INT32_RANGE[0]}, {_INT32_RANGE[1]}]: renumber the ids before resampling")
+    return vol
+
+
 def resample_volume(vol, geom, *, res=None, like=None, transform=None, interp="linear", default=0.0, integer_cast=False,
                     device=0):
     """Resample ``vol`` -- ``(Z, Y, X)`` or ``(n, Z, Y, X)`` volumes that share the geometry ``geom`` (anything with
@@ -16,12 +46,26 @@ def resample_volume(vol, geom, *, res=None, like=None, transform=None, interp="l
     isotropic (the reference's ``resample_volume``, utils/qmri_utils.py:62-80; the default with ``res=1.0``) or the grid
     ``like`` (anything with the four Get* methods including GetSize, e.g. a :class:`_resample.Geometry`).  ``transform``:
     4 x 4, maps a physical point of the output grid to a physical point of ``vol`` (``sitk.Resample``'s sense).
-    ``interp='linear'`` takes float32 and returns float32; ``'nearest'`` copies float32 or int32 (label / mask volumes).
+    ``interp='linear'`` takes float32 and returns float32; ``'nearest'`` copies float32 or int32 (label / mask volumes:
+    any integer type whose values fit int32 comes back as int32, one whose values do not is refused with a ValueError
+    that names their range).
     ``integer_cast``: truncate toward zero and clamp to int16's range, as a stack that keeps an int16 pixel type does.
-    numpy in, numpy out; CUDA tensor in, tensor out (asynchronous on the current stream).  Returns ``(out, geometry)``.
+    numpy in, numpy out; CUDA tensor in, tensor out (asynchronous on the current stream, except that an integer tensor
+    wider than int32 -- int64, uint32, uint64 -- is first reduced to its range and that range read back: one
+    synchronisation).  Returns ``(out, geometry)``.
     :mod:`fetal_t2mapping_amd._resample` states the definition in numpy; the result is bit-identical to it."""
     import torch
 
+    is_t = is_tensor(vol)
+    if not is_t:
+        vol = np.asarray(vol)
+    if is_t:  # the integer types torch has; bool and the floating types go through float32
+        as_int = not (vol.dtype.is_floating_point or vol.dtype.is_complex or vol.dtype == torch.bool)
+        wide = vol.dtype.itemsize > 4 or vol.dtype == torch.uint32
+    else:
+        as_int, wide = vol.dtype.kind in "iu", vol.dtype.itemsize > 4 or vol.dtype == np.uint32
+    if as_int and wide:  # before the library is asked for: the refusal needs no device
+        vol = _labels_fit_int32(vol, is_t)
     lib = require(*_abi.RECON_SYMBOLS)
     if interp not in _abi.INTERPS:
         raise ValueError(f"interp must be 'linear' or 'nearest', got {interp!r}")
@@ -36,9 +80,7 @@ def resample_volume(vol, geom, *, res=None, like=None, transform=None, interp="l
     src_geom = _resample.as_geometry(geom, shape[-3:])
     dst_geom = _resample.isotropic_geometry(src_geom, res) if like is None else _resample.as_geometry(like)
     A = _resample.index_affine(dst_geom, src_geom, transform)
-    is_t = is_tensor(vol)
     dev = pick_device((vol,), device)
-    as_int = (vol.dtype in (torch.int32, torch.int16, torch.uint8, torch.int8)) if is_t else (np.asarray(vol).dtype.kind in "iu")
     if as_int and interp != "nearest":
         raise ValueError("an integer volume is resampled with interp='nearest'")
     src = flat(vol, dev, dtype="int32" if as_int else "float32")

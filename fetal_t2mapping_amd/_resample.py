@@ -135,8 +135,11 @@ def resample(src, A, out_shape, interp="linear", default=0.0, integer_cast=False
     hi = [np.minimum(lo[k] + 1, n[k] - 1) for k in range(3)]
 
     def lerp(p, q, w):  # where w == 0 the upper sample is not looked at: an Inf / NaN there stays there
+        # An infinite p makes p + w (q - p) the NaN of Inf - Inf; the weighted mean it stands for is that Inf (NaN only
+        # against the opposite Inf), which p + q is -- and p + q is NaN wherever p or q is
         with np.errstate(all="ignore"):
-            return np.where(w == 0.0, p, p + w * (q - p))
+            r = p + w * (q - p)
+            return np.where(w == 0.0, p, np.where(np.isnan(r), p + q, r))
 
     def along_x(z, y):
         return lerp(v[z, y, lo[0]], v[z, y, hi[0]], d[0])

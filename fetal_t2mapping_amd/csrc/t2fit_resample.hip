@@ -43,6 +43,14 @@ __device__ inline float integer_cast(double r) {  // an int16 pixel type: toward
   return (float)r;
 }
 
+// One level of the interpolation, weight w in (0, 1): lo + w (hi - lo).  An infinite lo makes that the NaN of Inf - Inf,
+// where the weighted mean it stands for is that Inf (NaN only against the opposite Inf): lo + hi is just that, and is NaN
+// wherever lo or hi is.  Finite values never take the branch.
+__device__ inline double lerp(double lo, double hi, double w) {
+  const double r = lo + w * (hi - lo);
+  return __builtin_expect(r != r, 0) ? lo + hi : r;
+}
+
 // Linear sample of a volume of `n` at output index (ix, iy, iz); fetch(x, y, z) returns the node as a double.
 // Outside the volume the result is default_value and nothing is fetched.
 template <typename Fetch>
@@ -60,7 +68,7 @@ __device__ inline float sample_linear(const Fetch& fetch, const Dims n, const Af
     double r = fetch(x0, y, z);
     if (dx != 0.0) {
       const double hi = fetch(x1, y, z);
-      r = r + dx * (hi - r);
+      r = lerp(r, hi, dx);
     }
     return r;
   };
@@ -68,14 +76,14 @@ __device__ inline float sample_linear(const Fetch& fetch, const Dims n, const Af
     double r = row(z, y0);
     if (dy != 0.0) {
       const double hi = row(z, y1);
-      r = r + dy * (hi - r);
+      r = lerp(r, hi, dy);
     }
     return r;
   };
   double r = plane(z0);
   if (dz != 0.0) {
     const double hi = plane(z1);
-    r = r + dz * (hi - r);
+    r = lerp(r, hi, dz);
   }
   return icast ? integer_cast(r) : (float)r;
 }

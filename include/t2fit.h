@@ -394,7 +394,9 @@ int t2fit_tv_denoise_dev(const t2fit_tv_params *p, const float *in_dev, float *o
  * T2FIT_INTERP_LINEAR: b_a = clamp(floor(c_a), 0, n_a - 1), d_a = max(c_a - b_a, 0), upper neighbour min(b_a + 1, n_a - 1)
  * (the half-voxel rim replicates the edge); interpolation along x, then y, then z in float64 as lo + d (hi - lo); where
  * d_a == 0 the upper sample along a is not read and the result is lo (a resample onto the source's own nodes is the
- * identity bit for bit, and an Inf next to a node does not become a NaN); one rounding to float32 at the end.  With
+ * identity bit for bit, and an Inf next to a node does not become a NaN); where lo + d (hi - lo) is NaN (an infinite lo:
+ * Inf - Inf) the level is lo + hi, so a voxel whose nodes of non-zero weight hold an Inf is that Inf, and NaN only if they
+ * hold a NaN or both Infs; one rounding to float32 at the end.  With
  * T2FIT_RESAMPLE_INTEGER_CAST the float64 result is first truncated toward zero and clamped to [-32768, 32767] (a stack
  * that is int16 on disk and keeps its pixel type through sitk.Resample).
  * T2FIT_INTERP_NEAREST: the node floor(c_a + 0.5), clamped into the volume, is copied (float32 or int32 sources).

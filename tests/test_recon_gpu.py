@@ -2,7 +2,11 @@
 (fetal_t2mapping_amd/_resample.py), bit for bit: the single stage over orientations, odd sizes, a rigid transform,
 both interpolations, the integer cast, one and eight volumes; the fused reconstruction against the statement, against
 the chain of single stages and against itself; the raw entry points; a phantom whose merge beats every single stack; a
-whole-size call; recon.py and cli.py --reconstruct on files.  tests/test_recon_host.py covers what needs no device."""
+whole-size call; recon.py and cli.py --reconstruct on files; and the cases of tests/resample_cases.py (brick geometry of
+each lane-axis kernel, lane-axis choice, rim and ties on every axis, patterns only a 32-bit copy carries, non-finite nodes
+under interpolation, the saturating cast, small ragged reconstructions) bit-equal to the statement AND held to the
+reference written from the definition, through raw calls on pointers 4 bytes off a 256-byte boundary into sentinel-guarded
+buffers.  tests/test_recon_host.py covers what needs no device."""
 import ctypes as C
 import os
 
@@ -10,6 +14,7 @@ import numpy as np
 import pandas as pd
 import pytest
 
+import resample_cases as K
 from fetal_t2mapping_amd import _resample as R
 
 pytestmark = pytest.mark.gpu
@@ -321,3 +326,186 @@ def test_recon_writes_recon_1mm_and_cli_reconstruct_fits_the_same_maps(t2, tmp_p
     with pytest.raises(ValueError, match="the mask of sub-001_ses-01 has shape"):
         cli.process_t2maps(md, bids, te_ms, fit, fit_params, False, True, True, False, False, "bad",
                            reconstruct=args.reconstruct_args)
+
+
+# ---- the cases of tests/resample_cases.py: the statement bit for bit (a NaN that arithmetic made by position: its sign and
+# payload are not defined, numpy's inf - inf is 0xffc00000 on x86 and the device makes the positive quiet NaN) and the
+# reference written from the definition ----------------------------------------------------------------------------------
+SENTINEL = 0x5EA7C0DE
+GUARD = 64  # sentinel words on each side of an output
+
+
+def _guarded(words, n_words=None):
+    """An int32 device buffer [1 word | GUARD sentinels | payload | GUARD sentinels], all sentinel but the payload when one
+    is given: the payload starts 4 bytes past a 256-byte boundary.  Returns ``(buffer, payload pointer, payload slice)``."""
+    import torch
+
+    n = len(words) if words is not None else n_words
+    buf = torch.full((1 + GUARD + n + GUARD,), SENTINEL, dtype=torch.int32, device="cuda")
+    assert buf.data_ptr() % 256 == 0
+    where = slice(1 + GUARD, 1 + GUARD + n)
+    if words is not None:
+        buf[where] = torch.from_numpy(np.ascontiguousarray(words).view(np.int32).ravel()).cuda()
+    ptr = buf.data_ptr() + 4 * (1 + GUARD)
+    assert ptr % 256 == 4
+    return buf, ptr, where
+
+
+def _payload(buf, where):
+    """The payload of a guarded buffer after a call; everything around it must still be the sentinel."""
+    host = buf.cpu().numpy()
+    assert np.all(host[:where.start] == SENTINEL) and np.all(host[where.stop:] == SENTINEL), "written outside the output"
+    return host[where]
+
+
+def _raw_single_stage(case, volumes=None):
+    """The case through t2fit_resample_dev: source and output 4 bytes off a 256-byte boundary, the output guarded."""
+    import torch
+
+    from fetal_t2mapping_amd import _abi
+    from fetal_t2mapping_amd._lib import load
+
+    lib = load()
+    src = case.src if volumes is None or case.src.ndim == 3 else case.src[:volumes]
+    n_vol = src.shape[0] if src.ndim == 4 else 1
+    sbuf, sptr, _ = _guarded(src.ravel())
+    n_out = n_vol * int(np.prod(case.out_shape))
+    obuf, optr, where = _guarded(None, n_out)
+    A = (C.c_double * 12)(*case.A.ravel())
+    rc = lib.t2fit_resample_dev(sptr, _abi.RESAMPLE_I32 if src.dtype == np.int32 else _abi.RESAMPLE_F32, *src.shape[-3:], A, optr,
+                                *case.out_shape, n_vol, _abi.INTERPS[case.interp], float(case.default),
+                                _abi.RESAMPLE_INTEGER_CAST if case.integer_cast else 0,
+                                C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0, lib.t2fit_last_error().decode()
+    torch.cuda.synchronize()
+    out = _payload(obuf, where).view(src.dtype if case.interp == "nearest" else np.float32)
+    return out.reshape(((n_vol,) if src.ndim == 4 else ()) + case.out_shape)
+
+
+def _statement(case, volumes=None):
+    src = case.src if volumes is None or case.src.ndim == 3 else case.src[:volumes]
+    with np.errstate(all="ignore"):
+        return R.resample(src, case.A, case.out_shape, case.interp, case.default, case.integer_cast)
+
+
+
+@pytest.mark.parametrize("group", sorted(K.SINGLE_STAGE_GROUPS))
+def test_single_stage_cases_equal_the_statement_and_meet_the_reference(t2, group):
+    """Each case once with all its volumes and, where it has three, once with the first alone (the per-volume offset then
+    lands in the second and third volumes' bricks or does not exist).  Equality with the reference on the dyadic cases,
+    the bar |got - e| <= ulp32(e)/2 + 32 * 2^-53 * M on the others; nearest by all 32 bits."""
+    worst = (0.0, 0.0)
+    for case in K.SINGLE_STAGE_GROUPS[group]():
+        for volumes in ((None, 1) if case.n_vol == 3 else (None,)):
+            got = _raw_single_stage(case, volumes)
+            assert K.bits_differ(got, _statement(case, volumes), nan_by_position=case.interp == "linear") == 0, (case, volumes)
+            worst = max(worst, K.check(case, got, volumes if case.src.ndim == 4 else None))
+            if case.meta is not None:
+                K.rim_facts(case, got)
+    print(f"{group}: worst ratio to the bar {worst[0]:.4f}, excess over ulp32/2 in units of 32 * 2^-53 * M {worst[1]:.4f}")
+
+
+def test_wrapper_carries_labels_bit_for_bit_and_refuses_ids_beyond_int32(t2):
+    import torch
+
+    lab_case, flt_case = K.nearest_cases()[0], K.nearest_cases()[2]
+    g = R.Geometry(lab_case.src.shape[::-1], (2.0, 2.0, 2.0))
+    h = R.isotropic_geometry(g, 1.0)
+    A = R.index_affine(h, g)
+    for src, default in ((lab_case.src, K.INT32_MAX), (lab_case.src, K.INT32_MIN), (flt_case.src, -0.0), (flt_case.src, 1e39)):
+        got, _ = t2.resample_volume(src, g, res=1.0, interp="nearest", default=default)
+        K.check_nearest(got, K.reference_sample(src, A, h.shape, "nearest"), default)
+    # any integer type whose values fit goes through as int32 labels; one whose values do not is refused with their range
+    small = np.abs(lab_case.src.astype(np.int64)) % 70000
+    want, _ = t2.resample_volume(small.astype(np.int32), g, res=1.0, interp="nearest", default=-1)
+    t64 = torch.from_numpy(small)
+    for vol in (small, small.astype(np.uint32), small.astype(np.uint64), t64, t64.cuda(), t64.to(torch.uint32).cuda(),
+                t64.to(torch.uint64).cuda()):
+        got, _ = t2.resample_volume(vol, g, res=1.0, interp="nearest", default=-1)
+        if torch.is_tensor(got):
+            assert got.dtype == torch.int32 and (got.is_cuda or not vol.is_cuda)
+            got = got.cpu().numpy()
+        assert got.dtype == np.int32 and np.array_equal(got, want)
+    assert np.any(want > 2 ** 16)
+    big = small.copy()
+    big[1, 2, 3] = 2 ** 32 + 7
+    for vol in (torch.from_numpy(big), torch.from_numpy(big).cuda(), torch.from_numpy(-big).cuda(),
+                torch.from_numpy(big).to(torch.uint64).cuda()):
+        with pytest.raises(ValueError, match="int32") as err:
+            t2.resample_volume(vol, g, res=1.0, interp="nearest")
+        assert str(2 ** 32 + 7) in str(err.value)
+    big[1, 2, 3] = 2 ** 31 + 5  # fits uint32, not int32
+    with pytest.raises(ValueError, match="int32") as err:
+        t2.resample_volume(torch.from_numpy(big).to(torch.uint32).cuda(), g, res=1.0, interp="nearest")
+    assert f"[0, {2 ** 31 + 5}]" in str(err.value) or str(2 ** 31 + 5) in str(err.value)
+
+
+def _device_stages(t2, stacks, geoms, kw):
+    """The five single-stage calls of the chain, by hand."""
+    order, hi, a1, a2 = R.plan(geoms, kw["fixed"], kw["res"], kw["transforms"])
+    cast = kw.get("integer_cast", False)
+    H = [t2.resample_volume(stacks[o], geoms[o], res=kw["res"], integer_cast=cast)[0] for o in order]
+    Rm = [t2.resample_volume(H[m], hi[m], like=hi[0], transform=kw["transforms"].get(order[m]), integer_cast=cast)[0] for m in (1, 2)]
+    return {"H": H, "R": Rm}
+
+
+RECON_REFERENCED = [(f, r, 1, "both") for f in K.RECON_FIXED for r in K.RECON_RES] + [("sag", 1.0, 3, "far"), ("ax", 1.0, 1, "cast")]
+RECON_AGREEING = [(f, r, 3, "both") for f in K.RECON_FIXED for r in K.RECON_RES] + [("cor", 0.8, 1, "far"), ("sag", 0.8, 3, "cast")]
+
+
+@pytest.mark.parametrize("fixed,res,n_vol,kind", RECON_REFERENCED + RECON_AGREEING)
+def test_small_ragged_reconstructions_fused_chain_and_statement_agree_and_meet_the_reference(t2, fixed, res, n_vol, kind):
+    """(9, 8, 3) stacks of 1 x 1 x 2.5 mm, transforms on both moving stacks: the fixed grid is ragged against the fused
+    kernel's 16 x 8 x 4 brick on every axis (at res 1.0 it is (8, 8, 9): two of the axes fill their bricks exactly), the last
+    nodes of every stage-1 grid lie outside their stack.  The referenced cases also hold the device's own five stages and
+    its merge to the reference, stage 2 from the very stage-1 arrays it read."""
+    stacks, geoms, kw = K.recon_case(fixed, res, n_vol, kind)
+    with np.errstate(all="ignore"):
+        want, _, stages = R.reconstruct(stacks, geoms, return_stages=True, **kw)
+    assert K.ragged(want.shape) if res != 1.0 else want.shape[-3:] == (8, 8, 9)
+    K.recon_facts(kind, stages)
+    fused = t2.reconstruct_stacks(stacks, geoms, form="fused", **kw)[0].cpu().numpy()
+    chain = t2.reconstruct_stacks(stacks, geoms, form="chain", **kw)[0].cpu().numpy()
+    assert K.bits_differ(fused, want) == 0 and K.bits_differ(chain, want) == 0, (fixed, res, n_vol, kind)
+    if (fixed, res, n_vol, kind) in RECON_REFERENCED:
+        dev = _device_stages(t2, stacks, geoms, kw)
+        for name in ("H", "R"):
+            for got, host in zip(dev[name], stages[name]):
+                assert K.bits_differ(got, host) == 0, name
+        print(f"worst ratio to the bar {K.check_reconstruction(stacks, geoms, kw, fused, dev):.6f}")
+
+
+@pytest.mark.parametrize("form", ["fused", "chain"])
+def test_raw_reconstruction_on_offset_pointers_writes_nothing_outside_its_output(t2, form):
+    """Stacks and output 4 bytes off a 256-byte boundary, the output guarded by sentinels; the chain's workspace at the exact
+    byte count with sentinels after it."""
+    import torch
+
+    from fetal_t2mapping_amd import _abi
+    from fetal_t2mapping_amd._lib import load
+
+    lib = load()
+    stacks, geoms, kw = K.recon_case("cor", 0.8, 3, "both")
+    order, hi, a1, a2 = R.plan(geoms, kw["fixed"], kw["res"], kw["transforms"])
+    held = [_guarded(stacks[o].ravel()) for o in order]
+    lo_size = (C.c_int32 * 9)(*[v for o in order for v in stacks[o].shape[-3:]])
+    hi_size = (C.c_int32 * 9)(*[v for g in hi for v in g.shape])
+    A1 = (C.c_double * 36)(*np.concatenate([a.ravel() for a in a1]))
+    A2 = (C.c_double * 24)(*np.concatenate([a.ravel() for a in a2]))
+    ptrs = (C.c_void_p * 3)(*[ptr for _, ptr, _ in held])
+    obuf, optr, where = _guarded(None, 3 * int(np.prod(hi[0].shape)))
+    flags = _abi.RECON_CHAIN if form == "chain" else 0
+    need = C.c_size_t(0)
+    assert lib.t2fit_reconstruct_workspace_bytes(3, lo_size, hi_size, flags, C.byref(need)) == 0
+    assert (need.value > 0) == (form == "chain")
+    ws = torch.full((need.value + 256,), 0xA5, dtype=torch.uint8, device="cuda")
+    assert ws.data_ptr() % 256 == 0
+    rc = lib.t2fit_reconstruct_dev(ptrs, lo_size, A1, hi_size, A2, optr, 3, flags, ws.data_ptr() if need.value else None, need.value,
+                                   C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0, lib.t2fit_last_error().decode()
+    torch.cuda.synchronize()
+    assert torch.all(ws[need.value:] == 0xA5), "written past the workspace"
+    out = _payload(obuf, where).view(np.float32).reshape((3,) + hi[0].shape)
+    for buf, _, src_where in held:
+        _payload(buf, src_where)
+    assert K.bits_differ(out, R.reconstruct(stacks, geoms, **kw)[0]) == 0

@@ -352,3 +352,96 @@ def test_cli_reconstruct_flags_and_the_shared_volume_refusal(tmp_path, monkeypat
     with pytest.raises(ValueError, match="--reconstruct is not run on a volume that is shared"):
         cli.process_t2maps(pd.DataFrame(rows), str(tmp_path) + "/", [114], fit, fit_params, False, True, True, False, False,
                            "s", reconstruct=a.reconstruct_args)
+
+
+# ---- the statement against the reference written from the definition (tests/resample_cases.py) ------------------------
+import resample_cases as K  # noqa: E402
+
+
+
+def _statement(case, volumes=None):
+    src = case.src if volumes is None else case.src[:volumes]
+    with np.errstate(over="ignore"):
+        return R.resample(src, case.A, case.out_shape, case.interp, case.default, case.integer_cast)
+
+
+@pytest.mark.parametrize("group", sorted(K.SINGLE_STAGE_GROUPS))
+def test_statement_meets_the_reference_from_the_definition(group):
+    """Equality on the dyadic cases, the derived bar |got - e| <= ulp32(e)/2 + 32 * 2^-53 * M elsewhere; non-finite
+    results by class and position, nearest by bits."""
+    worst = (0.0, 0.0)
+    for case in K.SINGLE_STAGE_GROUPS[group]():
+        ref = K.reference(case)
+        assert ref.inside.any() and ref.coord_ratio <= 1.0, case
+        worst = max(worst, K.check(case, _statement(case)))
+        if case.n_vol == 3:
+            K.check(case, _statement(case, 1), volumes=1)
+    print(f"{group}: worst ratio to the bar {worst[0]:.4f}, excess over ulp32/2 in units of 32 * 2^-53 * M {worst[1]:.4f}")
+
+
+def test_the_cases_contain_what_they_are_there_for():
+    """The reference alone: the named cases reach the edges they are meant to reach."""
+    on = K.reference(K.cast_cases()[0])
+    exact = on.exact[on.inside & (on.cls == K.FINITE)]
+    assert on.negzero.any() and (exact == 32767).any() and (exact == -32768).any() and (on.cls == K.NAN).any()
+    assert any(e not in (32767, -32768, 0) and e < 0 for e in exact)
+    for case in K.non_finite_cases():
+        ref = K.reference(case)
+        cls = ref.cls[ref.inside]
+        assert all((cls == c).any() for c in (K.FINITE, K.POS_INF, K.NEG_INF, K.NAN)), case
+    whole = K.reference(K.non_finite_cases()[0])
+    assert whole.taps[whole.inside].max() == 4  # not 8: the whole-voxel axis has weight 0
+    for la in K.LANE_AXES:
+        for case in K.brick_cases(la):
+            ref = K.reference(case)
+            assert ref.inside.any() and (case.out_shape == (1, 1, 1) or not ref.inside.all()), case
+    for case in K.nearest_cases():
+        bits = K.reference(case).bits
+        wanted = (K.NAN_QUIET, K.NAN_SIGNALLING, 0x80000000) if case.src.dtype == np.float32 else (0x80000000, 0x7FFFFFFF, 16777217, 16777219)
+        assert all((bits == w).any() for w in wanted), case
+
+
+@pytest.mark.parametrize("la", K.LANE_AXES)
+def test_rim_and_tie_facts_of_the_statement_on_every_axis(la):
+    for case in K.rim_cases(la):
+        K.rim_facts(case, _statement(case))
+
+
+def test_merge_meets_the_reference_in_the_order_of_the_definition():
+    a, b, c = K.merge_inputs()
+    K.check_merge(R.merge(a, b, c), a, b, c)
+    assert R.merge(np.float32([2.0 ** 60]), np.float32([-2.0 ** 60]), np.float32([1.0]))[0] == np.float32(1.0 / 3.0)
+
+
+RECON_HOST_CASES = [(f, r, 1, "both") for f in K.RECON_FIXED for r in K.RECON_RES] + [("sag", 1.0, 3, "far"), ("ax", 1.0, 1, "cast")]
+
+
+@pytest.mark.parametrize("fixed,res,n_vol,kind", RECON_HOST_CASES)
+def test_reconstruct_meets_the_reference_stage_by_stage(fixed, res, n_vol, kind):
+    stacks, geoms, kw = K.recon_case(fixed, res, n_vol, kind)
+    with np.errstate(all="ignore"):
+        merged, grid, stages = R.reconstruct(stacks, geoms, return_stages=True, **kw)
+    assert merged.shape[0] == n_vol and (K.ragged(merged.shape) if res != 1.0 else merged.shape[-3:] == (8, 8, 9))
+    K.recon_facts(kind, stages)
+    print(f"{fixed} {res} {n_vol} {kind}: worst ratio to the bar {K.check_reconstruction(stacks, geoms, kw, merged, stages):.6f}")
+
+
+def test_resample_volume_refuses_labels_that_do_not_fit_int32_before_any_launch():
+    from fetal_t2mapping_amd import _gpu_resample
+
+    g = R.Geometry((4, 3, 2))
+    for bad, text in ((np.full((2, 3, 4), 2 ** 32 + 7, np.int64), "4294967303"), (np.full((2, 3, 4), 2 ** 31, np.uint32), "2147483648"),
+                      (np.array([[[-2 ** 31 - 1, 5]]], np.int64), "-2147483649"), (np.full((1, 1, 1), 2 ** 63, np.uint64), str(2 ** 63))):
+        with pytest.raises(ValueError, match="int32") as err:
+            _gpu_resample.resample_volume(bad, g, like=g, interp="nearest")
+        assert text in str(err.value), str(err.value)
+    import torch
+
+    # torch's unsigned 32- and 64-bit tensors too (torch does not reduce them: their bits are read as the signed type)
+    for bad, text in ((torch.tensor([[[7, 2 ** 31 + 1, 3]]], dtype=torch.int64).to(torch.uint32), f"[3, {2 ** 31 + 1}]"),
+                      (torch.tensor([[[2 ** 63, 5]]], dtype=torch.uint64), f"[5, {2 ** 63}]"),
+                      (torch.tensor([[[7, 2 ** 40]]], dtype=torch.uint64), f"[7, {2 ** 40}]"),
+                      (torch.full((2, 3, 4), -2 ** 31 - 1, dtype=torch.int64), str(-2 ** 31 - 1))):
+        with pytest.raises(ValueError, match="int32") as err:
+            _gpu_resample.resample_volume(bad, g, like=g, interp="nearest")
+        assert text in str(err.value), str(err.value)
