@@ -11,47 +11,84 @@ import numpy as np
 DEFAULT_WEIGHT, DEFAULT_EPS, DEFAULT_MAX_ITER = 0.1, 2e-4, 200
 
 
-def tv_problem(f, weight=DEFAULT_WEIGHT, eps=DEFAULT_EPS, max_iter=DEFAULT_MAX_ITER, dtype=np.float32):
+def _lo(n, a):
+    """The voxels whose neighbour x - e_a is inside."""
+    return tuple(slice(1, None) if b == a else slice(None) for b in range(n))
+
+
+def _hi(n, a):
+    """The voxels whose neighbour x + e_a is inside."""
+    return tuple(slice(0, -1) if b == a else slice(None) for b in range(n))
+
+
+def step_sizes(n, weight, T):
+    """``(tau, tau / weight)``: each formed in float64 and rounded to the working precision once."""
+    return T(1.0 / (2.0 * n)), T((1.0 / (2.0 * n)) / float(weight))
+
+
+def divergence(p):
+    """``d = ((-(p_0 + .. + p_{n-1})) + p_0[x - e_0]) + p_1[x - e_1] ..``, a term dropped where ``x - e_a`` is outside."""
+    n = len(p)
+    s = p[0] + p[1]
+    if n == 3:
+        s = s + p[2]
+    d = -s
+    for a in range(n):
+        d[_lo(n, a)] = d[_lo(n, a)] + p[a][_hi(n, a)]
+    return d
+
+
+def gradient(out):
+    """The forward differences of ``out`` along every axis, 0 where ``x + e_a`` is outside."""
+    n = out.ndim
+    g = []
+    for a in range(n):
+        ga = np.zeros(out.shape, out.dtype)
+        ga[_hi(n, a)] = out[_lo(n, a)] - out[_hi(n, a)]
+        g.append(ga)
+    return g
+
+
+def energy(d, nrm, weight):
+    """``(sum d^2 + weight sum |g|) / N``: squares and norms in the working precision, the two sums in float64."""
+    return (float(np.sum((d * d).astype(np.float64))) + float(weight) * float(np.sum(nrm.astype(np.float64)))) / d.size
+
+
+def update(p, g, nrm, tau, tw):
+    """``p_a = (p_a - tau g_a) / (1 + (tau / weight) |g|)``."""
+    den = tau.dtype.type(1.0) + tw * nrm
+    return [(p[a] - tau * g[a]) / den for a in range(len(p))]
+
+
+def tv_problem(f, weight=DEFAULT_WEIGHT, eps=DEFAULT_EPS, max_iter=DEFAULT_MAX_ITER, dtype=np.float32, history=None):
     """One problem: ``f`` is a 2-D slice or a 3-D volume, iterated in ``dtype``.  Returns ``(out, n_iter, E)`` with ``out``
-    in ``dtype``, ``n_iter`` the number of updates of p the result reflects and ``E`` the energy of the last iteration."""
+    in ``dtype``, ``n_iter`` the number of updates of p the result reflects and ``E`` the energy of the last iteration.
+    ``history``: a list that receives the energy of every iteration.
+    The steps are the module's functions above, looked up at every call (tests/denoise_cases.py replaces them one at a
+    time with wrong variants to show that its reference notices)."""
     T = np.dtype(dtype).type
     f = np.asarray(f).astype(T)
     n = f.ndim
     if n not in (2, 3):
         raise ValueError("a problem is a 2-D slice or a 3-D volume")
-    tau = T(1.0 / (2.0 * n))
-    tw = T((1.0 / (2.0 * n)) / float(weight))
-    one = T(1.0)
+    tau, tw = step_sizes(n, weight, T)
     p = [np.zeros(f.shape, T) for _ in range(n)]
-    lo = [tuple(slice(1, None) if b == a else slice(None) for b in range(n)) for a in range(n)]   # x with x - e_a inside
-    hi = [tuple(slice(0, -1) if b == a else slice(None) for b in range(n)) for a in range(n)]    # x with x + e_a inside
     e_init = e_prev = e = 0.0
     out = f
     n_iter = 0
     with np.errstate(all="ignore"):
         for i in range(int(max_iter)):
-            if i == 0:
-                d = np.zeros(f.shape, T)
-            else:
-                s = p[0] + p[1]
-                if n == 3:
-                    s = s + p[2]
-                d = -s
-                for a in range(n):
-                    d[lo[a]] = d[lo[a]] + p[a][hi[a]]
+            d = np.zeros(f.shape, T) if i == 0 else divergence(p)
             out = f + d
-            g = []
-            for a in range(n):
-                ga = np.zeros(f.shape, T)
-                ga[hi[a]] = out[lo[a]] - out[hi[a]]
-                g.append(ga)
+            g = gradient(out)
             sq = g[0] * g[0] + g[1] * g[1]
             if n == 3:
                 sq = sq + g[2] * g[2]
             nrm = np.sqrt(sq)
-            e = (float(np.sum((d * d).astype(np.float64))) + float(weight) * float(np.sum(nrm.astype(np.float64)))) / f.size
-            den = one + tw * nrm
-            p = [(p[a] - tau * g[a]) / den for a in range(n)]
+            e = energy(d, nrm, weight)
+            if history is not None:
+                history.append(e)
+            p = update(p, g, nrm, tau, tw)
             n_iter = i
             if i == 0:
                 e_init = e_prev = e

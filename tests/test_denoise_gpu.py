@@ -1,12 +1,17 @@
 """The TV-Chambolle denoiser on the device (csrc/t2fit_denoise.hip) against its numpy statement (fetal_t2mapping_amd/_tv.py):
-bit for bit at a fixed iteration count, iteration counts under the stop rule, independence of the problems of one call,
-in-place / repeat / entry-point identities, a whole-size stack, and the step inside the fit pipeline and the CLI.
-tests/test_denoise_host.py covers the definition, the argument checks and the flags without a device."""
+bit for bit at a fixed iteration count over the table of edge shapes of tests/denoise_cases.py, the exact 1-D minimiser,
+iteration counts under the stop rule, independence of the problems of one call, in-place / repeat / entry-point
+identities, raw calls with unaligned buffers on a caller's stream, groups of volumes, a whole-size stack, and the step
+inside the fit pipeline and the CLI.  tests/test_denoise_host.py holds the statement to the independent references and
+covers the argument checks and the flags without a device."""
 import ctypes as C
 import os
+import time
 
 import numpy as np
 import pytest
+
+import denoise_cases as K
 
 pytestmark = pytest.mark.gpu
 
@@ -22,32 +27,25 @@ def t2():
     return t2
 
 
-def _stack(shape, seed, sigma=20.0):
-    """Piecewise-constant slices (blocks of 300 / 900 / 1500 over a zero background) under Rician noise."""
-    rng = np.random.default_rng(seed)
-    n, z, y, x = shape
-    yy, xx = np.meshgrid(np.arange(y), np.arange(x), indexing="ij")
-    clean = np.zeros(shape)
-    for v in range(n):
-        for k in range(z):
-            img = np.where((yy > y // 5) & (xx > x // 6), 300.0, 0.0)
-            img = np.where((yy > y // 2) & (xx < x // 2 + k), 900.0 + 50.0 * v, img)
-            img = np.where((yy - y / 2) ** 2 + (xx - x / 2) ** 2 < (min(y, x) / 5 + k) ** 2, 1500.0, img)
-            clean[v, k] = img
-    noisy = np.hypot(clean + rng.normal(scale=sigma, size=shape), rng.normal(scale=sigma, size=shape))
-    return noisy.astype(np.float32), clean
-
-
+_stack = K.picture
 SIZES = [(2, 1, 64, 64), (2, 5, 37, 53), (1, 3, 256, 256), (2, 16, 17, 1)]
+assert [shape for shape, _, _ in K.SHAPES[:4]] == SIZES  # the table keeps the first four as they were, with _stack(seed=11)
+TABLE = [(shape, dims, precision) for precision in ("f32", "f64") for dims in (2, 3) for shape, dim_list, _ in K.SHAPES
+         if dims in dim_list]
 
 
-@pytest.mark.parametrize("shape", SIZES, ids=lambda s: "x".join(map(str, s)))
-@pytest.mark.parametrize("dims", [2, 3])
-@pytest.mark.parametrize("precision", ["f32", "f64"])
+@pytest.mark.parametrize("shape,dims,precision", TABLE, ids=[f"{p}-{d}-" + "x".join(map(str, s)) for s, d, p in TABLE])
 def test_fixed_iteration_count_is_bit_equal_to_the_numpy_statement(t2, shape, dims, precision):
+    """Every entry of denoise_cases.SHAPES (each names the branch of the kernels it reaches)."""
     from fetal_t2mapping_amd import _tv
 
-    a, _ = _stack(shape, seed=11)
+    a = np.array(K.stack(shape))  # (the shared case is read-only)
+    if shape in SIZES:
+        assert np.array_equal(a, _stack(shape, seed=11)[0])
+    if shape == (1, 1, 1025, 65):
+        assert K.tiles(shape, dims) == 66
+    if shape == (2, 33, 57, 5):
+        assert 65 <= K.tiles(shape, dims) <= 127 and K.tiles(shape, dims) % 64 != 0
     for max_iter in (1, 2, 7, 40):
         want, want_n, want_e = _tv.denoise_tv(a, 25.0, 0.0, max_iter, dims, precision)
         got, info = t2.denoise_tv(a, 25.0, eps=0.0, max_iter=max_iter, dims=dims, precision=precision, return_info=True)
@@ -56,6 +54,36 @@ def test_fixed_iteration_count_is_bit_equal_to_the_numpy_statement(t2, shape, di
         bad = int(np.sum(got.view(np.uint32) != want.view(np.uint32)))
         assert bad == 0, (shape, dims, precision, max_iter, bad, float(np.abs(got - want).max()))
         assert np.allclose(info["energy"], want_e, rtol=1e-12, atol=0.0)
+        if a.size == 1:  # one voxel: E = 0 at every iteration, the loop runs out, out == f
+            assert np.array_equal(got, a) and info["energy"][0] == 0.0
+    if a.size == 1:  # .. under the default eps as well: 0 < eps * 0 never holds
+        got, info = t2.denoise_tv(a, 25.0, dims=dims, precision=precision, return_info=True)
+        assert np.array_equal(got, a) and info["n_iter"].tolist() == [199] and info["energy"][0] == 0.0
+
+
+@pytest.mark.parametrize("n,weight", K.ONE_D, ids=[f"n{n}-w{w:g}" for n, w in K.ONE_D])
+def test_one_dimensional_problems_reach_the_exact_minimiser(t2, n, weight):
+    """A column, a row and a 3-D line after K iterations with eps = 0 against the exact minimiser of 1-D total variation
+    (denoise_cases.exact_1d: bounded least squares on the dual, no Chambolle).  float64: within the float64 statement's
+    own distance plus half a float32 ulp of the output for the final rounding; float32: within twice the float32
+    statement's distance.  The bars come from the statement on the CPU, never from the device."""
+    f, u = K.exact_1d(n, weight)
+    for form, (dims, shape) in K.ONE_D_FORMS.items():
+        _, dist64 = K.statement_1d(n, weight, form, K.K, "f64")
+        assert dist64 <= 1e-6, (form, dist64)  # the reference is converged before the device is looked at
+        _, dist32 = K.statement_1d(n, weight, form, K.K, "f32")
+        assert 0.0 < dist32 <= K.STATEMENT_DISTANCE["f32"]
+        a = np.array(f).reshape(shape(n))
+        for precision in ("f64", "f32"):
+            t0 = time.perf_counter()
+            got, info = t2.denoise_tv(a, weight, eps=0.0, max_iter=K.K, dims=dims, precision=precision, return_info=True)
+            dt = time.perf_counter() - t0
+            assert info["n_iter"].tolist() == [K.K - 1]
+            err = np.abs(got.reshape(-1).astype(np.float64) - u)
+            bar = dist64 + 0.5 * np.spacing(np.abs(got.reshape(-1))).astype(np.float64) if precision == "f64" else 2.0 * dist32
+            print(f"n {n} weight {weight} {form} {precision}: max |device - exact| {err.max():.3g}, statement f64 {dist64:.3g} "
+                  f"f32 {dist32:.3g}, {K.K} iterations in {dt:.3f} s")
+            assert np.all(err <= bar), (form, precision, float(err.max()), float(np.max(bar)))
 
 
 @pytest.mark.parametrize("dims,precision", [(2, "f32"), (2, "f64"), (3, "f32"), (3, "f64")])
@@ -63,15 +91,23 @@ def test_stop_rule_gives_the_iteration_counts_of_the_numpy_statement(t2, dims, p
     from fetal_t2mapping_amd import _tv
 
     a, _ = _stack((2, 6, 96, 80), seed=5)
-    for weight in (0.1, 10.0, 20.0, 40.0):
-        want, want_n, want_e = _tv.denoise_tv(a, weight, 2e-4, 200, dims, precision)
-        got, info = t2.denoise_tv(a, weight, dims=dims, precision=precision, return_info=True)
-        diff = np.flatnonzero(info["n_iter"] != want_n)
-        for k in diff:  # the bar is none; a marginal stop (|E_prev - E| within float64 rounding of the threshold) would show here
-            print(f"problem {k}: n_iter {info['n_iter'][k]} vs {want_n[k]}, E {info['energy'][k]!r} vs {want_e[k]!r}")
-        assert diff.size == 0, (weight, diff, info["n_iter"][diff], want_n[diff])
-        assert got.tobytes() == want.tobytes(), weight
-        print(f"dims {dims} {precision} weight {weight}: n_iter min {want_n.min()} mean {want_n.mean():.1f} max {want_n.max()}")
+    # the picture, and an entry of the table with several x tiles and a ragged quad; test_denoise_host.py keeps every
+    # iteration of every problem of both at least 1e-9 E_init away from the threshold
+    b = np.array(K.stop_stacks()[1])
+    assert np.array_equal(K.stop_stacks()[0], a) and b.shape[-1] > 64 and b.shape[-1] % 4 != 0
+    assert K.STOP_WEIGHTS == (0.1, 10.0, 20.0, 40.0)
+    for stack in (a, b):
+        for weight in (0.1, 10.0, 20.0, 40.0):
+            want, want_n, want_e = _tv.denoise_tv(stack, weight, 2e-4, 200, dims, precision)
+            got, info = t2.denoise_tv(stack, weight, dims=dims, precision=precision, return_info=True)
+            diff = np.flatnonzero(info["n_iter"] != want_n)
+            for k in diff:  # the bar is none; a marginal stop (|E_prev - E| within float64 rounding of the threshold) would show here
+                print(f"problem {k}: n_iter {info['n_iter'][k]} vs {want_n[k]}, E {info['energy'][k]!r} vs {want_e[k]!r}")
+            assert diff.size == 0, (weight, diff, info["n_iter"][diff], want_n[diff])
+            assert got.tobytes() == want.tobytes(), weight
+            assert np.allclose(info["energy"], want_e, rtol=1e-12, atol=0.0)
+            print(f"{stack.shape} dims {dims} {precision} weight {weight}: n_iter min {want_n.min()} mean {want_n.mean():.1f} "
+                  f"max {want_n.max()}")
     assert np.all(_tv.denoise_tv(a, 0.1, 2e-4, 200, 2, "f32")[1] == 1)  # the reference's setting: one update
 
 
@@ -132,6 +168,108 @@ def test_raw_ctypes_call_equals_the_wrapper(t2):
     assert lib.t2fit_tv_denoise_dev(C.byref(par), src.data_ptr(), dst.data_ptr(), 2, 3, 33, 44, ws.data_ptr() + 16, need.value,
                                     None, None, st) == _abi.E_INVALID
     assert b"aligned" in lib.t2fit_last_error()
+
+
+@pytest.mark.parametrize("dims", [2, 3])
+@pytest.mark.parametrize("precision", ["f32", "f64"])
+def test_raw_calls_on_another_stream_poisoned_workspace_and_offset_buffers(t2, dims, precision):
+    """ctypes calls on a caller's stream, the workspace all 0xFF (every float and double of it a NaN) before each call,
+    nx % 4 == 0: (a) in and out 4 bytes past a 256-byte boundary, (b) only out, (c) only in, (d) in place 4 bytes past,
+    (e) aligned with n_iter_dev and energy_dev NULL.  Every result bit-equal to the statement, at an even and an odd
+    n_iter; the words around every output buffer keep their bytes."""
+    import torch
+
+    from fetal_t2mapping_amd import _abi, _tv
+    from fetal_t2mapping_amd._lib import load
+
+    lib = load()
+    shape = (2, 3, 9, 68)
+    a = K.field(shape, seed=68)
+    n, pad, guard = a.size, 64, 0x5A5A5A5A
+    n_problems = len(K.problems(a, dims))
+    stream = torch.cuda.Stream()
+    st = C.c_void_p(stream.cuda_stream)
+
+    def buffer(shift):
+        """n floats that start `shift` * 4 bytes past a 256-byte boundary, guard words on both sides."""
+        buf = torch.full((n + 3 * pad,), guard, dtype=torch.int32, device="cuda")
+        assert buf.data_ptr() % 256 == 0
+        view = buf[pad + shift:pad + shift + n].view(torch.float32)
+        assert view.data_ptr() % 256 == 4 * shift
+        return buf, view
+
+    def guards_kept(buf, shift):
+        host = buf.cpu().numpy()
+        return bool(np.all(host[:pad + shift] == guard) and np.all(host[pad + shift + n:] == guard))
+
+    for max_iter in (7, 8):
+        par = _abi.T2FitTvParams()
+        assert lib.t2fit_tv_params_default(C.byref(par)) == _abi.OK
+        par.weight, par.eps, par.max_iter, par.dims, par.precision = 12.0, 0.0, max_iter, dims, _abi.PRECISIONS[precision]
+        want, want_n, want_e = _tv.denoise_tv(a, 12.0, 0.0, max_iter, dims, precision)
+        need = C.c_size_t()
+        assert lib.t2fit_tv_workspace_bytes(C.byref(par), *shape, C.byref(need)) == _abi.OK
+        for name, in_shift, out_shift, in_place, with_info in (("a", 1, 1, False, True), ("b", 0, 1, False, True),
+                                                               ("c", 1, 0, False, True), ("d", 1, 1, True, True),
+                                                               ("e", 0, 0, False, False)):
+            with torch.cuda.stream(stream):
+                ws = torch.empty(need.value + 256, dtype=torch.uint8, device="cuda")
+                ws.fill_(0xFF)
+                ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+                src_buf, src = buffer(in_shift)
+                src.copy_(torch.from_numpy(a.reshape(-1)))
+                dst_buf, dst = (src_buf, src) if in_place else buffer(out_shift)
+                n_iter = torch.full((n_problems,), -1, dtype=torch.int32, device="cuda")
+                energy = torch.full((n_problems,), -1.0, dtype=torch.float64, device="cuda")
+                rc = lib.t2fit_tv_denoise_dev(C.byref(par), src.data_ptr(), dst.data_ptr(), *shape, ws_ptr, need.value,
+                                              n_iter.data_ptr() if with_info else None,
+                                              energy.data_ptr() if with_info else None, st)
+                assert rc == _abi.OK, (name, lib.t2fit_last_error())
+                stream.synchronize()
+            what = (name, dims, precision, max_iter)
+            assert dst.cpu().numpy().tobytes() == want.tobytes(), what
+            assert guards_kept(dst_buf, out_shift), what
+            if not in_place:
+                assert src.cpu().numpy().tobytes() == a.tobytes() and guards_kept(src_buf, in_shift), what
+            if with_info:
+                assert np.array_equal(n_iter.cpu().numpy(), want_n) and np.all(want_n == max_iter - 1), what
+                assert np.allclose(energy.cpu().numpy(), want_e, rtol=1e-12, atol=0.0), what
+            else:
+                assert np.all(n_iter.cpu().numpy() == -1) and np.all(energy.cpu().numpy() == -1.0), what
+
+
+def test_groups_of_three_and_two_volumes_equal_the_whole_call(t2, monkeypatch):
+    """Five volumes under a max_workspace_bytes that fits exactly three: the wrapper halves 5 to 3, runs 3 and 2, and
+    returns the bytes of the whole call."""
+    from fetal_t2mapping_amd import _abi
+    from fetal_t2mapping_amd._gpu_tv import tv_params
+    from fetal_t2mapping_amd._lib import load
+
+    lib = load()
+    shape = (5, 2, 9, 12)
+    a = K.field(shape, seed=5)
+    par = tv_params(15.0)
+
+    def need(n_vol):
+        v = C.c_size_t()
+        assert lib.t2fit_tv_workspace_bytes(C.byref(par), n_vol, *shape[1:], C.byref(v)) == _abi.OK
+        return v.value
+
+    budget = need(3)
+    assert need(5) > budget and need(4) > budget and (5 + 1) // 2 == 3  # 5 does not fit, its half rounded up does
+    want, winfo = t2.denoise_tv(a, 15.0, return_info=True)
+    real, calls = lib.t2fit_tv_denoise_dev, []
+
+    def spy(*args):
+        calls.append((int(args[3]), int(args[8])))
+        return real(*args)
+
+    monkeypatch.setattr(lib, "t2fit_tv_denoise_dev", spy)
+    got, info = t2.denoise_tv(a, 15.0, return_info=True, max_workspace_bytes=budget)
+    assert calls == [(3, budget), (2, budget)]
+    assert got.tobytes() == want.tobytes() and np.array_equal(info["n_iter"], winfo["n_iter"])
+    assert info["energy"].tobytes() == winfo["energy"].tobytes()
+    assert len(set(info["n_iter"].tolist())) > 1  # (the problems differ: a wrong offset of a group's results would show)
 
 
 def test_whole_size_stack_at_one_sigma(t2):

@@ -1,5 +1,8 @@
 """Host side of the TV-Chambolle denoiser (no device): the numpy statement of the definition (fetal_t2mapping_amd/_tv.py)
-against properties that pin it independently of any implementation, the ABI of the built library (version still 5, the
+against properties that pin it independently of any implementation, against the two independent references of
+tests/denoise_cases.py (Chambolle's iteration in long double over the table of edge shapes, the exact 1-D minimiser),
+mutations of the statement that must each miss those bars, the stop-rule cases' distance from a marginal stop, the ABI of
+the built library (version still 5, the
 three additive entry points, the workspace arithmetic, every argument check refused with a message before HIP is
 touched), and the --denoise flags of the CLI.  tests/test_denoise_gpu.py runs the kernels."""
 import ctypes as C
@@ -7,6 +10,8 @@ import os
 
 import numpy as np
 import pytest
+
+import denoise_cases as K
 
 
 def _slice(seed=0, sigma=20.0, shape=(96, 80)):
@@ -95,6 +100,108 @@ def test_stack_is_the_slices_one_by_one_and_eps_zero_runs_out():
     assert n3.shape == (1,) and n3[0] == 8 and not np.array_equal(out3, out[0])
     thin, n_thin, _ = _tv.denoise_tv(np.ones((2, 5, 1), np.float32) * np.arange(5, dtype=np.float32)[None, :, None], 1.0, 0.0, 4)
     assert thin.shape == (2, 5, 1) and np.all(n_thin == 3)
+
+
+# ---- the statement against the independent references of denoise_cases.py ---------------------------------------------------
+@pytest.mark.parametrize("case", K.CASES, ids=K.case_id)
+def test_statement_equals_the_long_double_reference(case):
+    """out within TOL_p eps_p max |f| and the energy within TOL_p eps_p relative, after 1, 2, 7 and 40 updates, on every
+    problem of every case of the table, in both precisions (denoise_cases.TOL)."""
+    for precision in ("f32", "f64"):
+        r_out, r_e = K.check_statement(*case, precision)
+        print(f"{K.case_id(case)} {precision}: out {r_out:.3f} energy {r_e:.3f} (bar {K.TOL[precision]:.0f})")
+
+
+def test_the_measured_ratios_are_the_largest_the_statement_shows():
+    """TOL is 16 times MEASURED_RATIO; each figure is reached (to the digits written) on the case named beside it."""
+    for precision in ("f32", "f64"):
+        want_out, want_e = K.MEASURED_RATIO[precision]
+        r_out = K.statement_ratios(*K.WORST_OUT, precision)[0]
+        r_e = K.statement_ratios(*K.WORST_ENERGY, precision)[1]
+        print(precision, r_out, r_e)
+        assert 0.99 * want_out <= r_out <= want_out and 0.99 * want_e <= r_e <= want_e
+        assert K.TOL[precision] == 16 * max(want_out, want_e)
+
+
+def test_the_reference_by_its_own_definition():
+    """The long-double reference at a size where the definition can be written out by hand: two voxels in a row."""
+    f = np.array([[100.0, 160.0]])
+    w = 25.0
+    assert np.array_equal(K.ref_updates(f, w, 0), f) and K.ref_energy(f, w, 0) == w * 60.0 / 2
+    # one update: p_x(0) = -tau 60 / (1 + tau 60 / w), everything else 0; u = f - div p moves the two towards each other
+    p = -0.25 * 60.0 / (1.0 + 0.25 * 60.0 / w)
+    u = K.ref_updates(f, w, 1)
+    assert np.allclose(u.astype(np.float64), [[100.0 - p, 160.0 + p]], rtol=1e-15) and p < 0
+    assert abs(float(K.ref_energy(f, w, 1)) - (2 * p * p + w * (60.0 + 2 * p)) / 2) < 1e-12
+    assert K.tiles((1, 1, 1025, 65), 2) == 66 and K.tiles((2, 33, 57, 5), 3) == 72 and K.tiles((1, 1, 1, 1), 3) == 1
+
+
+def test_one_dimensional_problems_reach_the_exact_minimiser():
+    """The float64 statement with eps = 0 against the minimiser bounded least squares finds from the dual (its KKT
+    conditions are asserted where it is computed): within 1e-6 after K iterations as a column, a row and a volume, K the
+    smallest such count, and within rounding of the solver's u after 20000."""
+    worst = K.check_1d(K.K, 1e-6)
+    print(f"K = {K.K}: largest distance {worst:.4g}")
+    assert 0.99 * K.STATEMENT_DISTANCE["f64"] <= worst <= K.STATEMENT_DISTANCE["f64"]
+    assert K.statement_1d(48, 60.0, "volume", K.K - 1)[1] > 1e-6  # K is the smallest
+    worst32 = max(K.statement_1d(n, w, form, K.K, "f32")[1] for n, w in K.ONE_D for form in K.ONE_D_FORMS)
+    print(f"float32 statement at K: largest distance {worst32:.4g}")
+    assert 0.99 * K.STATEMENT_DISTANCE["f32"] <= worst32 <= K.STATEMENT_DISTANCE["f32"]
+    for n, w in K.ONE_D:
+        f, u = K.exact_1d(n, w)
+        dist = K.statement_1d(n, w, "row", 20000)[1]
+        print(f"n = {n}, weight {w}: {dist:.3g} from the exact minimiser after 20000 iterations")
+        # u = f - D^T z is itself rounded: up to n roundings of values of max |f|, and as many in the statement's
+        assert dist <= 2 * n * 2.0 ** -53 * float(np.max(f)) and dist <= K.ONE_D_CONVERGED
+        # another scaling of the weight is far away: the minimiser moves by 5 units and more between weight and 2 weight
+        assert np.max(np.abs(K.exact_1d(n, 2 * w)[1] - u)) > 5.0
+
+
+@pytest.mark.parametrize("name", sorted(K.MUTATIONS))
+def test_a_mutated_statement_fails(name):
+    """Each wrong variant of a step of _tv misses a bar on the case named beside it, in both precisions; the statement
+    itself passes there before and after."""
+    where = K.MUTATIONS[name][2]
+
+    def check():
+        if where == "1d":
+            K.statement_1d.cache_clear()
+            K.check_1d(K.K, 1e-6)
+        else:
+            for precision in ("f32", "f64"):
+                K.check_statement(*where, precision)
+
+    def fails():
+        if where == "1d":
+            K.statement_1d.cache_clear()
+            with pytest.raises(AssertionError):
+                K.check_1d(K.K, 1e-6)
+        else:
+            for precision in ("f32", "f64"):
+                with pytest.raises(AssertionError):
+                    K.check_statement(*where, precision)
+
+    check()
+    with K.mutated(name):
+        fails()
+    check()  # (the statement is itself again)
+
+
+def test_stop_rule_cases_are_not_marginal():
+    """The cases of test_denoise_gpu.py's stop-rule test, by the statement: on every iteration of every problem
+    |E_prev - E| is at least 1e-9 E_init away from the threshold (the kernel sums the energy in another order than
+    np.sum, to about 1e-12), and one call stops problems at odd and at even counts (the finish kernel picks the half of
+    the ping-pong pair by parity)."""
+    both = False
+    for a in K.stop_stacks():
+        for dims, precision in ((2, "f32"), (2, "f64"), (3, "f32"), (3, "f64")):
+            for weight in K.STOP_WEIGHTS:
+                n_iter, margin = K.stop_margins(a, weight, dims, precision)
+                print(f"{a.shape} dims {dims} {precision} weight {weight}: n_iter {n_iter.tolist()} margin {margin:.3g}")
+                assert margin >= K.STOP_MARGIN, (a.shape, dims, precision, weight, margin)
+                stopped = n_iter[n_iter < 199]
+                both = both or (np.any(stopped % 2 == 0) and np.any(stopped % 2 == 1))
+    assert both
 
 
 def test_built_library_keeps_abi_5_and_refuses_bad_denoise_arguments_without_a_device():
