@@ -70,6 +70,7 @@ MORPH_F32, MORPH_I32, MORPH_U8 = 0, 1, 2
 
 REGISTER_SUMS = 43
 REGISTER_MAX_BINS = 64
+REGISTER_MI_SUMS = 12
 
 # every symbol include/t2fit.h declares: (name, restype, argtypes)
 _P = C.c_void_p
@@ -124,6 +125,11 @@ SYMBOLS = [
                                                  C.POINTER(C.c_double), C.c_int, _P, _P, _P, C.c_size_t, _P]),
     ("t2fit_register_sums_lut_dev", C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
                                               C.POINTER(C.c_double), _P, _P, C.c_size_t, _P]),
+    ("t2fit_register_joint_hist_dev", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
+                                                C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double, C.c_double, _P, _P]),
+    ("t2fit_register_mi_workspace_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    ("t2fit_register_mi_gradient_dev", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_double, C.c_double, _P, C.c_int, C.c_int, C.c_int,
+                                                 _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _P, _P, C.c_size_t, _P]),
     ("t2fit_n4_workspace_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     ("t2fit_n4_log_dev", C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
     ("t2fit_n4_minmax_dev", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
@@ -155,7 +161,8 @@ ATLAS_SYMBOLS = ("t2fit_register_bin_dev", "t2fit_register_binned_workspace_byte
                  "t2fit_register_sums_lut_dev")
 N4_SYMBOLS = ("t2fit_n4_workspace_bytes", "t2fit_n4_log_dev", "t2fit_n4_minmax_dev", "t2fit_n4_histogram_dev", "t2fit_n4_weights_dev",
               "t2fit_n4_fit_dev", "t2fit_n4_field_dev", "t2fit_n4_apply_dev")
-LOOKED_UP = ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS
+MI_SYMBOLS = ("t2fit_register_joint_hist_dev", "t2fit_register_mi_workspace_bytes", "t2fit_register_mi_gradient_dev")
+LOOKED_UP = ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS + MI_SYMBOLS
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

@@ -38,16 +38,17 @@ def subject_mask(subject, mask):
 
 
 def atlas_labels(subject, subject_geom, template, template_geom, atlases, *, mask=None, bins=32, dof=12, levels=(4, 2, 1),
-                 max_iter=100, init="centroids"):
+                 max_iter=100, init="centroids", metric="cr"):
     """``(warped template float32, {name: int32 labels}, Registration)`` on the subject's grid: the brain is extracted
     (``mask``; None: ``build_mask``), the template (moving, its mask ``template > 0``) is registered onto it (fixed) with
-    the correlation ratio, and the found transform resamples the template (linear) and every atlas (nearest, 0 outside)."""
+    the correlation ratio (``metric`` 'cr') or Mattes mutual information ('mattes'), and the found transform resamples the
+    template (linear) and every atlas (nearest, 0 outside)."""
     subject, template = np.asarray(subject, np.float32), np.asarray(template, np.float32)
     atlases = check_atlases(atlases, template.shape)
     fmask = subject_mask(subject, mask)
     brain = extract_brain(subject, fmask)
     sg, tg = _resample.as_geometry(subject_geom, subject.shape), _resample.as_geometry(template_geom, template.shape)
-    found = _register.register_affine(brain, template, sg, tg, metric="cr", bins=bins, dof=dof, fixed_mask=fmask,
+    found = _register.register_affine(brain, template, sg, tg, metric=metric, bins=bins, dof=dof, fixed_mask=fmask,
                                       moving_mask=(template > 0).astype(np.uint8), levels=levels, max_iter=max_iter, init=init)
     a = _resample.index_affine(sg, tg, found.transform)
     warped = _resample.resample(template, a, subject.shape)

@@ -23,7 +23,7 @@ def extract_brain(vol, mask, *, device=0):
 
 
 def atlas_labels(subject, subject_geom, template, template_geom, atlases, *, mask=None, bins=32, dof=12, levels=(4, 2, 1),
-                 max_iter=100, init="centroids", device=0):
+                 max_iter=100, init="centroids", metric="cr", device=0):  # noqa: A002
     """The reference's ``build_jhu_ho_labels`` (utils/qmri_utils.py:1011-1037) without FSL: ``subject`` (float32
     ``(Z, Y, X)``, e.g. the first-echo reconstruction) is brain-extracted with ``mask`` (None: :func:`build_mask`), the
     ``template`` (e.g. MNI152 T1; its mask is ``template > 0``) is registered onto it by
@@ -32,7 +32,8 @@ def atlas_labels(subject, subject_geom, template, template_geom, atlases, *, mas
     nearest-neighbour interpolation (t2fit_resample_dev, int32, 0 outside) onto the subject's grid.  Returns ``(warped
     template float32, {name: int32 labels}, Registration)`` as numpy arrays; ``Registration.transform`` is the 4 x 4
     (subject point -> template point, LPS mm -- not FSL's convention).  Equal to :func:`_atlas.atlas_labels`.  Parity with
-    flirt is not pinned: the cost and the transform model are its, the optimizer and the (absent) search are not."""
+    flirt is not pinned: the cost and the transform model are its, the optimizer and the (absent) search are not.
+    ``metric``: 'cr', or 'mattes' for Mattes mutual information."""
     import torch
 
     dev = pick_device((subject, template, mask), device)
@@ -42,7 +43,7 @@ def atlas_labels(subject, subject_geom, template, template_geom, atlases, *, mas
     fmask = build_mask(s, device=dev.index) if mask is None else volume(mask, torch.uint8, dev, "mask")
     brain = extract_brain(s, fmask)
     sg, tg = _resample.as_geometry(subject_geom, tuple(s.shape)), _resample.as_geometry(template_geom, tuple(t.shape))
-    found = _gpu_register.register_affine(brain, t, sg, tg, metric="cr", bins=bins, dof=dof, fixed_mask=fmask,
+    found = _gpu_register.register_affine(brain, t, sg, tg, metric=metric, bins=bins, dof=dof, fixed_mask=fmask,
                                           moving_mask=(t > 0).to(torch.uint8), levels=levels, max_iter=max_iter, init=init,
                                           device=dev.index)
     warped = resample_volume(t, tg, like=sg, transform=found.transform)[0].cpu().numpy()

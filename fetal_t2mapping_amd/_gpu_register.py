@@ -84,12 +84,16 @@ class DeviceAffinePyramid(DevicePyramid):
     ``bins`` keeps a level's uint8 bin volume on the device (t2fit_register_bin_dev, once per level; the level's range
     inside its mask is read on the host, one copy of the level per level).  ``cr_sums`` queues
     t2fit_register_binned_sums_dev (N_b, S_b and the table) and t2fit_register_sums_lut_dev on the current stream -- no
-    host step in between -- and copies ``2 n_bins + 43`` doubles back, which waits for the stream."""
+    host step in between -- and copies ``2 n_bins + 43`` doubles back, which waits for the stream.  Mattes mutual
+    information takes a round trip per evaluation: ``joint_hist`` (t2fit_register_joint_hist_dev) copies the ``n_f n_m``
+    integers back, the host makes the metric and the table (:func:`_register.mattes_metric`), ``mi_sums`` uploads the
+    table and copies the 12 sums of t2fit_register_mi_gradient_dev back."""
 
     def __init__(self, fixed, fixed_mask, moving, moving_mask, dev):
         super().__init__(fixed, fixed_mask, moving, moving_mask, dev)
         self.lib = require(*(_abi.REGISTER_SYMBOLS + _abi.ATLAS_SYMBOLS))
         self._bufs = {}
+        self._mi_bufs = {}
 
     def bins(self, level, n_bins):
         lo, scale = _register.bin_range(level[0].cpu().numpy(), level[1].cpu().numpy(), n_bins)
@@ -126,6 +130,55 @@ class DeviceAffinePyramid(DevicePyramid):
         self.lut = host[2 * n_bins:3 * n_bins]
         return host[:2 * n_bins], host[3 * n_bins:]
 
+    def moving_range(self, level, n_m):
+        return _register.moving_bin_range(level[2].cpu().numpy(), level[3].cpu().numpy(), n_m)
+
+    def _mi_buffers(self, shape, n_f, n_m):
+        """(hist [n_f n_m] int64, table [n_f n_m] float64, sums [12] float64, workspace tensor, pointer, bytes)."""
+        import torch
+
+        key = (tuple(shape), int(n_f), int(n_m))
+        if key not in self._mi_bufs:
+            lib = require(*_abi.MI_SYMBOLS)
+            need = C.c_size_t(0)
+            check(lib.t2fit_register_mi_workspace_bytes(shape[0], shape[1], shape[2], C.byref(need)))
+            self._mi_bufs = {key: (torch.empty(n_f * n_m, dtype=torch.int64, device=self.dev),
+                                   torch.empty(n_f * n_m, dtype=torch.float64, device=self.dev),
+                                   torch.empty(_abi.REGISTER_MI_SUMS, dtype=torch.float64, device=self.dev))
+                             + workspace(need.value, self.dev) + (need.value,)}
+        return self._mi_bufs[key]
+
+    def joint_hist(self, level, bins, n_f, n_m, lo_m, scale_m, A):
+        import torch
+
+        _, fmask, moving, mmask = level[:4]
+        n_f, n_m = _register._check_bins(n_f), _register._check_moving_bins(n_m)
+        a = np.ascontiguousarray(A, np.float64).reshape(12)
+        with torch.cuda.device(self.dev):
+            hist = self._mi_buffers(fmask.shape, n_f, n_m)[0]
+            check(require(*_abi.MI_SYMBOLS).t2fit_register_joint_hist_dev(
+                bins.data_ptr(), fmask.data_ptr(), *fmask.shape, moving.data_ptr(), mmask.data_ptr(), *moving.shape,
+                a.ctypes.data_as(C.POINTER(C.c_double)), n_f, n_m, float(lo_m), float(scale_m), hist.data_ptr(), current_stream()))
+            return hist.cpu().numpy().view(np.uint64).reshape(n_f, n_m)  # (waits)
+
+    def mi_sums(self, level, bins, table, n_m, lo_m, scale_m, A):
+        import torch
+
+        _, fmask, moving, mmask = level[:4]
+        table = np.ascontiguousarray(table, np.float64)
+        if table.ndim != 2 or table.shape[1] != int(n_m):
+            raise ValueError("table is float64 (n_f, n_m)")
+        n_f, n_m = _register._check_bins(table.shape[0]), _register._check_moving_bins(n_m)
+        a = np.ascontiguousarray(A, np.float64).reshape(12)
+        with torch.cuda.device(self.dev):
+            _, table_dev, sums, _, ptr, nbytes = self._mi_buffers(fmask.shape, n_f, n_m)
+            table_dev.copy_(torch.from_numpy(table.ravel()))  # (pageable memory: the copy has left the host when it returns)
+            check(require(*_abi.MI_SYMBOLS).t2fit_register_mi_gradient_dev(
+                bins.data_ptr(), table_dev.data_ptr(), n_f, n_m, float(lo_m), float(scale_m), fmask.data_ptr(), *fmask.shape,
+                moving.data_ptr(), mmask.data_ptr(), *moving.shape, a.ctypes.data_as(C.POINTER(C.c_double)), sums.data_ptr(), ptr,
+                nbytes, current_stream()))
+            return sums.cpu().numpy()  # (waits)
+
 
 def _ones_like(t):
     import torch
@@ -149,7 +202,7 @@ def registration_sums(fixed, moving, A, *, fixed_mask=None, moving_mask=None, de
 
 
 def register_rigid(fixed, moving, fixed_geom, moving_geom, *, fixed_mask=None, moving_mask=None, levels=(4, 2, 1), max_iter=100,
-                   init=None, device=0):
+                   init=None, metric="corr", bins=32, moving_bins=32, device=0):  # noqa: A002
     """Register ``moving`` onto ``fixed``: float32 ``(Z, Y, X)`` volumes (numpy or CUDA tensors) with their geometries
     (anything with GetSpacing / GetOrigin / GetDirection).  The recipe is the reference's ``registration_itk``
     (utils/qmri_utils.py:167-221) made deterministic: correlation metric over every voxel of the fixed mask whose image
@@ -161,9 +214,15 @@ def register_rigid(fixed, moving, fixed_geom, moving_geom, *, fixed_mask=None, m
     the 4 x 4 (fixed point -> moving point, LPS mm) that ``reconstruct_stacks(transforms=)``, ``resample_volume(
     transform=)`` and ``recon.py --transforms`` take.  The sums of every iteration come from the GPU and one 43-double
     copy per iteration waits for the stream; parameters, iteration counts and stop reasons equal
-    :func:`_register.register_rigid`'s.  ValueError when the masks do not overlap.  Parity with elastix is not pinned."""
+    :func:`_register.register_rigid`'s.  ``metric='mattes'``: Mattes mutual information in place of the correlation, by
+    :func:`register_affine` with 6 degrees of freedom (``bins``, ``moving_bins``); the result keeps this function's
+    shape, six parameters.  ValueError when the masks do not overlap.  Parity with elastix is not pinned."""
     import torch
 
+    if _register.check_rigid_metric(metric) == "mattes":
+        return _register.rigid_from_affine(register_affine(
+            fixed, moving, fixed_geom, moving_geom, metric="mattes", bins=bins, moving_bins=moving_bins, dof=6, fixed_mask=fixed_mask,
+            moving_mask=moving_mask, levels=levels, max_iter=max_iter, init=_register.rigid_init(init), device=device))
     dev = pick_device((fixed, moving, fixed_mask, moving_mask), device)
     f, m = volume(fixed, torch.float32, dev, "fixed"), volume(moving, torch.float32, dev, "moving")
     pyramid = DevicePyramid(f, build_mask(f, device=dev.index) if fixed_mask is None else fixed_mask,
@@ -223,14 +282,43 @@ def registration_sums_lut(bins, lut, moving, A, *, fixed_mask=None, moving_mask=
         return pyramid.out.cpu().numpy()
 
 
+def joint_histogram(bins, moving, A, n_f, n_m, lo_m, scale_m, *, fixed_mask=None, moving_mask=None, device=0):
+    """The joint histogram of Mattes mutual information (t2fit_register_joint_hist_dev): uint64 ``(n_f, n_m)``, numpy.  A
+    counted voxel of fixed bin ``b`` (the uint8 ``bins`` volume, ``n_f`` in 1..64) adds the four cubic B-spline window
+    weights of its interpolated moving sample, in units of 2^-30, to row ``b`` (``n_m`` in 5..64 moving bins over
+    ``lo_m`` .. with ``scale_m``: :func:`_register.moving_bin_range`).  Integer for integer equal to
+    :func:`_register.joint_histogram` and the same from call to call.  Waits for the stream."""
+    import torch
+
+    dev = pick_device((bins, moving, fixed_mask, moving_mask), device)
+    b = _bins_tensor(bins, dev)
+    pyramid = _affine_pyramid(torch.zeros(tuple(b.shape), dtype=torch.float32, device=dev), moving, fixed_mask, moving_mask, device)
+    return pyramid.joint_hist(pyramid.level(1), b, n_f, n_m, lo_m, scale_m, A)
+
+
+def mi_gradient_sums(bins, table, moving, A, n_m, lo_m, scale_m, *, fixed_mask=None, moving_mask=None, device=0):
+    """The 12 float64 sums ``[4 a + j] = sum (c g_a) u_j`` of t2fit_register_mi_gradient_dev, numpy; ``table``: float64
+    ``(n_f, n_m)``, with :func:`_register.mattes_metric`'s they are ``d(-MI)/dA``.  Bit-identical to
+    :func:`_register.mi_gradient_sums`.  Waits for the stream."""
+    import torch
+
+    dev = pick_device((bins, moving, fixed_mask, moving_mask), device)
+    b = _bins_tensor(bins, dev)
+    pyramid = _affine_pyramid(torch.zeros(tuple(b.shape), dtype=torch.float32, device=dev), moving, fixed_mask, moving_mask, device)
+    return pyramid.mi_sums(pyramid.level(1), b, table, n_m, lo_m, scale_m, A)
+
+
 def register_affine(fixed, moving, fixed_geom, moving_geom, *, metric="cr", bins=32, dof=12, fixed_mask=None, moving_mask=None,  # noqa: A002
-                    levels=(4, 2, 1), max_iter=100, init=None, device=0):
+                    levels=(4, 2, 1), max_iter=100, init=None, moving_bins=32, device=0):
     """Register ``moving`` onto ``fixed`` with ``dof`` in (6, 7, 9, 12) degrees of freedom: ``x' = R K (x - centre) +
     centre + t`` (:func:`_register.compose_affine`: Euler angles, translation, log scales, shears) by the regular-step
     descent of :func:`register_rigid`.  ``metric='cr'``: the correlation ratio of the moving samples given the fixed
     volume binned into ``bins`` (1..64) bins -- what the reference asks of FSL's flirt for the T1 template onto a T2w
     volume; each level's bins span that level's fixed samples inside its mask.  ``'ncc'``: the squared correlation of
-    :func:`register_rigid`.  ``init``: None, 12 parameters, or 'centroids' (start at the translation between the masks'
+    :func:`register_rigid`.  ``'mattes'``: Mattes mutual information, the cost elastix's default rigid map minimises --
+    ``bins`` fixed bins (a zero-order window) and ``moving_bins`` (5..64) cubic B-spline bins over each level's moving
+    samples inside its mask, every counted voxel sampled; parity with elastix (random samples, another descent) is not
+    pinned.  ``init``: None, 12 parameters, or 'centroids' (start at the translation between the masks'
     centroids: a template and a subject do not share a frame).  Masks None: :func:`build_mask` on the device.  Returns a
     :class:`_register.Registration` with 12 parameters; they, the iteration counts and the stops equal
     :func:`_register.register_affine`'s.  Parity with flirt (another optimizer, another search) is not pinned."""
@@ -246,4 +334,4 @@ def register_affine(fixed, moving, fixed_geom, moving_geom, *, metric="cr", bins
     centre, scales = _register.affine_centre_and_scales(fmask_host, fg)
     p0 = _register.affine_init(init, fmask_host, fg, pyramid.full[3].cpu().numpy() if isinstance(init, str) else None, mg)
     return _register.optimize_affine(pyramid, fg, mg, centre, scales, metric=metric, bins=bins, dof=dof, levels=levels,
-                                     max_iter=max_iter, init=p0)
+                                     max_iter=max_iter, init=p0, moving_bins=moving_bins)

@@ -34,7 +34,9 @@ consecutive values (the last group padded with zeros) are each added by halving;
 
 **The affine registration across contrasts** (``register_affine``: the correlation ratio over a binned fixed volume, 6 to
 12 degrees of freedom; what the atlas-label stage of :mod:`_atlas` runs) is the last part of this module and builds on
-everything above without changing it."""
+everything above without changing it; so does **Mattes mutual information** (``metric="mattes"``: the cost elastix's
+default rigid map minimises, which is what the reference's ``registration_elastix`` runs), stated after the correlation
+ratio."""
 from __future__ import annotations
 
 import numpy as np
@@ -372,13 +374,41 @@ def optimize(pyramid, fixed_geom, moving_geom, centre, scales, *, levels=(4, 2, 
     return Registration(compose(p, centre), p, np.asarray(centre, np.float64), c, iterations, stops)
 
 
+def check_rigid_metric(metric):  # noqa: A002
+    if metric not in ("corr", "mattes"):
+        raise ValueError(f"metric is 'corr' or 'mattes', got {metric!r}")
+    return metric
+
+
+def rigid_from_affine(found):
+    """The :class:`Registration` of :func:`register_rigid` (six parameters) from a 6-dof one of :func:`register_affine`."""
+    p = found.parameters[:6].copy()
+    return Registration(compose(p, found.centre), p, found.centre, found.metric, found.iterations, found.stops)
+
+
+def rigid_init(init):
+    """The 12 parameters :func:`register_affine` starts from, given the six of :func:`register_rigid` (or None)."""
+    if init is None:
+        return None
+    p = np.array(init, np.float64)
+    if p.shape != (6,) or not np.all(np.isfinite(p)):
+        raise ValueError("init is (rx, ry, rz [rad], tx, ty, tz [mm]), finite")
+    return np.concatenate([p, np.zeros(6)])
+
+
 def register_rigid(fixed, moving, fixed_geom, moving_geom, *, fixed_mask=None, moving_mask=None, levels=(4, 2, 1),
-                   max_iter=100, init=None):
+                   max_iter=100, init=None, metric="corr", bins=32, moving_bins=32):  # noqa: A002
     """Register ``moving`` onto ``fixed`` (float32 ``(Z, Y, X)`` with their geometries); masks None: ``build_mask`` of
-    the volume.  Returns a :class:`Registration`.  The statement of ``t2map.register.register_rigid``."""
+    the volume.  ``metric``: 'corr' (the squared correlation) or 'mattes' (Mattes mutual information, through
+    :func:`register_affine` with 6 degrees of freedom, ``bins`` fixed and ``moving_bins`` moving bins).  Returns a
+    :class:`Registration`.  The statement of ``t2map.register.register_rigid``."""
     fixed, moving = np.asarray(fixed, np.float32), np.asarray(moving, np.float32)
     fmask = build_mask(fixed) if fixed_mask is None else fixed_mask
     mmask = build_mask(moving) if moving_mask is None else moving_mask
+    if check_rigid_metric(metric) == "mattes":
+        return rigid_from_affine(register_affine(fixed, moving, fixed_geom, moving_geom, metric="mattes", bins=bins,
+                                                 moving_bins=moving_bins, dof=6, fixed_mask=fmask, moving_mask=mmask, levels=levels,
+                                                 max_iter=max_iter, init=rigid_init(init)))
     pyramid = HostPyramid(fixed, fmask, moving, mmask)
     fg, mg = _resample.as_geometry(fixed_geom, fixed.shape), _resample.as_geometry(moving_geom, moving.shape)
     levels = check_levels(levels, fixed.shape, moving.shape)
@@ -508,6 +538,150 @@ def cr_metric(binned, sums_lut):
     return 1.0 + c, dc
 
 
+# ---- Mattes mutual information: the cost elastix's default rigid map minimises -----------------------------------------
+# The statement of include/t2fit.h's t2fit_register_joint_hist_dev and t2fit_register_mi_gradient_dev.  The fixed side
+# is the uint8 bin volume above (a zero-order window); the moving sample m goes through a cubic B-spline Parzen window
+# over n_m bins, two of them padding at each end (ITK's layout).  The joint histogram is made of integers (weights in
+# units of 2^-30), so its sums are exact in any order; the gradient's 12 sums go through the tree of the 43.
+MIN_MOVING_BINS = 5
+N_MI_SUMS = 12
+HIST_ONE = float(1 << 30)  # a weight of 1.0 in the histogram's units
+
+
+def _check_moving_bins(n_m):
+    n_m = int(n_m)
+    if not MIN_MOVING_BINS <= n_m <= MAX_BINS:
+        raise ValueError(f"moving_bins is in {MIN_MOVING_BINS}..{MAX_BINS}, got {n_m}")
+    return n_m
+
+
+def moving_bin_range(moving, moving_mask, n_m):
+    """``(lo_m, scale_m)`` of a level: ``lo_m`` / ``hi_m`` the smallest / largest moving sample inside the moving mask,
+    ``scale_m = (n_m - 4) / (hi_m - lo_m)`` in float64, 0 when they are equal.  ValueError on an empty mask."""
+    inside = np.asarray(moving, np.float32)[np.asarray(moving_mask) != 0]
+    if inside.size == 0:
+        raise ValueError("the moving mask is empty")
+    lo, hi = float(inside.min()), float(inside.max())
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError("the moving volume is not finite inside its mask")
+    return lo, (float(_check_moving_bins(n_m) - 4) / (hi - lo) if hi > lo else 0.0)
+
+
+def parzen_window(m, lo_m, scale_m, n_m):
+    """``(i0, w [4], dw [4])`` of float64 moving samples ``m``: ``t = (m - lo_m) * scale_m + 2`` kept in ``[2, n_m - 2]``
+    (anything else, a NaN too, becomes the nearer end: 2 for a NaN), ``i0 = min(floor(t), n_m - 3)``, ``u = t - i0``, and
+    on the bins ``i0 - 1 .. i0 + 2`` the uniform cubic B-spline basis in ``u`` and its derivative with respect to ``t``,
+    in the header's order of operations (``v = 1 - u``, ``u2 = u u``, ``u3 = u2 u``, ``v2 = v v``, ``v3 = v2 v``)."""
+    with np.errstate(all="ignore"):
+        t = (np.asarray(m, np.float64) - float(lo_m)) * float(scale_m) + 2.0
+        t = np.where(t >= 2.0, t, 2.0)
+        t = np.where(t <= float(n_m - 2), t, float(n_m - 2))
+        base = np.minimum(np.floor(t), float(n_m - 3))
+        u = t - base
+        v = 1.0 - u
+        u2, v2 = u * u, v * v
+        u3, v3 = u2 * u, v2 * v
+        w = [v3 / 6.0, ((3.0 * u3 - 6.0 * u2) + 4.0) / 6.0, (((-3.0 * u3 + 3.0 * u2) + 3.0 * u) + 1.0) / 6.0, u3 / 6.0]
+        dw = [-(v2 * 0.5), 1.5 * u2 - 2.0 * u, (-1.5 * u2 + u) + 0.5, u2 * 0.5]
+    return base.astype(np.int64), w, dw
+
+
+def _mi_bins(bins, fixed_mask, moving, moving_mask, n_f, n_m):
+    if bins is not None and np.asarray(bins).size > 1 << 32:
+        raise ValueError("the fixed volume has more than 2^32 voxels: a histogram entry could pass 2^63")
+    return _bins_and_masks(bins, fixed_mask, moving, moving_mask, n_f) + (_check_moving_bins(n_m),)
+
+
+def joint_histogram(bins, moving, A, n_f, n_m, lo_m, scale_m, fixed_mask=None, moving_mask=None):
+    """uint64 ``(n_f, n_m)``: a counted voxel of fixed bin ``b`` adds ``floor(w_j 2^30 + 0.5)`` to ``H[b][i0 - 1 + j]``,
+    ``j = 0..3`` (:func:`parzen_window` of its interpolant ``m``).  Counting rule and ``m`` as for the 43 sums; integer
+    sums, exact in any order."""
+    bins, fmask, moving, mmask, n_m = _mi_bins(bins, fixed_mask, moving, moving_mask, n_f, n_m)
+    a = np.asarray(A, np.float64).reshape(3, 4)
+    zero = np.zeros(bins.shape, np.float32)
+    hist = np.zeros(n_f * n_m, np.uint64)
+    for z0 in range(0, bins.shape[0], BZ):
+        nzc = min(BZ, bins.shape[0] - z0)
+        with np.errstate(all="ignore"):
+            t = _terms(zero, fmask, moving, mmask, a, z0, nzc)
+        counted = t[0] != 0.0
+        i0, w, _ = parzen_window(t[2][counted], lo_m, scale_m, n_m)
+        row = bins[z0:z0 + nzc][counted].astype(np.int64) * n_m
+        for j in range(4):
+            np.add.at(hist, row + i0 - 1 + j, np.floor(w[j] * HIST_ONE + 0.5).astype(np.uint64))
+    return hist.reshape(n_f, n_m)
+
+
+def mattes_metric(hist, n_f, n_m, scale_m):
+    """``(cost, table)`` from the joint histogram: with ``p = H / sum H`` and its marginals ``p_f``, ``p_m``, the cost is
+    ``-MI = -sum_{p > 0} p log(p / (p_f p_m))`` and ``table[b][k] = -(scale_m 2^30 / sum H) log(p / p_m)`` where ``p > 0``,
+    0 elsewhere: ``sum H 2^-30`` is the histogram's total in units of one voxel, and with the counted set held fixed (``p_f``
+    constant, ``sum dp = 0``) ``d(-MI)/dt_v = sum_j table[b_v][i0 - 1 + j] w'_j(u_v)``.  Host arithmetic, shared by the
+    statement and the device path.  ValueError when the histogram is empty: no voxel counts."""
+    n_f, n_m = _check_bins(n_f), _check_moving_bins(n_m)
+    h = np.asarray(hist)
+    if h.shape != (n_f, n_m) or h.dtype != np.uint64:
+        raise ValueError("hist is uint64 (n_f, n_m)")
+    total = sum(int(v) for v in h.ravel().tolist())
+    if total == 0:
+        raise ValueError("the registration has no voxel to compare: the masks do not overlap under this transform")
+    p = h.astype(np.float64) / float(total)
+    pf, pm = p.sum(axis=1), p.sum(axis=0)
+    some = p > 0.0
+    with np.errstate(all="ignore"):
+        mi = float(np.sum(np.where(some, p * np.log(np.where(some, p / (pf[:, None] * pm[None, :]), 1.0)), 0.0)))
+        table = np.where(some, -(float(scale_m) * HIST_ONE / float(total)) * np.log(np.where(some, p / pm[None, :], 1.0)), 0.0)
+    return -mi, np.ascontiguousarray(table, np.float64)
+
+
+def mi_gradient_sums(bins, table, moving, A, n_m, lo_m, scale_m, fixed_mask=None, moving_mask=None):
+    """float64 ``[12]``: ``[4 a + j] = sum (c g_a) u_j`` over the counted voxels, ``c = sum_j table[b][i0 - 1 + j] w'_j(u)``
+    (the four products added in ``j`` order from 0.0), ``c g_a`` rounded first, then ``u_j`` (``u_3 = 1`` is no
+    multiplication); a voxel that does not count adds +0.0; the tree of the 43 sums.  With :func:`mattes_metric`'s
+    table this is ``d(-MI)/dA``."""
+    table = np.asarray(table, np.float64)
+    if table.ndim != 2 or table.shape[1] != int(n_m):
+        raise ValueError("table is float64 (n_f, n_m)")
+    n_f = table.shape[0]
+    bins, fmask, moving, mmask, n_m = _mi_bins(bins, fixed_mask, moving, moving_mask, n_f, n_m)
+    a = np.asarray(A, np.float64).reshape(3, 4)
+    zero = np.zeros(bins.shape, np.float32)
+    flat = table.ravel()
+
+    def terms(z0, nzc):
+        t = _terms(zero, fmask, moving, mmask, a, z0, nzc)
+        counted = t[0] != 0.0
+        i0, _, dw = parzen_window(np.where(counted, t[2], float(lo_m)), lo_m, scale_m, n_m)
+        at = bins[z0:z0 + nzc].astype(np.int64) * n_m + i0 - 1
+        c = np.zeros(counted.shape, np.float64)
+        for j in range(4):
+            c = c + flat[at + j] * dw[j]
+        out = np.zeros((N_MI_SUMS,) + counted.shape, np.float64)
+        for k in range(3):
+            cg = c * t[6 + 4 * k + 3]                 # g_k: the "1 g_k 1" term of the 43
+            for j in range(4):
+                out[4 * k + j] = cg * _index(j, z0, counted.shape) if j < 3 else cg
+        return np.where(counted[None], out, 0.0)
+
+    return _tree(bins.shape, N_MI_SUMS, terms)
+
+
+def _index(j, z0, shape):
+    """``u_j`` (0: ix, 1: iy, 2: iz) of the planes ``z0 ..`` as float64, broadcast to ``shape`` (nzc, fy, fx)."""
+    nzc, fy, fx = shape
+    if j == 0:
+        return np.broadcast_to(np.arange(fx, dtype=np.float64)[None, None, :], shape)
+    if j == 1:
+        return np.broadcast_to(np.arange(fy, dtype=np.float64)[None, :, None], shape)
+    return np.broadcast_to(np.arange(z0, z0 + nzc, dtype=np.float64)[:, None, None], shape)
+
+
+def mattes_cost_and_gradient(bins, moving, A, n_f, n_m, lo_m, scale_m, fixed_mask=None, moving_mask=None):
+    """``(-MI, d(-MI)/dA [3, 4])`` at ``A``: :func:`joint_histogram`, :func:`mattes_metric`, :func:`mi_gradient_sums`."""
+    cost, table = mattes_metric(joint_histogram(bins, moving, A, n_f, n_m, lo_m, scale_m, fixed_mask, moving_mask), n_f, n_m, scale_m)
+    return cost, mi_gradient_sums(bins, table, moving, A, n_m, lo_m, scale_m, fixed_mask, moving_mask).reshape(3, 4)
+
+
 # ---- affine transform: rotation, translation, log scales, shears ---------------------------------------------------------
 N_AFFINE = 12
 DOFS = (6, 7, 9, 12)
@@ -592,15 +766,29 @@ class HostAffinePyramid(HostPyramid):
         binned = binned_sums(bins, moving, A, n_bins, fmask, mmask)
         return binned, registration_sums_lut(bins, lut_from_binned(binned), moving, A, fmask, mmask)
 
+    def moving_range(self, level, n_m):
+        return moving_bin_range(level[2], level[3], n_m)
+
+    def joint_hist(self, level, bins, n_f, n_m, lo_m, scale_m, A):
+        _, fmask, moving, mmask = level[:4]
+        return joint_histogram(bins, moving, A, n_f, n_m, lo_m, scale_m, fmask, mmask)
+
+    def mi_sums(self, level, bins, table, n_m, lo_m, scale_m, A):
+        _, fmask, moving, mmask = level[:4]
+        return mi_gradient_sums(bins, table, moving, A, n_m, lo_m, scale_m, fmask, mmask)
+
 
 def optimize_affine(pyramid, fixed_geom, moving_geom, centre, scales, *, metric="cr", bins=32, dof=12, levels=(4, 2, 1),  # noqa: A002
-                    max_iter=100, init=None):
+                    max_iter=100, init=None, moving_bins=32):
     """The regular-step descent of :func:`optimize` over ``q`` with ``p = E q`` (:func:`dof_basis`): the gradient is
     ``E^T dC/dp``, a tied parameter's scale the sum of its members'.  ``metric``: 'cr' (each level's bins come from that
-    level's fixed volume inside its mask) or 'ncc' (the 43 sums as they are).  ``init``: 12 parameters."""
-    if metric not in ("cr", "ncc"):
-        raise ValueError(f"metric is 'cr' or 'ncc', got {metric!r}")
+    level's fixed volume inside its mask), 'ncc' (the 43 sums as they are) or 'mattes' (Mattes mutual information: the
+    fixed bins of 'cr' and ``moving_bins`` cubic B-spline bins over each level's moving samples inside its mask).
+    ``init``: 12 parameters."""
+    if metric not in ("cr", "ncc", "mattes"):
+        raise ValueError(f"metric is 'cr', 'ncc' or 'mattes', got {metric!r}")
     n_bins = _check_bins(bins)
+    n_m = _check_moving_bins(moving_bins)
     e = dof_basis(dof)
     p0 = np.zeros(N_AFFINE) if init is None else np.array(init, np.float64)
     if p0.shape != (N_AFFINE,) or not np.all(np.isfinite(p0)):
@@ -611,13 +799,18 @@ def optimize_affine(pyramid, fixed_geom, moving_geom, centre, scales, *, metric=
     for s in levels:
         level = pyramid.level(s)
         fg, mg = level_geometry(fixed_geom, s), level_geometry(moving_geom, s)
-        level_bins = pyramid.bins(level, n_bins) if metric == "cr" else None
+        level_bins = pyramid.bins(level, n_bins) if metric != "ncc" else None
+        lo_m, scale_m = pyramid.moving_range(level, n_m) if metric == "mattes" else (0.0, 0.0)
 
         def evaluate(q):
             p = p0 + e @ q
             a = _resample.index_affine(fg, mg, compose_affine(p, centre))
-            c, dc = cr_metric(*pyramid.cr_sums(level, level_bins, n_bins, a)) if metric == "cr" else _correlation(
-                pyramid.sums(level, a))
+            if metric == "mattes":
+                c, table = mattes_metric(pyramid.joint_hist(level, level_bins, n_bins, n_m, lo_m, scale_m, a), n_bins, n_m, scale_m)
+                dc = np.asarray(pyramid.mi_sums(level, level_bins, table, n_m, lo_m, scale_m, a), np.float64).reshape(3, 4)
+            else:
+                c, dc = cr_metric(*pyramid.cr_sums(level, level_bins, n_bins, a)) if metric == "cr" else _correlation(
+                    pyramid.sums(level, a))
             return c, (e.T @ affine_parameter_gradient(dc, p, centre, fg, mg)) / q_scales
 
         step, prev, n_it, stop = initial_step(s), None, 0, "iterations"
@@ -666,9 +859,10 @@ def affine_init(init, fixed_mask, fixed_geom, moving_mask, moving_geom):
 
 
 def register_affine(fixed, moving, fixed_geom, moving_geom, *, metric="cr", bins=32, dof=12, fixed_mask=None,  # noqa: A002
-                    moving_mask=None, levels=(4, 2, 1), max_iter=100, init=None):
+                    moving_mask=None, levels=(4, 2, 1), max_iter=100, init=None, moving_bins=32):
     """Register ``moving`` onto ``fixed`` with up to 12 degrees of freedom and the correlation ratio ('cr', for volumes
-    of different contrast) or the squared correlation ('ncc').  Masks None: ``build_mask`` of the volume.  Returns a
+    of different contrast), the squared correlation ('ncc') or Mattes mutual information ('mattes', ``bins`` fixed and
+    ``moving_bins`` moving bins).  Masks None: ``build_mask`` of the volume.  Returns a
     :class:`Registration` whose ``parameters`` are the 12 of :func:`compose_affine`.  The statement of
     ``t2map.register.register_affine``."""
     fixed, moving = np.asarray(fixed, np.float32), np.asarray(moving, np.float32)
@@ -680,4 +874,4 @@ def register_affine(fixed, moving, fixed_geom, moving_geom, *, metric="cr", bins
     centre, scales = affine_centre_and_scales(pyramid.full[1], fg)
     p0 = affine_init(init, pyramid.full[1], fg, pyramid.full[3], mg)
     return optimize_affine(pyramid, fg, mg, centre, scales, metric=metric, bins=bins, dof=dof, levels=levels,
-                           max_iter=max_iter, init=p0)
+                           max_iter=max_iter, init=p0, moving_bins=moving_bins)

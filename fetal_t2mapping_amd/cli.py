@@ -822,6 +822,8 @@ def parse_arguments(argv=None):
                         "moving point); a missing file is the identity")
     p.add_argument("--recon_register", action="store_true",
                    help="with --reconstruct: find the transforms of the moving stacks on the GPU (recon.py --register)")
+    p.add_argument("--recon_register_metric", choices=["corr", "mattes"], default="corr",
+                   help="with --recon_register / --recon_register_echoes: the cost (recon.py --register_metric; default corr)")
     p.add_argument("--recon_n4", action="store_true",
                    help="with --reconstruct: N4 bias-field correction of the acquired stacks on the GPU first (recon.py --n4 "
                         "with its defaults)")
@@ -846,7 +848,7 @@ def parse_arguments(argv=None):
     args = p.parse_args(argv)
     args.reconstruct_args = None
     given = [f for f in ("--recon_fixed", "--recon_res", "--recon_transforms", "--recon_register", "--recon_register_echoes",
-                         "--recon_n4")
+                         "--recon_n4", "--recon_register_metric")
              if any(a == f or a.startswith(f + "=") for a in (argv if argv is not None else sys.argv[1:]))]
     if given and not args.reconstruct:
         p.error(f"{given[0]} has no effect without --reconstruct")
@@ -862,6 +864,10 @@ def parse_arguments(argv=None):
             args.reconstruct_args["register"] = True
         if args.recon_register_echoes:
             args.reconstruct_args["register_echoes"] = True
+        if args.recon_register_metric != "corr":
+            if not (args.recon_register or args.recon_register_echoes):
+                p.error("--recon_register_metric has no effect without --recon_register / --recon_register_echoes")
+            args.reconstruct_args["register_metric"] = args.recon_register_metric
         if args.recon_n4:
             from .recon import N4_DEFAULTS
 

@@ -3,14 +3,21 @@
 // metric evaluation inside the reference's registration_itk (utils/qmri_utils.py:167-221: correlation metric, masks,
 // linear interpolator); the optimizer stays on the host (fetal_t2mapping_amd/_register.py, which also states every
 // kernel here in numpy).  The correlation-ratio half of the affine registration (t2fit_register_bin_dev,
-// t2fit_register_binned_sums_dev, t2fit_register_sums_lut_dev) lives here too: same bricks, same tree.
+// t2fit_register_binned_sums_dev, t2fit_register_sums_lut_dev) lives here too: same bricks, same tree; and so does Mattes
+// mutual information (t2fit_register_joint_hist_dev, t2fit_register_mi_gradient_dev).
 //
 //   register_sums_kernel    a workgroup owns a brick of 64 x 4 x 8 fixed voxels: lanes along x (coalesced fixed and mask
 //                           reads; the eight moving taps of neighbouring lanes are neighbours along the image of the
 //                           fixed x axis), a wave per y, every lane walks its 8 voxels in z.  43 float64 accumulators
 //                           per lane; the wave adds them with a fixed xor butterfly (32, 16, .. 1: lane 0 holds the
 //                           halving tree), the four waves meet in LDS, and 43 lanes store the brick's slab.
-//                           <true>: f is lut[bin] of a uint8 bin volume instead of the fixed sample, nothing else differs.
+//                           <kFromLut>: f is lut[bin] of a uint8 bin volume instead of the fixed sample, nothing else
+//                           differs.  <kFromMi>: 12 accumulators, (c g_a) u_j with c from the table T[n_f][n_m], which the
+//                           workgroup stages in LDS once; a voxel gathers four consecutive entries of one row.
+//   register_joint_hist_kernel  the joint histogram of Mattes mutual information: a workgroup walks bricks (a grid stride)
+//                           and adds the four fixed-point window weights of every counted voxel into its own uint64 table
+//                           in LDS with 64-bit integer LDS atomics, then adds the table's nonzero entries to global memory
+//                           with 64-bit integer atomics.  Integer adds are exact in any order.
 //   register_binned_kernel  the same brick; a lane keeps the (bin, m) of its 8 voxels in registers.  The bins present in a
 //                           wave are one 64-bit word (an OR butterfly of 1 << bin); only those run the sum's butterfly --
 //                           an absent bin's column values are all +0.0 and so is their tree.  The counts are whole
@@ -18,7 +25,8 @@
 //   register_reduce_kernel  one pass of the tree over the slabs: a workgroup adds 256 consecutive values of one sum by
 //                           halving in LDS.  Passes repeat until one value per sum is left.
 //   shrink kernels          a pyramid level: the mean (the "any") of s^3 blocks, one thread per output voxel.
-// The order of every addition is a function of the sizes alone; there is no atomic anywhere.  Compiled with
+// The order of every floating-point addition is a function of the sizes alone; there is no floating-point atomic
+// anywhere (the histogram's integer atomics are the only atomics).  Compiled with
 // -ffp-contract=off: every multiply and add rounds once, as numpy's do.
 #include <hip/hip_runtime.h>
 
@@ -43,12 +51,20 @@ static_assert(kBX == 64 && kBX * kBY == kBlock, "a wave per row of the brick");
 static_assert(kFan == kBlock, "a value per thread");
 
 constexpr int kMaxBins = 64;  // the bins of a wave fit one 64-bit presence word
+constexpr int kMinMovingBins = 5;
+constexpr int kMiSums = T2FIT_REGISTER_MI_SUMS;
+constexpr int kHistGrid = 2048;  // workgroups of the joint histogram at most: each flushes its table once
+
+enum SumsMode { kFromFixed = 0, kFromLut = 1, kFromMi = 2 };
 
 struct SumsArgs {
-  const float* fixed;        // <false>
-  const uint8_t* bins;       // <true>: f = lut[bins[at]]
-  const double* lut;
+  const float* fixed;        // <kFromFixed>
+  const uint8_t* bins;       // <kFromLut>: f = lut[bins[at]]; <kFromMi> and the histogram: the row of the table
+  const double* lut;         // <kFromMi>: the table T[n_bins][n_m]
   int n_bins;
+  int n_m;                   // Mattes: the moving bins, t = (m - lo_m) * scale_m + 2
+  double lo_m, scale_m;
+  unsigned long long* hist;  // the joint histogram [n_bins][n_m]
   const uint8_t* fixed_mask;
   const float* moving;
   const uint8_t* moving_mask;
@@ -103,9 +119,42 @@ __device__ inline bool sample(const float* moving, const uint8_t* moving_mask, c
   return true;
 }
 
-template <bool kLut>
+// The cubic B-spline Parzen window of a moving sample (include/t2fit.h has the order of operations): returns i0, and the
+// four weights (<false>) or their derivatives with respect to t (<true>) on the bins i0 - 1 .. i0 + 2.  2 <= i0 <= n_m - 3
+// whatever m is (a NaN lands at t = 2), so the bins stay inside a row of n_m.
+template <bool kDeriv>
+__device__ inline int parzen(double m, double lo, double scale, int n_m, double* w) {
+  double t = (m - lo) * scale + 2.0;
+  const double top = (double)(n_m - 2), last = (double)(n_m - 3);
+  t = t >= 2.0 ? t : 2.0;
+  t = t <= top ? t : top;
+  double base = floor(t);
+  base = base < last ? base : last;
+  const double u = t - base, v = 1.0 - u, u2 = u * u, v2 = v * v;
+  if (kDeriv) {
+    w[0] = -(v2 * 0.5);
+    w[1] = 1.5 * u2 - 2.0 * u;
+    w[2] = (-1.5 * u2 + u) + 0.5;
+    w[3] = u2 * 0.5;
+  } else {
+    const double u3 = u2 * u, v3 = v2 * v;
+    w[0] = v3 / 6.0;
+    w[1] = ((3.0 * u3 - 6.0 * u2) + 4.0) / 6.0;
+    w[2] = (((-3.0 * u3 + 3.0 * u2) + 3.0 * u) + 1.0) / 6.0;
+    w[3] = u3 / 6.0;
+  }
+  return (int)base;
+}
+
+template <int kMode>
 __global__ __launch_bounds__(kBlock) void register_sums_kernel(const SumsArgs a) {
-  __shared__ double rows[kBY][kSums];
+  constexpr int kN = kMode == kFromMi ? kMiSums : kSums;
+  __shared__ double rows[kBY][kN];
+  extern __shared__ double mi_table[];  // <kFromMi>: [n_bins][n_m], the launch sizes it
+  if constexpr (kMode == kFromMi) {
+    for (int i = threadIdx.x; i < a.n_bins * a.n_m; i += kBlock) mi_table[i] = a.lut[i];
+    __syncthreads();
+  }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int t = blockIdx.x;
   const int bx = t % a.bricks_x;
@@ -114,9 +163,9 @@ __global__ __launch_bounds__(kBlock) void register_sums_kernel(const SumsArgs a)
   const int x = bx * kBX + lane, y = by * kBY + wave;
   const bool column = x < a.f.nx && y < a.f.ny;
   const Dims n = a.m;
-  double acc[kSums];
+  double acc[kN];
 #pragma unroll
-  for (int q = 0; q < kSums; ++q) acc[q] = 0.0;
+  for (int q = 0; q < kN; ++q) acc[q] = 0.0;
 #pragma unroll 1
   for (int k = 0; k < kBZ; ++k) {
     const int z = bz * kBZ + k;
@@ -125,36 +174,93 @@ __global__ __launch_bounds__(kBlock) void register_sums_kernel(const SumsArgs a)
     if (a.fixed_mask[at] == 0) continue;
     double m, g[3];
     if (!sample<true>(a.moving, a.moving_mask, n, a.A, x, y, z, m, g)) continue;
-    const double f = kLut ? a.lut[bin_of(a.bins[at], a.n_bins)] : (double)a.fixed[at];
     const double u[3] = {(double)x, (double)y, (double)z};
-    acc[0] = acc[0] + 1.0;
-    acc[1] = acc[1] + f;
-    acc[2] = acc[2] + m;
-    acc[3] = acc[3] + f * f;
-    acc[4] = acc[4] + m * m;
-    acc[5] = acc[5] + f * m;
+    if constexpr (kMode == kFromMi) {
+      double dw[4];
+      const int i0 = parzen<true>(m, a.lo_m, a.scale_m, a.n_m, dw);
+      const double* row = mi_table + bin_of(a.bins[at], a.n_bins) * a.n_m + (i0 - 1);
+      double c = 0.0;
 #pragma unroll
-    for (int w = 0; w < 3; ++w) {
+      for (int j = 0; j < 4; ++j) c = c + row[j] * dw[j];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const double wg = w == 0 ? g[c] : (w == 1 ? f * g[c] : m * g[c]);
-        const int q = 6 + 4 * (3 * w + c);
+      for (int d = 0; d < 3; ++d) {
+        const double cg = c * g[d];
 #pragma unroll
-        for (int j = 0; j < 3; ++j) acc[q + j] = acc[q + j] + wg * u[j];
-        acc[q + 3] = acc[q + 3] + wg;
+        for (int j = 0; j < 3; ++j) acc[4 * d + j] = acc[4 * d + j] + cg * u[j];
+        acc[4 * d + 3] = acc[4 * d + 3] + cg;
+      }
+    } else {
+      const double f = kMode == kFromLut ? a.lut[bin_of(a.bins[at], a.n_bins)] : (double)a.fixed[at];
+      acc[0] = acc[0] + 1.0;
+      acc[1] = acc[1] + f;
+      acc[2] = acc[2] + m;
+      acc[3] = acc[3] + f * f;
+      acc[4] = acc[4] + m * m;
+      acc[5] = acc[5] + f * m;
+#pragma unroll
+      for (int w = 0; w < 3; ++w) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const double wg = w == 0 ? g[c] : (w == 1 ? f * g[c] : m * g[c]);
+          const int q = 6 + 4 * (3 * w + c);
+#pragma unroll
+          for (int j = 0; j < 3; ++j) acc[q + j] = acc[q + j] + wg * u[j];
+          acc[q + 3] = acc[q + 3] + wg;
+        }
       }
     }
   }
 #pragma unroll
-  for (int q = 0; q < kSums; ++q) {
+  for (int q = 0; q < kN; ++q) {
     const double s = wave_butterfly(acc[q]);
     if (lane == 0) rows[wave][q] = s;
   }
   __syncthreads();
-  if (threadIdx.x < kSums) {
+  if (threadIdx.x < kN) {
     const int q = threadIdx.x;
     a.slabs[(int64_t)q * a.n_bricks + blockIdx.x] = (rows[0][q] + rows[2][q]) + (rows[1][q] + rows[3][q]);
   }
+}
+
+// hist[b][i0 - 1 + j] += floor(w_j 2^30 + 0.5) for every counted voxel; the caller has zeroed hist
+__global__ __launch_bounds__(kBlock) void register_joint_hist_kernel(const SumsArgs a) {
+  extern __shared__ unsigned long long mi_hist[];  // [n_bins][n_m], the launch sizes it
+  const int n_entries = a.n_bins * a.n_m;
+  for (int i = threadIdx.x; i < n_entries; i += kBlock) mi_hist[i] = 0ull;
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t brick = blockIdx.x; brick < a.n_bricks; brick += gridDim.x) {
+    int t = (int)brick;
+    const int bx = t % a.bricks_x;
+    t /= a.bricks_x;
+    const int by = t % a.bricks_y, bz = t / a.bricks_y;
+    const int x = bx * kBX + lane, y = by * kBY + wave;
+    if (x >= a.f.nx || y >= a.f.ny) continue;
+#pragma unroll 1
+    for (int k = 0; k < kBZ; ++k) {
+      const int z = bz * kBZ + k;
+      if (z >= a.f.nz) break;
+      const int64_t at = ((int64_t)z * a.f.ny + y) * a.f.nx + x;
+      if (a.fixed_mask[at] == 0) continue;
+      double m, w[4];
+      if (!sample<false>(a.moving, a.moving_mask, a.m, a.A, x, y, z, m, nullptr)) continue;
+      const int i0 = parzen<false>(m, a.lo_m, a.scale_m, a.n_m, w);
+      unsigned long long* row = mi_hist + bin_of(a.bins[at], a.n_bins) * a.n_m + (i0 - 1);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const unsigned long long q = (unsigned long long)floor(w[j] * 1073741824.0 + 0.5);
+        if (q != 0ull) atomicAdd(&row[j], q);
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < n_entries; i += kBlock)
+    if (mi_hist[i] != 0ull) atomicAdd(&a.hist[i], mi_hist[i]);
+}
+
+__global__ __launch_bounds__(kBlock) void register_zero_hist_kernel(unsigned long long* __restrict__ hist, int n) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) hist[i] = 0ull;
 }
 
 // slabs[b] = N_b and slabs[n_bins + b] = S_b of the brick, by the tree of the 43 sums
@@ -327,6 +433,7 @@ SumsArgs sums_args(const uint8_t* fixed_mask_dev, int fz, int fy, int fx, const 
                    int my, int mx, const double* A, const Plan& plan, void* workspace_dev) {
   SumsArgs a;
   a.fixed = nullptr, a.bins = nullptr, a.lut = nullptr, a.n_bins = 1;
+  a.n_m = kMinMovingBins, a.lo_m = 0.0, a.scale_m = 0.0, a.hist = nullptr;
   a.fixed_mask = fixed_mask_dev, a.moving = moving_dev, a.moving_mask = moving_mask_dev;
   a.f = Dims{fz, fy, fx}, a.m = Dims{mz, my, mx};
   for (int i = 0; i < 12; ++i) a.A.m[i] = A[i];
@@ -346,6 +453,14 @@ void reduce_passes(const Plan& plan, int n_sums, void* workspace_dev, double* ou
     hipLaunchKernelGGL(register_reduce_kernel, dim3((unsigned)n_out, n_sums), dim3(kBlock), 0, st, (const double*)(ws + plan.pass_at[p]),
                        plan.pass_n[p], out, n_out);
   }
+}
+
+// the checks the two Mattes entry points share, after the NULL checks
+int mi_check(const std::string& w, int n_f, int n_m, double lo_m, double scale_m) {
+  if (n_f < 1 || n_f > kMaxBins) return t2fit::fail(T2FIT_E_INVALID, w + ": n_f is outside 1..64");
+  if (n_m < kMinMovingBins || n_m > kMaxBins) return t2fit::fail(T2FIT_E_INVALID, w + ": n_m is outside 5..64");
+  if (!std::isfinite(lo_m) || !std::isfinite(scale_m)) return t2fit::fail(T2FIT_E_INVALID, w + ": lo_m / scale_m is not finite");
+  return T2FIT_OK;
 }
 
 int shrink_check(const std::string& w, const void* src, const void* out, int nz, int ny, int nx, int s, Dims* o) {
@@ -396,7 +511,7 @@ int t2fit_register_sums_dev(const float* fixed_dev, const uint8_t* fixed_mask_de
                                             std::to_string(plan.total) + " needed (t2fit_register_workspace_bytes)");
   SumsArgs a = sums_args(fixed_mask_dev, fz, fy, fx, moving_dev, moving_mask_dev, mz, my, mx, A, plan, workspace_dev);
   a.fixed = fixed_dev;
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(register_sums_kernel<false>), dim3((unsigned)a.n_bricks), dim3(kBlock), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(register_sums_kernel<kFromFixed>), dim3((unsigned)a.n_bricks), dim3(kBlock), 0, (hipStream_t)stream, a);
   reduce_passes(plan, kSums, workspace_dev, sums_dev, (hipStream_t)stream);
   T2_HIP(hipGetLastError());
   return T2FIT_OK;
@@ -467,8 +582,72 @@ int t2fit_register_sums_lut_dev(const uint8_t* bins_dev, const double* lut_dev, 
     return t2fit::fail(T2FIT_E_INVALID, w + ": sums_dev / lut_dev is not aligned to 8 bytes");
   SumsArgs a = sums_args(fixed_mask_dev, fz, fy, fx, moving_dev, moving_mask_dev, mz, my, mx, A, plan, workspace_dev);
   a.bins = bins_dev, a.lut = lut_dev, a.n_bins = n_bins;
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(register_sums_kernel<true>), dim3((unsigned)a.n_bricks), dim3(kBlock), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(register_sums_kernel<kFromLut>), dim3((unsigned)a.n_bricks), dim3(kBlock), 0, (hipStream_t)stream, a);
   reduce_passes(plan, kSums, workspace_dev, sums_dev, (hipStream_t)stream);
+  T2_HIP(hipGetLastError());
+  return T2FIT_OK;
+}
+
+int t2fit_register_joint_hist_dev(const uint8_t* bins_dev, const uint8_t* fixed_mask_dev, int fz, int fy, int fx, const float* moving_dev,
+                                  const uint8_t* moving_mask_dev, int mz, int my, int mx, const double* A, int n_f, int n_m, double lo_m,
+                                  double scale_m, uint64_t* hist_dev, void* stream) {
+  const std::string w("t2fit_register_joint_hist_dev");
+  if (!bins_dev || !fixed_mask_dev || !moving_dev || !moving_mask_dev || !A || !hist_dev)
+    return t2fit::fail(T2FIT_E_INVALID, w + ": bins_dev / fixed_mask_dev / moving_dev / moving_mask_dev / A / hist_dev is NULL");
+  int rc = mi_check(w, n_f, n_m, lo_m, scale_m);
+  if (rc != T2FIT_OK) return rc;
+  Plan plan;
+  if ((rc = sums_plan(w, fz, fy, fx, &plan, kMiSums)) != T2FIT_OK) return rc;
+  if ((int64_t)fz * fy * fx > ((int64_t)1 << 32))
+    return t2fit::fail(T2FIT_E_INVALID, w + ": the fixed volume has more than 2^32 voxels (a histogram entry could pass 2^63)");
+  if (t2fit::count_voxels(1, mz, my, mx) < 0)
+    return t2fit::fail(T2FIT_E_INVALID, w + ": the moving sizes must all be >= 1 and the volume at most 2^40 elements");
+  if (!t2fit::finite12(A)) return t2fit::fail(T2FIT_E_INVALID, w + ": A has a non-finite entry");
+  if (reinterpret_cast<uintptr_t>(moving_dev) & 3) return t2fit::fail(T2FIT_E_INVALID, w + ": moving_dev is not aligned to 4 bytes");
+  if (reinterpret_cast<uintptr_t>(hist_dev) & 7) return t2fit::fail(T2FIT_E_INVALID, w + ": hist_dev is not aligned to 8 bytes");
+  hipStream_t st = (hipStream_t)stream;
+  SumsArgs a = sums_args(fixed_mask_dev, fz, fy, fx, moving_dev, moving_mask_dev, mz, my, mx, A, plan, nullptr);
+  a.slabs = nullptr;
+  a.bins = bins_dev, a.n_bins = n_f, a.n_m = n_m, a.lo_m = lo_m, a.scale_m = scale_m;
+  a.hist = reinterpret_cast<unsigned long long*>(hist_dev);
+  const int n_entries = n_f * n_m;
+  const unsigned grid = (unsigned)(a.n_bricks < kHistGrid ? a.n_bricks : kHistGrid);
+  hipLaunchKernelGGL(register_zero_hist_kernel, dim3((unsigned)ceil_div(n_entries, kBlock)), dim3(kBlock), 0, st, a.hist, n_entries);
+  hipLaunchKernelGGL(register_joint_hist_kernel, dim3(grid), dim3(kBlock), (size_t)n_entries * sizeof(unsigned long long), st, a);
+  T2_HIP(hipGetLastError());
+  return T2FIT_OK;
+}
+
+int t2fit_register_mi_workspace_bytes(int fz, int fy, int fx, size_t* bytes) {
+  if (!bytes) return t2fit::fail(T2FIT_E_INVALID, "t2fit_register_mi_workspace_bytes: bytes is NULL");
+  Plan plan;
+  const int rc = sums_plan("t2fit_register_mi_workspace_bytes", fz, fy, fx, &plan, kMiSums);
+  if (rc != T2FIT_OK) return rc;
+  *bytes = plan.total;
+  return T2FIT_OK;
+}
+
+int t2fit_register_mi_gradient_dev(const uint8_t* bins_dev, const double* table_dev, int n_f, int n_m, double lo_m, double scale_m,
+                                   const uint8_t* fixed_mask_dev, int fz, int fy, int fx, const float* moving_dev,
+                                   const uint8_t* moving_mask_dev, int mz, int my, int mx, const double* A, double* sums_dev,
+                                   void* workspace_dev, size_t workspace_bytes, void* stream) {
+  const std::string w("t2fit_register_mi_gradient_dev");
+  if (!bins_dev || !table_dev || !fixed_mask_dev || !moving_dev || !moving_mask_dev || !A || !sums_dev || !workspace_dev)
+    return t2fit::fail(T2FIT_E_INVALID,
+                       w + ": bins_dev / table_dev / fixed_mask_dev / moving_dev / moving_mask_dev / A / sums_dev / workspace_dev is NULL");
+  int rc = mi_check(w, n_f, n_m, lo_m, scale_m);
+  if (rc != T2FIT_OK) return rc;
+  Plan plan;
+  if ((rc = sums_plan(w, fz, fy, fx, &plan, kMiSums)) != T2FIT_OK) return rc;
+  if ((rc = sums_check(w, moving_dev, mz, my, mx, A, workspace_dev, workspace_bytes, plan, "t2fit_register_mi_workspace_bytes")) != T2FIT_OK)
+    return rc;
+  if ((reinterpret_cast<uintptr_t>(sums_dev) & 7) || (reinterpret_cast<uintptr_t>(table_dev) & 7))
+    return t2fit::fail(T2FIT_E_INVALID, w + ": sums_dev / table_dev is not aligned to 8 bytes");
+  SumsArgs a = sums_args(fixed_mask_dev, fz, fy, fx, moving_dev, moving_mask_dev, mz, my, mx, A, plan, workspace_dev);
+  a.bins = bins_dev, a.lut = table_dev, a.n_bins = n_f, a.n_m = n_m, a.lo_m = lo_m, a.scale_m = scale_m;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(register_sums_kernel<kFromMi>), dim3((unsigned)a.n_bricks), dim3(kBlock),
+                     (size_t)n_f * n_m * sizeof(double), (hipStream_t)stream, a);
+  reduce_passes(plan, kMiSums, workspace_dev, sums_dev, (hipStream_t)stream);
   T2_HIP(hipGetLastError());
   return T2FIT_OK;
 }

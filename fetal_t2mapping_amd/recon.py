@@ -8,7 +8,8 @@ onto the ax grid and the three are averaged (run_reconstruct_volume, :359-391), 
 Rigid transforms of the moving stacks come from one of two places.  ``--transforms DIR`` supplies them as 4 x 4 text
 matrices (fixed point -> moving point, LPS millimetres); a missing file is the identity, the reference's own reading of
 ``recon_1mm`` when nothing moved.  ``--register`` finds them on the GPU (``t2map.register.register_rigid``: the recipe of the
-reference's registration_itk, not elastix, which the reference calls; parity unpinned): per echo, each moving 1 mm
+reference's registration_itk, or with ``--register_metric mattes`` the Mattes mutual information that elastix, which the
+reference calls, minimises -- over every voxel and by another descent; parity unpinned): per echo, each moving 1 mm
 volume onto the fixed one (utils/qmri_utils.py:82-136), and ``--write_transforms DIR`` saves them where
 ``--transforms`` reads them.  ``--register_echoes`` registers every merged echo onto the first one and resamples it
 (:376-383).  Each echo is reconstructed once: the reference runs its loop body for each of the three rows of an echo and
@@ -19,6 +20,11 @@ build_jhu_ho_labels (utils/qmri_utils.py:953-974, :1011-1037) without FSL: per (
 volume is masked by its recon_1mm_mask (``recon_1mm_bet``), the template is registered onto it on the GPU
 (``t2map.atlas.atlas_labels``: 12 degrees of freedom, correlation ratio; not flirt, parity unpinned) and written on the subject's
 grid as ``recon_1mm_mni152``, every atlas as ``recon_1mm_<NAME>`` -- the name ``cli.py --roi_stats NAME`` opens.
+
+``--register_to_lf`` (``--hf --in_vivo``) stands for the reference's register_high_to_low_field (utils/qmri_utils.py:1039-1051,
+step 3bis of run_qmri_reconstruction.py): every 1.5 T recon_1mm volume is registered rigidly (Mattes mutual information) onto
+the 0.55 T one of the same subject -- the same path with ``ses-01`` and ``te-114`` --, resampled onto that grid and written
+back over itself.  The 0.55 T data must have been processed first.
 
 ``--n4`` stands for the reference's run_biasfield_correction2 (utils/qmri_utils.py:296-357) without SimpleITK's N4 filter:
 per (sub, ses) and orientation one log bias field is estimated on the raw stack of one echo (``--n4_echo MS``; default the
@@ -32,6 +38,7 @@ from __future__ import annotations
 
 import argparse
 import os
+import re
 import sys
 import time
 
@@ -98,12 +105,18 @@ def _same_transforms(a, b):
     return sorted(a) == sorted(b) and all(np.array_equal(a[o], b[o]) for o in a)
 
 
+def _metric_args(register_metric):
+    """The keyword of ``register_rigid`` for ``--register_metric``: none for its default."""
+    return {} if register_metric == "corr" else {"metric": register_metric}
+
+
 def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False, transforms_dir=None, register=False,
-                 write_transforms=None, register_echoes=False, device=0):
+                 write_transforms=None, register_echoes=False, register_metric="corr", device=0):
     """Stages 1 and 2 and the merge of the echoes of one batch (`acqs`: the fixed orientation's metadata row of every
     echo).  The transforms of an echo are read (``transforms_dir``) or found (``register``); echoes with the same
     transforms share a call, so without either the batch is one call.  ``register_echoes``: every merged echo but the
-    first is registered onto the first and resampled onto it by one more single stage.  Returns ``(float32 CUDA tensor
+    first is registered onto the first and resampled onto it by one more single stage.  ``register_metric``: 'corr' or
+    'mattes', for both.  Returns ``(float32 CUDA tensor
     (n, Z, Y, X), header, transforms per echo)``."""
     import torch
 
@@ -112,7 +125,7 @@ def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False
     if register:
         stacks = {o: torch.from_numpy(np.ascontiguousarray(stacks[o], np.float32)).to(dev) for o in stacks}
         per_echo = [register_stacks({o: stacks[o][i] for o in stacks}, geoms, fixed=fixed, res=res, integer_cast=integer_cast,
-                                    device=device) for i in range(n)]
+                                    device=device, **_metric_args(register_metric)) for i in range(n)]
         if write_transforms:
             for acq, t in zip(acqs, per_echo):
                 save_transforms(write_transforms, acq, t)
@@ -139,7 +152,7 @@ def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False
     if register_echoes:
         grid = _resample.as_geometry(header, tuple(merged.shape[1:]))
         for i in range(1, n):
-            found = t2map.register.register_rigid(merged[0], merged[i], grid, grid, device=device)
+            found = t2map.register.register_rigid(merged[0], merged[i], grid, grid, device=device, **_metric_args(register_metric))
             merged[i] = t2map.resample_volume(merged[i], grid, like=grid, transform=found.transform,
                                               integer_cast=integer_cast, device=device)[0]
     return merged, header, per_echo
@@ -253,11 +266,11 @@ def n4_batch(sitk, bids_path, batch, stacks, n4, device=0):
 
 def process_recon(metadata, bids_path, *, fixed="ax", res=1.0, transforms_dir=None, write_resamp=False, denoise=True,
                   integer_cast=None, register=False, write_transforms=None, register_echoes=False, n4=None, write_n4=False,
-                  device=0):
+                  register_metric="corr", device=0):
     """Reconstruct every echo of every (prj, sub, ses) of `metadata` that has the three orientations and write it.
     The echoes of a subject whose stacks share their geometry per orientation go through one call.  ``integer_cast``:
     None keeps the pixel type as the reference does (cast when the stacks are int16 on disk).  ``register`` /
-    ``write_transforms`` / ``register_echoes``: see :func:`merge_echoes`.  ``n4``: None, or the keyword arguments of
+    ``write_transforms`` / ``register_echoes`` / ``register_metric``: see :func:`merge_echoes`.  ``n4``: None, or the keyword arguments of
     :func:`correct_stacks` (``--n4``): the stacks are bias-corrected before step 1 and are no longer integers, so the
     pixel type is not kept unless ``integer_cast`` says so; ``write_n4`` writes them under ``n4``.  Returns the paths
     written under ``recon_1mm``."""
@@ -293,7 +306,8 @@ def process_recon(metadata, bids_path, *, fixed="ax", res=1.0, transforms_dir=No
                         print(f"Image saved in : {path}")
             merged, header, _ = merge_echoes(stacks, geoms, [it[1][fixed] for it in batch], fixed=fixed, res=res,
                                              integer_cast=cast, transforms_dir=transforms_dir, register=register,
-                                             write_transforms=write_transforms, register_echoes=register_echoes, device=device)
+                                             write_transforms=write_transforms, register_echoes=register_echoes,
+                                             register_metric=register_metric, device=device)
             if denoise:
                 merged = t2map.denoise_tv(merged, out=merged)
             torch.cuda.synchronize(merged.device)
@@ -365,11 +379,61 @@ def parse_atlas_spec(spec):
     return name, path
 
 
-def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fixed="ax", dof=12, bins=32, device=0):
+LF_SESSION, LF_ECHO = "ses-01", "te-114"          # the 0.55 T volume every 1.5 T one is registered onto
+LF_EXCLUDED = (("sub-003", 299), ("sub-004", 299))  # (sub, echo time [ms]) the reference leaves where they are
+
+
+def low_field_path(high_path):
+    """The fixed image of ``--register_to_lf``: the same path with ``ses-NN`` -> ``ses-01`` and ``te-N`` -> ``te-114``."""
+    return re.sub(r"te-\d+", LF_ECHO, re.sub(r"ses-\d{2}", LF_SESSION, high_path))
+
+
+def process_register_to_lf(metadata, bids_path, *, write_transforms=None, device=0):
+    """``--register_to_lf``: every high-field recon_1mm volume of `metadata` is registered rigidly onto its low-field
+    counterpart (:func:`low_field_path`) with Mattes mutual information, resampled linearly onto that grid and written over
+    the moving file, as the reference's register_high_to_low_field does.  A volume whose counterpart is missing is
+    skipped with a line; ``write_transforms``: the 4 x 4 (fixed point -> moving point) goes there as
+    ``<sub>_<ses>_te-<ms>_<orientation>_to_lf.txt``.  Returns the paths written."""
+    sitk = _sitk()
+    written = []
+    for (prj, sub, ses, echotime), sub_md in metadata.groupby(["prj", "sub", "ses", "EchoTime"]):
+        for _, acq in sub_md.iterrows():
+            if (sub, int(round(float(echotime) * 1000))) in LF_EXCLUDED:
+                continue
+            moving_path = get_img_path(bids_path, acq, recon_dirname).replace(" ", "")
+            fixed_path = low_field_path(moving_path)
+            if not (os.path.isfile(fixed_path) and os.path.isfile(moving_path)):
+                print(f"Warning: {fixed_path if os.path.isfile(moving_path) else moving_path} does not exist. "
+                      f"Registration of {os.path.basename(moving_path)} to the low field is skipped.")
+                continue
+            t0 = time.time()
+            fixed_img, moving_img = sitk.ReadImage(fixed_path), sitk.ReadImage(moving_path)
+            fixed = np.asarray(sitk.GetArrayFromImage(fixed_img), np.float32)
+            moving = np.asarray(sitk.GetArrayFromImage(moving_img), np.float32)
+            found = t2map.register.register_rigid(fixed, moving, fixed_img, moving_img, metric="mattes", device=device)
+            out = t2map.resample_volume(moving, moving_img, like=_resample.as_geometry(fixed_img, fixed.shape),
+                                        transform=found.transform, device=device)[0]
+            img = sitk.GetImageFromArray(np.asarray(out, np.float32))
+            img.SetSpacing(fixed_img.GetSpacing()), img.SetOrigin(fixed_img.GetOrigin()), img.SetDirection(fixed_img.GetDirection())
+            sitk.WriteImage(img, moving_path)
+            written.append(moving_path)
+            if write_transforms:
+                os.makedirs(write_transforms, exist_ok=True)
+                path = transform_path(write_transforms, acq, acq["ImageOrientationPatientSTR"], echo=True).replace(".txt", "_to_lf.txt")
+                np.savetxt(path, found.transform, fmt="%.17g")
+                written.append(path)
+            print(f"Image saved in : {moving_path}")
+            print(f"... registered to the low field: -MI {found.metric:.4f}, iterations {found.iterations}, "
+                  f"{round(time.time() - t0, 4)} sec")
+    return written
+
+
+def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fixed="ax", dof=12, bins=32, metric="cr", device=0):  # noqa: A002
     """``--atlas_labels``: for every (sub, ses), from the first echo's recon_1mm volume and recon_1mm_mask: the masked volume
     under recon_1mm_bet, the registered template under recon_1mm_mni152 with the 4 x 4 transform beside it (``.txt``:
     subject point -> template point, LPS millimetres, the text form of --write_transforms; not FSL's convention), and
-    every atlas (int32, nearest neighbour) under recon_1mm_<NAME>.  Returns the paths written."""
+    every atlas (int32, nearest neighbour) under recon_1mm_<NAME>.  ``metric``: 'cr' or 'mattes'.  Returns the paths
+    written."""
     sitk = _sitk()
     template_img = sitk.ReadImage(template_path)
     template = np.asarray(sitk.GetArrayFromImage(template_img), np.float32)
@@ -400,7 +464,7 @@ def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fix
         t0 = time.time()
         subject = np.asarray(sitk.GetArrayFromImage(img), np.float32)
         warped, labels, found = t2map.atlas.atlas_labels(subject, img, template, template_img, atlases, mask=mask, dof=dof, bins=bins,
-                                                   device=device)
+                                                   device=device, **({} if metric == "cr" else {"metric": metric}))
         write(t2map.atlas.extract_brain(subject, mask), img, get_img_path(bids_path, acq, atlas_bet_dirname).replace(" ", ""))
         template_out = get_img_path(bids_path, acq, atlas_template_dirname).replace(" ", "")
         write(warped, img, template_out)
@@ -408,13 +472,13 @@ def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fix
         written.append(template_out.replace(".nii.gz", ".txt"))
         for name, lab in labels.items():
             write(lab, img, get_img_path(bids_path, acq, recon_dirname + "_" + name).replace(" ", ""))
-        print(f"... atlas labels of {sub}_{ses}: CR {found.metric:.4f}, iterations {found.iterations}, "
+        print(f"... atlas labels of {sub}_{ses}: {'CR' if metric == 'cr' else '-MI'} {found.metric:.4f}, iterations {found.iterations}, "
               f"{round(time.time() - t0, 4)} sec")
     return written
 
 
 def reconstruct_subject(sitk, bids_path, sub_md, sub, ses, *, fixed="ax", res=1.0, transforms_dir=None, integer_cast=None,
-                        register=False, register_echoes=False, n4=None, device=0):
+                        register=False, register_echoes=False, n4=None, register_metric="corr", device=0):
     """cli.py --reconstruct: the echoes of one (sub, ses) (`sub_md`: its metadata rows) reconstructed in memory.  Every
     echo must have the three orientations and the echoes must share their grids.  ``n4``: as :func:`process_recon`.
     Returns ``(volumes: list of (Z, Y, X) float32 arrays in EchoTime order, header)``."""
@@ -431,7 +495,7 @@ def reconstruct_subject(sitk, bids_path, sub_md, sub, ses, *, fixed="ax", res=1.
         stacks, cast = n4_batch(sitk, bids_path, batches[0], stacks, n4, device), bool(integer_cast)
     merged, header, _ = merge_echoes(stacks, geoms, [it[1][fixed] for it in ready], fixed=fixed, res=res, integer_cast=cast,
                                      transforms_dir=transforms_dir, register=register, register_echoes=register_echoes,
-                                     device=device)
+                                     register_metric=register_metric, device=device)
     host = merged.cpu().numpy()
     return [host[i] for i in range(host.shape[0])], header
 
@@ -461,6 +525,15 @@ def parse_arguments(argv=None):
                    help="with --register: save the transforms as <sub>_<ses>_te-<ms>_<orientation>.txt, which --transforms reads")
     p.add_argument("--register_echoes", action="store_true",
                    help="after the merge, register every echo onto the first one and resample it; off by default")
+    p.add_argument("--register_metric", choices=["corr", "mattes"], default="corr",
+                   help="with --register / --register_echoes: corr = the squared correlation of registration_itk (default); "
+                        "mattes = Mattes mutual information, 32 x 32 bins, the cost of elastix's default rigid map (every "
+                        "voxel sampled, another descent: parity with elastix unpinned)")
+    p.add_argument("--register_to_lf", action="store_true",
+                   help="--hf --in_vivo: after the reconstruction, register every recon_1mm volume rigidly (Mattes mutual "
+                        "information) onto the 0.55 T one of the subject (same path, ses-01, te-114), resample it onto that grid "
+                        "and write it over itself (the reference's register_high_to_low_field); --write_transforms applies; "
+                        "off by default")
     p.add_argument("--write_resamp", action="store_true", help="also write the 1 mm volume of every stack under resamp_1mm/")
     p.add_argument("--no_denoise", action="store_true",
                    help="skip the TV-Chambolle pass the reference applies to the merged volume (denoising=True)")
@@ -481,6 +554,8 @@ def parse_arguments(argv=None):
                    help="with --atlas_labels: a label image on the template's grid, repeatable (ho=..., jhu=...)")
     p.add_argument("--atlas_dof", type=int, choices=[6, 7, 9, 12], default=12, help="degrees of freedom (default 12, as flirt's)")
     p.add_argument("--atlas_bins", type=int, default=32, help="bins of the correlation ratio, 1..64 (default 32)")
+    p.add_argument("--atlas_metric", choices=["cr", "mattes"], default="cr",
+                   help="with --atlas_labels: cr = the correlation ratio (default, flirt's cost); mattes = Mattes mutual information")
     p.add_argument("--n4", action="store_true",
                    help="N4 bias-field correction of the acquired stacks on the GPU before step 1 (the reference's "
                         "run_biasfield_correction2; parity with ITK unpinned): per orientation one log field, estimated on one "
@@ -539,7 +614,9 @@ def parse_arguments(argv=None):
         p.error(f"--transforms {args.transforms!r} is not a directory")
     if args.transforms is not None and (args.register or args.register_echoes):
         p.error("--transforms supplies the transforms: it does not go with --register / --register_echoes, which find them")
-    if args.write_transforms is not None and not args.register:
+    if args.register_to_lf and not (args.hf and args.in_vivo):
+        p.error("--register_to_lf goes with --hf --in_vivo: it registers the 1.5 T volumes onto the 0.55 T ones")
+    if args.write_transforms is not None and not (args.register or args.register_to_lf):
         p.error("--write_transforms has no effect without --register")
     return args
 
@@ -555,12 +632,14 @@ def main(argv=None):
     process_recon(metadata, bids_path, fixed=args.fixed, res=args.res, transforms_dir=args.transforms,
                   write_resamp=args.write_resamp, denoise=not args.no_denoise, register=args.register,
                   write_transforms=args.write_transforms, register_echoes=args.register_echoes, n4=args.n4_args,
-                  write_n4=args.write_n4, device=args.device)
+                  write_n4=args.write_n4, register_metric=args.register_metric, device=args.device)
+    if args.register_to_lf:
+        process_register_to_lf(metadata, bids_path, write_transforms=args.write_transforms, device=args.device)
     if args.phantom_masks:
         process_phantom_masks(metadata, bids_path, seeds=args.seeds, fixed=args.fixed, device=args.device)
     if args.atlas_labels:
         process_atlas_labels(metadata, bids_path, args.atlas_template, args.atlas_specs, fixed=args.fixed, dof=args.atlas_dof,
-                             bins=args.atlas_bins, device=args.device)
+                             bins=args.atlas_bins, metric=args.atlas_metric, device=args.device)
 
 
 if __name__ == "__main__":

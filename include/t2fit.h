@@ -628,6 +628,63 @@ int t2fit_register_sums_lut_dev(const uint8_t *bins_dev, const double *lut_dev, 
                                 int my, int mx, const double *A, double *sums_dev, void *workspace_dev,
                                 size_t workspace_bytes, void *stream);
 
+/* ---- Mattes mutual information: the joint histogram and the gradient's sums ---------------------------------------------
+ * The device half of a registration by the cost that elastix's default "rigid" parameter map minimises, which is what
+ * the reference's registration_elastix runs (utils/qmri_utils.py:82-91, :1039-1051): Mattes mutual information with a
+ * zero-order window on the fixed image and a cubic B-spline Parzen window on the moving image.  One evaluation is
+ * t2fit_register_joint_hist_dev, the metric and the table T on the host (fetal_t2mapping_amd/_register.py:
+ * mattes_metric, which also restates everything here in numpy; the device results equal it bit for bit), and
+ * t2fit_register_mi_gradient_dev.  Same cost and window as elastix, another sampler (every voxel that counts, not a
+ * random subset per iteration) and another descent: parity with elastix is not pinned.  Additive to ABI 5:
+ * three new symbols (look them up).
+ *
+ * The counting rule, the interpolant m, the node gradient g_a with its flat rule, u = (ix, iy, iz, 1), "every product
+ * rounds once, no fused multiply-add" and THE SUMMATION TREE are those written above for the 43 sums.
+ * FIXED SIDE: the uint8 bin volume of t2fit_register_bin_dev, n_f in 1..64, a byte above n_f - 1 counts as n_f - 1.
+ * MOVING SIDE: n_m in 5..64 bins, two of them padding at each end.  The host chooses lo_m / hi_m = the smallest / largest
+ * moving sample inside the moving mask and scale_m = (n_m - 4) / (hi_m - lo_m), 0 when they are equal.  Per counted
+ * voxel, in float64, each operation rounding once and in this order:
+ *   t = (m - lo_m) * scale_m + 2;  t = t >= 2 ? t : 2;  t = t <= n_m - 2 ? t : n_m - 2   (a NaN becomes 2)
+ *   i0 = min(floor(t), n_m - 3);   u = t - i0;  v = 1 - u;  u2 = u u;  v2 = v v;  u3 = u2 u;  v3 = v2 v
+ *   w_0 = v3 / 6    w_1 = ((3 u3 - 6 u2) + 4) / 6    w_2 = (((-3 u3 + 3 u2) + 3 u) + 1) / 6    w_3 = u3 / 6
+ *   w'_0 = -(v2 0.5)    w'_1 = 1.5 u2 - 2 u    w'_2 = (-1.5 u2 + u) + 0.5    w'_3 = u2 0.5
+ * w_j is the weight of bin i0 - 1 + j (the uniform cubic B-spline basis), w'_j its derivative with respect to t.  No pow,
+ * nothing from libm but floor, no contraction.  m = hi_m gives i0 = n_m - 3, u = 1: bins n_m - 4 .. n_m - 1; m = lo_m
+ * gives i0 = 2, u = 0: bins 1 .. 4; an m beyond the mask's range lands where the nearer of the two does.
+ * JOINT HISTOGRAM: H[b_f][k], uint64 [n_f][n_m]; a counted voxel adds q_j = (uint64)floor(w_j * 2^30 + 0.5) to
+ * H[b_f][i0 - 1 + j], j = 0..3.  Integer sums, exact in any order (64-bit integer atomics, LDS then global; no
+ * floating-point atomics).  A fixed volume of more than 2^32 voxels is refused, so no entry can pass 2^63.
+ * METRIC (host): p = H / sum H with marginals p_f, p_m; MI = sum_{p > 0} p log(p / (p_f p_m)), the cost is -MI.  sum H
+ * counts in units of 2^-30 voxel, so T[b_f][k] = -(scale_m * 2^30 / sum H) log(p / p_m) where p > 0, 0 elsewhere.  With the
+ * counted set held fixed p_f does not depend on the transform and sum dp = 0, hence d(-MI)/dA[a][j] = sum_v c_v g_a u_j
+ * with c_v = sum_j T[b_f][i0 - 1 + j] w'_j(u), the four products added in j order from 0.0.
+ * GRADIENT SUMS: float64 [12], [4 a + j] = sum (c g_a) u_j, c g_a rounded first, then u_j (u_3 = 1 is no multiplication),
+ * through the tree; a voxel that does not count adds +0.0.
+ *
+ * Both calls are asynchronous on `stream`; no allocation, copy or synchronisation; A is a HOST pointer read before the
+ * call returns.  Checked before HIP is touched (T2FIT_E_INVALID and a message): a NULL pointer, n_f outside 1..64, n_m
+ * outside 5..64, a size < 1, a non-finite entry of A, lo_m or scale_m, moving_dev not aligned to 4 bytes, hist_dev /
+ * table_dev / sums_dev not aligned to 8, a workspace that is not aligned to 256 bytes or too small.
+ *
+ * t2fit_register_joint_hist_dev zeroes hist_dev on the stream, then adds (two launches). */
+#define T2FIT_REGISTER_MI_SUMS 12
+int t2fit_register_joint_hist_dev(const uint8_t *bins_dev, const uint8_t *fixed_mask_dev, int fz, int fy, int fx,
+                                  const float *moving_dev, const uint8_t *moving_mask_dev, int mz, int my, int mx,
+                                  const double *A, int n_f, int n_m, double lo_m, double scale_m, uint64_t *hist_dev,
+                                  void *stream);
+
+/* As t2fit_register_workspace_bytes with 12 values per slab in place of 43. */
+int t2fit_register_mi_workspace_bytes(int fz, int fy, int fx, size_t *bytes);
+
+/* table_dev: device float64 [n_f][n_m]; sums_dev: device float64 [12]; workspace_dev: at least
+ * t2fit_register_mi_workspace_bytes bytes, aligned to 256.  The kernel of the 43 sums with 12 accumulators and the table
+ * staged in LDS; one launch for the slabs and one per pass. */
+int t2fit_register_mi_gradient_dev(const uint8_t *bins_dev, const double *table_dev, int n_f, int n_m, double lo_m,
+                                   double scale_m, const uint8_t *fixed_mask_dev, int fz, int fy, int fx,
+                                   const float *moving_dev, const uint8_t *moving_mask_dev, int mz, int my, int mx,
+                                   const double *A, double *sums_dev, void *workspace_dev, size_t workspace_bytes,
+                                   void *stream);
+
 /* ---- N4 bias-field correction: log image, sharpening histogram, B-spline fit, field -------------------------------------
  * The device half of the reference's run_biasfield_correction / run_biasfield_correction2 (utils/qmri_utils.py:254-357),
  * which call sitk.N4BiasFieldCorrectionImageFilter.  The definition is written from the N4 paper (Tustison 2010), the
