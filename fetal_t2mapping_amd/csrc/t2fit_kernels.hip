@@ -386,10 +386,13 @@ template <typename T, int NPAR, int NTE = 0> struct LmLaneAdaptor {
   template <int J> __device__ static void take_sample(Solver&, float) {}
 };
 
+// `P` as it lies in a kernel's argument segment (constant address space: read by scalar loads)
+using KernargParams = const __attribute__((address_space(4))) LaneParams*;
+
 template <class A, int kChunk, bool kTrace, bool kExtras, int kWg = kBlock, bool kRegs = false>
 __device__ __forceinline__ void persistent_fit(const LaneParams& P, const float* __restrict__ echoes, int layout,
                                                const uint8_t* __restrict__ mask, int64_t n_vox, const DevMaps& m,
-                                               unsigned long long* next_chunk, int refill_min, int take, double* ghist_all) {
+                                               unsigned long long* next_chunk, int refill_min, int take, double* ghist_all, KernargParams Pk) {
   extern __shared__ float lds[];
   constexpr int NP = A::NP;
   // kRegs: samples and voxel queue in registers, LDS for the correction pairs only -- the form launched as one-wave
@@ -419,10 +422,16 @@ __device__ __forceinline__ void persistent_fit(const LaneParams& P, const float*
   ObjCtx c;
   c.P = &P;
   c.y = y;
-  // table start point and bounds: uniform, read once
-  double box_x0[3], box_lb[3], box_ub[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) { box_x0[j] = P.x0[j]; box_lb[j] = P.lb[j]; box_ub[j] = P.ub[j]; }
+  // The uniform inputs that only the refill path reads -- the table start point and box, the no-prior bounds, `norm` and
+  // `no_prior` -- are not held in scalar registers for the life of the wave (18 of them for the box alone, spilled to
+  // lanes of a vector register and read back beside the solver round): the refill path reads them each time through
+  // `Pk`, the kernel's own pointer to `P` in its argument segment, behind a barrier the optimiser cannot see through, so
+  // the loads stay where they are written.
+  auto refill_params = [Pk] {
+    auto kp = Pk;
+    asm volatile("" : "+s"(kp));
+    return kp;
+  };
   // diagnostic builds (t2fit_diag.h): nothing in the product
   T2_STAMPS_BEGIN(queue - wave * kQueueCap + (kBlock / 64) * kQueueCap, wave, lane, c)
   T2_RECORD_PLACEMENT(next_chunk, blockIdx.x * (kWg / 64) + wave, lane)
@@ -587,7 +596,8 @@ __device__ __forceinline__ void persistent_fit(const LaneParams& P, const float*
               ymax = sv > ymax ? sv : ymax;
             }
         }
-        if (P.norm) {
+        const auto* const Pr = refill_params();
+        if (Pr->norm) {
           if constexpr (A::kNte > 0) {
 #pragma unroll
             for (int j = 0; j < 8; ++j)
@@ -607,12 +617,12 @@ __device__ __forceinline__ void persistent_fit(const LaneParams& P, const float*
         }
         if constexpr (A::kNte > 0)
           static_for<0, 8>([&](auto JC) { A::template take_sample<decltype(JC)::value>(s, first8[decltype(JC)::value]); });
-        double lb[3], ub[3];
+        double box_x0[3], lb[3], ub[3];
 #pragma unroll
-        for (int j = 0; j < 3; ++j) { lb[j] = box_lb[j]; ub[j] = box_ub[j]; }
-        if (P.no_prior) {  // run_t2mapping.py:243-245
-          lb[0] = (double)y0; ub[0] = P.np_k_ub;
-          lb[1] = P.np_t2_lb; ub[1] = P.np_t2_ub;
+        for (int j = 0; j < 3; ++j) { box_x0[j] = Pr->x0[j]; lb[j] = Pr->lb[j]; ub[j] = Pr->ub[j]; }
+        if (Pr->no_prior) {  // run_t2mapping.py:243-245
+          lb[0] = (double)y0; ub[0] = Pr->np_k_ub;
+          lb[1] = Pr->np_t2_lb; ub[1] = Pr->np_t2_ub;
         }
         bool feasible = true;
 #pragma unroll
@@ -620,6 +630,7 @@ __device__ __forceinline__ void persistent_fit(const LaneParams& P, const float*
         if (!feasible || !finite) {  // nothing to iterate on (fit_lane_t documents both cases)
           LaneResult r;
           r.nit = 0; r.nfev = 0; r.fun = NAN;
+#pragma unroll
           for (int j = 0; j < 3; ++j)
             r.x[j] = !feasible ? (j < NP ? NAN : 0.0) : (j < NP ? t2_clip(box_x0[j], lb[j], ub[j]) : 0.0);
           r.status = !feasible ? T2FIT_ST_INFEASIBLE : T2FIT_ST_NONFINITE;
@@ -687,7 +698,9 @@ __global__ __launch_bounds__(kWg, kWavesPerSimd) void fit_persistent_kernel(cons
                                                                     const uint8_t* __restrict__ mask, int64_t n_vox,
                                                                     DevMaps m, unsigned long long* next_chunk, int refill_min,
                                                                     int take, double* ghist) {
-  persistent_fit<A, kChunk, kTrace, kExtras, kWg, kRegs>(P, echoes, layout, mask, n_vox, m, next_chunk, refill_min, take, ghist);
+  // (`P` is this kernel's first argument: it lies at the start of the argument segment)
+  persistent_fit<A, kChunk, kTrace, kExtras, kWg, kRegs>(P, echoes, layout, mask, n_vox, m, next_chunk, refill_min, take, ghist,
+                                                         (KernargParams)__builtin_amdgcn_kernarg_segment_ptr());
 }
 
 // Residual map (utils/t2map_utils.py:62-89) and optional R^2 from float32 maps already on the device.

@@ -201,7 +201,8 @@ T2_HD void dcstep(double& stx, double& fx, double& dx, double& sty, double& fy, 
 // START call of dcsrch: validates the first step and initialises the search state.
 T2_HD void dcsrch_start(double f, double g, double stp, double ftol, double stpmin, double stpmax, LsState& s) {
   const double xtrapu = 4.0;
-  const bool bad = stp < stpmin || stp > stpmax || g >= 0.0;  // (the state below is dead after an error)
+  const bool below = stp < stpmin, above = stp > stpmax, uphill = g >= 0.0;
+  const bool bad = below | above | uphill;  // (the state below is dead after an error)
   s.brackt = false;
   s.stage = 1;
   s.finit = f; s.ginit = g; s.gtest = ftol * s.ginit;
@@ -499,14 +500,21 @@ struct Lbfgsb : PairRegs<HOME == PAIRS_REG && MODEL != T2FIT_MODEL_GAUSSIAN, 10>
         // block below, whose registers it must not add to); same operations, same summation order (RowSums4)
         RowSums4<NTE> sums;
         sums.init();
+        // (the rotation works on a copy: rotating `ys` itself gave the samples a second version at the end of this block,
+        // and every round of the kernel -- this block is off the usual path -- paid NTE register moves to merge the two)
+        float yr[NTE > 0 ? NTE : 1];
+        if constexpr (NTE > 0) {
+          T2_UNROLL
+          for (int j = 0; j < NTE; ++j) yr[j] = ys[j];
+        }
         T2_NOUNROLL
         for (int i = 0; i < n; ++i) {
           float yf;
-          if constexpr (NTE > 0) {  // register-resident samples: always read ys[0], rotate by one (see the Rician loop below)
-            yf = ys[0];
+          if constexpr (NTE > 0) {  // register-resident samples: always read yr[0], rotate by one (see the Rician loop below)
+            yf = yr[0];
             T2_UNROLL
-            for (int j = 0; j + 1 < NTE; ++j) ys[j] = ys[j + 1];
-            ys[NTE - 1] = yf;
+            for (int j = 0; j + 1 < NTE; ++j) yr[j] = yr[j + 1];
+            yr[NTE - 1] = yf;
           } else {
             yf = c.sample(i);
           }
@@ -676,24 +684,28 @@ struct Lbfgsb : PairRegs<HOME == PAIRS_REG && MODEL != T2FIT_MODEL_GAUSSIAN, 10>
     if constexpr (kPairRegs) {
       // The trips are the indices of `hr`: trip t works on pair number t - (M - col), lanes with fewer than M pairs sit
       // out the FIRST trips.  Pair number p is in ring slot (head + p) mod M, so trip t reads slot (head + col + t) mod M
-      // whether the lane takes part in it or not: the slot is stepped and the next one fetched by every lane at every
-      // trip (a slot nobody uses, where the trip is not the lane's: it is LDS, and nobody uses what it returns), and
-      // the register set of a trip is its parity for every lane -- no copy, no select on where a lane's pairs start.
-      auto fetch = [&](int qs, int set) {
+      // whether the lane takes part in it or not (a slot nobody uses, where the trip is not the lane's: it is LDS, and
+      // nobody uses what it returns), and the register set of a trip is its parity for every lane -- no copy, no select
+      // on where a lane's pairs start.  The slot is not stepped: with q0 the lane's first slot, trip t reads q0 + t, or
+      // q0 + t - M once that is past the end of the ring.  Two offsets are formed once -- slot q0, and M slots less --
+      // and a trip picks one by a compare with a constant; the trip number is a constant distance from it, which the
+      // LDS instruction carries as its offset.
+      const int slot = PAIR_L * hstride;
+      const int q0r = head + col, q0 = q0r >= M ? q0r - M : q0r;
+      const int ia = q0 * slot, ib = ia - M * slot;
+      auto fetch = [&](auto TC, int set) {
+        constexpr int tf = decltype(TC)::value;
+        // (either arm is a slot of the ring: ib is only added to where q0 + tf >= M)
+        const double* p = (tf == 0 || q0 < M - tf) ? hist + (ia + tf * slot) : hist + (ib + tf * slot);
         T2_UNROLL
-        for (int i = 1; i < N - 1; ++i) rp[set][i] = hratio(qs, i - 1);
+        for (int i = 1; i < N - 1; ++i) rp[set][i] = p[(i - 1) * hstride];
         T2_UNROLL
-        for (int i = 0; i < N; ++i) yp[set][i] = hy(qs, i);
+        for (int i = 0; i < N; ++i) yp[set][i] = p[(N - 2 + i) * hstride];
       };
-      int q = head + col;
-      q = q >= M ? q - M : q;
-      fetch(q, 0);
+      fetch(std::integral_constant<int, 0>{}, 0);
       static_for<0, M>([&](auto IC) {
         constexpr int t = decltype(IC)::value, cur = t & 1, nxt = cur ^ 1;
-        if constexpr (t + 1 < M) {
-          q = q + 1 == M ? 0 : q + 1;
-          fetch(q, nxt);
-        }
+        if constexpr (t + 1 < M) fetch(std::integral_constant<int, t + 1>{}, nxt);
         if (t >= M - col) {
           rp[cur][N - 1] = this->hr[t];
           // B s for s = (1, rp[1], rp[2]), the scaling and the update: as in the other forms below
@@ -1170,12 +1182,18 @@ struct Lbfgsb : PairRegs<HOME == PAIRS_REG && MODEL != T2FIT_MODEL_GAUSSIAN, 10>
     for (int i = 0; i < N; ++i) {  // (selects, no branches; the quotient of a skipped variable is computed and dropped)
       const double a1 = d[i];
       // lower bound limits a decreasing variable, upper bound an increasing one
-      const double a2 = (a1 < 0.0 ? lb[i] : ub[i]) - x[i];
-      const bool at_bound = a1 < 0.0 ? a2 >= 0.0 : a2 <= 0.0;
-      const bool limits = a1 < 0.0 ? a1 * stpmx < a2 : a1 * stpmx > a2;
+      const bool dec = a1 < 0.0, moves = a1 != 0.0;
+      const double a2 = (dec ? lb[i] : ub[i]) - x[i];
+      // The two tests of the library -- a2 >= 0 and a1 * stpmx < a2 for a decreasing variable, a2 <= 0 and
+      // a1 * stpmx > a2 for an increasing one -- are made once, on the decreasing case mirrored: -a2 and |a1| (a change
+      // of sign is exact and (-a1) * stpmx == -(a1 * stpmx), so both predicates are what they were; the quotient below
+      // is the library's a2 / a1).
+      const double a2m = dec ? -a2 : a2;
+      const bool at_bound = moves & (a2m <= 0.0);
+      const bool limits = moves & (lb_abs(a1) * stpmx > a2m);
       const double q = t2_fdiv(a2, a1);
-      const double cand = at_bound ? 0.0 : (limits ? q : stpmx);
-      stpmx = a1 != 0.0 ? cand : stpmx;
+      const double lim = limits ? q : stpmx;
+      stpmx = at_bound ? 0.0 : lim;
     }
     stpmx = nit == 0 ? 1.0 : stpmx;
     stp = 1.0;  // every variable is boxed, so the first step is not rescaled by 1/|d|
@@ -1188,7 +1206,9 @@ struct Lbfgsb : PairRegs<HOME == PAIRS_REG && MODEL != T2FIT_MODEL_GAUSSIAN, 10>
     ifun = 1;
     T2_BLK_END(c, 6, t_l)
     // what this pass amounts to, by value selects (no early exits above: the block is one straight line)
-    const int out = ended ? GO_DONE : (restart ? GO_BEGIN : ((ls.task != LS_FG || ifun - 1 >= P.maxls) ? GO_FAIL : GO_TRIAL));
+    const bool ls_off = ls.task != LS_FG, ls_spent = ifun - 1 >= P.maxls;
+    const int out_ls = (ls_off | ls_spent) ? GO_FAIL : GO_TRIAL;
+    const int out = ended ? GO_DONE : (restart ? GO_BEGIN : out_ls);
     set_trial(out == GO_TRIAL);
     return out;
   }
