@@ -85,32 +85,45 @@ T2_HD float t2_exp(float x) { return expf(x); }
 T2_HD float t2_rsqrt(float x) { return 1.0f / sqrtf(x); }
 T2_HD float t2_rcp(float x) { return 1.0f / x; }
 #endif
+// The reciprocal, quotient and reciprocal-root sequences below are plain FMA arithmetic on a hardware seed (`_seq`, host and
+// device, as for the square roots further down): tests/test_lane_solver_hostsim.py runs them on the CPU from a seed of float32
+// precision (coarser than v_rcp_f64 / v_rsq_f64) against the correctly rounded results; tests/test_device_arithmetic_gpu.py runs
+// the device entry points, fed by the hardware's seeds, on the GPU.  What they return for zero, infinite, NaN and denormal
+// operands, and which call sites can see such operands: DESIGN.md section 5d.
 // reciprocal good to ~1 ulp without the IEEE division sequence (v_rcp_f64 seed, two Newton steps);
 // used only where the last bit is immaterial (scalings inside the quasi-Newton matrix rebuild)
-#if defined(__HIP_DEVICE_COMPILE__)
-T2_HD double t2_fast_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
+T2_HD double t2_fast_rcp_seq(double x, double r) {  // r ~ 1 / x to 2^-23 or better
   r = fma(fma(-x, r, 1.0), r, r);
   r = fma(fma(-x, r, 1.0), r, r);
   return r;
 }
-#else
-T2_HD double t2_fast_rcp(double x) { return 1.0 / x; }
-#endif
 // a / b through the 1-ulp reciprocal and one residual correction: the correctly rounded quotient in all but
-// rare last-bit cases, with a dependent chain about half as long as the IEEE division sequence.  Used
-// between objective evaluations (step lengths, breakpoints, the 3x3 solve), where a wave at one wave per
+// rare last-bit cases (measured shares: DESIGN.md section 5d; never more than 1 ulp off:
+// test_device_arithmetic_gpu.py::test_divisions_*), with a dependent chain about half as long as the IEEE division sequence.
+// Used between objective evaluations (step lengths, breakpoints, the 3x3 solve), where a wave at one wave per
 // SIMD waits on exactly these chains.
-#if defined(__HIP_DEVICE_COMPILE__)
-T2_HD double t2_fdiv(double a, double b) {
-  const double r = t2_fast_rcp(b);
+T2_HD double t2_fdiv_seq(double a, double b, double seed) {  // seed ~ 1 / b
+  const double r = t2_fast_rcp_seq(b, seed);
   const double q = a * r;
   return fma(fma(-q, b, a), r, q);
 }
+// 1 / sqrt(x) to ~1 ulp for x > 0 (v_rsq_f64 seed, two Newton steps), same use as t2_fast_rcp
+T2_HD double t2_fast_rsqrt_seq(double x, double y) {  // y ~ 1 / sqrt(x)
+  const double hx = 0.5 * x;
+  y = fma(fma(-hx * y, y, 0.5), y, y);
+  y = fma(fma(-hx * y, y, 0.5), y, y);
+  return y;
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+T2_HD double t2_fast_rcp(double x) { return t2_fast_rcp_seq(x, __builtin_amdgcn_rcp(x)); }
+T2_HD double t2_fdiv(double a, double b) { return t2_fdiv_seq(a, b, __builtin_amdgcn_rcp(b)); }
 T2_HD double t2_rcp_for_div(double b) { return t2_fast_rcp(b); }  // r for t2_div_by_rcp(a, b, r) below
+T2_HD double t2_fast_rsqrt(double x) { return t2_fast_rsqrt_seq(x, __builtin_amdgcn_rsq(x)); }
 #else
+T2_HD double t2_fast_rcp(double x) { return 1.0 / x; }
 T2_HD double t2_fdiv(double a, double b) { return a / b; }
 T2_HD double t2_rcp_for_div(double b) { return 1.0 / b; }
+T2_HD double t2_fast_rsqrt(double x) { return 1.0 / sqrt(x); }
 #endif
 // a / b from r = 1/b (correctly rounded) with one residual correction: the correctly rounded quotient
 // except for rare last-bit cases, at three FMA-class operations instead of an IEEE division sequence
@@ -119,27 +132,31 @@ T2_HD double t2_div_by_rcp(double a, double b, double r) {
   return fma(fma(-q, b, a), r, q);
 }
 T2_HD double t2_rsqrt(double x) { return 1.0 / sqrt(x); }
-// 1 / sqrt(x) to ~1 ulp for x > 0 (v_rsq_f64 seed, two Newton steps), same use as t2_fast_rcp
-#if defined(__HIP_DEVICE_COMPILE__)
-T2_HD double t2_fast_rsqrt(double x) {
-  double y = __builtin_amdgcn_rsq(x);
-  const double hx = 0.5 * x;
-  y = fma(fma(-hx * y, y, 0.5), y, y);
-  y = fma(fma(-hx * y, y, 0.5), y, y);
-  return y;
-}
-#else
-T2_HD double t2_fast_rsqrt(double x) { return 1.0 / sqrt(x); }
-#endif
 T2_HD double t2_rcp(double x) { return 1.0 / x; }
 T2_HD float t2_sqrt(float x) { return sqrtf(x); }
 
 // exp() and sqrt() of the objective evaluations, device side: the device library's own float64 sequences
 // (same constants, same operations, same order: bit-identical results) without their range handling.
 // exp: arguments here are -te/T2 or -2te/T2 with T2 >= the lower bound, never positive: the overflow select is
-// dead code, and ldexp() already delivers the denormal and zero results of the underflow select (checked against
-// the library down to -1.4e9; config_check keeps the argument above that).  sqrt: arguments are
-// k^2 E + sigma^2 in [0, 1e10]: the 2^-767 rescaling never triggers; zero stays exact (see below).
+// dead code, and ldexp() already delivers the denormal and zero results of the underflow select (held against the
+// library's exp on the GPU down to -1.4e9 by tests/test_device_arithmetic_gpu.py::test_exp_core_*; config_check keeps the
+// argument above that).  sqrt: arguments are k^2 E + sigma^2 in [0, 1e10]; zero stays exact (see below).  Below 2^-767 the
+// library rescales and this sequence does not: such radicands are reachable (a sigma bound of 0 and 2 TE / T2 in (532, 745))
+// and come out finite, non-negative and below 2^-383 (1 + 2^-20), far under half an ulp of any non-zero float32 sample
+// (test_sqrt_core_below_the_library_rescaling).
+// the square root's FMA sequence from a reciprocal-root seed y (plain arithmetic, host and device: the same steps as
+// t2_sqrt_from_seed_seq below, h not handed out).  A seed capped at a finite value yields an exact 0 for x = 0.
+T2_HD double t2_sqrt_core_seq(double x, double y) {
+  double g = x * y, h = y * 0.5;
+  const double r = fma(-h, g, 0.5);
+  g = fma(g, r, g);
+  double d = fma(-g, g, x);
+  h = fma(h, r, h);
+  g = fma(d, h, g);
+  d = fma(-g, g, x);
+  g = fma(d, h, g);
+  return g;
+}
 #if defined(__HIP_DEVICE_COMPILE__)
 T2_HD double t2_exp_core(double x) {
   const double n = __builtin_rint(x * 0x1.71547652b82fep+0);
@@ -160,29 +177,22 @@ T2_HD double t2_exp_core(double x) {
 }
 T2_HD double t2_sqrt_core(double x) {
   // rsq(0) = inf would turn the iteration into NaN; capped at 1e300 (far above rsq of any normal number, so
-  // nothing else changes) every step below yields an exact 0 for x = 0: one v_min instead of a compare and
+  // nothing else changes) every step of the sequence yields an exact 0 for x = 0: one v_min instead of a compare and
   // two selects behind each of the 32 square roots of an evaluation
-  const double y = fmin(__builtin_amdgcn_rsq(x), 1e300);
-  double g = x * y, h = y * 0.5;
-  const double r = fma(-h, g, 0.5);
-  g = fma(g, r, g);
-  double d = fma(-g, g, x);
-  h = fma(h, r, h);
-  g = fma(d, h, g);
-  d = fma(-g, g, x);
-  g = fma(d, h, g);
-  return g;
+  return t2_sqrt_core_seq(x, fmin(__builtin_amdgcn_rsq(x), 1e300));
 }
 #else
 T2_HD double t2_exp_core(double x) { return exp(x); }
 T2_HD double t2_sqrt_core(double x) { return sqrt(x); }
 #endif
 
-// The square root of x together with h = 1 / (2 sqrt(x)) (to ~2^-51), and the square root of a value NEAR x from that h:
+// The square root of x together with h = 1 / (2 sqrt(x)) (to 2^-45: one coupled Newton step on a seed good to 2^-23; 2^-47.8
+// measured with v_rsq_f64), and the square root of a value NEAR x from that h:
 // the four radicands of one echo of a forward-difference evaluation differ by the step, parts in 1e8 or less, so the three
 // displaced ones start from the first one's refined reciprocal root (one more coupled Newton step brings g and h to ~1e-15 of
 // the new argument's, then the same residual correction as above) -- 6 instead of 11 instructions each.  Both sequences end in
-// g + (a - g^2) h with g within an ulp and h good to 2^-50: the correctly rounded root, the same bits (Markstein).
+// g + (a - g^2) h with g within an ulp and h good to 2^-45: the correctly rounded root, the same bits (Markstein; held on
+// the GPU with the hardware's seed by tests/test_device_arithmetic_gpu.py::test_shared_seed_roots_are_the_correctly_rounded_ones).
 // x > 0 and |a - x| <= 2^-20 x are the caller's business (Lbfgsb::eval checks both once per evaluation).
 // The sequences are plain FMA arithmetic (`_seq`, host and device: tests/test_lane_solver_hostsim.py runs them on the CPU
 // from a seed as coarse as the hardware's, against the correctly rounded sqrt); the device entry points feed them v_rsq_f64.
@@ -210,7 +220,7 @@ T2_HD double t2_sqrt_near_seq(double a, double h) {
   const double d = fma(-g, g, a);
   return fma(d, hi, g);
 }
-// sqrt(a) from h = 1 / (2 sqrt(a)) good to 2^-50 (the Rician lane keeps only h across its Chebyshev loop)
+// sqrt(a) from h = 1 / (2 sqrt(a)) good to 2^-45 (the Rician lane keeps only h across its Chebyshev loop)
 T2_HD double t2_sqrt_from_h_seq(double a, double h) {
   const double g0 = a * (h + h);
   return fma(fma(-g0, g0, a), h, g0);
@@ -385,7 +395,7 @@ T2_TABLE double t2_i0e_Bp[30] = {
 #endif
 // `near` (wave-uniform; the caller's guarantee that ax[1..3] lie within 2^-20, relative, of ax[0]): the reciprocals of the
 // (8, inf) series -- 32 / x before the recurrence, the division by sqrt(x) after it -- come from ONE reciprocal square root
-// (t2_sqrt_core_h of ax[0], a coupled Newton step to each of the others): h = 1 / (2 sqrt(x)) to 2^-50 gives 1 / x = (2h)^2
+// (t2_sqrt_core_h of ax[0], a coupled Newton step to each of the others): h = 1 / (2 sqrt(x)) to 2^-45 gives 1 / x = (2h)^2
 // and 1 / sqrt(x) = 2h as the multipliers of the same quotient-and-residual steps, and sqrt(x) itself after the
 // recurrence as x * 2h and one residual correction.  Only the four h stay live across the loop.
 T2_HD void t2_i0e4_by_lane(const double* ax, bool lane_small, double* r, bool near = false) {
@@ -491,7 +501,8 @@ T2_HD void t2_i0e4_by_lane(const double* ax, bool lane_small, double* r, bool ne
 
 // log() of i0e's values (positive normal numbers in (0, 1]) the way fdlibm's __ieee754_log computes it: argument reduction to
 // [sqrt(2)/2, sqrt(2)), s = f / (2 + f), a degree-7 polynomial in s^2, the exponent times ln 2 in two pieces; error below
-// 1 ulp, about 35 instructions.  The device library's log is a double-double evaluation of about 75 instructions, and the
+// 1 ulp (tests/test_lane_solver_hostsim.py::test_lean_log_is_within_one_ulp; with the frexp builtins and t2_fdiv on the GPU:
+// tests/test_device_arithmetic_gpu.py::test_lean_log_on_the_device), about 35 instructions.  The device library's log is a double-double evaluation of about 75 instructions, and the
 // Rician likelihood takes four logs per echo and evaluation: 30 % of its evaluation.  Neither is the reference's log (numpy's)
 // bit for bit -- log is one of the functions the one-ulp yardstick perturbs -- and measured on 20 000 voxels against the
 // live oracle the leaner one agrees at least as often: T2 within 1 ms 98.31 % against 98.26 %, iteration count equal 99.37 %

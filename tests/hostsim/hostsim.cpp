@@ -280,3 +280,77 @@ extern "C" int hostsim_i0e4_by_lane_near(const double* x, int64_t n, double* out
   }
   return 0;
 }
+
+// ---- the reciprocal, quotient, reciprocal-root and square-root sequences (t2fit_lane.h `_seq`) from a coarse seed ----
+// The seed has float32 precision at any exponent: the float32 reciprocal (root) of the operand's mantissa, scaled back.
+// That is coarser than the hardware's v_rcp_f64 / v_rsq_f64: what holds here holds for any seed of that quality.
+static double coarse_rcp(double b) {
+  int e;
+  const double m = frexp(b, &e);
+  return ldexp((double)(1.0f / (float)m), -e);
+}
+// seed_bits > 0: the seed rounded to that many significant bits (a seed far coarser than any hardware's)
+static double coarse_rsqrt(double x, int seed_bits = 0) {
+  int e;
+  double m = frexp(x, &e);
+  if (e & 1) { m += m; --e; }
+  double y = (double)(1.0f / sqrtf((float)m));  // in (0.7, 1.42)
+  if (seed_bits > 0) y = ldexp(nearbyint(ldexp(y, seed_bits)), -seed_bits);
+  return ldexp(y, -e / 2);
+}
+
+// a / b (t2_fdiv_seq; t2_div_by_rcp on t2_fast_rcp_seq performs the same operations) and 1 / b (t2_fast_rcp_seq)
+extern "C" int hostsim_div_seq(const double* a, const double* b, int64_t n, double* quot, double* rcp) {
+  for (int64_t v = 0; v < n; ++v) {
+    const double seed = coarse_rcp(b[v]);
+    quot[v] = t2_fdiv_seq(a[v], b[v], seed);
+    rcp[v] = t2_fast_rcp_seq(b[v], seed);
+    if (t2_div_by_rcp(a[v], b[v], rcp[v]) != quot[v]) return -1;
+  }
+  return 0;
+}
+
+// 1 / sqrt(x) (t2_fast_rsqrt_seq) and sqrt(x) (t2_sqrt_core_seq, seed capped at `cap` as the device entry caps it: x = 0 gets
+// the cap itself, where the hardware's seed is +inf).  seed_bits: see coarse_rsqrt.
+extern "C" int hostsim_root_seq(const double* x, int64_t n, double cap, int seed_bits, double* rsqrt_out, double* sqrt_out) {
+  for (int64_t v = 0; v < n; ++v) {
+    const double seed = x[v] == 0.0 ? (double)INFINITY : coarse_rsqrt(x[v], seed_bits);
+    rsqrt_out[v] = t2_fast_rsqrt_seq(x[v], seed);
+    sqrt_out[v] = t2_sqrt_core_seq(x[v], fmin(seed, cap));
+  }
+  return 0;
+}
+
+// One Lbfgsb<MODEL>::eval at `x` for any of the three models (run-time echo count, or the echo-count specialisation when
+// nte_special): out = f, g0, g1, g2 (g2 = 0 for the two-parameter model).  Set up as in hostsim_rician_eval; the device
+// probe (tests/devprobe) does the same on the GPU.
+extern "C" int hostsim_eval_at(const t2fit_config* cfg, const float* row, const double* x, int nte_special, double* out) {
+  const LaneParams P = make_lane_params(*cfg);
+  float buf[T2FIT_MAX_TE];
+  for (int i = 0; i < cfg->n_te; ++i) buf[i] = row[i];
+  bool finite;
+  float y0_raw;
+  ObjCtx c = prepare_samples(P, buf, 1, finite, y0_raw);
+  double lb[3], ub[3];
+  lane_bounds(P, y0_raw, lb, ub);
+  double hist[60] = {};
+  auto run = [&](auto& s) {
+    using S = std::remove_reference_t<decltype(s)>;
+    s.init(x, lb, ub, hist, 1);
+    for (int j = 0; j < S::N; ++j) s.x[j] = x[j];
+    if constexpr (S::kNte > 0)
+      for (int i = 0; i < S::kNte; ++i) s.ys[i] = buf[i];
+    s.eval(c);
+    out[0] = s.f;
+    for (int j = 0; j < 3; ++j) out[1 + j] = j < S::N ? s.g[j] : 0.0;
+  };
+  if (nte_special && cfg->n_te != 6) return -1;
+  if (P.model == T2FIT_MODEL_GAUSSIAN) {
+    if (nte_special) { Lbfgsb<T2FIT_MODEL_GAUSSIAN, 6> s; run(s); } else { Lbfgsb<T2FIT_MODEL_GAUSSIAN> s; run(s); }
+  } else if (P.model == T2FIT_MODEL_GAUSSIAN_RICIAN) {
+    if (nte_special) { Lbfgsb<T2FIT_MODEL_GAUSSIAN_RICIAN, 6> s; run(s); } else { Lbfgsb<T2FIT_MODEL_GAUSSIAN_RICIAN> s; run(s); }
+  } else {
+    if (nte_special) { Lbfgsb<T2FIT_MODEL_RICIAN, 6> s; run(s); } else { Lbfgsb<T2FIT_MODEL_RICIAN> s; run(s); }
+  }
+  return 0;
+}

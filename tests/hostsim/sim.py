@@ -179,3 +179,38 @@ def i0e4_by_lane_near(x):
     L.hostsim_i0e4_by_lane_near.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     assert L.hostsim_i0e4_by_lane_near(x.ctypes.data, len(x), out.ctypes.data, ref.ctypes.data) == 0
     return out, ref
+
+
+def div_seq(a, b):
+    """(a / b, 1 / b) through t2_fdiv_seq / t2_fast_rcp_seq from a reciprocal seed of float32 precision."""
+    L = lib()
+    a = np.ascontiguousarray(a, np.float64)
+    b = np.ascontiguousarray(b, np.float64)
+    quot, rcp = np.empty_like(a), np.empty_like(a)
+    L.hostsim_div_seq.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    assert L.hostsim_div_seq(a.ctypes.data, b.ctypes.data, a.size, quot.ctypes.data, rcp.ctypes.data) == 0
+    return quot, rcp
+
+
+def root_seq(x, cap=1e300, seed_bits=0):
+    """(1 / sqrt(x), sqrt(x)) through t2_fast_rsqrt_seq / t2_sqrt_core_seq from a reciprocal-root seed of float32
+    precision -- rounded to `seed_bits` significant bits if that is given -- capped at `cap` (x = 0: the cap itself)."""
+    L = lib()
+    x = np.ascontiguousarray(x, np.float64)
+    rs, sq = np.empty_like(x), np.empty_like(x)
+    L.hostsim_root_seq.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
+    assert L.hostsim_root_seq(x.ctypes.data, x.size, cap, int(seed_bits), rs.ctypes.data, sq.ctypes.data) == 0
+    return rs, sq
+
+
+def eval_at(cfg, rows, xs, nte_special=False):
+    """One Lbfgsb::eval per row (any model).  rows: (n, n_te) float32, xs: (n, 3) float64 -> (n, 4): f, g0, g1, g2."""
+    L = lib()
+    rows = np.ascontiguousarray(rows, np.float32)
+    xs = np.ascontiguousarray(xs, np.float64)
+    out = np.zeros((len(xs), 4))
+    L.hostsim_eval_at.argtypes = [C.POINTER(_abi.T2FitConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    for i in range(len(xs)):
+        rc = L.hostsim_eval_at(C.byref(cfg), rows[i].ctypes.data, xs[i].ctypes.data, int(nte_special), out[i].ctypes.data)
+        assert rc == 0, rc
+    return out
