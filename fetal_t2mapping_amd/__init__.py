@@ -15,6 +15,8 @@ from .t2map import atlas  # the atlas-label stage: atlas.atlas_labels, atlas.ext
 from .t2map import bias  # the N4 bias-field correction: bias.n4_correct, bias.apply_field
 from .t2map import (binary_close, binary_dilate, binary_erode, binary_open, binary_threshold, build_mask, fill_holes,
                     mask_from_labels, phantom_labels, phantom_mask, relabel, seed_labels, synthseg_to_feta)
+from .t2map import sr  # the super-resolution reconstruction: sr.reconstruct_sr, sr.sr_forward, sr.sr_adjoint, sr.sr_box
+from ._gpu_sr import reconstruct_sr, sr_adjoint, sr_box, sr_forward  # the same four, by their own names
 
 __all__ = ["BootMaps", "BootStats", "RoiStats", "T2Maps", "bootstrap_volume", "compute_residuals", "denoise_tv", "dense_labels",
            "estimate_background_sigma", "fit_table", "fit_volume", "fit_voxel", "fit_voxels", "fit_voxels_trace", "label_stats",
@@ -22,4 +24,4 @@ __all__ = ["BootMaps", "BootStats", "RoiStats", "T2Maps", "bootstrap_volume", "c
            "stack_mask_flatten", "synth_replica", "union_mask_dev",
            "binary_close", "binary_dilate", "binary_erode", "binary_open", "binary_threshold", "build_mask", "fill_holes",
            "mask_from_labels", "phantom_labels", "phantom_mask", "relabel", "seed_labels", "synthseg_to_feta", "register",
-           "atlas", "bias"]
+           "atlas", "bias", "sr"]

@@ -68,6 +68,10 @@ MORPH_OPS = {"dilate": MORPH_DILATE, "erode": MORPH_ERODE, "close": MORPH_CLOSE,
 MORPH_UNBOUNDED = 1  # flags bit
 MORPH_F32, MORPH_I32, MORPH_U8 = 0, 1, 2
 
+SR_PROFILE_BOX, SR_PROFILE_BSPLINE3 = 0, 1
+SR_PROFILES = {"box": SR_PROFILE_BOX, "bspline3": SR_PROFILE_BSPLINE3}
+SR_MAX_STACKS = 6
+
 REGISTER_SUMS = 43
 REGISTER_MAX_BINS = 64
 REGISTER_MI_SUMS = 12
@@ -106,6 +110,14 @@ SYMBOLS = [
                                                     C.POINTER(C.c_size_t)]),
     ("t2fit_reconstruct_dev", C.c_int, [C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_double), _P, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    ("t2fit_sr_plan_host", C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    ("t2fit_sr_workspace_bytes", C.c_int, [C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.POINTER(C.c_size_t)]),
+    ("t2fit_sr_forward_dev", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_int32), C.c_int, C.c_double, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    ("t2fit_sr_adjoint_dev", C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double), _P, C.c_double, _P,
+                                       C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ("t2fit_morph_workspace_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     ("t2fit_binary_threshold_dev", C.c_int, [_P, C.c_int, C.c_int64, C.c_double, C.c_double, _P, _P]),
     ("t2fit_binary_morph_dev", C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -162,7 +174,8 @@ ATLAS_SYMBOLS = ("t2fit_register_bin_dev", "t2fit_register_binned_workspace_byte
 N4_SYMBOLS = ("t2fit_n4_workspace_bytes", "t2fit_n4_log_dev", "t2fit_n4_minmax_dev", "t2fit_n4_histogram_dev", "t2fit_n4_weights_dev",
               "t2fit_n4_fit_dev", "t2fit_n4_field_dev", "t2fit_n4_apply_dev")
 MI_SYMBOLS = ("t2fit_register_joint_hist_dev", "t2fit_register_mi_workspace_bytes", "t2fit_register_mi_gradient_dev")
-LOOKED_UP = ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS + MI_SYMBOLS
+SR_SYMBOLS = ("t2fit_sr_plan_host", "t2fit_sr_workspace_bytes", "t2fit_sr_forward_dev", "t2fit_sr_adjoint_dev")
+LOOKED_UP = ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS + MI_SYMBOLS + SR_SYMBOLS
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

@@ -1,0 +1,237 @@
+"""Super-resolution reconstruction of the thick-slice stacks on the GPU: the acquisition operator, its adjoint and the
+proximal-gradient loop over them; :mod:`fetal_t2mapping_amd._sr` states all three in numpy."""
+import ctypes as C
+
+import numpy as np
+
+from . import _abi, _resample, _sr
+from ._gpu import current_stream, flat, is_tensor, pick_device, release, require, workspace
+from ._gpu_resample import reconstruct_stacks, resample_volume
+from ._gpu_tv import tv_params
+from ._lib import check
+
+
+def _doubles(a):
+    a = np.ascontiguousarray(a, np.float64).ravel()
+    return (C.c_double * a.size)(*a)
+
+
+def sr_box(B, profile="box", rel_thickness=1.0):
+    """``(Binv (3, 4), radius (x, y, z))`` of t2fit_sr_plan_host for the support of this profile: host arithmetic."""
+    lib = require(*_abi.SR_SYMBOLS)
+    _, hw = _sr.profile_params(profile, rel_thickness)
+    binv, radius = (C.c_double * 12)(), (C.c_int32 * 3)()
+    check(lib.t2fit_sr_plan_host(_doubles(np.asarray(B, np.float64).reshape(12)), _doubles((1.0, 1.0, hw)), binv, radius))
+    return np.array(binv, np.float64).reshape(3, 4), tuple(int(v) for v in radius)
+
+
+def _shape4(a, what):
+    shape = tuple(int(v) for v in a.shape)
+    if len(shape) not in (3, 4):
+        raise ValueError(f"{what} must be (Z, Y, X) or (n, Z, Y, X), got shape {shape}")
+    return (1,) + shape if len(shape) == 3 else shape
+
+
+def _mask(mask, dev, n):
+    """None stays None (the entry points take NULL); otherwise flat uint8 0 / 1."""
+    import torch
+
+    if mask is None:
+        return None
+    m = mask if is_tensor(mask) else torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0).view(np.uint8))
+    m = (m != 0).to(dev, torch.uint8).contiguous().reshape(-1)
+    if m.numel() != n:
+        raise ValueError(f"a stack mask has {m.numel()} elements, its stack has {n}")
+    return m
+
+
+def _forward(lib, x, hr_shape, n_vol, B, box, pid, rel, y, mask, lr_shape, out, n_out):
+    """Queue t2fit_sr_forward_dev on flat device tensors (None: NULL)."""
+    ptr = lambda t: None if t is None else t.data_ptr()
+    radius = (C.c_int32 * 3)(*box[1])
+    check(lib.t2fit_sr_forward_dev(ptr(x), *hr_shape, n_vol, _doubles(B), _doubles(box[0]), radius, pid, float(rel), ptr(y),
+                                   ptr(mask), *lr_shape, ptr(out), ptr(n_out), current_stream()))
+
+
+def _adjoint(lib, r, n_list, masks, lr_shapes, B, pids, rels, x, tau, out, hr_shape, n_vol):
+    """Queue t2fit_sr_adjoint_dev on flat device tensors; ``masks`` is a list that may hold None."""
+    n_s = len(r)
+    ptrs = lambda ts: (C.c_void_p * n_s)(*[None if t is None else t.data_ptr() for t in ts])
+    check(lib.t2fit_sr_adjoint_dev(n_s, ptrs(r), ptrs(n_list), ptrs(masks), (C.c_int32 * (3 * n_s))(*[v for s in lr_shapes for v in s]),
+                                   _doubles(np.concatenate([np.asarray(b, np.float64).ravel() for b in B])),
+                                   (C.c_int32 * n_s)(*pids), _doubles(rels), None if x is None else x.data_ptr(), float(tau),
+                                   out.data_ptr(), *hr_shape, n_vol, current_stream()))
+
+
+def sr_forward(x, B, lr_shape, *, profile="box", rel_thickness=1.0, y=None, mask=None, hr_shape=None, device=0):
+    """One stack of the acquisition operator on the GPU: ``(out, N)`` as :func:`_sr.forward` defines them, bit for bit.
+    ``x``: float32 ``(Z, Y, X)`` or ``(n, Z, Y, X)`` on the high-resolution grid (None with ``hr_shape``: the weights only,
+    ``out`` is None); ``B``: 3 x 4 from :func:`_resample.index_affine` (grid index -> stack index); ``rel_thickness``: slice
+    thickness / slice spacing; ``y`` like the result: the residual ``A x - y``; ``mask``: the samples that count.  numpy in,
+    numpy out; CUDA tensor in, tensors out (asynchronous on the current stream).  ``N`` is float64 ``lr_shape``."""
+    import torch
+
+    lib = require(*_abi.SR_SYMBOLS)
+    pid = _sr._profile_id(profile)
+    _sr.profile_params(pid, rel_thickness)
+    lr_shape = tuple(int(v) for v in lr_shape)
+    if len(lr_shape) != 3:
+        raise ValueError("lr_shape is (Z, Y, X)")
+    if x is None:
+        if hr_shape is None:
+            raise ValueError("the weights alone (x=None) need hr_shape")
+        shape, is_t = (1,) + tuple(int(v) for v in hr_shape), False
+    else:
+        shape, is_t = _shape4(x, "x"), is_tensor(x)
+    n_vol, n_l = shape[0], int(np.prod(lr_shape))
+    b = np.asarray(B, np.float64).reshape(3, 4)
+    box = sr_box(b, pid, rel_thickness)
+    dev = pick_device((x, y, mask), device)
+    with torch.cuda.device(dev):
+        xt = None if x is None else flat(x, dev)
+        yt = None if y is None else flat(y, dev, n_vol * n_l, "y")
+        mt = _mask(mask, dev, n_l)
+        n_out = torch.empty(lr_shape, dtype=torch.float64, device=dev)
+        out = None if x is None else torch.empty((n_vol,) + lr_shape, dtype=torch.float32, device=dev)
+        _forward(lib, xt, shape[-3:], n_vol, b, box, pid, rel_thickness, yt, mt, lr_shape, out, n_out)
+        release(xt, yt, mt)
+    if out is not None and len(x.shape) == 3:
+        out = out[0]
+    host = (lambda t: t) if is_t else (lambda t: None if t is None else t.cpu().numpy())
+    return host(out), host(n_out)
+
+
+def sr_adjoint(r, N, B, profile, rel_thickness, hr_shape, *, masks=None, x=None, tau=0.0, device=0):
+    """``sum_s A_s^T r_s`` (or ``x - tau`` times it) on the grid ``hr_shape`` as :func:`_sr.adjoint` defines it, bit for
+    bit: lists over 1 to 6 stacks of residuals, of the normalisers :func:`sr_forward` returned and of affines; ``profile`` and
+    ``rel_thickness`` per stack or one for all.  numpy in, numpy out; CUDA tensors in, tensor out."""
+    import torch
+
+    lib = require(*_abi.SR_SYMBOLS)
+    n_s = len(r)
+    if not 1 <= n_s <= _abi.SR_MAX_STACKS or len(N) != n_s or len(B) != n_s:
+        raise ValueError(f"between 1 and {_abi.SR_MAX_STACKS} stacks with one N and one B each")
+    pids = [_sr._profile_id(p) for p in ([profile] * n_s if isinstance(profile, (str, int)) else profile)]
+    rels = [float(v) for v in ([rel_thickness] * n_s if np.ndim(rel_thickness) == 0 else rel_thickness)]
+    for p, t in zip(pids, rels):
+        _sr.profile_params(p, t)
+    masks = [None] * n_s if masks is None else list(masks)
+    shapes = [_shape4(v, "a residual") for v in r]
+    if len({s[0] for s in shapes}) != 1:
+        raise ValueError("the residuals differ in their number of volumes")
+    n_vol = shapes[0][0]
+    hr_shape = tuple(int(v) for v in hr_shape)
+    is_t = is_tensor(r[0])
+    dev = pick_device(list(r) + [x], device)
+    with torch.cuda.device(dev):
+        rt = [flat(v, dev) for v in r]
+        nt = [flat(v, dev, int(np.prod(s[-3:])), "N", dtype="float64") for v, s in zip(N, shapes)]
+        mt = [_mask(m, dev, int(np.prod(s[-3:]))) for m, s in zip(masks, shapes)]
+        xt = None if x is None else flat(x, dev, n_vol * int(np.prod(hr_shape)), "x")
+        out = torch.empty((n_vol,) + hr_shape, dtype=torch.float32, device=dev)
+        _adjoint(lib, rt, nt, mt, [s[-3:] for s in shapes], B, pids, rels, xt, tau, out, hr_shape, n_vol)
+        release(xt, *rt, *nt, *mt)
+    if len(r[0].shape) == 3:
+        out = out[0]
+    return out if is_t else out.cpu().numpy()
+
+
+def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thickness=None, profile="box",
+                   weight=_sr.DEFAULT_WEIGHT, n_iter=_sr.DEFAULT_N_ITER, prox_iter=_sr.DEFAULT_PROX_ITER, stack_masks=None,
+                   x0=None, return_info=False, device=0):
+    """TV-regularised super-resolution reconstruction of 1 to 6 thick-slice stacks on the GPU.  Each slice is modelled as
+    the slice-profile average of the ``res`` mm volume x on the ``fixed`` stack's isotropic grid, and per echo
+
+        1/2 sum_s ||A_s x - y_s||^2 + weight * TV(x)
+
+    is reduced by ``n_iter`` proximal-gradient steps from ``x0`` (default: the averaged merge of
+    :func:`reconstruct_stacks` when the stacks are ax, cor and sag, else the fixed stack's own linear resample); the prox is
+    :func:`denoise_tv` in 3-D with ``prox_iter`` iterations.  ``weight`` is in intensity units of the stacks (0: plain
+    iterative back-projection).  ``stacks`` / ``geoms``: {name: float32 ``(nTE, Z, Y, X)`` or ``(Z, Y, X)``} and their
+    geometries; ``transforms``: {moving stack: 4 x 4, fixed point -> moving point}; ``thickness``: slice thickness in mm, one
+    number or {name: mm} (default: the slice spacing); ``profile``: ``'box'`` or ``'bspline3'``; ``stack_masks``: {name: the
+    samples that count, ``(Z, Y, X)``}.
+    Returns ``(echoes, header)`` like :func:`reconstruct_stacks`: a float32 CUDA tensor ``(nTE, Z, Y, X)`` and a
+    ``nifti.Image`` over an empty array with the grid's geometry; with ``return_info`` also ``{"tau", "column_max", "N"}``.
+    The step size is read back once before the loop (one synchronisation); the loop itself queues 3 + stacks launch groups
+    per iteration and does not synchronise.  :func:`_sr.reconstruct_sr` states the definition in numpy; same bits."""
+    import torch
+
+    from . import nifti
+
+    lib = require(*(_abi.SR_SYMBOLS + _abi.TV_SYMBOLS))
+    if not (float(weight) >= 0.0 and np.isfinite(weight)) or int(n_iter) < 0 or int(prox_iter) < 1:
+        raise ValueError("weight must be finite and >= 0, n_iter >= 0, prox_iter >= 1")
+    pid = _sr._profile_id(profile)
+    names = [o for o in geoms if o in stacks]
+    shapes = {o: _shape4(stacks[o], f"stack {o!r}") for o in names}
+    if len({len(stacks[o].shape) for o in names}) > 1 or len({s[0] for s in shapes.values()}) > 1:
+        raise ValueError(f"the stacks must all be (Z, Y, X) or all (nTE, Z, Y, X) with one number of echoes, got "
+                         f"{ {o: tuple(stacks[o].shape) for o in names} }")
+    g = {o: _resample.as_geometry(geoms[o], shapes[o][-3:]) for o in names}
+    order, hi, B, rels = _sr.sr_plan(g, fixed, res, transforms, thickness)
+    n_s, n_vol, hr_shape = len(order), shapes[order[0]][0], hi.shape
+    lr_shapes = [shapes[o][-3:] for o in order]
+    boxes = [sr_box(B[s], pid, rels[s]) for s in range(n_s)]
+    dev = pick_device([stacks[o] for o in order], device)
+    lo_size = (C.c_int32 * (3 * n_s))(*[v for s in lr_shapes for v in s])
+    need = C.c_size_t(0)
+    check(lib.t2fit_sr_workspace_bytes(n_s, lo_size, *hr_shape, n_vol, C.byref(need)))
+    n_h = int(np.prod(hr_shape))
+    with torch.cuda.device(dev):
+        y = [flat(stacks[o], dev) for o in order]
+        masks = [_mask(None if stack_masks is None else stack_masks.get(o), dev, int(np.prod(s))) for o, s in zip(order, lr_shapes)]
+        # x_0 before the workspace is carved: the merge has a workspace of its own
+        if x0 is not None:
+            x = flat(x0, dev, n_vol * n_h, "x0").clone()
+        elif sorted(order) == sorted(_resample.ORIENTATIONS):
+            x = reconstruct_stacks({o: stacks[o] for o in order}, g, fixed=fixed, res=res, transforms=transforms, device=dev.index)[0].reshape(-1)
+        else:
+            x = resample_volume(y[0].reshape((n_vol,) + lr_shapes[0]), g[order[0]], like=hi)[0].reshape(-1)
+        ws, base = workspace(need.value, dev)
+        off = base - ws.data_ptr()
+
+        def carve(nbytes, dtype):
+            nonlocal off
+            t = ws[off:off + nbytes].view(dtype)
+            off += (nbytes + 255) // 256 * 256
+            return t
+
+        z = carve(4 * n_vol * n_h, torch.float32)
+        N, r = [], []
+        for s in lr_shapes:
+            N.append(carve(8 * int(np.prod(s)), torch.float64))
+            r.append(carve(4 * n_vol * int(np.prod(s)), torch.float32))
+        assert off - (base - ws.data_ptr()) == need.value
+        # the normalisers, then tau from the per-stack column sums A_s^T 1 (z and r_s serve as scratch)
+        col_max = []
+        for s in range(n_s):
+            _forward(lib, None, hr_shape, 1, B[s], boxes[s], pid, rels[s], None, None, lr_shapes[s], None, N[s])
+            ones = r[s][:N[s].numel()]
+            ones.copy_(((N[s] > 0) if masks[s] is None else (N[s] > 0) & (masks[s] != 0)).to(torch.float32))
+            _adjoint(lib, [ones], [N[s]], [masks[s]], [lr_shapes[s]], [B[s]], [pid], [rels[s]], None, 0.0, z, hr_shape, 1)
+            col_max.append(z[:n_h].max())
+        col_max = [float(v) for v in torch.stack(col_max).tolist()]  # the one read-back
+        tau = _sr.step_size(col_max)
+        if float(weight) > 0.0:
+            par = tv_params(tau * float(weight), 0.0, int(prox_iter), 3, "f32")
+            tv_need = C.c_size_t(0)
+            check(lib.t2fit_tv_workspace_bytes(C.byref(par), n_vol, *hr_shape, C.byref(tv_need)))
+            tv_ws, tv_ptr = workspace(tv_need.value, dev)
+        stream = current_stream()
+        for _ in range(int(n_iter)):
+            for s in range(n_s):
+                _forward(lib, x, hr_shape, n_vol, B[s], boxes[s], pid, rels[s], y[s], masks[s], lr_shapes[s], r[s], None)
+            if float(weight) > 0.0:
+                _adjoint(lib, r, N, masks, lr_shapes, B, [pid] * n_s, rels, x, tau, z, hr_shape, n_vol)
+                check(lib.t2fit_tv_denoise_dev(C.byref(par), z.data_ptr(), x.data_ptr(), n_vol, *hr_shape, tv_ptr, tv_need.value,
+                                               None, None, stream))
+            else:
+                _adjoint(lib, r, N, masks, lr_shapes, B, [pid] * n_s, rels, x, tau, x, hr_shape, n_vol)
+        info = {"tau": tau, "column_max": col_max, "N": [n.clone().reshape(s) for n, s in zip(N, lr_shapes)]} if return_info else None
+        if float(weight) > 0.0:
+            release(tv_ws)
+        release(ws, *y, *[m for m in masks if m is not None])
+    out = x.reshape((n_vol,) + hr_shape)
+    header = nifti.Image(np.zeros((0, 0, 0), np.float32), hi.GetSpacing(), hi.GetOrigin(), hi.GetDirection())
+    return (out, header, info) if return_info else (out, header)

@@ -1,0 +1,347 @@
+"""Super-resolution reconstruction of thick-slice stacks, restated in numpy: the executable statement of the
+definition in include/t2fit.h (t2fit_sr_plan_host, t2fit_sr_forward_dev, t2fit_sr_adjoint_dev).  Each thick slice is
+modelled as the slice-profile average of the 1 mm volume x; the reconstruction inverts that model per echo,
+
+    minimise  1/2 sum_s ||A_s x - y_s||^2  +  weight * TV(x)        (TV: isotropic, forward differences, as _tv.py)
+
+by proximal gradient from the averaged merge: ``x <- prox(x - tau sum_s A_s^T (A_s x - y_s))``.  The prox of
+``tau * weight * TV`` is :func:`_tv.denoise_tv` with ``dims=3``, whose ``weight`` w stands for exactly one times TV (its
+fixed point minimises ``1/2 ||u - f||^2 + w TV(u)``: substitute p = w q in the update of :func:`_tv.update` and Chambolle's
+iteration for lambda = w appears), so it is called with ``w = tau * weight``.
+
+Arrays are ``(Z, Y, X)`` or ``(n, Z, Y, X)``, x fastest.  ``B`` (3 x 4, from :func:`_resample.index_affine`) maps an
+integer index v of the high-resolution grid H to the continuous stack index ``u = coord(B, v)``; the weight of the pair
+(stack sample j, voxel v) is ``(tri(u_x - j_x) * tri(u_y - j_y)) * prof(u_z - j_z)`` and BOTH directions compute it from
+that u, so the matrix and its transpose hold the same bits.  Sums are float64, one rounding per operation in the order
+written, candidates in ascending (z, y, x); a candidate of weight 0 is skipped, so the result does not depend on the
+candidate boxes, which only have to cover the support.  Host code for tests and baselines: the product path is the HIP
+kernel."""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _resample, _tv
+
+BOX, BSPLINE3 = 0, 1
+PROFILES = {"box": BOX, "bspline3": BSPLINE3}
+MAX_STACKS = 6
+BSPLINE3_FWHM = 1.4447034489287527  # full width at half maximum of the cubic B-spline: 2 x, x^3 / 2 - x^2 + 1 / 3 = 0
+DEFAULT_WEIGHT, DEFAULT_N_ITER, DEFAULT_PROX_ITER = 16.0, 8, 5  # the sweep they come from
+
+
+def _profile_id(profile):
+    if profile in PROFILES:
+        return PROFILES[profile]
+    if profile in (BOX, BSPLINE3) and not isinstance(profile, str):
+        return int(profile)
+    raise ValueError(f"profile must be one of {sorted(PROFILES)}, got {profile!r}")
+
+
+def profile_params(profile, rel_thickness):
+    """``(par, half_width)`` in slice-index units of a profile whose thickness is ``rel_thickness`` slice spacings: box
+    ``par = h = rel / 2``, support ``-h <= d < h``; bspline3 ``par = a = rel / BSPLINE3_FWHM``, ``prof(d) = beta3(|d| / a)``,
+    support ``|d| < 2 a``."""
+    rel = float(rel_thickness)
+    if not (rel > 0.0 and np.isfinite(rel)):
+        raise ValueError(f"the slice thickness must be finite and > 0, got {rel_thickness!r}")
+    if _profile_id(profile) == BOX:
+        return rel / 2.0, rel / 2.0
+    a = rel / BSPLINE3_FWHM
+    return a, 2.0 * a
+
+
+def tri(d):
+    return np.maximum(0.0, 1.0 - np.abs(d))
+
+
+def prof(d, profile, par):
+    if profile == BOX:
+        return np.where((d >= -par) & (d < par), 1.0, 0.0)
+    t = np.abs(d) / par
+    q = 2.0 - t
+    inner = (2.0 / 3.0 - t * t) + 0.5 * ((t * t) * t)
+    outer = ((q * q) * q) / 6.0
+    return np.where(t < 1.0, inner, np.where(t < 2.0, outer, 0.0))
+
+
+def pair_weight(ux, uy, uz, jx, jy, jz, profile, par):
+    """``w(j, v)`` from the stack coordinate u of v and the sample index j (float64 arrays that broadcast)."""
+    return (tri(ux - jx) * tri(uy - jy)) * prof(uz - jz, profile, par)
+
+
+def _coord(a, k, ix, iy, iz):
+    return ((a[k, 0] * ix + a[k, 1] * iy) + a[k, 2] * iz) + a[k, 3]
+
+
+def _grid(start, shape):
+    """Index grids ix, iy, iz (float64, broadcastable to ``shape`` (Z, Y, X)) of the box at ``start`` (x, y, z)."""
+    iz = np.arange(start[2], start[2] + shape[0], dtype=np.float64)[:, None, None]
+    iy = np.arange(start[1], start[1] + shape[1], dtype=np.float64)[None, :, None]
+    ix = np.arange(start[0], start[0] + shape[2], dtype=np.float64)[None, None, :]
+    return ix, iy, iz
+
+
+def plan_box(B, half):
+    """The host half of the forward operator (t2fit_sr_plan_host, same arithmetic): the inverse ``Binv`` (3 x 4, stack
+    index -> continuous H index) and integer radii (x, y, z) such that every voxel v with a non-zero weight for sample j
+    lies within ``radius`` of ``floor(coord(Binv, j) + 0.5)`` on each axis.  ``half`` (x, y, z): half-widths of the support
+    in stack-index units.  ``radius_a = ceil(sum_b |Binv[a, b]| half_b) + 1``: the sum bounds the support around the exact
+    preimage, 1/2 goes to the rounding of the centre, the rest to the inverse's own rounding."""
+    b = np.asarray(B, np.float64).reshape(3, 4)
+    half = np.asarray(half, np.float64).reshape(3)
+    if not (np.all(np.isfinite(b)) and np.all(np.isfinite(half)) and np.all(half > 0)):
+        raise ValueError("B must be finite and the half-widths finite and > 0")
+    m = b[:, :3]
+    c = np.empty((3, 3), np.float64)  # cofactors
+    c[0, 0] = m[1, 1] * m[2, 2] - m[1, 2] * m[2, 1]
+    c[0, 1] = m[1, 2] * m[2, 0] - m[1, 0] * m[2, 2]
+    c[0, 2] = m[1, 0] * m[2, 1] - m[1, 1] * m[2, 0]
+    c[1, 0] = m[0, 2] * m[2, 1] - m[0, 1] * m[2, 2]
+    c[1, 1] = m[0, 0] * m[2, 2] - m[0, 2] * m[2, 0]
+    c[1, 2] = m[0, 1] * m[2, 0] - m[0, 0] * m[2, 1]
+    c[2, 0] = m[0, 1] * m[1, 2] - m[0, 2] * m[1, 1]
+    c[2, 1] = m[0, 2] * m[1, 0] - m[0, 0] * m[1, 2]
+    c[2, 2] = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
+    det = (m[0, 0] * c[0, 0] + m[0, 1] * c[0, 1]) + m[0, 2] * c[0, 2]
+    if not (np.isfinite(det) and det != 0.0):
+        raise ValueError("B is singular")
+    inv = np.empty((3, 4), np.float64)
+    radius = []
+    for a in range(3):
+        for k in range(3):
+            inv[a, k] = c[k, a] / det
+        inv[a, 3] = -((inv[a, 0] * b[0, 3] + inv[a, 1] * b[1, 3]) + inv[a, 2] * b[2, 3])
+        reach = (abs(inv[a, 0]) * half[0] + abs(inv[a, 1]) * half[1]) + abs(inv[a, 2]) * half[2]
+        if not (np.isfinite(reach) and reach < 2.0 ** 20):
+            raise ValueError("B is singular")
+        radius.append(int(np.ceil(reach)) + 1)
+    return inv, tuple(radius)
+
+
+def _volumes(x):
+    x = np.asarray(x)
+    if x.ndim not in (3, 4):
+        raise ValueError("a volume is (Z, Y, X) or (n, Z, Y, X)")
+    return x.reshape((-1,) + x.shape[-3:]), x.ndim == 3
+
+
+def forward(x, B, lr_shape, profile="box", rel_thickness=1.0, *, y=None, mask=None, hr_shape=None, start=(0, 0, 0),
+            shape=None, out_dtype=np.float32, box=None):
+    """``(out, N)`` of one stack: ``N[j] = sum_v w(j, v)`` (float64) and ``out[j] = (sum_v w x[v]) / N[j]``, minus ``y[j]``
+    when ``y`` is given; 0 where the sample does not count (``N[j] <= 0`` or its ``mask`` is 0).  ``x = None`` (then give
+    ``hr_shape``): the weights only, ``out`` is None.  ``start`` (x, y, z) and ``shape`` (Z, Y, X): the box of samples to
+    evaluate (``y`` and ``mask`` still cover the whole stack), by default all of ``lr_shape``.  ``box``: ``(Binv, radius)``
+    to walk instead of :func:`plan_box`'s."""
+    pid = _profile_id(profile)
+    par, hw = profile_params(pid, rel_thickness)
+    b = np.asarray(B, np.float64).reshape(3, 4)
+    if x is not None:
+        xv, single = _volumes(x)
+        hr_shape = xv.shape[-3:]
+    else:
+        xv, single = None, True
+    hz, hy, hx = (int(v) for v in hr_shape)
+    lr_shape = tuple(int(v) for v in lr_shape)
+    shape = lr_shape if shape is None else tuple(int(v) for v in shape)
+    binv, radius = plan_box(b, (1.0, 1.0, hw)) if box is None else box
+    jx, jy, jz = _grid(start, shape)
+    k = [np.broadcast_to(np.floor(_coord(binv, a, jx, jy, jz) + 0.5), shape) for a in range(3)]
+    n_sum = np.zeros(shape, np.float64)
+    acc = None if xv is None else np.zeros((len(xv),) + shape, np.float64)
+    for dz in range(-radius[2], radius[2] + 1):
+        vz = k[2] + dz
+        in_z = (vz >= 0) & (vz <= hz - 1)
+        if not in_z.any():
+            continue
+        for dy in range(-radius[1], radius[1] + 1):
+            vy = k[1] + dy
+            in_zy = in_z & (vy >= 0) & (vy <= hy - 1)
+            if not in_zy.any():
+                continue
+            for dx in range(-radius[0], radius[0] + 1):
+                vx = k[0] + dx
+                inside = in_zy & (vx >= 0) & (vx <= hx - 1)
+                if not inside.any():
+                    continue
+                w = pair_weight(_coord(b, 0, vx, vy, vz), _coord(b, 1, vx, vy, vz), _coord(b, 2, vx, vy, vz), jx, jy, jz, pid, par)
+                use = inside & (w > 0.0)
+                if not use.any():
+                    continue
+                n_sum = np.where(use, n_sum + w, n_sum)
+                if acc is not None:
+                    iz, iy, ix = (np.clip(v, 0, n - 1).astype(np.int64) for v, n in ((vz, hz), (vy, hy), (vx, hx)))
+                    with np.errstate(all="ignore"):
+                        acc = np.where(use, acc + w * xv[:, iz, iy, ix].astype(np.float64), acc)
+    if acc is None:
+        return None, n_sum
+    sub = tuple(slice(s, s + n) for s, n in zip(start[::-1], shape))
+    counts = n_sum > 0.0
+    if mask is not None:
+        counts &= np.asarray(mask).reshape(lr_shape)[sub] != 0
+    with np.errstate(all="ignore"):
+        out = acc / np.where(counts, n_sum, 1.0)
+        if y is not None:
+            out = out - np.asarray(y).reshape((-1,) + lr_shape)[(slice(None),) + sub].astype(np.float64)
+        out = np.where(counts, out, 0.0).astype(out_dtype)
+    return (out[0] if single else out), n_sum
+
+
+def adjoint(r, N, B, profile, rel_thickness, hr_shape, *, masks=None, x=None, tau=0.0, start=(0, 0, 0), shape=None,
+            out_dtype=np.float32):
+    """``sum_s A_s^T r_s`` on the grid ``hr_shape``: lists over the stacks of residuals ``r[s]`` (``(lz, ly, lx)`` or
+    ``(n, lz, ly, lx)``), normalisers ``N[s]`` (float64, from :func:`forward`), affines, profiles and thicknesses (a scalar
+    profile / thickness serves all).  One float64 accumulator per voxel runs over the stacks in order and, within a stack,
+    over its candidate samples in ascending (z, y, x): ``acc += (w * r[j]) / N[j]`` for the samples that count.  With ``x``:
+    ``x - tau * acc``.  ``start`` / ``shape``: the box of voxels to evaluate."""
+    n_s = len(r)
+    if not 1 <= n_s <= MAX_STACKS:
+        raise ValueError(f"between 1 and {MAX_STACKS} stacks, got {n_s}")
+    profiles = [profile] * n_s if isinstance(profile, (str, int)) else list(profile)
+    rels = [rel_thickness] * n_s if np.ndim(rel_thickness) == 0 else list(rel_thickness)
+    masks = [None] * n_s if masks is None else list(masks)
+    hr_shape = tuple(int(v) for v in hr_shape)
+    shape = hr_shape if shape is None else tuple(int(v) for v in shape)
+    rv = [_volumes(v) for v in r]
+    single = rv[0][1]
+    n_vol = len(rv[0][0])
+    vx, vy, vz = _grid(start, shape)
+    acc = np.zeros((n_vol,) + shape, np.float64)
+    for s in range(n_s):
+        rs = rv[s][0]
+        lz, ly, lx = rs.shape[-3:]
+        pid = _profile_id(profiles[s])
+        par, hw = profile_params(pid, rels[s])
+        b = np.asarray(B[s], np.float64).reshape(3, 4)
+        ns = np.asarray(N[s], np.float64).reshape(lz, ly, lx)
+        ms = None if masks[s] is None else np.asarray(masks[s]).reshape(lz, ly, lx) != 0
+        u = [np.broadcast_to(_coord(b, a, vx, vy, vz), shape) for a in range(3)]
+        f = [np.floor(u[0]), np.floor(u[1]), np.floor(u[2] - hw)]
+        for cz in range(int(np.floor(2.0 * hw)) + 3):
+            jz = f[2] + cz
+            in_z = (jz >= 0) & (jz <= lz - 1)
+            if not in_z.any():
+                continue
+            for cy in (0, 1):
+                jy = f[1] + cy
+                in_zy = in_z & (jy >= 0) & (jy <= ly - 1)
+                for cx in (0, 1):
+                    jx = f[0] + cx
+                    inside = in_zy & (jx >= 0) & (jx <= lx - 1)
+                    if not inside.any():
+                        continue
+                    w = pair_weight(u[0], u[1], u[2], jx, jy, jz, pid, par)
+                    iz, iy, ix = (np.clip(v, 0, n - 1).astype(np.int64) for v, n in ((jz, lz), (jy, ly), (jx, lx)))
+                    nj = ns[iz, iy, ix]
+                    use = inside & (w > 0.0) & (nj > 0.0)
+                    if ms is not None:
+                        use &= ms[iz, iy, ix]
+                    if not use.any():
+                        continue
+                    with np.errstate(all="ignore"):
+                        acc = np.where(use, acc + (w * rs[:, iz, iy, ix].astype(np.float64)) / np.where(use, nj, 1.0), acc)
+    if x is not None:
+        sub = tuple(slice(s, s + n) for s, n in zip(start[::-1], shape))
+        xs = np.asarray(x).reshape((-1,) + hr_shape)[(slice(None),) + sub].astype(np.float64)
+        with np.errstate(all="ignore"):
+            acc = xs - float(tau) * acc
+    out = acc.astype(out_dtype)
+    return out[0] if single else out
+
+
+def counted(N, mask=None):
+    """1.0 where a sample counts, else 0.0 (float32): the residual whose adjoint is ``A^T 1``."""
+    c = np.asarray(N) > 0.0
+    if mask is not None:
+        c &= np.asarray(mask).reshape(c.shape) != 0
+    return c.astype(np.float32)
+
+
+def step_size(column_max):
+    """``tau = 1 / sum_s max_v (A_s^T 1)[v]``: the rows of A_s sum to 1, so ``||A_s||^2 <= ||A_s||_1 ||A_s||_inf`` is at
+    most the largest column sum.  The sum runs over the stacks in order, in float64."""
+    total = 0.0
+    for m in column_max:
+        total = total + float(m)
+    if not (total > 0.0 and np.isfinite(total)):
+        raise ValueError("no stack sample counts on this grid: nothing to reconstruct from")
+    return 1.0 / total
+
+
+def sr_plan(geoms, fixed="ax", res=1.0, transforms=None, thickness=None):
+    """``(order, H, B list, rel_thickness list)``: the fixed stack first, then the others as ``geoms`` lists them; ``H`` the
+    fixed stack's isotropic grid; ``B[s] = index_affine(H, G_s, T_s)``; the thickness of each stack in units of its slice
+    spacing (``thickness``: mm, a number for all stacks or {name: mm}; default the slice spacing itself)."""
+    if fixed not in geoms:
+        raise ValueError(f"the fixed stack {fixed!r} is not among {list(geoms)}")
+    order = [fixed] + [o for o in geoms if o != fixed]
+    if not 1 <= len(order) <= MAX_STACKS:
+        raise ValueError(f"between 1 and {MAX_STACKS} stacks, got {len(order)}")
+    transforms = transforms or {}
+    unknown = [k for k in transforms if k not in order[1:]]
+    if unknown:
+        raise ValueError(f"transforms are given per moving stack {order[1:]}, got {unknown}")
+    lo = [_resample.as_geometry(geoms[o]) for o in order]
+    hi = _resample.isotropic_geometry(lo[0], res)
+    b = [_resample.index_affine(hi, g, transforms.get(o)) for o, g in zip(order, lo)]
+    rel = []
+    for o, g in zip(order, lo):
+        t = thickness.get(o) if isinstance(thickness, dict) else thickness
+        t = g.GetSpacing()[2] if t is None else float(t)
+        if not (t > 0.0 and np.isfinite(t)):
+            raise ValueError(f"the slice thickness must be finite and > 0, got {t!r} for {o!r}")
+        rel.append(t / g.GetSpacing()[2])
+    return order, hi, b, rel
+
+
+def initial_volume(stacks, geoms, order, hi, res, transforms):
+    """``x_0``: the averaged merge when the stacks are exactly ax, cor and sag, else the fixed stack's own linear resample."""
+    if sorted(order) == sorted(_resample.ORIENTATIONS):
+        return _resample.reconstruct(stacks, geoms, order[0], res, transforms)[0]
+    g = _resample.as_geometry(geoms[order[0]], np.asarray(stacks[order[0]]).shape[-3:])
+    return _resample.resample(np.asarray(stacks[order[0]], np.float32), _resample.index_affine(hi, g), hi.shape)
+
+
+def iterate(x, y, N, B, profile, rels, tau, weight, prox_iter, masks=None, out_dtype=np.float32):
+    """One proximal-gradient step on ``x`` ``(n, Z, Y, X)``: residuals of every stack, the update ``z``, the TV prox."""
+    r = [forward(x, B[s], y[s].shape[-3:], profile, rels[s], y=y[s], mask=None if masks is None else masks[s],
+                 out_dtype=out_dtype)[0] for s in range(len(y))]
+    z = adjoint(r, N, B, profile, rels, x.shape[-3:], masks=masks, x=x, tau=tau, out_dtype=out_dtype)
+    if not weight > 0.0:
+        return z
+    if np.dtype(out_dtype) == np.float32:
+        return _tv.denoise_tv(z, tau * weight, eps=0.0, max_iter=prox_iter, dims=3, precision="f32")[0]
+    return np.stack([_tv.tv_problem(v, tau * weight, 0.0, prox_iter, np.float64)[0] for v in z])
+
+
+def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thickness=None, profile="box",
+                   weight=DEFAULT_WEIGHT, n_iter=DEFAULT_N_ITER, prox_iter=DEFAULT_PROX_ITER, stack_masks=None, x0=None,
+                   return_info=False, out_dtype=np.float32):
+    """The whole reconstruction on the host, argument for argument ``t2map.reconstruct_sr``.  Returns ``(x, Geometry of H)``
+    and with ``return_info`` also ``{"tau", "N", "column_max"}``."""
+    if not (float(weight) >= 0.0 and np.isfinite(weight)) or int(n_iter) < 0 or int(prox_iter) < 1:
+        raise ValueError("weight must be finite and >= 0, n_iter >= 0, prox_iter >= 1")
+    pid = _profile_id(profile)
+    names = [o for o in geoms if o in stacks]
+    shapes = {o: np.asarray(stacks[o]).shape for o in names}
+    geoms = {o: _resample.as_geometry(geoms[o], shapes[o][-3:]) for o in names}
+    order, hi, B, rels = sr_plan(geoms, fixed, res, transforms, thickness)
+    y = [_volumes(np.asarray(stacks[o], np.float32))[0] for o in order]
+    if len({len(v) for v in y}) != 1:
+        raise ValueError(f"the stacks differ in their number of echoes: {shapes}")
+    masks = None if stack_masks is None else [stack_masks.get(o) for o in order]
+    N = [forward(None, B[s], y[s].shape[-3:], pid, rels[s], hr_shape=hi.shape)[1] for s in range(len(y))]
+    col = [adjoint([counted(N[s], None if masks is None else masks[s])], [N[s]], [B[s]], pid, [rels[s]], hi.shape,
+                   masks=None if masks is None else [masks[s]], out_dtype=out_dtype) for s in range(len(y))]
+    col_max = [v.max() for v in col]
+    tau = step_size(col_max)
+    x = initial_volume(stacks, geoms, order, hi, res, transforms) if x0 is None else np.asarray(x0)
+    x = x.reshape((-1,) + hi.shape).astype(out_dtype)
+    if len(x) != len(y[0]):
+        raise ValueError("x0 does not have the stacks' number of echoes")
+    for _ in range(int(n_iter)):
+        x = iterate(x, y, N, B, pid, rels, tau, float(weight), int(prox_iter), masks, out_dtype)
+    if np.asarray(stacks[order[0]]).ndim == 3:
+        x = x[0]
+    if return_info:
+        return x, hi, {"tau": tau, "N": N, "column_max": col_max}
+    return x, hi

@@ -829,6 +829,9 @@ def parse_arguments(argv=None):
                         "with its defaults)")
     p.add_argument("--recon_register_echoes", action="store_true",
                    help="with --reconstruct: register every merged echo onto the first one (recon.py --register_echoes)")
+    from .recon import add_sr_arguments, sr_arguments
+
+    add_sr_arguments(p, "recon_")
     p.add_argument("--build_mask", choices=["phantom"], default=None,
                    help="build the masks of every echo and the vial labels on the GPU from the volumes about to be fitted "
                         "(after --reconstruct if given) instead of reading recon_1mm_mask / recon_1mm_label: phantom = the "
@@ -848,7 +851,7 @@ def parse_arguments(argv=None):
     args = p.parse_args(argv)
     args.reconstruct_args = None
     given = [f for f in ("--recon_fixed", "--recon_res", "--recon_transforms", "--recon_register", "--recon_register_echoes",
-                         "--recon_n4", "--recon_register_metric")
+                         "--recon_n4", "--recon_register_metric", "--recon_method")
              if any(a == f or a.startswith(f + "=") for a in (argv if argv is not None else sys.argv[1:]))]
     if given and not args.reconstruct:
         p.error(f"{given[0]} has no effect without --reconstruct")
@@ -872,6 +875,9 @@ def parse_arguments(argv=None):
             from .recon import N4_DEFAULTS
 
             args.reconstruct_args["n4"] = dict(N4_DEFAULTS)
+    sr = sr_arguments(p, args, "recon_", argv)  # after the check above: --recon_method needs --reconstruct
+    if sr is not None:
+        args.reconstruct_args["sr"] = sr
     args.build_mask_args = None
     if args.phantom_seeds is not None and not args.build_mask:
         p.error("--phantom_seeds has no effect without --build_mask phantom")

@@ -44,7 +44,7 @@ import time
 
 import numpy as np
 
-from . import _resample, t2map
+from . import _resample, _sr, t2map
 from .cli import (_sitk, build_phantom_subject, get_img_path, load_seeds, mask_dirname, phantom_labels_dirname, recon_dirname,
                   set_metadata)
 
@@ -111,12 +111,14 @@ def _metric_args(register_metric):
 
 
 def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False, transforms_dir=None, register=False,
-                 write_transforms=None, register_echoes=False, register_metric="corr", device=0):
+                 write_transforms=None, register_echoes=False, register_metric="corr", sr=None, device=0):
     """Stages 1 and 2 and the merge of the echoes of one batch (`acqs`: the fixed orientation's metadata row of every
     echo).  The transforms of an echo are read (``transforms_dir``) or found (``register``); echoes with the same
     transforms share a call, so without either the batch is one call.  ``register_echoes``: every merged echo but the
     first is registered onto the first and resampled onto it by one more single stage.  ``register_metric``: 'corr' or
-    'mattes', for both.  Returns ``(float32 CUDA tensor
+    'mattes', for both.  ``sr``: None for the averaged merge, or the keyword arguments of ``t2map.sr.reconstruct_sr``
+    (``--recon_method sr``: the super-resolution reconstruction, which starts from that merge and keeps the float result,
+    whatever ``integer_cast`` says).  Returns ``(float32 CUDA tensor
     (n, Z, Y, X), header, transforms per echo)``."""
     import torch
 
@@ -142,8 +144,11 @@ def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False
     merged = None
     for g in groups:
         part = stacks if len(g) == n else {o: stacks[o][g] for o in stacks}
-        out, header = t2map.reconstruct_stacks(part, geoms, fixed=fixed, res=res, transforms=per_echo[g[0]],
-                                               integer_cast=integer_cast, device=device)
+        if sr is not None:
+            out, header = t2map.sr.reconstruct_sr(part, geoms, fixed=fixed, res=res, transforms=per_echo[g[0]], device=device, **sr)
+        else:
+            out, header = t2map.reconstruct_stacks(part, geoms, fixed=fixed, res=res, transforms=per_echo[g[0]],
+                                                   integer_cast=integer_cast, device=device)
         if len(g) == n:
             merged = out
         else:
@@ -266,13 +271,14 @@ def n4_batch(sitk, bids_path, batch, stacks, n4, device=0):
 
 def process_recon(metadata, bids_path, *, fixed="ax", res=1.0, transforms_dir=None, write_resamp=False, denoise=True,
                   integer_cast=None, register=False, write_transforms=None, register_echoes=False, n4=None, write_n4=False,
-                  register_metric="corr", device=0):
+                  register_metric="corr", sr=None, device=0):
     """Reconstruct every echo of every (prj, sub, ses) of `metadata` that has the three orientations and write it.
     The echoes of a subject whose stacks share their geometry per orientation go through one call.  ``integer_cast``:
     None keeps the pixel type as the reference does (cast when the stacks are int16 on disk).  ``register`` /
     ``write_transforms`` / ``register_echoes`` / ``register_metric``: see :func:`merge_echoes`.  ``n4``: None, or the keyword arguments of
     :func:`correct_stacks` (``--n4``): the stacks are bias-corrected before step 1 and are no longer integers, so the
-    pixel type is not kept unless ``integer_cast`` says so; ``write_n4`` writes them under ``n4``.  Returns the paths
+    pixel type is not kept unless ``integer_cast`` says so; ``write_n4`` writes them under ``n4``.  ``sr``: see
+    :func:`merge_echoes` (same file names).  Returns the paths
     written under ``recon_1mm``."""
     import torch
 
@@ -307,7 +313,7 @@ def process_recon(metadata, bids_path, *, fixed="ax", res=1.0, transforms_dir=No
             merged, header, _ = merge_echoes(stacks, geoms, [it[1][fixed] for it in batch], fixed=fixed, res=res,
                                              integer_cast=cast, transforms_dir=transforms_dir, register=register,
                                              write_transforms=write_transforms, register_echoes=register_echoes,
-                                             register_metric=register_metric, device=device)
+                                             register_metric=register_metric, sr=sr, device=device)
             if denoise:
                 merged = t2map.denoise_tv(merged, out=merged)
             torch.cuda.synchronize(merged.device)
@@ -478,9 +484,9 @@ def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fix
 
 
 def reconstruct_subject(sitk, bids_path, sub_md, sub, ses, *, fixed="ax", res=1.0, transforms_dir=None, integer_cast=None,
-                        register=False, register_echoes=False, n4=None, register_metric="corr", device=0):
+                        register=False, register_echoes=False, n4=None, register_metric="corr", sr=None, device=0):
     """cli.py --reconstruct: the echoes of one (sub, ses) (`sub_md`: its metadata rows) reconstructed in memory.  Every
-    echo must have the three orientations and the echoes must share their grids.  ``n4``: as :func:`process_recon`.
+    echo must have the three orientations and the echoes must share their grids.  ``n4``, ``sr``: as :func:`process_recon`.
     Returns ``(volumes: list of (Z, Y, X) float32 arrays in EchoTime order, header)``."""
     echoes = [(float(te), {acq["ImageOrientationPatientSTR"]: acq for _, acq in te_md.iterrows()})
               for te, te_md in sub_md.groupby("EchoTime")]
@@ -495,9 +501,47 @@ def reconstruct_subject(sitk, bids_path, sub_md, sub, ses, *, fixed="ax", res=1.
         stacks, cast = n4_batch(sitk, bids_path, batches[0], stacks, n4, device), bool(integer_cast)
     merged, header, _ = merge_echoes(stacks, geoms, [it[1][fixed] for it in ready], fixed=fixed, res=res, integer_cast=cast,
                                      transforms_dir=transforms_dir, register=register, register_echoes=register_echoes,
-                                     register_metric=register_metric, device=device)
+                                     register_metric=register_metric, sr=sr, device=device)
     host = merged.cpu().numpy()
     return [host[i] for i in range(host.shape[0])], header
+
+
+SR_FLAGS = ("sr_weight", "sr_iter", "sr_profile", "sr_thickness")
+
+
+def add_sr_arguments(p, prefix):
+    """``--recon_method`` and the ``--sr_*`` flags (cli.py gives them the prefix ``recon_``)."""
+    p.add_argument("--recon_method", choices=["average", "sr"], default="average",
+                   help="average: resample every stack to the grid and average them (default, the reference's); sr: the "
+                        "TV-regularised super-resolution reconstruction, which models every thick slice as the slice-profile "
+                        "average of the 1 mm volume and inverts that model, starting from the average")
+    p.add_argument(f"--{prefix}sr_weight", type=float, default=_sr.DEFAULT_WEIGHT,
+                   help=f"sr: weight of the total variation, in intensity units (default {_sr.DEFAULT_WEIGHT}; 0: plain "
+                        "iterative back-projection)")
+    p.add_argument(f"--{prefix}sr_iter", type=int, default=_sr.DEFAULT_N_ITER,
+                   help=f"sr: proximal-gradient iterations (default {_sr.DEFAULT_N_ITER})")
+    p.add_argument(f"--{prefix}sr_profile", choices=sorted(_sr.PROFILES), default="box",
+                   help="sr: slice profile, box or a cubic B-spline of that full width at half maximum (default box)")
+    p.add_argument(f"--{prefix}sr_thickness", type=float, default=None, metavar="MM",
+                   help="sr: slice thickness [mm] (default: each stack's slice spacing)")
+
+
+def sr_arguments(p, args, prefix, argv):
+    """None for ``--recon_method average`` (an ``sr`` flag is then an error), else the keyword arguments of reconstruct_sr."""
+    given = [f"--{prefix}{f}" for f in SR_FLAGS
+             if any(a == f"--{prefix}{f}" or a.startswith(f"--{prefix}{f}=") for a in (argv if argv is not None else sys.argv[1:]))]
+    if args.recon_method != "sr":
+        if given:
+            p.error(f"{given[0]} has no effect without --recon_method sr")
+        return None
+    weight, n_iter, thick = (getattr(args, f"{prefix}sr_{k}") for k in ("weight", "iter", "thickness"))
+    if not (weight >= 0.0 and np.isfinite(weight)):
+        p.error(f"--{prefix}sr_weight must be a finite number >= 0")
+    if n_iter < 0:
+        p.error(f"--{prefix}sr_iter must be >= 0")
+    if thick is not None and not (thick > 0.0 and np.isfinite(thick)):
+        p.error(f"--{prefix}sr_thickness must be a positive number")
+    return {"weight": weight, "n_iter": n_iter, "profile": getattr(args, f"{prefix}sr_profile"), "thickness": thick}
 
 
 def parse_arguments(argv=None):
@@ -569,8 +613,10 @@ def parse_arguments(argv=None):
     p.add_argument("--n4_scale", type=float, default=N4_DEFAULTS["scale"],
                    help="with --n4: factor on the corrected stacks (default 1; run_biasfield_correction's 0.25 is --n4_scale 0.25)")
     p.add_argument("--write_n4", action="store_true", help="with --n4: also write the corrected stacks under derivatives/n4/")
+    add_sr_arguments(p, "")
     p.add_argument("--device", type=int, default=0, help="HIP device ordinal")
     args = p.parse_args(argv)
+    args.sr_args = sr_arguments(p, args, "", argv)
     given = [f for f in ("--n4_fwhm_cor", "--n4_fwhm", "--n4_echo", "--n4_scale", "--write_n4")
              if any(a == f or a.startswith(f + "=") for a in (argv if argv is not None else sys.argv[1:]))]
     if given and not args.n4:
@@ -632,7 +678,7 @@ def main(argv=None):
     process_recon(metadata, bids_path, fixed=args.fixed, res=args.res, transforms_dir=args.transforms,
                   write_resamp=args.write_resamp, denoise=not args.no_denoise, register=args.register,
                   write_transforms=args.write_transforms, register_echoes=args.register_echoes, n4=args.n4_args,
-                  write_n4=args.write_n4, register_metric=args.register_metric, device=args.device)
+                  write_n4=args.write_n4, register_metric=args.register_metric, sr=args.sr_args, device=args.device)
     if args.register_to_lf:
         process_register_to_lf(metadata, bids_path, write_transforms=args.write_transforms, device=args.device)
     if args.phantom_masks:

@@ -27,6 +27,7 @@ resampling, merge      ``_gpu_resample``   ``_resample``
 masks, phantom labels  ``_gpu_morph``      ``_morph``
 rigid registration     ``_gpu_register``   ``_register`` (and the optimizer, which is host code); here as ``register``
 atlas labels           ``_gpu_atlas``      ``_atlas`` (affine registration by the correlation ratio: ``register``); here as ``atlas``
+super-resolution       ``_gpu_sr``         ``_sr`` (operator, adjoint and the proximal-gradient loop; the prox is ``_tv``); here as ``sr``
 N4 bias field          ``_gpu_bias``       ``_bias`` (and the sharpening table, the refinement and the loop, which are host code); here as ``bias``
 =====================  ==================  ===========================================================
 
@@ -43,4 +44,5 @@ from . import _gpu_bias as bias  # noqa: F401  (a namespace: bias.n4_correct, bi
 from . import _gpu_register as register  # noqa: F401  (a namespace: register.register_rigid, .register_affine, ..)
 from ._gpu_resample import RECON_FORMS, reconstruct_stacks, resample_volume  # noqa: F401
 from ._gpu_roi import ROI_MAX_LABELS, RoiStats, dense_labels, roi_erode, roi_frame, roi_stats, roi_table  # noqa: F401
+from . import _gpu_sr as sr  # noqa: F401  (a namespace: sr.reconstruct_sr, sr.sr_forward, sr.sr_adjoint, sr.sr_box)
 from ._gpu_tv import denoise_tv, tv_params  # noqa: F401

@@ -445,6 +445,76 @@ int t2fit_reconstruct_dev(const float *const *stacks_dev, const int32_t *lo_size
                           const double *A2, float *out_dev, int n_vol, int flags, void *workspace_dev, size_t workspace_bytes,
                           void *stream);
 
+/* ---- Super-resolution reconstruction: the acquisition operator of a thick-slice stack and its adjoint -------------------
+ * The averaged merge above interpolates each stack to 1 mm and so keeps the blur of the slice thickness along three axes.
+ * Here a thick slice is modelled as the slice-profile average of the 1 mm volume and that model is inverted, per echo,
+ *   minimise over x:  1/2 sum_s ||A_s x - y_s||^2 + weight * TV(x)       (TV isotropic with forward differences)
+ * by proximal gradient from the averaged merge, x <- prox(x - tau sum_s A_s^T (A_s x - y_s)).  The prox of tau weight TV
+ * is t2fit_tv_denoise_dev with dims = 3, whose `weight` w stands for exactly one times TV (its fixed point minimises
+ * 1/2 ||u - f||^2 + w TV(u)), so it is called with w = tau * weight, eps = 0 and max_iter = the prox iterations;
+ * tau = 1 / sum_s max_v (A_s^T 1)[v] (the rows of A_s sum to 1, so ||A_s||^2 is at most its largest column sum).  The
+ * loop is host code over the two entry points below (fetal_t2mapping_amd/_gpu_sr.py); fetal_t2mapping_amd/_sr.py restates
+ * operator, adjoint and loop in numpy and the device results are bit-identical to it.  Additive to ABI 5.
+ *
+ * H is the high-resolution grid (hz, hy, hx), stack s a grid (lz, ly, lx), x fastest.  B (12 doubles, the index affine of
+ * t2fit_resample_dev) maps an integer H index v to the continuous stack index u = c(B, v), the expression and rounding
+ * order of c_a above.  The weight of the pair (sample j, voxel v) is separable in the stack's own axes,
+ *   w(j, v) = (tri(u_x - j_x) * tri(u_y - j_y)) * prof(u_z - j_z),   tri(d) = max(0, 1 - |d|),
+ * with thickness = slice thickness / slice spacing (> 0) and one of two polynomial profiles:
+ *   T2FIT_SR_PROFILE_BOX       prof(d) = 1 for -h <= d < h, else 0, h = thickness / 2 (half-open: abutting slices
+ *                              partition the axis)
+ *   T2FIT_SR_PROFILE_BSPLINE3  prof(d) = beta3(|d| / a), a = thickness / 1.4447034489287527 (the cubic B-spline's full
+ *                              width at half maximum, so the profile's is the thickness): with t = |d| / a,
+ *                              (2/3 - t t) + 0.5 ((t t) t) for t < 1, ((q q) q) / 6 with q = 2 - t for t < 2, else 0.
+ * Both directions form w from the very same u, so the operator and its adjoint hold the same bits.  In float64, one
+ * rounding per operation as written, a pair of weight 0 skipped:
+ *   N[j]         = sum_v w(j, v)                           v inside H, ascending (z, y, x)
+ *   (A x)[j]     = (sum_v w(j, v) x[v]) / N[j]             same order; x widened to float64
+ *   a sample counts iff N[j] > 0 and its mask byte (when a mask is given) is not 0
+ *   r[j]         = (A x)[j] - y[j] if the sample counts (just (A x)[j] without y), else 0;  rounded to float32 once
+ *   g[v]         = sum_s sum_j (w_s(j, v) r_s[j]) / N_s[j]   stacks in order, then the samples that count in ascending
+ *                                                            (z, y, x), one accumulator
+ *   out[v]       = g[v] (x_dev NULL), or x[v] - tau g[v];  rounded to float32 once
+ * The forward kernel looks for its voxels in the box |v_a - floor(c(Binv, j)_a + 0.5)| <= radius[a]; the box only has to
+ * cover the support, the result does not depend on it. */
+#define T2FIT_SR_PROFILE_BOX 0
+#define T2FIT_SR_PROFILE_BSPLINE3 1
+#define T2FIT_SR_MAX_STACKS 6
+
+/* Host arithmetic, no device: the inverse Binv[12] of B (by cofactors) and radius[3] (x, y, z) for supports of half-widths
+ * half[3] (x, y, z) in stack-index units -- (1, 1, h) for the box, (1, 1, 2 a) for the B-spline:
+ *   radius[a] = ceil(sum_b |Binv[4a + b]| half[b]) + 1
+ * (the sum bounds the support around the exact preimage, 1/2 goes to the rounded centre, the rest to rounding).  Refuses
+ * NULL pointers, non-finite entries, half-widths <= 0, a singular B (determinant 0 or a reach beyond 2^20 voxels). */
+int t2fit_sr_plan_host(const double *B, const double *half, double *Binv, int32_t *radius);
+
+/* Bytes of one buffer that holds what a loop over the two calls below keeps: up(4 n_vol |H|) for the update z plus, per
+ * stack, up(8 |L_s|) for N_s and up(4 n_vol |L_s|) for r_s, up(v) = v rounded up to 256.  lo_size: (nz, ny, nx) per stack.
+ * Plain arithmetic, no device; refuses n_stacks outside 1 .. T2FIT_SR_MAX_STACKS, sizes < 1 and more than 2^40 elements. */
+int t2fit_sr_workspace_bytes(int n_stacks, const int32_t *lo_size, int hz, int hy, int hx, int n_vol, size_t *bytes);
+
+/* One stack forward: out_dev [n_vol][lz][ly][lx] = r above from x_dev [n_vol][hz][hy][hx] and y_dev (same layout as
+ * out_dev, or NULL for A x itself); mask_dev uint8 [lz][ly][lx] or NULL; N_dev float64 [lz][ly][lx] receives N, or NULL.
+ * x_dev = out_dev = NULL with N_dev: the weights only.  One thread per sample walks its box once per chunk of 4 echoes.
+ * Asynchronous on `stream`: one launch, no allocation, copy or synchronisation.  Checked before HIP is touched
+ * (T2FIT_E_INVALID and a message): NULL B / Binv / radius, nothing to write, x_dev without out_dev or the reverse, n_vol or a
+ * size < 1, more than 2^40 elements, non-finite B / Binv, a radius < 1, an unknown profile, thickness <= 0 or not finite,
+ * float pointers not aligned to 4 bytes (N_dev: 8), out_dev == x_dev. */
+int t2fit_sr_forward_dev(const float *x_dev, int hz, int hy, int hx, int n_vol, const double *B, const double *Binv,
+                         const int32_t *radius, int profile, double thickness, const float *y_dev, const uint8_t *mask_dev, int lz,
+                         int ly, int lx, float *out_dev, double *N_dev, void *stream);
+
+/* All stacks back: out_dev [n_vol][hz][hy][hx] = g, or x - tau g with x_dev (out_dev == x_dev is allowed).  r_dev, N_dev,
+ * mask_dev: HOST arrays of n_stacks device pointers (mask_dev or any of its entries may be NULL); lo_size 3, B 12, profile 1,
+ * thickness 1 entries per stack.  N_dev[s] is what t2fit_sr_forward_dev wrote.  One thread per voxel, every stack in one
+ * pass: 2 x 2 in-plane candidates times the floor(2 half-width) + 3 slices from floor(u_z - half-width) on.  Asynchronous on
+ * `stream`: one launch.  Checked before HIP is touched: NULL pointers (x_dev and masks excepted), n_stacks outside 1 ..
+ * T2FIT_SR_MAX_STACKS, sizes as above, non-finite B or tau, an unknown profile, thickness <= 0 or not finite, alignment as
+ * above, a residual that is out_dev. */
+int t2fit_sr_adjoint_dev(int n_stacks, const float *const *r_dev, const double *const *N_dev, const uint8_t *const *mask_dev,
+                         const int32_t *lo_size, const double *B, const int32_t *profile, const double *thickness,
+                         const float *x_dev, double tau, float *out_dev, int hz, int hy, int hx, int n_vol, void *stream);
+
 /* ---- Masks and phantom labels: binary morphology, hole filling, seed labels, relabelling ------------------------------
  * What the reference builds on the host before a fit can start (utils/qmri_utils.py): build_mask (:223-252),
  * build_phantom_masks (:591-623), build_phantom_labels_v2 (:868-933), build_mask_from_labels (:935-951) and the lookup of
