@@ -71,6 +71,7 @@ MORPH_F32, MORPH_I32, MORPH_U8 = 0, 1, 2
 SR_PROFILE_BOX, SR_PROFILE_BSPLINE3 = 0, 1
 SR_PROFILES = {"box": SR_PROFILE_BOX, "bspline3": SR_PROFILE_BSPLINE3}
 SR_MAX_STACKS = 6
+SR_SLICE_RECORD_BYTES = 208
 
 REGISTER_SUMS = 43
 REGISTER_MAX_BINS = 64
@@ -118,6 +119,13 @@ SYMBOLS = [
     ("t2fit_sr_adjoint_dev", C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32),
                                        C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double), _P, C.c_double, _P,
                                        C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    ("t2fit_sr_slice_table_bytes", C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
+    ("t2fit_sr_slice_table_host", C.c_int, [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, _P, C.c_size_t]),
+    ("t2fit_sr_slice_forward_dev", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_double, _P, _P, C.c_int, C.c_int,
+                                             C.c_int, _P, _P, _P]),
+    ("t2fit_sr_slice_adjoint_dev", C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_double), _P, C.c_double, _P, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, _P]),
     ("t2fit_morph_workspace_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     ("t2fit_binary_threshold_dev", C.c_int, [_P, C.c_int, C.c_int64, C.c_double, C.c_double, _P, _P]),
     ("t2fit_binary_morph_dev", C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -175,7 +183,9 @@ N4_SYMBOLS = ("t2fit_n4_workspace_bytes", "t2fit_n4_log_dev", "t2fit_n4_minmax_d
               "t2fit_n4_fit_dev", "t2fit_n4_field_dev", "t2fit_n4_apply_dev")
 MI_SYMBOLS = ("t2fit_register_joint_hist_dev", "t2fit_register_mi_workspace_bytes", "t2fit_register_mi_gradient_dev")
 SR_SYMBOLS = ("t2fit_sr_plan_host", "t2fit_sr_workspace_bytes", "t2fit_sr_forward_dev", "t2fit_sr_adjoint_dev")
-LOOKED_UP = ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS + MI_SYMBOLS + SR_SYMBOLS
+SR_SLICE_SYMBOLS = ("t2fit_sr_slice_table_bytes", "t2fit_sr_slice_table_host", "t2fit_sr_slice_forward_dev",
+                    "t2fit_sr_slice_adjoint_dev")
+LOOKED_UP = ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS + MI_SYMBOLS + SR_SYMBOLS + SR_SLICE_SYMBOLS
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

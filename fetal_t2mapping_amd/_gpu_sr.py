@@ -136,9 +136,124 @@ def sr_adjoint(r, N, B, profile, rel_thickness, hr_shape, *, masks=None, x=None,
     return out if is_t else out.cpu().numpy()
 
 
+# ---- a rigid pose per slice ----------------------------------------------------------------------------------------------
+def sr_slice_table(B_slices, profile="box", rel_thickness=1.0):
+    """The slice table of t2fit_sr_slice_table_host for a stack whose slice k has the affine ``B_slices[k]`` (``(lz, 3,
+    4)``): a uint8 numpy array of ``208 lz`` bytes (B, Binv, radii per slice; include/t2fit.h has the layout).  Host
+    arithmetic; refuses what t2fit_sr_plan_host refuses, for every slice."""
+    lib = require(*_abi.SR_SLICE_SYMBOLS)
+    b = np.ascontiguousarray(B_slices, np.float64)
+    if b.ndim != 3 or b.shape[1:] != (3, 4) or b.shape[0] < 1:
+        raise ValueError(f"one 3 x 4 affine per slice, (lz, 3, 4), got shape {b.shape}")
+    pid = _sr._profile_id(profile)
+    _sr.profile_params(pid, rel_thickness)
+    need = C.c_size_t(0)
+    check(lib.t2fit_sr_slice_table_bytes(len(b), C.byref(need)))
+    table = np.zeros(need.value, np.uint8)
+    check(lib.t2fit_sr_slice_table_host(len(b), b.ctypes.data_as(C.POINTER(C.c_double)), pid, float(rel_thickness),
+                                        table.ctypes.data_as(C.c_void_p), need.value))
+    return table
+
+
+def _table(table, dev, lz):
+    """A slice table on the device (8-byte aligned: a fresh allocation); ``table``: bytes from :func:`sr_slice_table`."""
+    import torch
+
+    t = table if is_tensor(table) else torch.from_numpy(np.ascontiguousarray(table, np.uint8))
+    t = t.to(dev).contiguous().reshape(-1)
+    if t.dtype != torch.uint8 or t.numel() != _abi.SR_SLICE_RECORD_BYTES * lz:
+        raise ValueError(f"a slice table of {lz} slices is {_abi.SR_SLICE_RECORD_BYTES * lz} bytes of uint8")
+    return t
+
+
+def _forward_slices(lib, x, hr_shape, n_vol, table, pid, rel, y, mask, lr_shape, out, n_out):
+    """Queue t2fit_sr_slice_forward_dev on flat device tensors (None: NULL)."""
+    ptr = lambda t: None if t is None else t.data_ptr()
+    check(lib.t2fit_sr_slice_forward_dev(ptr(x), *hr_shape, n_vol, table.data_ptr(), pid, float(rel), ptr(y), ptr(mask), *lr_shape,
+                                         ptr(out), ptr(n_out), current_stream()))
+
+
+def _adjoint_slices(lib, r, n_list, masks, tables, lr_shapes, pids, rels, x, tau, out, hr_shape, n_vol):
+    """Queue t2fit_sr_slice_adjoint_dev on flat device tensors; ``masks`` is a list that may hold None."""
+    n_s = len(r)
+    ptrs = lambda ts: (C.c_void_p * n_s)(*[None if t is None else t.data_ptr() for t in ts])
+    check(lib.t2fit_sr_slice_adjoint_dev(n_s, ptrs(r), ptrs(n_list), ptrs(masks), ptrs(tables),
+                                         (C.c_int32 * (3 * n_s))(*[v for s in lr_shapes for v in s]), (C.c_int32 * n_s)(*pids),
+                                         _doubles(rels), None if x is None else x.data_ptr(), float(tau), out.data_ptr(), *hr_shape,
+                                         n_vol, current_stream()))
+
+
+def sr_forward_slices(x, B_slices, lr_shape, *, profile="box", rel_thickness=1.0, y=None, mask=None, hr_shape=None, device=0):
+    """:func:`sr_forward` with an affine per slice (``B_slices``: ``(lz, 3, 4)``), as :func:`_sr.forward_slices` defines it,
+    bit for bit: sample ``j`` takes its weights from ``B_slices[j_z]``."""
+    import torch
+
+    lib = require(*_abi.SR_SLICE_SYMBOLS)
+    pid = _sr._profile_id(profile)
+    lr_shape = tuple(int(v) for v in lr_shape)
+    if len(lr_shape) != 3:
+        raise ValueError("lr_shape is (Z, Y, X)")
+    table = sr_slice_table(_sr._slice_affine_list(B_slices, lr_shape[0]), pid, rel_thickness)
+    if x is None:
+        if hr_shape is None:
+            raise ValueError("the weights alone (x=None) need hr_shape")
+        shape, is_t = (1,) + tuple(int(v) for v in hr_shape), False
+    else:
+        shape, is_t = _shape4(x, "x"), is_tensor(x)
+    n_vol, n_l = shape[0], int(np.prod(lr_shape))
+    dev = pick_device((x, y, mask), device)
+    with torch.cuda.device(dev):
+        xt = None if x is None else flat(x, dev)
+        yt = None if y is None else flat(y, dev, n_vol * n_l, "y")
+        mt = _mask(mask, dev, n_l)
+        tt = _table(table, dev, lr_shape[0])
+        n_out = torch.empty(lr_shape, dtype=torch.float64, device=dev)
+        out = None if x is None else torch.empty((n_vol,) + lr_shape, dtype=torch.float32, device=dev)
+        _forward_slices(lib, xt, shape[-3:], n_vol, tt, pid, rel_thickness, yt, mt, lr_shape, out, n_out)
+        release(xt, yt, mt, tt)
+    if out is not None and len(x.shape) == 3:
+        out = out[0]
+    host = (lambda t: t) if is_t else (lambda t: None if t is None else t.cpu().numpy())
+    return host(out), host(n_out)
+
+
+def sr_adjoint_slices(r, N, B_slices, profile, rel_thickness, hr_shape, *, masks=None, x=None, tau=0.0, device=0):
+    """:func:`sr_adjoint` with an affine per slice (``B_slices[s]``: ``(lz_s, 3, 4)``), as :func:`_sr.adjoint_slices` defines
+    it, bit for bit: within a stack every slice in ascending index, culled per tile of voxels on the device."""
+    import torch
+
+    lib = require(*_abi.SR_SLICE_SYMBOLS)
+    n_s = len(r)
+    if not 1 <= n_s <= _abi.SR_MAX_STACKS or len(N) != n_s or len(B_slices) != n_s:
+        raise ValueError(f"between 1 and {_abi.SR_MAX_STACKS} stacks with one N and one list of slice affines each")
+    pids = [_sr._profile_id(p) for p in ([profile] * n_s if isinstance(profile, (str, int)) else profile)]
+    rels = [float(v) for v in ([rel_thickness] * n_s if np.ndim(rel_thickness) == 0 else rel_thickness)]
+    masks = [None] * n_s if masks is None else list(masks)
+    shapes = [_shape4(v, "a residual") for v in r]
+    if len({s[0] for s in shapes}) != 1:
+        raise ValueError("the residuals differ in their number of volumes")
+    tables = [sr_slice_table(_sr._slice_affine_list(b, s[-3]), p, t) for b, s, p, t in zip(B_slices, shapes, pids, rels)]
+    n_vol = shapes[0][0]
+    hr_shape = tuple(int(v) for v in hr_shape)
+    is_t = is_tensor(r[0])
+    dev = pick_device(list(r) + [x], device)
+    with torch.cuda.device(dev):
+        rt = [flat(v, dev) for v in r]
+        nt = [flat(v, dev, int(np.prod(s[-3:])), "N", dtype="float64") for v, s in zip(N, shapes)]
+        mt = [_mask(m, dev, int(np.prod(s[-3:]))) for m, s in zip(masks, shapes)]
+        tt = [_table(t, dev, s[-3]) for t, s in zip(tables, shapes)]
+        xt = None if x is None else flat(x, dev, n_vol * int(np.prod(hr_shape)), "x")
+        out = torch.empty((n_vol,) + hr_shape, dtype=torch.float32, device=dev)
+        _adjoint_slices(lib, rt, nt, mt, tt, [s[-3:] for s in shapes], pids, rels, xt, tau, out, hr_shape, n_vol)
+        release(xt, *rt, *nt, *mt, *tt)
+    if len(r[0].shape) == 3:
+        out = out[0]
+    return out if is_t else out.cpu().numpy()
+
+
 def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thickness=None, profile="box",
                    weight=_sr.DEFAULT_WEIGHT, n_iter=_sr.DEFAULT_N_ITER, prox_iter=_sr.DEFAULT_PROX_ITER, stack_masks=None,
-                   x0=None, return_info=False, device=0):
+                   x0=None, return_info=False, device=0, slice_transforms=None):
     """TV-regularised super-resolution reconstruction of 1 to 6 thick-slice stacks on the GPU.  Each slice is modelled as
     the slice-profile average of the ``res`` mm volume x on the ``fixed`` stack's isotropic grid, and per echo
 
@@ -150,7 +265,11 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
     iterative back-projection).  ``stacks`` / ``geoms``: {name: float32 ``(nTE, Z, Y, X)`` or ``(Z, Y, X)``} and their
     geometries; ``transforms``: {moving stack: 4 x 4, fixed point -> moving point}; ``thickness``: slice thickness in mm, one
     number or {name: mm} (default: the slice spacing); ``profile``: ``'box'`` or ``'bspline3'``; ``stack_masks``: {name: the
-    samples that count, ``(Z, Y, X)``}.
+    samples that count, ``(Z, Y, X)``}.  ``slice_transforms``: {stack name: ``(lz, 4, 4)``}, a rigid pose per slice (fixed
+    point -> stack point) that takes the place of the stack's transform for that slice; the fixed stack may have an entry,
+    stacks without one carry their stack transform on every slice.  Then the normalisers, the step size and the loop run on
+    the slice operators (:func:`sr_forward_slices`, :func:`sr_adjoint_slices`) and ``x0`` stays the merge; None takes the
+    stack-wise path.
     Returns ``(echoes, header)`` like :func:`reconstruct_stacks`: a float32 CUDA tensor ``(nTE, Z, Y, X)`` and a
     ``nifti.Image`` over an empty array with the grid's geometry; with ``return_info`` also ``{"tau", "column_max", "N"}``.
     The step size is read back once before the loop (one synchronisation); the loop itself queues 3 + stacks launch groups
@@ -159,7 +278,7 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
 
     from . import nifti
 
-    lib = require(*(_abi.SR_SYMBOLS + _abi.TV_SYMBOLS))
+    lib = require(*(_abi.SR_SYMBOLS + _abi.TV_SYMBOLS + (() if slice_transforms is None else _abi.SR_SLICE_SYMBOLS)))
     if not (float(weight) >= 0.0 and np.isfinite(weight)) or int(n_iter) < 0 or int(prox_iter) < 1:
         raise ValueError("weight must be finite and >= 0, n_iter >= 0, prox_iter >= 1")
     pid = _sr._profile_id(profile)
@@ -172,7 +291,11 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
     order, hi, B, rels = _sr.sr_plan(g, fixed, res, transforms, thickness)
     n_s, n_vol, hr_shape = len(order), shapes[order[0]][0], hi.shape
     lr_shapes = [shapes[o][-3:] for o in order]
-    boxes = [sr_box(B[s], pid, rels[s]) for s in range(n_s)]
+    if slice_transforms is None:
+        boxes, tables = [sr_box(B[s], pid, rels[s]) for s in range(n_s)], None
+    else:
+        slices = _sr.slice_plan(order, hi, g, B, lr_shapes, slice_transforms)
+        boxes, tables = None, [sr_slice_table(slices[s], pid, rels[s]) for s in range(n_s)]
     dev = pick_device([stacks[o] for o in order], device)
     lo_size = (C.c_int32 * (3 * n_s))(*[v for s in lr_shapes for v in s])
     need = C.c_size_t(0)
@@ -203,13 +326,29 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
             N.append(carve(8 * int(np.prod(s)), torch.float64))
             r.append(carve(4 * n_vol * int(np.prod(s)), torch.float32))
         assert off - (base - ws.data_ptr()) == need.value
+        if tables is None:
+            def fwd(s, xs, nv, ys, ms, out, n_out):
+                _forward(lib, xs, hr_shape, nv, B[s], boxes[s], pid, rels[s], ys, ms, lr_shapes[s], out, n_out)
+
+            def adj(idx, rs, xs, step, out, nv):
+                _adjoint(lib, rs, [N[s] for s in idx], [masks[s] for s in idx], [lr_shapes[s] for s in idx], [B[s] for s in idx],
+                         [pid] * len(idx), [rels[s] for s in idx], xs, step, out, hr_shape, nv)
+        else:
+            tables = [_table(t, dev, lr_shapes[s][0]) for s, t in enumerate(tables)]  # uploaded once, reused across the loop
+
+            def fwd(s, xs, nv, ys, ms, out, n_out):
+                _forward_slices(lib, xs, hr_shape, nv, tables[s], pid, rels[s], ys, ms, lr_shapes[s], out, n_out)
+
+            def adj(idx, rs, xs, step, out, nv):
+                _adjoint_slices(lib, rs, [N[s] for s in idx], [masks[s] for s in idx], [tables[s] for s in idx],
+                                [lr_shapes[s] for s in idx], [pid] * len(idx), [rels[s] for s in idx], xs, step, out, hr_shape, nv)
         # the normalisers, then tau from the per-stack column sums A_s^T 1 (z and r_s serve as scratch)
         col_max = []
         for s in range(n_s):
-            _forward(lib, None, hr_shape, 1, B[s], boxes[s], pid, rels[s], None, None, lr_shapes[s], None, N[s])
+            fwd(s, None, 1, None, None, None, N[s])
             ones = r[s][:N[s].numel()]
             ones.copy_(((N[s] > 0) if masks[s] is None else (N[s] > 0) & (masks[s] != 0)).to(torch.float32))
-            _adjoint(lib, [ones], [N[s]], [masks[s]], [lr_shapes[s]], [B[s]], [pid], [rels[s]], None, 0.0, z, hr_shape, 1)
+            adj([s], [ones], None, 0.0, z, 1)
             col_max.append(z[:n_h].max())
         col_max = [float(v) for v in torch.stack(col_max).tolist()]  # the one read-back
         tau = _sr.step_size(col_max)
@@ -221,17 +360,17 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
         stream = current_stream()
         for _ in range(int(n_iter)):
             for s in range(n_s):
-                _forward(lib, x, hr_shape, n_vol, B[s], boxes[s], pid, rels[s], y[s], masks[s], lr_shapes[s], r[s], None)
+                fwd(s, x, n_vol, y[s], masks[s], r[s], None)
             if float(weight) > 0.0:
-                _adjoint(lib, r, N, masks, lr_shapes, B, [pid] * n_s, rels, x, tau, z, hr_shape, n_vol)
+                adj(range(n_s), r, x, tau, z, n_vol)
                 check(lib.t2fit_tv_denoise_dev(C.byref(par), z.data_ptr(), x.data_ptr(), n_vol, *hr_shape, tv_ptr, tv_need.value,
                                                None, None, stream))
             else:
-                _adjoint(lib, r, N, masks, lr_shapes, B, [pid] * n_s, rels, x, tau, x, hr_shape, n_vol)
+                adj(range(n_s), r, x, tau, x, n_vol)
         info = {"tau": tau, "column_max": col_max, "N": [n.clone().reshape(s) for n, s in zip(N, lr_shapes)]} if return_info else None
         if float(weight) > 0.0:
             release(tv_ws)
-        release(ws, *y, *[m for m in masks if m is not None])
+        release(ws, *y, *[m for m in masks if m is not None], *(tables or []))
     out = x.reshape((n_vol,) + hr_shape)
     header = nifti.Image(np.zeros((0, 0, 0), np.float32), hi.GetSpacing(), hi.GetOrigin(), hi.GetDirection())
     return (out, header, info) if return_info else (out, header)

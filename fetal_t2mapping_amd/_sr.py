@@ -15,7 +15,12 @@ integer index v of the high-resolution grid H to the continuous stack index ``u 
 that u, so the matrix and its transpose hold the same bits.  Sums are float64, one rounding per operation in the order
 written, candidates in ascending (z, y, x); a candidate of weight 0 is skipped, so the result does not depend on the
 candidate boxes, which only have to cover the support.  Host code for tests and baselines: the product path is the HIP
-kernel."""
+kernel.
+
+A stack acquired slice by slice from a moving subject has a rigid pose per slice: :func:`forward_slices`,
+:func:`adjoint_slices` and ``reconstruct_sr(slice_transforms=...)`` take an affine per slice (``(lz, 3, 4)``, from
+:func:`slice_affines`), sample ``j`` forming its weights from ``u = coord(B[j_z], v)``; the statement of
+t2fit_sr_slice_forward_dev / t2fit_sr_slice_adjoint_dev."""
 from __future__ import annotations
 
 import numpy as np
@@ -248,6 +253,211 @@ def adjoint(r, N, B, profile, rel_thickness, hr_shape, *, masks=None, x=None, ta
     return out[0] if single else out
 
 
+# ---- a rigid pose per slice ----------------------------------------------------------------------------------------------
+def slice_affines(hi, geom, slice_transforms):
+    """``(lz, 3, 4)``: ``B[k] = index_affine(hi, geom, slice_transforms[k])``, the index affine of slice k of the stack
+    ``geom`` whose pose is ``slice_transforms[k]`` (4 x 4, fixed point -> stack point)."""
+    g = _resample.as_geometry(geom)
+    t = np.asarray(slice_transforms, np.float64)
+    lz = int(g.GetSize()[2])
+    if t.shape != (lz, 4, 4):
+        raise ValueError(f"slice transforms must be (lz, 4, 4) = ({lz}, 4, 4), got shape {t.shape}")
+    if not np.all(np.isfinite(t)):
+        raise ValueError("slice transforms must be finite")
+    return np.stack([_resample.index_affine(hi, g, t[k]) for k in range(lz)])
+
+
+def compose_slice_transforms(stack_transform, motion, geom):
+    """``(lz, 4, 4)`` fixed point -> stack point: the stack's transform (4 x 4 or None) followed, for slice k, by the rigid
+    motion ``motion[k] = (rx, ry, rz [rad], tx, ty, tz [mm])`` in the convention of :func:`_register.compose`, applied about
+    the physical centre of slice k of ``geom``."""
+    from . import _register
+
+    g = _resample.as_geometry(geom)
+    nx, ny, lz = (int(v) for v in g.GetSize())
+    motion = np.asarray(motion, np.float64)
+    if motion.shape != (lz, 6) or not np.all(np.isfinite(motion)):
+        raise ValueError(f"motion must be finite (lz, 6) = ({lz}, 6), got shape {motion.shape}")
+    base = np.eye(4) if stack_transform is None else np.asarray(stack_transform, np.float64)
+    if base.shape != (4, 4) or not np.all(np.isfinite(base)):
+        raise ValueError("the stack transform must be a finite 4 x 4 matrix")
+    m, o = _resample._index_to_point(g)
+    out = np.empty((lz, 4, 4), np.float64)
+    for k in range(lz):
+        centre = o + m @ np.array([(nx - 1) / 2.0, (ny - 1) / 2.0, float(k)])
+        out[k] = _register.compose(motion[k], centre) @ base
+    return out
+
+
+def _slice_affine_list(B, lz):
+    b = np.asarray(B, np.float64)
+    if b.shape != (lz, 3, 4):
+        raise ValueError(f"one 3 x 4 affine per slice: expected shape ({lz}, 3, 4), got {b.shape}")
+    return b
+
+
+def forward_slices(x, B, lr_shape, profile="box", rel_thickness=1.0, *, y=None, mask=None, hr_shape=None, start=(0, 0, 0),
+                   shape=None, out_dtype=np.float32):
+    """:func:`forward` with an affine per slice, ``B`` ``(lz, 3, 4)``: sample ``j`` takes its weights from ``B[j_z]`` and
+    walks the box of :func:`plan_box` of that affine (here every slice walks the largest of the radii: the box only has to
+    cover the support).  The terms of a sample and their order are those of :func:`forward` with its slice's affine, so
+    equal affines give its bits."""
+    pid = _profile_id(profile)
+    par, hw = profile_params(pid, rel_thickness)
+    lr_shape = tuple(int(v) for v in lr_shape)
+    bs = _slice_affine_list(B, lr_shape[0])
+    if x is not None:
+        xv, single = _volumes(x)
+        hr_shape = xv.shape[-3:]
+    else:
+        xv, single = None, True
+    hz, hy, hx = (int(v) for v in hr_shape)
+    shape = lr_shape if shape is None else tuple(int(v) for v in shape)
+    ks = range(int(start[2]), int(start[2]) + shape[0])
+    plans = [plan_box(bs[k], (1.0, 1.0, hw)) for k in ks]
+    radius = [max(p[1][a] for p in plans) for a in range(3)]
+    b = np.stack([bs[k] for k in ks])[:, :, :, None, None]  # [slice of the box][row][column], broadcast over (y, x)
+    binv = np.stack([p[0] for p in plans])[:, :, :, None, None]
+    co = lambda m, a, ix, iy, iz: ((m[:, a, 0] * ix + m[:, a, 1] * iy) + m[:, a, 2] * iz) + m[:, a, 3]
+    jx, jy, jz = _grid(start, shape)
+    k = [np.broadcast_to(np.floor(co(binv, a, jx, jy, jz) + 0.5), shape) for a in range(3)]
+    n_sum = np.zeros(shape, np.float64)
+    acc = None if xv is None else np.zeros((len(xv),) + shape, np.float64)
+    for dz in range(-radius[2], radius[2] + 1):
+        vz = k[2] + dz
+        in_z = (vz >= 0) & (vz <= hz - 1)
+        if not in_z.any():
+            continue
+        for dy in range(-radius[1], radius[1] + 1):
+            vy = k[1] + dy
+            in_zy = in_z & (vy >= 0) & (vy <= hy - 1)
+            if not in_zy.any():
+                continue
+            for dx in range(-radius[0], radius[0] + 1):
+                vx = k[0] + dx
+                inside = in_zy & (vx >= 0) & (vx <= hx - 1)
+                if not inside.any():
+                    continue
+                w = pair_weight(co(b, 0, vx, vy, vz), co(b, 1, vx, vy, vz), co(b, 2, vx, vy, vz), jx, jy, jz, pid, par)
+                use = inside & (w > 0.0)
+                if not use.any():
+                    continue
+                n_sum = np.where(use, n_sum + w, n_sum)
+                if acc is not None:
+                    iz, iy, ix = (np.clip(v, 0, n - 1).astype(np.int64) for v, n in ((vz, hz), (vy, hy), (vx, hx)))
+                    with np.errstate(all="ignore"):
+                        acc = np.where(use, acc + w * xv[:, iz, iy, ix].astype(np.float64), acc)
+    if acc is None:
+        return None, n_sum
+    sub = tuple(slice(s, s + n) for s, n in zip(start[::-1], shape))
+    counts = n_sum > 0.0
+    if mask is not None:
+        counts &= np.asarray(mask).reshape(lr_shape)[sub] != 0
+    with np.errstate(all="ignore"):
+        out = acc / np.where(counts, n_sum, 1.0)
+        if y is not None:
+            out = out - np.asarray(y).reshape((-1,) + lr_shape)[(slice(None),) + sub].astype(np.float64)
+        out = np.where(counts, out, 0.0).astype(out_dtype)
+    return (out[0] if single else out), n_sum
+
+
+def adjoint_slices(r, N, B, profile, rel_thickness, hr_shape, *, masks=None, x=None, tau=0.0, start=(0, 0, 0), shape=None,
+                   out_dtype=np.float32):
+    """:func:`adjoint` with an affine per slice, ``B[s]`` ``(lz_s, 3, 4)``.  One float64 accumulator per voxel runs over the
+    stacks in order, within a stack over ALL slices in ascending index k (not position in space), within a slice over the
+    2 x 2 in-plane candidates ``(floor(u_y) + cy, floor(u_x) + cx)`` in ascending (cy, cx) with ``u = coord(B[s][k], v)``:
+    ``acc += (w * r[j]) / N[j]`` for the samples that count and have ``w > 0``.  Equal affines give :func:`adjoint`'s bits:
+    the non-zero terms and their order are the same."""
+    n_s = len(r)
+    if not 1 <= n_s <= MAX_STACKS:
+        raise ValueError(f"between 1 and {MAX_STACKS} stacks, got {n_s}")
+    profiles = [profile] * n_s if isinstance(profile, (str, int)) else list(profile)
+    rels = [rel_thickness] * n_s if np.ndim(rel_thickness) == 0 else list(rel_thickness)
+    masks = [None] * n_s if masks is None else list(masks)
+    hr_shape = tuple(int(v) for v in hr_shape)
+    shape = hr_shape if shape is None else tuple(int(v) for v in shape)
+    rv = [_volumes(v) for v in r]
+    single = rv[0][1]
+    n_vol = len(rv[0][0])
+    vx, vy, vz = _grid(start, shape)
+    acc = np.zeros((n_vol,) + shape, np.float64)
+    for s in range(n_s):
+        rs = rv[s][0]
+        lz, ly, lx = rs.shape[-3:]
+        pid = _profile_id(profiles[s])
+        par, _ = profile_params(pid, rels[s])
+        bs = _slice_affine_list(B[s], lz)
+        ns = np.asarray(N[s], np.float64).reshape(lz, ly, lx)
+        ms = None if masks[s] is None else np.asarray(masks[s]).reshape(lz, ly, lx) != 0
+        for k in range(lz):
+            with np.errstate(all="ignore"):
+                reached = prof(np.broadcast_to(_coord(bs[k], 2, vx, vy, vz), shape) - float(k), pid, par) > 0.0
+            if not reached.any():
+                continue  # every pair of this slice has weight 0
+            # the box of voxels the profile reaches: outside it every weight is 0 and the accumulator stays as it is
+            box = tuple(slice(int(np.argmax(m)), len(m) - int(np.argmax(m[::-1]))) for m in
+                        (reached.any(axis=(1, 2)), reached.any(axis=(0, 2)), reached.any(axis=(0, 1))))
+            gx, gy, gz = vx[:, :, box[2]], vy[:, box[1], :], vz[box[0], :, :]
+            sub_shape = tuple(b.stop - b.start for b in box)
+            part = acc[(slice(None),) + box]
+            with np.errstate(all="ignore"):
+                u = [np.broadcast_to(_coord(bs[k], a, gx, gy, gz), sub_shape) for a in range(3)]
+                f = [np.floor(u[0]), np.floor(u[1])]
+            for cy in (0, 1):
+                jy = f[1] + cy
+                in_y = (jy >= 0) & (jy <= ly - 1)
+                for cx in (0, 1):
+                    jx = f[0] + cx
+                    inside = in_y & (jx >= 0) & (jx <= lx - 1)
+                    if not inside.any():
+                        continue
+                    with np.errstate(all="ignore"):
+                        w = pair_weight(u[0], u[1], u[2], jx, jy, float(k), pid, par)
+                        iy, ix = (np.clip(np.where(inside, v, 0), 0, n - 1).astype(np.int64) for v, n in ((jy, ly), (jx, lx)))
+                    nj = ns[k, iy, ix]
+                    use = inside & (w > 0.0) & (nj > 0.0)
+                    if ms is not None:
+                        use &= ms[k, iy, ix]
+                    if not use.any():
+                        continue
+                    with np.errstate(all="ignore"):
+                        part = np.where(use, part + (w * rs[:, k, iy, ix].astype(np.float64)) / np.where(use, nj, 1.0), part)
+            acc[(slice(None),) + box] = part
+    if x is not None:
+        sub = tuple(slice(s, s + n) for s, n in zip(start[::-1], shape))
+        xs = np.asarray(x).reshape((-1,) + hr_shape)[(slice(None),) + sub].astype(np.float64)
+        with np.errstate(all="ignore"):
+            acc = xs - float(tau) * acc
+    out = acc.astype(out_dtype)
+    return out[0] if single else out
+
+
+def check_slice_transforms(slice_transforms, order, lr_shapes):
+    """``{stack name: (lz, 4, 4) float64}`` after the refusals: unknown names, wrong shapes, non-finite entries."""
+    unknown = [k for k in slice_transforms if k not in order]
+    if unknown:
+        raise ValueError(f"slice transforms are given per stack {list(order)}, got {unknown}")
+    out = {}
+    for o, t in slice_transforms.items():
+        t = np.asarray(t, np.float64)
+        lz = int(lr_shapes[list(order).index(o)][0])
+        if t.shape != (lz, 4, 4):
+            raise ValueError(f"slice transforms of stack {o!r} must be (lz, 4, 4) = ({lz}, 4, 4), got shape {t.shape}")
+        if not np.all(np.isfinite(t)):
+            raise ValueError(f"slice transforms of stack {o!r} have a non-finite entry")
+        out[o] = t
+    return out
+
+
+def slice_plan(order, hi, geoms, B, lr_shapes, slice_transforms):
+    """The affines of every slice of every stack, a list over ``order`` of ``(lz, 3, 4)``: from the stack's entry of
+    ``slice_transforms`` where it has one, else the stack's own affine ``B[s]`` on every slice."""
+    st = check_slice_transforms(slice_transforms, order, lr_shapes)
+    return [slice_affines(hi, _resample.as_geometry(geoms[o]), st[o]) if o in st
+            else np.repeat(np.asarray(B[s], np.float64).reshape(1, 3, 4), int(lr_shapes[s][0]), axis=0)
+            for s, o in enumerate(order)]
+
+
 def counted(N, mask=None):
     """1.0 where a sample counts, else 0.0 (float32): the residual whose adjoint is ``A^T 1``."""
     c = np.asarray(N) > 0.0
@@ -313,11 +523,26 @@ def iterate(x, y, N, B, profile, rels, tau, weight, prox_iter, masks=None, out_d
     return np.stack([_tv.tv_problem(v, tau * weight, 0.0, prox_iter, np.float64)[0] for v in z])
 
 
+def iterate_slices(x, y, N, B, profile, rels, tau, weight, prox_iter, masks=None, out_dtype=np.float32):
+    """:func:`iterate` on the slice operators: ``B[s]`` is ``(lz_s, 3, 4)``."""
+    r = [forward_slices(x, B[s], y[s].shape[-3:], profile, rels[s], y=y[s], mask=None if masks is None else masks[s],
+                        out_dtype=out_dtype)[0] for s in range(len(y))]
+    z = adjoint_slices(r, N, B, profile, rels, x.shape[-3:], masks=masks, x=x, tau=tau, out_dtype=out_dtype)
+    if not weight > 0.0:
+        return z
+    if np.dtype(out_dtype) == np.float32:
+        return _tv.denoise_tv(z, tau * weight, eps=0.0, max_iter=prox_iter, dims=3, precision="f32")[0]
+    return np.stack([_tv.tv_problem(v, tau * weight, 0.0, prox_iter, np.float64)[0] for v in z])
+
+
 def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thickness=None, profile="box",
                    weight=DEFAULT_WEIGHT, n_iter=DEFAULT_N_ITER, prox_iter=DEFAULT_PROX_ITER, stack_masks=None, x0=None,
-                   return_info=False, out_dtype=np.float32):
+                   return_info=False, out_dtype=np.float32, slice_transforms=None):
     """The whole reconstruction on the host, argument for argument ``t2map.reconstruct_sr``.  Returns ``(x, Geometry of H)``
-    and with ``return_info`` also ``{"tau", "N", "column_max"}``."""
+    and with ``return_info`` also ``{"tau", "N", "column_max"}``.  ``slice_transforms``: ``{stack name: (lz, 4, 4)}``, a pose
+    per slice (fixed point -> stack point) in place of the stack's transform; the fixed stack may have an entry, stacks
+    without one carry their stack transform on every slice.  Then N, tau and the loop run on :func:`forward_slices` and
+    :func:`adjoint_slices`; ``x0`` stays the merge.  None: the stack-wise operators."""
     if not (float(weight) >= 0.0 and np.isfinite(weight)) or int(n_iter) < 0 or int(prox_iter) < 1:
         raise ValueError("weight must be finite and >= 0, n_iter >= 0, prox_iter >= 1")
     pid = _profile_id(profile)
@@ -329,9 +554,13 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
     if len({len(v) for v in y}) != 1:
         raise ValueError(f"the stacks differ in their number of echoes: {shapes}")
     masks = None if stack_masks is None else [stack_masks.get(o) for o in order]
-    N = [forward(None, B[s], y[s].shape[-3:], pid, rels[s], hr_shape=hi.shape)[1] for s in range(len(y))]
-    col = [adjoint([counted(N[s], None if masks is None else masks[s])], [N[s]], [B[s]], pid, [rels[s]], hi.shape,
-                   masks=None if masks is None else [masks[s]], out_dtype=out_dtype) for s in range(len(y))]
+    fwd, adj, step = forward, adjoint, iterate
+    if slice_transforms is not None:
+        B = slice_plan(order, hi, geoms, B, [v.shape[-3:] for v in y], slice_transforms)
+        fwd, adj, step = forward_slices, adjoint_slices, iterate_slices
+    N = [fwd(None, B[s], y[s].shape[-3:], pid, rels[s], hr_shape=hi.shape)[1] for s in range(len(y))]
+    col = [adj([counted(N[s], None if masks is None else masks[s])], [N[s]], [B[s]], pid, [rels[s]], hi.shape,
+               masks=None if masks is None else [masks[s]], out_dtype=out_dtype) for s in range(len(y))]
     col_max = [v.max() for v in col]
     tau = step_size(col_max)
     x = initial_volume(stacks, geoms, order, hi, res, transforms) if x0 is None else np.asarray(x0)
@@ -339,7 +568,7 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
     if len(x) != len(y[0]):
         raise ValueError("x0 does not have the stacks' number of echoes")
     for _ in range(int(n_iter)):
-        x = iterate(x, y, N, B, pid, rels, tau, float(weight), int(prox_iter), masks, out_dtype)
+        x = step(x, y, N, B, pid, rels, tau, float(weight), int(prox_iter), masks, out_dtype)
     if np.asarray(stacks[order[0]]).ndim == 3:
         x = x[0]
     if return_info:

@@ -92,6 +92,49 @@ def save_transforms(transforms_dir, acq, transforms):
     return paths
 
 
+def slice_transforms_path(transforms_dir, acq, orientation, echo=False):
+    """:func:`transform_path` with ``_slices`` before the extension: the rigid pose of every slice of stack `orientation`."""
+    return transform_path(transforms_dir, acq, orientation, echo)[:-len(".txt")] + "_slices.txt"
+
+
+def load_slice_transforms(transforms_dir, acq, geoms, fixed="ax"):
+    """{orientation: (lz, 4, 4)} for the files that exist under `transforms_dir` (None: no directory given), the fixed stack
+    included; lookup order as :func:`load_transforms`.  A file holds ``lz`` rows of 16 numbers, the 4 x 4 (fixed point ->
+    stack point) of each slice row-major; another row count than the stack's slice count is an error naming the file."""
+    out = {}
+    if not transforms_dir:
+        return out
+    for o in [fixed] + _resample.moving_order(fixed):
+        if o not in geoms:
+            continue
+        own = [slice_transforms_path(transforms_dir, acq, o, echo=True)] if "EchoTime" in acq else []
+        for path in own + [slice_transforms_path(transforms_dir, acq, o)]:
+            if os.path.exists(path):
+                m = np.atleast_2d(np.loadtxt(path, dtype=np.float64))
+                lz = int(_resample.as_geometry(geoms[o]).GetSize()[2])
+                if m.ndim != 2 or m.shape[1] != 16 or not np.all(np.isfinite(m)):
+                    raise ValueError(f"{path}: expected rows of 16 finite numbers (a 4 x 4 per slice, row-major)")
+                if m.shape[0] != lz:
+                    raise ValueError(f"{path}: {m.shape[0]} rows, but stack {o!r} has {lz} slices")
+                out[o] = m.reshape(lz, 4, 4)
+                break
+    return out
+
+
+def save_slice_transforms(transforms_dir, acq, slice_transforms):
+    """Write {orientation: (lz, 4, 4)} of the echo of `acq` where :func:`load_slice_transforms` reads it, one row of 16
+    numbers per slice, digits enough for the float64 to come back bit for bit.  Returns the paths."""
+    os.makedirs(transforms_dir, exist_ok=True)
+    paths = []
+    for o, m in slice_transforms.items():
+        m = np.asarray(m, np.float64)
+        if m.ndim != 3 or m.shape[1:] != (4, 4):
+            raise ValueError(f"slice transforms of {o!r} must be (lz, 4, 4), got shape {m.shape}")
+        paths.append(slice_transforms_path(transforms_dir, acq, o, echo=True))
+        np.savetxt(paths[-1], m.reshape(len(m), 16), fmt="%.17g")
+    return paths
+
+
 def register_stacks(stacks, geoms, *, fixed="ax", res=1.0, integer_cast=False, device=0, **register_args):
     """{moving orientation: 4 x 4} of one echo: every stack ``(Z, Y, X)`` is resampled to its own ``res`` mm grid (stage 1)
     and each moving volume ``H_m`` is registered onto the fixed one ``H_0`` (``t2map.register.register_rigid``)."""
@@ -118,7 +161,8 @@ def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False
     first is registered onto the first and resampled onto it by one more single stage.  ``register_metric``: 'corr' or
     'mattes', for both.  ``sr``: None for the averaged merge, or the keyword arguments of ``t2map.sr.reconstruct_sr``
     (``--recon_method sr``: the super-resolution reconstruction, which starts from that merge and keeps the float result,
-    whatever ``integer_cast`` says).  Returns ``(float32 CUDA tensor
+    whatever ``integer_cast`` says); its entry ``slice_transforms_dir`` (``--sr_slice_transforms``) names a directory of
+    :func:`load_slice_transforms` files, read per echo and passed on as ``slice_transforms``.  Returns ``(float32 CUDA tensor
     (n, Z, Y, X), header, transforms per echo)``."""
     import torch
 
@@ -133,10 +177,15 @@ def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False
                 save_transforms(write_transforms, acq, t)
     else:
         per_echo = [load_transforms(transforms_dir, acq, fixed) for acq in acqs]
+    slices_dir = None
+    if sr is not None and "slice_transforms_dir" in sr:
+        sr = dict(sr)
+        slices_dir = sr.pop("slice_transforms_dir")
+    per_slice = [load_slice_transforms(slices_dir, acq, geoms, fixed) for acq in acqs]
     groups = []
     for i in range(n):
         for g in groups:
-            if _same_transforms(per_echo[g[0]], per_echo[i]):
+            if _same_transforms(per_echo[g[0]], per_echo[i]) and _same_transforms(per_slice[g[0]], per_slice[i]):
                 g.append(i)
                 break
         else:
@@ -145,7 +194,9 @@ def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False
     for g in groups:
         part = stacks if len(g) == n else {o: stacks[o][g] for o in stacks}
         if sr is not None:
-            out, header = t2map.sr.reconstruct_sr(part, geoms, fixed=fixed, res=res, transforms=per_echo[g[0]], device=device, **sr)
+            poses = {"slice_transforms": per_slice[g[0]]} if slices_dir else {}
+            out, header = t2map.sr.reconstruct_sr(part, geoms, fixed=fixed, res=res, transforms=per_echo[g[0]], device=device, **sr,
+                                                  **poses)
         else:
             out, header = t2map.reconstruct_stacks(part, geoms, fixed=fixed, res=res, transforms=per_echo[g[0]],
                                                    integer_cast=integer_cast, device=device)
@@ -506,7 +557,7 @@ def reconstruct_subject(sitk, bids_path, sub_md, sub, ses, *, fixed="ax", res=1.
     return [host[i] for i in range(host.shape[0])], header
 
 
-SR_FLAGS = ("sr_weight", "sr_iter", "sr_profile", "sr_thickness")
+SR_FLAGS = ("sr_weight", "sr_iter", "sr_profile", "sr_thickness", "sr_slice_transforms")
 
 
 def add_sr_arguments(p, prefix):
@@ -524,6 +575,10 @@ def add_sr_arguments(p, prefix):
                    help="sr: slice profile, box or a cubic B-spline of that full width at half maximum (default box)")
     p.add_argument(f"--{prefix}sr_thickness", type=float, default=None, metavar="MM",
                    help="sr: slice thickness [mm] (default: each stack's slice spacing)")
+    p.add_argument(f"--{prefix}sr_slice_transforms", default=None, metavar="DIR",
+                   help="sr: a rigid pose per slice, for stacks of a subject that moved between slices: "
+                        "<DIR>/<sub>_<ses>_[te-<ms>_]<orientation>_slices.txt with one row of 16 numbers per slice, the 4 x 4 "
+                        "(fixed point -> stack point, LPS millimetres) row-major; stacks without a file keep their stack transform")
 
 
 def sr_arguments(p, args, prefix, argv):
@@ -541,7 +596,11 @@ def sr_arguments(p, args, prefix, argv):
         p.error(f"--{prefix}sr_iter must be >= 0")
     if thick is not None and not (thick > 0.0 and np.isfinite(thick)):
         p.error(f"--{prefix}sr_thickness must be a positive number")
-    return {"weight": weight, "n_iter": n_iter, "profile": getattr(args, f"{prefix}sr_profile"), "thickness": thick}
+    out = {"weight": weight, "n_iter": n_iter, "profile": getattr(args, f"{prefix}sr_profile"), "thickness": thick}
+    slices_dir = getattr(args, f"{prefix}sr_slice_transforms")
+    if slices_dir is not None:
+        out["slice_transforms_dir"] = slices_dir
+    return out
 
 
 def parse_arguments(argv=None):

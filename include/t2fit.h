@@ -515,6 +515,59 @@ int t2fit_sr_adjoint_dev(int n_stacks, const float *const *r_dev, const double *
                          const int32_t *lo_size, const double *B, const int32_t *profile, const double *thickness,
                          const float *x_dev, double tau, float *out_dev, int hz, int hy, int hx, int n_vol, void *stream);
 
+/* ---- Super-resolution with a rigid pose per slice ---------------------------------------------------------------------
+ * A stack acquired slice by slice from a moving subject is sharp within each slice, but every slice has its own pose.
+ * Slice k of stack s then has its own index affine B[s][k] (12 doubles, H index -> continuous stack index) and the weight of
+ * the pair (sample j = (j_x, j_y, j_z), voxel v) becomes
+ *   w(j, v) = (tri(u_x - j_x) * tri(u_y - j_y)) * prof(u_z - j_z),     u = c(B[s][j_z], v)
+ * Nothing else of the definition above changes: tri, both profiles and the half-open box, N[j] summed over v in ascending
+ * (z, y, x) with zero weights skipped, the forward value (sum w x) / N - y, what "counts" means, float64 sums with one
+ * rounding per operation and no atomics.  The adjoint's one accumulator per voxel runs over the stacks in order, within a
+ * stack over ALL slices in ascending k (by index, not by position in space), and within a slice over the 2 x 2 in-plane
+ * candidates (floor(u_y) + cy, floor(u_x) + cx) in ascending (cy, cx) with u from that slice's affine:
+ *   acc += (w * r[j]) / N[j]   for the samples that count and have w > 0;   out = acc, or x - tau acc.
+ * If every slice of a stack carries the stack's own affine, N, forward, adjoint and update are bit-identical to
+ * t2fit_sr_forward_dev / t2fit_sr_adjoint_dev: the non-zero terms and their order are the same.
+ * fetal_t2mapping_amd/_sr.py (forward_slices, adjoint_slices) restates both in numpy; same bits.  Additive to ABI 5.
+ *
+ * An affine per slice does not fit a kernel's argument segment, so the affines travel as a table in device memory: one
+ * record of T2FIT_SR_SLICE_RECORD_BYTES = 208 bytes per slice, slice k at byte 208 k,
+ *   bytes   0 ..  95   B[12]     float64, the slice's index affine
+ *   bytes  96 .. 191   Binv[12]  float64, its inverse as t2fit_sr_plan_host forms it
+ *   bytes 192 .. 203   radius[3] int32 (x, y, z), of t2fit_sr_plan_host for half-widths (1, 1, the profile's)
+ *   bytes 204 .. 207   0
+ * t2fit_sr_slice_table_host packs it on the host (no device; it validates every slice exactly as t2fit_sr_plan_host does
+ * -- NULL, non-finite entries, a singular affine, a reach beyond 2^20 voxels -- before it writes a byte, and refuses
+ * lz < 1, an unknown profile, a bad thickness and a buffer smaller than t2fit_sr_slice_table_bytes says); the caller
+ * uploads the blob once and reuses it across the loop.  The table is data, not a trusted argument: whatever it holds, both
+ * kernels terminate and stay inside their buffers (ranges are clamped to the grid; a non-finite centre or coordinate gives
+ * an empty range). */
+#define T2FIT_SR_SLICE_RECORD_BYTES 208
+int t2fit_sr_slice_table_bytes(int lz, size_t *bytes);
+int t2fit_sr_slice_table_host(int lz, const double *B /* [lz][12] */, int profile, double thickness, void *table_host,
+                              size_t bytes);
+
+/* t2fit_sr_forward_dev with table_dev (device memory, lz records, aligned to 8 bytes) in place of B / Binv / radius: sample
+ * j walks the box of radii radius[j_z] around floor(c(Binv[j_z], j) + 0.5).  A workgroup lies inside one slice, so the
+ * record is read once per wave.  Asynchronous on `stream`: one launch, no allocation, copy or synchronisation.  Checked
+ * before HIP is touched: as t2fit_sr_forward_dev, and table_dev NULL or not aligned to 8 bytes. */
+int t2fit_sr_slice_forward_dev(const float *x_dev, int hz, int hy, int hx, int n_vol, const void *table_dev, int profile,
+                               double thickness, const float *y_dev, const uint8_t *mask_dev, int lz, int ly, int lx,
+                               float *out_dev, double *N_dev, void *stream);
+
+/* t2fit_sr_adjoint_dev with table_dev, a HOST array of n_stacks device pointers to the stacks' tables, in place of B.  A
+ * workgroup owns a tile of 16 x 4 x 4 voxels.  Per stack, in passes of 256 slices, each lane bounds the tile's stack
+ * coordinates under one slice's affine (interval arithmetic on the tile's index box, widened by 2^-40 of the terms'
+ * magnitude for rounding) and keeps the slice iff the u_z bounds meet [k - half-width, k + half-width] and the u_x / u_y
+ * bounds meet [-1, lx] / [-1, ly]; the survivors are listed in ascending k and every lane walks the list, forming the pair
+ * weight from its own u.  The cull drops no slice that contributes and zero weights are skipped, so the result is the
+ * definition's.  Any number of slices.  Asynchronous on `stream`: one launch.  Checked before HIP is touched: as
+ * t2fit_sr_adjoint_dev, and a table pointer that is NULL or not aligned to 8 bytes. */
+int t2fit_sr_slice_adjoint_dev(int n_stacks, const float *const *r_dev, const double *const *N_dev,
+                               const uint8_t *const *mask_dev, const void *const *table_dev, const int32_t *lo_size,
+                               const int32_t *profile, const double *thickness, const float *x_dev, double tau, float *out_dev,
+                               int hz, int hy, int hx, int n_vol, void *stream);
+
 /* ---- Masks and phantom labels: binary morphology, hole filling, seed labels, relabelling ------------------------------
  * What the reference builds on the host before a fit can start (utils/qmri_utils.py): build_mask (:223-252),
  * build_phantom_masks (:591-623), build_phantom_labels_v2 (:868-933), build_mask_from_labels (:935-951) and the lookup of
