@@ -16,7 +16,9 @@ from ._lib import check
 class BootStats:
     """Bootstrap maps of one parameter, ``(Z, Y, X)`` float32: ``mean`` of the counted replicas, ``bias`` = mean - the
     fitted value, ``std`` (ddof = 1, NaN when fewer than two replicas count), ``ci_lo`` / ``ci_hi`` = numpy's default
-    percentiles at 100 alpha / 2 and 100 (1 - alpha / 2) (None when no interval was asked for).  Zeros outside the mask."""
+    percentiles at 100 alpha / 2 and 100 (1 - alpha / 2) (None when no interval was asked for).  Zeros outside the mask.
+    Where the fitted value is not finite (``maps=`` with T2 = +inf), ``mean``, ``std`` and the percentiles are still those
+    of the counted refits; only ``bias`` is then -inf or NaN."""
     mean: object
     bias: object
     std: object

@@ -128,6 +128,11 @@ __global__ __launch_bounds__(kBlock) void boot_synth_kernel(const SynthArgs a) {
 // Per masked voxel m (rank in the mask) and requested parameter p, about the original fitted value c: sum (x - c),
 // sum (x - c)^2 in float64 (shifted, so the variance does not cancel), min and max (all replicas equal <=> std = 0
 // exactly) and the count of replicas that count: status CONVERGED and every requested value finite.
+//
+// The shift is a device for the rounding, not part of the result: a fitted value that is not finite (T2 = +inf of a
+// flat signal, handed in as a map) still has finite refits, and their mean and std must not become inf - inf.  Such a
+// centre shifts by 0; a finite one by itself, bit for bit as before.  Both kernels use this one function.
+__device__ inline double boot_shift(float centre) { return isfinite(centre) ? (double)centre : 0.0; }
 struct AccumArgs {
   const int64_t* idx;
   int64_t n_masked;
@@ -161,7 +166,7 @@ __global__ __launch_bounds__(kBlock) void boot_accum_kernel(const AccumArgs a) {
   for (int p = 0; p < 3; ++p) {
     if (!a.rep[p]) continue;
     if (ok) {
-      const double d = (double)x[p] - (double)a.centre[p][v];
+      const double d = (double)x[p] - boot_shift(a.centre[p][v]);
       a.sum[p][m] += d;
       a.sumsq[p][m] += d * d;
       a.vmin[p][m] = n == 0 ? x[p] : fminf(a.vmin[p][m], x[p]);
@@ -238,7 +243,7 @@ __global__ __launch_bounds__(64) void boot_final_kernel(const FinalArgs a) {
   const int64_t mm = act ? m : 0;
   const int n = act ? a.n_ok[mm] : 0;
   const int64_t v = a.idx[mm];
-  const double c = (double)a.centre[v];
+  const double c = (double)a.centre[v], shift = boot_shift(a.centre[v]);
   const double nan = __longlong_as_double(0x7ff8000000000000LL);
   double dmean = nan, sd = nan;
   if (n >= 1) dmean = a.sum[mm] / (double)n;
@@ -259,8 +264,10 @@ __global__ __launch_bounds__(64) void boot_final_kernel(const FinalArgs a) {
     }
   }
   if (!act) return;
-  if (a.mean) a.mean[v] = (float)(c + dmean);
-  if (a.bias) a.bias[v] = (float)dmean;
+  const double mean = shift + dmean;
+  if (a.mean) a.mean[v] = (float)mean;
+  // a finite centre: the shifted mean is the bias, unrounded; otherwise mean - c by IEEE rules (-inf for c = +inf, NaN for NaN)
+  if (a.bias) a.bias[v] = (float)(shift == c ? dmean : mean - c);
   if (a.std) a.std[v] = (float)sd;
   if (a.ci_lo) a.ci_lo[v] = (float)lo;
   if (a.ci_hi) a.ci_hi[v] = (float)hi;

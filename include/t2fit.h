@@ -266,7 +266,11 @@ int t2fit_roi_stats_dev(const float *map_dev, const int32_t *roi_dev, int64_t n_
  * Zeros outside the mask.  With n_ok counted replicas of the voxel: mean and bias = mean - fitted value (NaN when
  * n_ok = 0), std with ddof = 1 (NaN when n_ok < 2), ci_lo / ci_hi = numpy's default ("linear") percentiles at
  * 100 alpha / 2 and 100 (1 - alpha / 2) of the counted replicas (NaN when n_ok = 0).  The call is in interval mode when
- * a ci_lo or ci_hi pointer of a requested parameter is set. */
+ * a ci_lo or ci_hi pointer of a requested parameter is set.
+ * A fitted value that is not finite (T2 = +inf of a flat signal, or NaN, in a map handed in) does not spoil the
+ * statistics of the replicas: mean, std and the percentiles are those of the counted refits, which are finite; only
+ * bias = mean - fitted value follows IEEE arithmetic (-inf for +inf, NaN for NaN).  Internally the sums are taken about
+ * the fitted value when it is finite and about 0 otherwise. */
 typedef struct t2fit_boot_maps {
   float *mean[3];
   float *bias[3];

@@ -169,3 +169,47 @@ def test_cli_bootstrap_flags_refusals_and_file_names(tmp_path):
         assert got == [t2.replace("_t2map_", f"_{tag}map_") for tag in R.BOOT_TAGS] and len(set(got)) == 5
         assert os.path.relpath(got[0], bids) == (f"{acq['prj']}/derivatives/recon_1mm_t2map/{acq['sub']}/{acq['ses']}/anat/"
                                                  f"{acq['sub']}_{acq['ses']}_recon_1mm_sim-7_T2stdmap_ada-{fit}.nii.gz")
+
+
+def test_crafted_bootstrap_case_has_every_count_ties_on_both_bounds_and_few_samples_near_zero():
+    """tests/boot_cases.py by its float64 statement alone (no device, no library): what the device tests rely on."""
+    import boot_cases as BC
+
+    t2, k, s, names = BC.maps()
+    assert t2.shape == BC.SHAPE and BC.N == 651 and BC.N % 4 and BC.N % 64
+    y, counted, near, t2_fit = BC.predict()
+    assert y.shape == (BC.R, 2, BC.N) and BC.R == 16
+    n = counted.sum(axis=0)
+    hist = np.bincount(n, minlength=BC.R + 1)
+    print("count histogram 0..R:", hist.tolist())
+    assert hist.size == BC.R + 1 and np.all(hist > 0)  # every count 0..R occurs
+    upper = int(np.sum(np.sum(t2_fit == BC.T2_BOUNDS[1], axis=0) >= 2))
+    lower = int(np.sum(np.sum(t2_fit == BC.T2_BOUNDS[0], axis=0) >= 2))
+    print(f"voxels with two or more counted refits on the T2 bound: upper {upper}, lower {lower}")
+    assert upper >= 50 and lower >= 10
+    flat = names.reshape(-1)
+    same = flat == "k1500_s0"  # the s = 0 class: every replica is the clean signal, and counts
+    assert same.sum() >= 10 and np.all(s.reshape(-1)[same] == 0.0) and np.all(n[same] == BC.R)
+    assert np.all(y[:, :, same] == y[:1, :, same]) and np.all(y[:, :, same] > 0.0)
+    for name in ("zero_s0", "t2_nan", "k_nan", "k_inf"):  # never count
+        assert (flat == name).sum() >= 3 and np.all(n[flat == name] == 0), name
+    for name in ("t2_inf_k60", "t2_inf_k2000", "t2_zero", "steep"):
+        assert (flat == name).sum() >= 3, name
+    assert np.all(n[flat == "t2_inf_k60"] >= 2) and np.all(n[flat == "steep"] == BC.R)
+    print(f"voxels with a sample within {BC.NEAR} s of zero: {int(near.sum())} of {BC.N}")
+    assert near.mean() <= 0.01
+    # voxels whose counted T2 refits are all equal while the shifted sums the kernel keeps round to a positive variance:
+    # only the min / max it keeps as well make their std exactly 0
+    x = np.where(counted, t2_fit, np.nan)
+    rounds_up = [int(i) for i in np.flatnonzero((n >= 2) & np.isfinite(t2.reshape(-1)))
+                 if np.nanmin(x[:, i]) == np.nanmax(x[:, i])
+                 and BC.shifted_variance_of_equal(np.nanmax(x[:, i]), t2.reshape(-1)[i], int(n[i])) > 0.0]
+    print(f"voxels of equal refits whose shifted variance rounds above 0: {rounds_up}")
+    assert len(rounds_up) >= 3
+    # the masks of the mask-count tests: exact counts, both ends of the volume set in some and clear in others
+    counts = (0, 1, 63, 64, 65, 255, 256, 257)
+    masks = BC.masks_with(counts)
+    assert [int(m.sum()) for m in masks] == list(counts)
+    for end in (0, -1):
+        ends = {int(m.reshape(-1)[end]) for m in masks[1:]}
+        assert ends == {0, 1}
