@@ -2,13 +2,17 @@
 and against scipy.ndimage, exactly: threshold, run-list dilation / erosion / closing / opening over shapes that exercise
 the word tail, both borders, in place and out of place; hole filling in 3-D and per plane, with a channel that needs
 several tile sweeps; seed labels and relabelling; the recipes against restatements of the reference's host functions;
-repeatability; argument errors; recon.py --phantom_masks and cli.py --build_mask phantom on files."""
+repeatability; argument errors; recon.py --phantom_masks and cli.py --build_mask phantom on files.  With the cases of
+tests/morph_cases.py: dilation and erosion where about half of the voxels change, every run offset against a response
+pasted from the definition, the sweep counts of the hole filling against a model of its tiles, degenerate volumes, and
+raw calls into guarded memory."""
 import ctypes as C
 import glob
 import json
 import os
 import sys
 
+import morph_cases as K
 import numpy as np
 import pandas as pd
 import pytest
@@ -353,3 +357,194 @@ def test_recon_phantom_masks_and_cli_build_mask_phantom(t2, tmp_path, monkeypatc
     with pytest.raises(SystemExit):
         cli.parse_arguments(["--path", str(tmp_path), "--csv", "x.csv", "--in_vivo", "--gaussian", "--lf", "--sim", "x",
                              "--build_mask", "phantom", "--phantom_seeds", str(seeds_file)])
+
+
+# ---- balanced inputs: about half of the voxels change (morph_cases.py) -----------------------------------------------------
+def _tensor(a):
+    import torch
+
+    return torch.from_numpy(np.asarray(a).astype(np.uint8)).cuda()
+
+
+@pytest.mark.parametrize("shape", K.GENERAL_SHAPES + K.FLAT_SHAPES)
+def test_balanced_dilate_erode_equal_statement_and_scipy(t2, shape):
+    import torch
+
+    device = {"dilate": t2.binary_dilate, "erode": t2.binary_erode}
+    in_place = set()
+    for i, (name, n, border, op) in enumerate(K.cases(shape, K.ELEMENTS, (1, 2), general=shape in K.GENERAL_SHAPES)):
+        a, fp = np.array(K.balanced(shape, name, n, op)), K.ELEMENTS[name]  # (a writable copy)
+        got = device[op](a if i % 2 else _tensor(a), fp, iterations=n, border_value=border)  # numpy and tensor input in turn
+        assert np.array_equal(_host(got), getattr(M, op)(a, fp, n, border)), (name, n, border, op)
+        assert np.array_equal(_host(got), K.expected(shape, name, n, border, op)), (name, n, border, op)
+        again = device[op](_tensor(a) if i % 2 else a, fp, iterations=n, border_value=border)
+        assert torch.equal(got, again), (name, n, border, op)  # the same bytes from a second call
+        if name == "two_runs" and n == 2 and border == 1 and op not in in_place:
+            in_place.add(op)
+            buf = _tensor(a)
+            assert device[op](buf, fp, iterations=n, border_value=border, out=buf).data_ptr() == buf.data_ptr()
+            assert torch.equal(buf, got), op
+    assert in_place == {"dilate", "erode"}
+
+
+@pytest.mark.parametrize("shape", K.GENERAL_SHAPES + K.FLAT_SHAPES)
+def test_balanced_close_open_equal_statement_and_scipy(t2, shape):
+    import torch
+
+    device = {"close": t2.binary_close, "open": t2.binary_open}
+    turn = 0
+    todo = [(name, 1, False) for name in sorted(K.ELEMENTS)] + [("two_runs", 2, False), ("wide", 2, False)]
+    for name, n, unbounded in todo + [("two_runs", 3, True), ("ball234", 1, True)]:  # two_runs three times: a reach of 12
+        fp = K.ELEMENTS[name]
+        for op, source in (("close", "dilate"), ("open", "erode")):
+            a = np.array(K.balanced(shape, name, n, source))
+            for border in ((0,) if unbounded else (0, 1)):
+                turn += 1
+                got = device[op](a if turn % 2 else _tensor(a), fp, iterations=n, border_value=border, unbounded=unbounded)
+                what = (name, n, unbounded, op, border)
+                assert np.array_equal(_host(got), getattr(M, op)(a, fp, n, border, unbounded)), what
+                want = K.scipy_close_open(op, a, fp, n, border, unbounded)
+                assert np.array_equal(_host(got), want), what
+                assert K.is_thin(shape, name, n) or (want.any() and not want.all()), what
+                again = device[op](_tensor(a) if turn % 2 else a, fp, iterations=n, border_value=border, unbounded=unbounded)
+                assert torch.equal(got, again), what
+
+
+# ---- every run offset, by impulse response -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("which", ["dilate", "dual", "erode0"])
+@pytest.mark.parametrize("name", sorted(K.IMPULSES))
+def test_every_run_offset_equals_the_pasted_response(t2, name, which):
+    a = np.array(K.impulse_volume(name))
+    element = M.footprint_runs(K.all_runs_footprint())
+    assert len(element[0]) == 2145
+    if which == "dilate":
+        got, statement = t2.binary_dilate(a, element), M.dilate(a, element)
+    else:
+        border = 1 if which == "dual" else 0
+        got, statement = t2.binary_erode(~a, element, border_value=border), M.erode(~a, element, 1, border)
+    want = K.impulse_expected(name, which)
+    got = _host(got)
+    wrong = np.argwhere(got != want)
+    assert len(wrong) == 0, (len(wrong), wrong[:5].tolist())
+    assert np.array_equal(got, statement)
+    assert want.any() and not want.all()
+
+
+# ---- hole filling: sweep counts and degenerate volumes -----------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(K.CHANNELS))
+def test_fill_holes_channel_sweep_counts(t2, name):
+    import torch
+
+    a, axis, by_hand = K.CHANNELS[name]
+    model, model_sweeps = K.sweep_model(a, axis)
+    want = ndi.binary_fill_holes(a) if axis is None else K.fill_per_plane(a, axis)
+    assert np.array_equal(model, want) and model_sweeps == by_hand
+    got, sweeps = t2.fill_holes(a, slice_axis=axis, return_sweeps=True)
+    print(f"{name}: {sweeps} sweeps on the device, {model_sweeps} in the model")
+    assert np.array_equal(_host(got), want)
+    assert sweeps == model_sweeps
+    again, sweeps2 = t2.fill_holes(_tensor(a), slice_axis=axis, return_sweeps=True)
+    assert sweeps2 == sweeps and torch.equal(again, got)
+
+
+@pytest.mark.parametrize("name", sorted(K.DEGENERATE))
+def test_fill_holes_degenerate_volumes(t2, name):
+    a = K.DEGENERATE[name]
+    for axis in (None, 0, 1, 2):
+        want = ndi.binary_fill_holes(a) if axis is None else K.fill_per_plane(a, axis)
+        got, sweeps = t2.fill_holes(a, slice_axis=axis, return_sweeps=True)
+        assert np.array_equal(_host(got), want), axis
+        assert np.array_equal(want, M.fill_holes(a, axis)), axis
+        assert sweeps == K.sweep_model(a, axis)[1], axis
+
+
+# ---- raw calls into guarded memory ---------------------------------------------------------------------------------------------
+GUARD = 4096
+
+
+class _Guarded:
+    """`nbytes` device bytes that start `offset` bytes past a 256-byte boundary, inside a buffer filled with 0xA5."""
+
+    def __init__(self, nbytes, offset=0, content=None):
+        import torch
+
+        self.buf = torch.full((nbytes + 2 * GUARD + 512,), 0xA5, dtype=torch.uint8, device="cuda")
+        self.at = GUARD + (offset - self.buf.data_ptr() - GUARD) % 256
+        self.ptr, self.nbytes = self.buf.data_ptr() + self.at, nbytes
+        assert self.ptr % 256 == offset
+        if content is not None:
+            raw = np.ascontiguousarray(content).view(np.uint8).ravel()
+            assert raw.size == nbytes
+            self.buf[self.at:self.at + nbytes] = torch.from_numpy(raw.copy()).cuda()
+
+    def bytes(self):
+        """The content, after checking that nothing was written before or after it."""
+        host = self.buf.cpu().numpy()
+        assert np.all(host[:self.at] == 0xA5) and np.all(host[self.at + self.nbytes:] == 0xA5)
+        return host[self.at:self.at + self.nbytes]
+
+
+def test_raw_calls_keep_to_the_workspace_and_the_output_and_leave_the_input(t2):
+    import torch
+
+    from fetal_t2mapping_amd._lib import load
+
+    lib = load()
+    shape = (17, 33, 70)
+    n = int(np.prod(shape))
+    fp = K.two_runs()
+    runs, size = M.footprint_runs(fp)
+    size = np.asarray(size, np.int32)
+    stream = torch.cuda.Stream()
+    st = C.c_void_p(stream.cuda_stream)
+
+    def workspace(reach):
+        need = C.c_size_t(0)
+        assert lib.t2fit_morph_workspace_bytes(*shape, reach, C.byref(need)) == _abi.OK
+        return _Guarded(need.value)  # exactly as long as the call asks for
+
+    def check(ws, inp, a):
+        assert np.any(ws.bytes() != 0xA5)  # used, and nothing written before or after it
+        assert np.array_equal(inp.bytes(), a.astype(np.uint8).ravel())  # the input is as it was
+
+    with torch.cuda.stream(stream):
+        # erosion by the asymmetric element, border 1, twice
+        a = K.balanced(shape, "two_runs", 2, "erode")
+        inp, out, ws = _Guarded(n, 1, a.astype(np.uint8)), _Guarded(n, 3), workspace(0)
+        assert inp.ptr % 2 == 1
+        assert lib.t2fit_binary_morph_dev(_abi.MORPH_ERODE, inp.ptr, out.ptr, *shape, size.ctypes.data, runs.ctypes.data, len(runs),
+                                          2, 1, 0, ws.ptr, ws.nbytes, st) == _abi.OK
+        stream.synchronize()
+        assert np.array_equal(out.bytes().reshape(shape), M.erode(a, fp, 2, 1))
+        check(ws, inp, a)
+        # the closing on the unbounded domain: the packed grid is larger than the volume by the reach on every side
+        a = K.balanced(shape, "two_runs", 2, "dilate")
+        inp, out, ws = _Guarded(n, 5, a.astype(np.uint8)), _Guarded(n, 7), workspace(4 * 2)
+        assert lib.t2fit_binary_morph_dev(_abi.MORPH_CLOSE, inp.ptr, out.ptr, *shape, size.ctypes.data, runs.ctypes.data, len(runs),
+                                          2, 0, _abi.MORPH_UNBOUNDED, ws.ptr, ws.nbytes, st) == _abi.OK
+        stream.synchronize()
+        assert np.array_equal(out.bytes().reshape(shape), M.close(a, fp, 2, unbounded=True))
+        check(ws, inp, a)
+        # hole filling
+        a = _shells(shape)
+        inp, out, ws = _Guarded(n, 9, a.astype(np.uint8)), _Guarded(n, 11), workspace(0)
+        sweeps = C.c_int32(-1)
+        assert lib.t2fit_fill_holes_dev(inp.ptr, out.ptr, *shape, -1, ws.ptr, ws.nbytes, C.byref(sweeps), st) == _abi.OK
+        stream.synchronize()
+        want = M.fill_holes(a)
+        assert int(want.sum() - a.sum()) > 0 and np.array_equal(out.bytes().reshape(shape), want)
+        assert sweeps.value == K.sweep_model(a)[1]
+        check(ws, inp, a)
+        # seed labels, both output types
+        seeds = np.array([(10, 12, 9), (14, 12, 9), (0, 0, 0), (69, 32, 16), (66, 3, 5)], np.int32)
+        labels = np.array([3, 250, 7, 1, 9], np.int32)
+        ball, ball_size = M.footprint_runs(M.ball(3))
+        ball_size = np.asarray(ball_size, np.int32)
+        for out_type, dtype, offset in ((_abi.MORPH_U8, np.uint8, 13), (_abi.MORPH_I32, np.int32, 4)):
+            out, ws = _Guarded(n * np.dtype(dtype).itemsize, offset), workspace(0)
+            assert lib.t2fit_seed_labels_dev(seeds.ctypes.data, labels.ctypes.data, len(seeds), ball_size.ctypes.data, ball.ctypes.data,
+                                             len(ball), *shape, out.ptr, out_type, ws.ptr, ws.nbytes, st) == _abi.OK
+            stream.synchronize()
+            assert np.array_equal(out.bytes().view(dtype).reshape(shape), M.seed_labels(shape, seeds, labels, M.ball(3), dtype))
+            assert np.any(ws.bytes() != 0xA5)
+    torch.cuda.synchronize()
