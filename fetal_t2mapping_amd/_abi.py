@@ -74,6 +74,7 @@ SR_MAX_STACKS = 6
 SR_SLICE_RECORD_BYTES = 208
 
 REGISTER_SUMS = 43
+SVR_RECORD_BYTES = 128
 REGISTER_MAX_BINS = 64
 REGISTER_MI_SUMS = 12
 
@@ -150,6 +151,12 @@ SYMBOLS = [
     ("t2fit_register_mi_workspace_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     ("t2fit_register_mi_gradient_dev", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_double, C.c_double, _P, C.c_int, C.c_int, C.c_int,
                                                  _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _P, _P, C.c_size_t, _P]),
+    ("t2fit_svr_table_bytes", C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
+    ("t2fit_svr_table_host", C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8),
+                                       C.c_int, C.POINTER(C.c_int32), _P, C.c_size_t]),
+    ("t2fit_svr_workspace_bytes", C.c_int, [C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_size_t)]),
+    ("t2fit_svr_sums_dev", C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32), _P, _P, C.c_int, C.c_int, C.c_int, _P,
+                                     C.c_int, _P, _P, C.c_size_t, _P]),
     ("t2fit_n4_workspace_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     ("t2fit_n4_log_dev", C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
     ("t2fit_n4_minmax_dev", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
@@ -185,7 +192,8 @@ MI_SYMBOLS = ("t2fit_register_joint_hist_dev", "t2fit_register_mi_workspace_byte
 SR_SYMBOLS = ("t2fit_sr_plan_host", "t2fit_sr_workspace_bytes", "t2fit_sr_forward_dev", "t2fit_sr_adjoint_dev")
 SR_SLICE_SYMBOLS = ("t2fit_sr_slice_table_bytes", "t2fit_sr_slice_table_host", "t2fit_sr_slice_forward_dev",
                     "t2fit_sr_slice_adjoint_dev")
-LOOKED_UP = ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS + MI_SYMBOLS + SR_SYMBOLS + SR_SLICE_SYMBOLS
+SVR_SYMBOLS = ("t2fit_svr_table_bytes", "t2fit_svr_table_host", "t2fit_svr_workspace_bytes", "t2fit_svr_sums_dev")
+LOOKED_UP = ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS + MI_SYMBOLS + SR_SYMBOLS + SR_SLICE_SYMBOLS + SVR_SYMBOLS
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

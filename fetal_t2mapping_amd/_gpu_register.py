@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _abi, _register, _resample
+from . import _abi, _register, _resample, _svr
 from ._gpu import current_stream, pick_device, require, volume, workspace
 from ._gpu_morph import build_mask
 from ._lib import check
@@ -335,3 +335,118 @@ def register_affine(fixed, moving, fixed_geom, moving_geom, *, metric="cr", bins
     p0 = _register.affine_init(init, fmask_host, fg, pyramid.full[3].cpu().numpy() if isinstance(init, str) else None, mg)
     return _register.optimize_affine(pyramid, fg, mg, centre, scales, metric=metric, bins=bins, dof=dof, levels=levels,
                                      max_iter=max_iter, init=p0, moving_bins=moving_bins)
+
+
+# ---- slice-to-volume registration ------------------------------------------------------------------------------------------
+_as_volume = volume  # (the functions below have an argument of that name)
+
+
+class DeviceSlices:
+    """The stacks, their masks, the volume and its mask as CUDA tensors, with the table, the sums and the workspace of
+    t2fit_svr_sums_dev sized for ``n_slices`` records: everything stays on the device; ``sums`` uploads the packed table
+    (128 bytes a record) and downloads ``(K, 43)`` doubles, which waits for the stream."""
+
+    def __init__(self, stacks, stack_masks, moving, moving_mask, n_slices, dev):
+        import torch
+
+        self.lib = require(*_abi.SVR_SYMBOLS)
+        self.dev = dev
+        if not 1 <= len(stacks) <= _abi.SR_MAX_STACKS:
+            raise ValueError(f"between 1 and {_abi.SR_MAX_STACKS} stacks, got {len(stacks)}")
+        stack_masks = [None] * len(stacks) if stack_masks is None else list(stack_masks)
+        if len(stack_masks) != len(stacks):
+            raise ValueError("one mask (or None) per stack")
+        self.stacks = [volume(v, torch.float32, dev, "a stack") for v in stacks]
+        self.masks = [None if m is None else volume(m, torch.uint8, dev, "a stack mask") for m in stack_masks]
+        self.moving = volume(moving, torch.float32, dev, "volume")
+        self.moving_mask = None if moving_mask is None else volume(moving_mask, torch.uint8, dev, "volume_mask")
+        if any(m is not None and m.shape != v.shape for v, m in zip(self.stacks, self.masks)) or (
+                self.moving_mask is not None and self.moving_mask.shape != self.moving.shape):
+            raise ValueError("a mask has the shape of its volume")
+        self.n = int(n_slices)
+        n_s = len(self.stacks)
+        self.shapes = [tuple(int(d) for d in v.shape) for v in self.stacks]
+        self.lo_size = (C.c_int32 * (3 * n_s))(*[d for s in self.shapes for d in s])
+        self.fixed_ptrs = (C.c_void_p * n_s)(*[v.data_ptr() for v in self.stacks])
+        self.mask_ptrs = (C.c_void_p * n_s)(*[None if m is None else m.data_ptr() for m in self.masks])
+        need, table = C.c_size_t(0), C.c_size_t(0)
+        check(self.lib.t2fit_svr_workspace_bytes(n_s, self.lo_size, self.n, C.byref(need)))
+        check(self.lib.t2fit_svr_table_bytes(self.n, C.byref(table)))
+        with torch.cuda.device(dev):
+            self.ws, self.ws_ptr = workspace(need.value, dev)
+            self.ws_bytes = need.value
+            self.table = torch.empty(table.value, dtype=torch.uint8, device=dev)
+            self.out = torch.empty((self.n, _abi.REGISTER_SUMS), dtype=torch.float64, device=dev)
+        self.table_host = np.zeros(table.value, np.uint8)
+
+    def sums(self, A, stack, slice_, active=None):
+        a, s, k, act = _svr.check_records(A, stack, slice_, active)
+        if len(a) != self.n:
+            raise ValueError(f"{self.n} records were planned, got {len(a)}")
+        # (the packing refuses a non-finite A and an index out of range before a byte is written)
+        check(self.lib.t2fit_svr_table_host(self.n, a.ctypes.data_as(C.POINTER(C.c_double)), s.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            k.ctypes.data_as(C.POINTER(C.c_int32)), act.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                            len(self.stacks), self.lo_size, self.table_host.ctypes.data_as(C.c_void_p),
+                                            self.table_host.size))
+        return self.sums_of_table(self.table_host)
+
+    def sums_of_table(self, table_bytes):
+        """The sums of a packed table (uint8 ``[128 K]``, taken as data: whatever it holds)."""
+        import torch
+
+        with torch.cuda.device(self.dev):
+            self.table.copy_(torch.from_numpy(np.ascontiguousarray(table_bytes, np.uint8).reshape(-1)))  # (pageable: the copy has left the host)
+            check(self.lib.t2fit_svr_sums_dev(len(self.stacks), self.fixed_ptrs, self.mask_ptrs, self.lo_size, self.moving.data_ptr(),
+                                              None if self.moving_mask is None else self.moving_mask.data_ptr(), *self.moving.shape,
+                                              self.table.data_ptr(), self.n, self.out.data_ptr(), self.ws_ptr, self.ws_bytes,
+                                              current_stream()))
+            return self.out.cpu().numpy()  # (waits)
+
+
+def slice_sums(stacks, volume, A, stack, slice_, *, active=None, stack_masks=None, volume_mask=None, device=0):  # noqa: A002
+    """float64 ``(K, 43)``, numpy: the 43 sums of the correlation metric of record ``r`` = slice ``slice_[r]`` of
+    ``stacks[stack[r]]`` (a list of float32 ``(Z, Y, X)``, numpy or CUDA tensors) sampled from ``volume`` at its own index
+    affine ``A[r]`` (slice index ``(ix, iy, k)`` -> continuous volume index), all in one launch (t2fit_svr_sums_dev).
+    ``active``: 0 gives a row of zeros; masks None: all ones.  Refuses a non-finite ``A`` and an index out of range.
+    Bit-identical to :func:`_svr.slice_sums` and the same from call to call.  Waits for the stream."""
+    dev = pick_device(list(stacks) + [volume, volume_mask], device)
+    n = len(np.asarray(stack).ravel())
+    return DeviceSlices(stacks, stack_masks, volume, volume_mask, n, dev).sums(A, stack, slice_, active)
+
+
+def register_slices(stacks, geoms, volume, volume_geom, *, transforms=None, stack_masks=None, volume_mask=None, echo=0, init=None,  # noqa: A002
+                    max_iter=_svr.MAX_ITER, step=_svr.STEP, min_step=_svr.MIN_STEP, min_count=_svr.MIN_COUNT, device=0):
+    """Slice-to-volume registration: every slice of every stack is registered rigidly onto ``volume`` with the correlation
+    metric, and the poses ``reconstruct_sr(slice_transforms=)`` takes come back.  ``stacks`` / ``geoms``: {name: float32
+    ``(Z, Y, X)`` or ``(nTE, Z, Y, X)`` (``echo`` is used), numpy or CUDA tensors} and their geometries; ``volume``:
+    float32 ``(Z, Y, X)`` on ``volume_geom``; ``transforms``: {name: 4 x 4 stack transform, fixed point -> stack point};
+    ``stack_masks``: {name: ``(Z, Y, X)``}, a stack without one gets :func:`build_mask` on the device; ``volume_mask``:
+    None is all ones; ``init``: {name: ``(lz, 6)``} parameters to start from.  Slice ``k`` moves by ``p = (rx, ry, rz [rad],
+    tx, ty, tz [mm])`` about the centroid of its own mask, regular-step descent from ``step`` mm (halved when the gradient
+    turns; stops at ``min_step``, gradient 1e-6 or ``max_iter`` moves), one full-resolution level; all slices advance in
+    lockstep with one batched evaluation per iteration (t2fit_svr_sums_dev: a 128-byte record per slice up, 43 doubles per
+    slice down), a finished slice is no longer evaluated.  No slice makes the call raise: fewer than ``min_count``
+    counted voxels or no metric at the first evaluation is status 'rejected' (the stack's own pose), later 'lost' (the last
+    pose that had a metric).  Returns a :class:`_svr.SliceRegistration`; parameters, iterations and status equal
+    :func:`_svr.register_slices`'s."""
+    import torch
+
+    _svr.check_options(max_iter, step, min_step, min_count)
+    names = _svr._stack_names(stacks, geoms)
+    dev = pick_device([stacks[o] for o in names] + [volume, volume_mask], device)
+    ys = []
+    for o in names:
+        v = stacks[o] if torch.is_tensor(stacks[o]) else np.asarray(stacks[o], np.float32)
+        if len(v.shape) not in (3, 4):
+            raise ValueError(f"stack {o!r} must be (Z, Y, X) or (nTE, Z, Y, X), got shape {tuple(v.shape)}")
+        ys.append(_as_volume(v if len(v.shape) == 3 else v[int(echo)], torch.float32, dev, f"stack {o!r}"))
+    stack_masks = stack_masks or {}
+    masks = [build_mask(y, device=dev.index) if stack_masks.get(o) is None else stack_masks[o] for o, y in zip(names, ys)]
+    lzs = [int(y.shape[0]) for y in ys]
+    slices = DeviceSlices(ys, masks, volume, volume_mask, sum(lzs), dev)
+    s_of = np.array([s for s, lz in enumerate(lzs) for _ in range(lz)], np.int32)
+    k_of = np.array([k for lz in lzs for k in range(lz)], np.int32)
+    host_masks = [m.cpu().numpy() for m in slices.masks]  # the masks to the host, once: centres and scales
+    return _svr.register_with(lambda a, active: slices.sums(a, s_of, k_of, active), names, geoms, host_masks,
+                              _resample.as_geometry(volume_geom, tuple(slices.moving.shape)), transforms, init,
+                              max_iter=int(max_iter), step=float(step), min_step=float(min_step), min_count=int(min_count))

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _abi, _resample, _sr
+from . import _abi, _resample, _sr, _svr
 from ._gpu import current_stream, flat, is_tensor, pick_device, release, require, workspace
 from ._gpu_resample import reconstruct_stacks, resample_volume
 from ._gpu_tv import tv_params
@@ -374,3 +374,26 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
     out = x.reshape((n_vol,) + hr_shape)
     header = nifti.Image(np.zeros((0, 0, 0), np.float32), hi.GetSpacing(), hi.GetOrigin(), hi.GetDirection())
     return (out, header, info) if return_info else (out, header)
+
+
+def reconstruct_svr(stacks, geoms, *, rounds=2, echo=0, slice_masks=None, volume_mask=None, max_iter=_svr.MAX_ITER, step=_svr.STEP,
+                    min_step=_svr.MIN_STEP, min_count=_svr.MIN_COUNT, **sr):
+    """Motion-corrected super-resolution: the slice poses :func:`reconstruct_sr` takes are found here, not given.  From the
+    merge (``reconstruct_sr`` with no iteration), ``rounds`` times: every slice of every stack is registered onto echo
+    ``echo`` of the current volume (``t2map.register.register_slices``, warm-started from the last round; ``slice_masks``:
+    {name: ``(Z, Y, X)``} of the registration, None: ``build_mask`` of the stack; ``volume_mask``, ``max_iter``, ``step``,
+    ``min_step``, ``min_count`` are its arguments) and the volume is reconstructed again with the poses found.  Every other
+    keyword is :func:`reconstruct_sr`'s (``device`` too); ``slice_transforms`` and ``return_info`` are refused.  Returns
+    ``(echoes, header, found)``: ``found`` is the :class:`_svr.SliceRegistration` of the last round, ``found.transforms``
+    what ``slice_transforms=`` and ``recon.py --sr_slice_transforms`` read.  :func:`_svr.reconstruct_svr` states it in numpy;
+    same bits."""
+    from ._gpu_register import register_slices
+
+    _svr.check_options(max_iter, step, min_step, min_count)
+    device = sr.get("device", 0)
+
+    def register(*args, **kw):
+        return register_slices(*args, device=device, **kw)
+
+    return _svr.drive(reconstruct_sr, register, stacks, geoms, rounds, echo, slice_masks, volume_mask,
+                      dict(max_iter=max_iter, step=step, min_step=min_step, min_count=min_count), sr)

@@ -14,6 +14,10 @@
 //                           <kFromLut>: f is lut[bin] of a uint8 bin volume instead of the fixed sample, nothing else
 //                           differs.  <kFromMi>: 12 accumulators, (c g_a) u_j with c from the table T[n_f][n_m], which the
 //                           workgroup stages in LDS once; a voxel gathers four consecutive entries of one row.
+//   svr_sums_kernel         slice-to-volume registration (t2fit_svr_sums_dev): the same 43 sums for every slice of every
+//                           stack in one launch, each slice under the affine of its record in a device table.  A workgroup
+//                           owns a brick of 64 x 32 voxels of one slice; a lane adds 8 rows before the butterfly, so the
+//                           cross-lane exchange is paid once per 8 voxels as in the volume's kernel.
 //   register_joint_hist_kernel  the joint histogram of Mattes mutual information: a workgroup walks bricks (a grid stride)
 //                           and adds the four fixed-point window weights of every counted voxel into its own uint64 table
 //                           in LDS with 64-bit integer LDS atomics, then adds the table's nonzero entries to global memory
@@ -32,6 +36,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <string>
 
 #include "t2fit_affine.h"
@@ -86,14 +91,15 @@ __device__ inline double wave_butterfly(double v) {
   return v;
 }
 
-// whether the fixed voxel (x, y, z), whose mask byte is set, counts; if so its interpolant m and, <true>, dm/dc
-template <bool kGrad>
+// whether the fixed voxel (x, y, z), whose mask byte is set, counts; if so its interpolant m and, <true>, dm/dc.
+// <.., true>: moving_mask may be NULL (all ones)
+template <bool kGrad, bool kMaskOptional = false>
 __device__ inline bool sample(const float* moving, const uint8_t* moving_mask, const Dims n, const Affine& A, int x, int y, int z,
                               double& m, double* g) {
   const double cx = coord(A, 0, x, y, z), cy = coord(A, 1, x, y, z), cz = coord(A, 2, x, y, z);
   if (!(inside_axis(cx, n.nx) && inside_axis(cy, n.ny) && inside_axis(cz, n.nz))) return false;
   const int qx = clamp_index(floor(cx + 0.5), n.nx), qy = clamp_index(floor(cy + 0.5), n.ny), qz = clamp_index(floor(cz + 0.5), n.nz);
-  if (moving_mask[((int64_t)qz * n.ny + qy) * n.nx + qx] == 0) return false;
+  if ((!kMaskOptional || moving_mask) && moving_mask[((int64_t)qz * n.ny + qy) * n.nx + qx] == 0) return false;
   const int x0 = clamp_index(floor(cx), n.nx), y0 = clamp_index(floor(cy), n.ny), z0 = clamp_index(floor(cz), n.nz);
   double dx = cx - (double)x0, dy = cy - (double)y0, dz = cz - (double)z0;
   dx = dx < 0.0 ? 0.0 : dx;
@@ -219,6 +225,102 @@ __global__ __launch_bounds__(kBlock) void register_sums_kernel(const SumsArgs a)
   if (threadIdx.x < kN) {
     const int q = threadIdx.x;
     a.slabs[(int64_t)q * a.n_bricks + blockIdx.x] = (rows[0][q] + rows[2][q]) + (rows[1][q] + rows[3][q]);
+  }
+}
+
+// ---- slice-to-volume registration: the 43 sums of every slice of every stack, each under its own affine ----------------
+constexpr int kSvrBY = 32, kSvrRows = 8;  // a brick of a slice: 64 (x) x 32 (y); a wave owns 8 rows of it
+constexpr int kSvrMaxStacks = T2FIT_SR_MAX_STACKS;
+static_assert(kSvrRows * kBY == kSvrBY, "four waves of eight rows");
+
+struct SvrRec {  // the layout include/t2fit.h documents: 128 bytes
+  Affine A;
+  int32_t stack, slice, active;
+  int32_t pad[5];
+};
+static_assert(sizeof(SvrRec) == T2FIT_SVR_RECORD_BYTES && alignof(SvrRec) == 8, "the record is 128 bytes");
+
+struct SvrStack {
+  const float* fixed;
+  const uint8_t* mask;  // NULL: all ones
+  int lz, ly, lx;
+  int bricks_x, n_bricks;
+};
+
+struct SvrArgs {
+  SvrStack s[kSvrMaxStacks];
+  int n_stacks;
+  const float* moving;
+  const uint8_t* moving_mask;  // NULL: all ones
+  Dims m;
+  const SvrRec* table;  // [n_slices]
+  int max_bricks;       // the slabs of a record: row (43 record + q), max_bricks values
+  double* slabs;
+};
+
+// Workgroup (brick b, record r): blockIdx.x = r * max_bricks + b.  The record's address is the same in every lane, so the
+// affine and the indices are read once per wave.  The table is data: an inactive record, a stack or slice index out of
+// range and a brick past the stack's count write a slab of +0.0; a non-finite affine fails the inside test everywhere.
+__global__ __launch_bounds__(kBlock) void svr_sums_kernel(const SvrArgs a) {
+  __shared__ double rows[kBY][kSums];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = (int)(blockIdx.x / (unsigned)a.max_bricks), b = (int)(blockIdx.x % (unsigned)a.max_bricks);
+  const SvrRec& rec = a.table[r];
+  double* slab = a.slabs + (int64_t)r * kSums * a.max_bricks + b;
+  const int s = rec.stack, k = rec.slice;
+  bool live = rec.active != 0 && s >= 0 && s < a.n_stacks;
+  const SvrStack& st = a.s[live ? s : 0];
+  live = live && k >= 0 && k < st.lz && b < st.n_bricks;
+  if (!live) {
+    if (threadIdx.x < kSums) slab[(int64_t)threadIdx.x * a.max_bricks] = 0.0;
+    return;
+  }
+  const int bx = b % st.bricks_x, by = b / st.bricks_x;
+  const int x = bx * kBX + lane, ly = st.ly, lx = st.lx;
+  const float* fixed = st.fixed + (int64_t)k * ly * lx;
+  const uint8_t* fmask = st.mask ? st.mask + (int64_t)k * ly * lx : nullptr;
+  const Affine A = rec.A;
+  const Dims n = a.m;
+  double acc[kSums];
+#pragma unroll
+  for (int q = 0; q < kSums; ++q) acc[q] = 0.0;
+#pragma unroll 1
+  for (int i = 0; i < kSvrRows; ++i) {
+    const int y = by * kSvrBY + wave * kSvrRows + i;
+    if (x >= lx || y >= ly) continue;
+    const int64_t at = (int64_t)y * lx + x;
+    if (fmask && fmask[at] == 0) continue;
+    double m, g[3];
+    if (!sample<true, true>(a.moving, a.moving_mask, n, A, x, y, k, m, g)) continue;
+    const double u[3] = {(double)x, (double)y, (double)k};
+    const double f = (double)fixed[at];
+    acc[0] = acc[0] + 1.0;
+    acc[1] = acc[1] + f;
+    acc[2] = acc[2] + m;
+    acc[3] = acc[3] + f * f;
+    acc[4] = acc[4] + m * m;
+    acc[5] = acc[5] + f * m;
+#pragma unroll
+    for (int w = 0; w < 3; ++w) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const double wg = w == 0 ? g[c] : (w == 1 ? f * g[c] : m * g[c]);
+        const int q = 6 + 4 * (3 * w + c);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) acc[q + j] = acc[q + j] + wg * u[j];
+        acc[q + 3] = acc[q + 3] + wg;
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < kSums; ++q) {
+    const double v = wave_butterfly(acc[q]);
+    if (lane == 0) rows[wave][q] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kSums) {
+    const int q = threadIdx.x;
+    slab[(int64_t)q * a.max_bricks] = (rows[0][q] + rows[2][q]) + (rows[1][q] + rows[3][q]);
   }
 }
 
@@ -476,9 +578,142 @@ int shrink_check(const std::string& w, const void* src, const void* out, int nz,
   return T2FIT_OK;
 }
 
+// slice-to-volume registration: the bricks of every stack's slices, and the passes over 43 n_slices rows of max_bricks
+struct SvrPlan {
+  int bricks_x[kSvrMaxStacks], n_bricks[kSvrMaxStacks];
+  int max_bricks;
+  int64_t rows;  // 43 n_slices
+  int n_pass;
+  int64_t pass_n[kMaxPasses];
+  size_t pass_at[kMaxPasses];
+  size_t total;
+};
+
+int svr_plan(const std::string& w, int n_stacks, const int32_t* lo_size, int n_slices, SvrPlan* plan) {
+  if (n_stacks < 1 || n_stacks > kSvrMaxStacks) return t2fit::fail(T2FIT_E_INVALID, w + ": n_stacks must be 1 .. T2FIT_SR_MAX_STACKS");
+  if (n_slices < 1) return t2fit::fail(T2FIT_E_INVALID, w + ": n_slices must be >= 1");
+  plan->max_bricks = 0;
+  for (int s = 0; s < n_stacks; ++s) {
+    const int lz = lo_size[3 * s], ly = lo_size[3 * s + 1], lx = lo_size[3 * s + 2];
+    if (t2fit::count_voxels(1, lz, ly, lx) < 0)
+      return t2fit::fail(T2FIT_E_INVALID, w + ": the sizes of a stack must all be >= 1 and the stack at most 2^40 elements");
+    plan->bricks_x[s] = ceil_div(lx, kBX);
+    const int64_t bricks = (int64_t)plan->bricks_x[s] * ceil_div(ly, kSvrBY);
+    if (bricks > INT32_MAX) return t2fit::fail(T2FIT_E_INVALID, w + ": a slice has more than 2^31-1 bricks");
+    plan->n_bricks[s] = (int)bricks;
+    if (plan->n_bricks[s] > plan->max_bricks) plan->max_bricks = plan->n_bricks[s];
+  }
+  if ((int64_t)n_slices * plan->max_bricks > INT32_MAX)
+    return t2fit::fail(T2FIT_E_INVALID, w + ": more than 2^31-1 workgroups (n_slices times the largest brick count of a slice)");
+  plan->rows = (int64_t)kSums * n_slices;
+  plan->n_pass = 0;
+  plan->total = 0;
+  for (int64_t n = plan->max_bricks;; n = ceil_div(n, (int64_t)kFan)) {
+    plan->pass_n[plan->n_pass] = n;
+    plan->pass_at[plan->n_pass] = plan->total;
+    plan->total += align_up((size_t)n * (size_t)plan->rows * sizeof(double), kAlign);
+    ++plan->n_pass;
+    if (n <= kFan) break;
+  }
+  return T2FIT_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int t2fit_svr_table_bytes(int n_slices, size_t* bytes) {
+  const std::string w("t2fit_svr_table_bytes");
+  if (!bytes) return t2fit::fail(T2FIT_E_INVALID, w + ": bytes is NULL");
+  if (n_slices < 1) return t2fit::fail(T2FIT_E_INVALID, w + ": n_slices must be >= 1");
+  *bytes = (size_t)n_slices * sizeof(SvrRec);
+  return T2FIT_OK;
+}
+
+int t2fit_svr_table_host(int n_slices, const double* A, const int32_t* stack, const int32_t* slice, const uint8_t* active, int n_stacks,
+                         const int32_t* lo_size, void* table_host, size_t bytes) {
+  const std::string w("t2fit_svr_table_host");
+  if (!A || !stack || !slice || !active || !lo_size || !table_host)
+    return t2fit::fail(T2FIT_E_INVALID, w + ": A / stack / slice / active / lo_size / table_host is NULL");
+  SvrPlan plan;
+  const int rc = svr_plan(w, n_stacks, lo_size, n_slices, &plan);
+  if (rc != T2FIT_OK) return rc;
+  if (bytes < (size_t)n_slices * sizeof(SvrRec))
+    return t2fit::fail(T2FIT_E_INVALID, w + ": the table is smaller than t2fit_svr_table_bytes says");
+  for (int r = 0; r < n_slices; ++r) {  // every record is checked before a byte is written
+    if (!t2fit::finite12(A + 12 * r)) return t2fit::fail(T2FIT_E_INVALID, w + ": record " + std::to_string(r) + ": A has a non-finite entry");
+    if (stack[r] < 0 || stack[r] >= n_stacks)
+      return t2fit::fail(T2FIT_E_INVALID, w + ": record " + std::to_string(r) + ": the stack index is outside 0 .. n_stacks - 1");
+    if (slice[r] < 0 || slice[r] >= lo_size[3 * stack[r]])
+      return t2fit::fail(T2FIT_E_INVALID, w + ": record " + std::to_string(r) + ": the slice index is outside its stack");
+  }
+  for (int r = 0; r < n_slices; ++r) {
+    SvrRec rec = {};
+    for (int i = 0; i < 12; ++i) rec.A.m[i] = A[12 * r + i];
+    rec.stack = stack[r], rec.slice = slice[r], rec.active = active[r] != 0;
+    std::memcpy(static_cast<char*>(table_host) + (size_t)r * sizeof(SvrRec), &rec, sizeof(SvrRec));
+  }
+  return T2FIT_OK;
+}
+
+int t2fit_svr_workspace_bytes(int n_stacks, const int32_t* lo_size, int n_slices, size_t* bytes) {
+  const std::string w("t2fit_svr_workspace_bytes");
+  if (!lo_size || !bytes) return t2fit::fail(T2FIT_E_INVALID, w + ": lo_size / bytes is NULL");
+  SvrPlan plan;
+  const int rc = svr_plan(w, n_stacks, lo_size, n_slices, &plan);
+  if (rc != T2FIT_OK) return rc;
+  *bytes = plan.total;
+  return T2FIT_OK;
+}
+
+int t2fit_svr_sums_dev(int n_stacks, const float* const* fixed_dev, const uint8_t* const* fixed_mask_dev, const int32_t* lo_size,
+                       const float* moving_dev, const uint8_t* moving_mask_dev, int mz, int my, int mx, const void* table_dev,
+                       int n_slices, double* sums_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  const std::string w("t2fit_svr_sums_dev");
+  if (!fixed_dev || !lo_size || !moving_dev || !table_dev || !sums_dev || !workspace_dev)
+    return t2fit::fail(T2FIT_E_INVALID, w + ": fixed_dev / lo_size / moving_dev / table_dev / sums_dev / workspace_dev is NULL");
+  SvrPlan plan;
+  const int rc = svr_plan(w, n_stacks, lo_size, n_slices, &plan);
+  if (rc != T2FIT_OK) return rc;
+  if (t2fit::count_voxels(1, mz, my, mx) < 0)
+    return t2fit::fail(T2FIT_E_INVALID, w + ": the moving sizes must all be >= 1 and the volume at most 2^40 elements");
+  SvrArgs a = {};
+  for (int s = 0; s < n_stacks; ++s) {
+    if (!fixed_dev[s]) return t2fit::fail(T2FIT_E_INVALID, w + ": a stack pointer is NULL");
+    if (reinterpret_cast<uintptr_t>(fixed_dev[s]) & 3) return t2fit::fail(T2FIT_E_INVALID, w + ": a stack is not aligned to 4 bytes");
+    a.s[s].fixed = fixed_dev[s], a.s[s].mask = fixed_mask_dev ? fixed_mask_dev[s] : nullptr;
+    a.s[s].lz = lo_size[3 * s], a.s[s].ly = lo_size[3 * s + 1], a.s[s].lx = lo_size[3 * s + 2];
+    a.s[s].bricks_x = plan.bricks_x[s], a.s[s].n_bricks = plan.n_bricks[s];
+  }
+  if (reinterpret_cast<uintptr_t>(moving_dev) & 3) return t2fit::fail(T2FIT_E_INVALID, w + ": moving_dev is not aligned to 4 bytes");
+  if ((reinterpret_cast<uintptr_t>(sums_dev) & 7) || (reinterpret_cast<uintptr_t>(table_dev) & 7))
+    return t2fit::fail(T2FIT_E_INVALID, w + ": sums_dev / table_dev is not aligned to 8 bytes");
+  if (reinterpret_cast<uintptr_t>(workspace_dev) & (kAlign - 1))
+    return t2fit::fail(T2FIT_E_INVALID, w + ": workspace_dev is not aligned to 256 bytes");
+  if (workspace_bytes < plan.total)
+    return t2fit::fail(T2FIT_E_INVALID, w + ": workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " +
+                                            std::to_string(plan.total) + " needed (t2fit_svr_workspace_bytes)");
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace_dev);
+  a.n_stacks = n_stacks, a.moving = moving_dev, a.moving_mask = moving_mask_dev, a.m = Dims{mz, my, mx};
+  a.table = static_cast<const SvrRec*>(table_dev), a.max_bricks = plan.max_bricks;
+  a.slabs = reinterpret_cast<double*>(ws + plan.pass_at[0]);
+  hipLaunchKernelGGL(svr_sums_kernel, dim3((unsigned)((int64_t)n_slices * plan.max_bricks)), dim3(kBlock), 0, st, a);
+  constexpr int64_t kRowsPerLaunch = 65535;  // the y extent of a grid
+  for (int p = 0; p < plan.n_pass; ++p) {
+    const bool last = p + 1 == plan.n_pass;
+    const int64_t n = plan.pass_n[p], n_out = last ? 1 : plan.pass_n[p + 1];
+    const double* in = reinterpret_cast<const double*>(ws + plan.pass_at[p]);
+    double* out = last ? sums_dev : reinterpret_cast<double*>(ws + plan.pass_at[p + 1]);
+    for (int64_t q0 = 0; q0 < plan.rows; q0 += kRowsPerLaunch) {
+      const int64_t q_n = plan.rows - q0 < kRowsPerLaunch ? plan.rows - q0 : kRowsPerLaunch;
+      hipLaunchKernelGGL(register_reduce_kernel, dim3((unsigned)n_out, (unsigned)q_n), dim3(kBlock), 0, st, in + q0 * n, n, out + q0 * n_out,
+                         n_out);
+    }
+  }
+  T2_HIP(hipGetLastError());
+  return T2FIT_OK;
+}
 
 int t2fit_register_workspace_bytes(int fz, int fy, int fx, size_t* bytes) {
   if (!bytes) return t2fit::fail(T2FIT_E_INVALID, "t2fit_register_workspace_bytes: bytes is NULL");

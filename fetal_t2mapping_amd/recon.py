@@ -162,7 +162,9 @@ def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False
     'mattes', for both.  ``sr``: None for the averaged merge, or the keyword arguments of ``t2map.sr.reconstruct_sr``
     (``--recon_method sr``: the super-resolution reconstruction, which starts from that merge and keeps the float result,
     whatever ``integer_cast`` says); its entry ``slice_transforms_dir`` (``--sr_slice_transforms``) names a directory of
-    :func:`load_slice_transforms` files, read per echo and passed on as ``slice_transforms``.  Returns ``(float32 CUDA tensor
+    :func:`load_slice_transforms` files, read per echo and passed on as ``slice_transforms``; its entry ``estimate_slices``
+    (``--sr_estimate_slices``) is the number of rounds of ``t2map.sr.reconstruct_svr``, which finds those poses on the first
+    echo of each call, and ``write_slice_transforms_dir`` where they are written for every echo.  Returns ``(float32 CUDA tensor
     (n, Z, Y, X), header, transforms per echo)``."""
     import torch
 
@@ -177,10 +179,11 @@ def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False
                 save_transforms(write_transforms, acq, t)
     else:
         per_echo = [load_transforms(transforms_dir, acq, fixed) for acq in acqs]
-    slices_dir = None
-    if sr is not None and "slice_transforms_dir" in sr:
+    slices_dir = rounds = write_slices = None
+    if sr is not None:
         sr = dict(sr)
-        slices_dir = sr.pop("slice_transforms_dir")
+        slices_dir, rounds = sr.pop("slice_transforms_dir", None), sr.pop("estimate_slices", None)
+        write_slices = sr.pop("write_slice_transforms_dir", None)
     per_slice = [load_slice_transforms(slices_dir, acq, geoms, fixed) for acq in acqs]
     groups = []
     for i in range(n):
@@ -193,7 +196,12 @@ def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False
     merged = None
     for g in groups:
         part = stacks if len(g) == n else {o: stacks[o][g] for o in stacks}
-        if sr is not None:
+        if sr is not None and rounds:
+            out, header, found = t2map.sr.reconstruct_svr(part, geoms, rounds=rounds, fixed=fixed, res=res, transforms=per_echo[g[0]],
+                                                          device=device, **sr)
+            for i in g if write_slices else ():
+                save_slice_transforms(write_slices, acqs[i], found.transforms)
+        elif sr is not None:
             poses = {"slice_transforms": per_slice[g[0]]} if slices_dir else {}
             out, header = t2map.sr.reconstruct_sr(part, geoms, fixed=fixed, res=res, transforms=per_echo[g[0]], device=device, **sr,
                                                   **poses)
@@ -557,7 +565,8 @@ def reconstruct_subject(sitk, bids_path, sub_md, sub, ses, *, fixed="ax", res=1.
     return [host[i] for i in range(host.shape[0])], header
 
 
-SR_FLAGS = ("sr_weight", "sr_iter", "sr_profile", "sr_thickness", "sr_slice_transforms")
+SR_FLAGS = ("sr_weight", "sr_iter", "sr_profile", "sr_thickness", "sr_slice_transforms", "sr_estimate_slices",
+            "sr_write_slice_transforms")
 
 
 def add_sr_arguments(p, prefix):
@@ -579,6 +588,11 @@ def add_sr_arguments(p, prefix):
                    help="sr: a rigid pose per slice, for stacks of a subject that moved between slices: "
                         "<DIR>/<sub>_<ses>_[te-<ms>_]<orientation>_slices.txt with one row of 16 numbers per slice, the 4 x 4 "
                         "(fixed point -> stack point, LPS millimetres) row-major; stacks without a file keep their stack transform")
+    p.add_argument(f"--{prefix}sr_estimate_slices", type=int, default=None, metavar="ROUNDS",
+                   help="sr: find the pose of every slice instead of reading it: ROUNDS times, register every slice of every "
+                        f"stack onto the current volume and reconstruct again with the poses found (not with --{prefix}sr_slice_transforms)")
+    p.add_argument(f"--{prefix}sr_write_slice_transforms", default=None, metavar="DIR",
+                   help=f"sr: write the poses --{prefix}sr_estimate_slices found where --{prefix}sr_slice_transforms reads them")
 
 
 def sr_arguments(p, args, prefix, argv):
@@ -600,6 +614,17 @@ def sr_arguments(p, args, prefix, argv):
     slices_dir = getattr(args, f"{prefix}sr_slice_transforms")
     if slices_dir is not None:
         out["slice_transforms_dir"] = slices_dir
+    rounds, write_dir = (getattr(args, f"{prefix}sr_{k}") for k in ("estimate_slices", "write_slice_transforms"))
+    if rounds is not None:
+        if slices_dir is not None:
+            p.error(f"--{prefix}sr_estimate_slices finds the poses that --{prefix}sr_slice_transforms reads: give one of them")
+        if rounds < 1:
+            p.error(f"--{prefix}sr_estimate_slices must be >= 1")
+        out["estimate_slices"] = rounds
+    if write_dir is not None:
+        if rounds is None:
+            p.error(f"--{prefix}sr_write_slice_transforms needs --{prefix}sr_estimate_slices")
+        out["write_slice_transforms_dir"] = write_dir
     return out
 
 

@@ -28,6 +28,8 @@ masks, phantom labels  ``_gpu_morph``      ``_morph``
 rigid registration     ``_gpu_register``   ``_register`` (and the optimizer, which is host code); here as ``register``
 atlas labels           ``_gpu_atlas``      ``_atlas`` (affine registration by the correlation ratio: ``register``); here as ``atlas``
 super-resolution       ``_gpu_sr``         ``_sr`` (operator, adjoint and the proximal-gradient loop; the prox is ``_tv``); here as ``sr``
+slice-to-volume        ``_gpu_register``,  ``_svr`` (batched per-slice sums, transform model, lockstep descent and driver, which are host
+registration           ``_gpu_sr``         code); here as ``register.register_slices``, ``register.slice_sums``, ``sr.reconstruct_svr``
 N4 bias field          ``_gpu_bias``       ``_bias`` (and the sharpening table, the refinement and the loop, which are host code); here as ``bias``
 =====================  ==================  ===========================================================
 

@@ -812,6 +812,55 @@ int t2fit_register_mi_gradient_dev(const uint8_t *bins_dev, const double *table_
                                    const double *A, double *sums_dev, void *workspace_dev, size_t workspace_bytes,
                                    void *stream);
 
+/* ---- Slice-to-volume registration: the 43 sums of every slice of every stack, batched ------------------------------------
+ * The device half of the step that finds the per-slice poses t2fit_sr_slice_*_dev consume: one launch evaluates the
+ * correlation metric's 43 sums of K slices, each slice of each stack under an affine of its own, against one volume.  The
+ * metric arithmetic, the transform model and the descent that advances all slices in lockstep are host code
+ * (fetal_t2mapping_amd/_svr.py, which also restates everything here in numpy; the device results equal it bit for bit;
+ * DESIGN.md 8l).  Additive to ABI 5: four new symbols (look them up).
+ *
+ * PER SLICE.  The fixed image is plane k of stack s, float32 [ly][lx], with the stack's mask plane (a NULL mask: all ones);
+ * the moving image is the volume [mz][my][mx] with its mask (NULL: all ones).  A_k (12 doubles, the order of evaluation of
+ * t2fit_resample_dev) maps the slice index (ix, iy, k) to a continuous index of the volume.  The counting rule, f, m, g_a,
+ * the flat-gradient rule, the 43 terms and their rounding order are those of t2fit_register_sums_dev with
+ * u = (ix, iy, k, 1): u_z is the slice's index in its stack.  A voxel that does not count adds +0.0; slot 42 stays +0.0.
+ *
+ * THE SLICE TREE is a function of (ly, lx) alone and differs from the volume's on purpose (a slice has no z to walk).
+ * The slice is cut into bricks of 64 (x) x 32 (y) voxels, padded with zeros.  In a brick, column x of row group w (0..3)
+ * adds its rows y = 32 by + 8 w + r, r = 0..7, in order starting from 0.0; the 64 columns of a row group are added by
+ * halving; the 4 row groups as (w0 + w2) + (w1 + w3): the brick's slab.  The slabs, in (by, bx) order, bx fastest, are
+ * reduced in the passes of 256 written above for t2fit_register_sums_dev.  In a batch every slice is padded with slabs of
+ * +0.0 up to the largest slab count of any stack; adding +0.0 changes no bit of a sum.
+ *
+ * THE TABLE: a record of T2FIT_SVR_RECORD_BYTES = 128 bytes per slice, record r at byte 128 r: A[12] float64, then int32
+ * stack, slice, active, and 5 pad words of 0.  Records may come in any order and a (stack, slice) pair more than once.
+ * sums_dev: device float64 [n_slices][43], row r for record r.  A record with active == 0, or whose stack index is outside
+ * 0 .. n_stacks - 1 or whose slice index is outside its stack, gives a row of +0.0: the table is data, not a trusted
+ * argument, and whatever it holds the kernel ends and stays inside its buffers.  A non-finite A counts no voxel (the
+ * inside test is false for NaN).  t2fit_svr_table_host packs the table on the host (no device) and refuses, before it
+ * writes a byte: a NULL pointer, n_slices < 1, n_stacks outside 1 .. T2FIT_SR_MAX_STACKS, a size < 1, a non-finite A, a
+ * stack or slice index out of range, a buffer smaller than t2fit_svr_table_bytes says.  lo_size: int32 [n_stacks][3] =
+ * (lz, ly, lx).
+ *
+ * t2fit_svr_workspace_bytes: with n_0 = the largest ceil(lx / 64) ceil(ly / 32) of any stack and n_{p+1} = ceil(n_p / 256)
+ * while n_p > 256, the sum over the passes of up(43 * 8 * n_slices * n_p), up(v) = v rounded up to 256.
+ *
+ * t2fit_svr_sums_dev: fixed_dev / fixed_mask_dev are HOST arrays of n_stacks device pointers (fixed_mask_dev or an entry
+ * of it may be NULL: all ones); one launch for the slabs, one per pass (split where 43 n_slices exceeds a grid's y
+ * extent).  Asynchronous on `stream`; no allocation, copy or synchronisation.  Checked before HIP is touched
+ * (T2FIT_E_INVALID and a message): a NULL pointer, n_stacks outside 1 .. T2FIT_SR_MAX_STACKS, n_slices < 1, a size < 1,
+ * more than 2^40 elements in a stack or the volume, more than 2^31-1 workgroups, float pointers not aligned to 4 bytes,
+ * sums_dev or table_dev not aligned to 8, a workspace that is not aligned to 256 bytes or too small. */
+#define T2FIT_SVR_RECORD_BYTES 128
+int t2fit_svr_table_bytes(int n_slices, size_t *bytes);
+int t2fit_svr_table_host(int n_slices, const double *A /* [n][12] */, const int32_t *stack, const int32_t *slice,
+                         const uint8_t *active, int n_stacks, const int32_t *lo_size, void *table_host, size_t bytes);
+int t2fit_svr_workspace_bytes(int n_stacks, const int32_t *lo_size, int n_slices, size_t *bytes);
+int t2fit_svr_sums_dev(int n_stacks, const float *const *fixed_dev, const uint8_t *const *fixed_mask_dev,
+                       const int32_t *lo_size, const float *moving_dev, const uint8_t *moving_mask_dev, int mz, int my,
+                       int mx, const void *table_dev, int n_slices, double *sums_dev, void *workspace_dev,
+                       size_t workspace_bytes, void *stream);
+
 /* ---- N4 bias-field correction: log image, sharpening histogram, B-spline fit, field -------------------------------------
  * The device half of the reference's run_biasfield_correction / run_biasfield_correction2 (utils/qmri_utils.py:254-357),
  * which call sitk.N4BiasFieldCorrectionImageFilter.  The definition is written from the N4 paper (Tustison 2010), the
