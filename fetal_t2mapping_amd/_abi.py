@@ -72,6 +72,12 @@ SR_PROFILE_BOX, SR_PROFILE_BSPLINE3 = 0, 1
 SR_PROFILES = {"box": SR_PROFILE_BOX, "bspline3": SR_PROFILE_BSPLINE3}
 SR_MAX_STACKS = 6
 SR_SLICE_RECORD_BYTES = 208
+SR_ROBUST_MAX_SLICES = 4096
+
+
+class T2FitSrRobustParams(C.Structure):
+    _fields_ = [("slice_threshold", C.c_double), ("huber", C.c_double), ("sigma_floor", C.c_double), ("min_count", C.c_int32),
+                ("flags", C.c_int32)]
 
 REGISTER_SUMS = 43
 SVR_RECORD_BYTES = 128
@@ -127,6 +133,10 @@ SYMBOLS = [
     ("t2fit_sr_slice_adjoint_dev", C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32),
                                              C.POINTER(C.c_int32), C.POINTER(C.c_double), _P, C.c_double, _P, C.c_int, C.c_int, C.c_int,
                                              C.c_int, _P]),
+    ("t2fit_sr_robust_params_default", C.c_int, [C.POINTER(T2FitSrRobustParams)]),
+    ("t2fit_sr_robust_workspace_bytes", C.c_int, [C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_size_t)]),
+    ("t2fit_sr_robust_dev", C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32), C.c_int,
+                                      C.POINTER(T2FitSrRobustParams), _P, _P, _P, _P]),
     ("t2fit_morph_workspace_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     ("t2fit_binary_threshold_dev", C.c_int, [_P, C.c_int, C.c_int64, C.c_double, C.c_double, _P, _P]),
     ("t2fit_binary_morph_dev", C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -193,7 +203,9 @@ SR_SYMBOLS = ("t2fit_sr_plan_host", "t2fit_sr_workspace_bytes", "t2fit_sr_forwar
 SR_SLICE_SYMBOLS = ("t2fit_sr_slice_table_bytes", "t2fit_sr_slice_table_host", "t2fit_sr_slice_forward_dev",
                     "t2fit_sr_slice_adjoint_dev")
 SVR_SYMBOLS = ("t2fit_svr_table_bytes", "t2fit_svr_table_host", "t2fit_svr_workspace_bytes", "t2fit_svr_sums_dev")
-LOOKED_UP = ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS + MI_SYMBOLS + SR_SYMBOLS + SR_SLICE_SYMBOLS + SVR_SYMBOLS
+SR_ROBUST_SYMBOLS = ("t2fit_sr_robust_params_default", "t2fit_sr_robust_workspace_bytes", "t2fit_sr_robust_dev")
+LOOKED_UP = (ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS + MI_SYMBOLS + SR_SYMBOLS + SR_SLICE_SYMBOLS + SVR_SYMBOLS
+             + SR_ROBUST_SYMBOLS)
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

@@ -251,9 +251,64 @@ def sr_adjoint_slices(r, N, B_slices, profile, rel_thickness, hr_shape, *, masks
     return out if is_t else out.cpu().numpy()
 
 
+# ---- outlier weighting ---------------------------------------------------------------------------------------------------
+def robust_struct(params):
+    """``t2fit_sr_robust_params`` from the checked dict of :func:`_sr.robust_params`."""
+    return _abi.T2FitSrRobustParams(params["slice_threshold"], params["huber"], params["sigma_floor"], params["min_count"], 0)
+
+
+def _robust(lib, r, n_list, masks, lr_shapes, n_vol, par, sums, weights, sigma2):
+    """Queue t2fit_sr_robust_dev on flat device tensors; ``masks`` is a list that may hold None."""
+    n_s = len(r)
+    ptrs = lambda ts: (C.c_void_p * n_s)(*[None if t is None else t.data_ptr() for t in ts])
+    check(lib.t2fit_sr_robust_dev(n_s, ptrs(r), ptrs(n_list), ptrs(masks), (C.c_int32 * (3 * n_s))(*[v for s in lr_shapes for v in s]),
+                                  n_vol, C.byref(par), sums.data_ptr(), weights.data_ptr(), sigma2.data_ptr(), current_stream()))
+
+
+def sr_robust_weights(r, N, *, masks=None, device=0, **params):
+    """The outlier weighting of the robust loop on the residuals of 1 to 6 stacks, as :func:`_sr.robust_step` defines it, bit
+    for bit: ``r`` a list of float32 residuals ``(lz, ly, lx)`` or ``(n, lz, ly, lx)``, ``N`` the normalisers of
+    :func:`sr_forward`, ``masks`` a list that may hold None; ``params``: ``slice_threshold``, ``huber``, ``min_count``,
+    ``sigma_floor`` (:data:`_sr.ROBUST_DEFAULTS`).  Returns ``(weighted r, slice weights, sigma2, sums)``: lists over the
+    stacks of residuals like ``r`` (the inputs stay as they are) and of ``(n, lz)`` float64 weights, ``(n,)`` and
+    ``(n, n_slices, 2)`` float64.  numpy in, numpy out; CUDA tensors in, tensors out (asynchronous on the current stream)."""
+    import torch
+
+    lib = require(*_abi.SR_ROBUST_SYMBOLS)
+    par = robust_struct(_sr.robust_params(params or True))
+    n_s = len(r)
+    if not 1 <= n_s <= _abi.SR_MAX_STACKS or len(N) != n_s:
+        raise ValueError(f"between 1 and {_abi.SR_MAX_STACKS} stacks with one N each")
+    masks = [None] * n_s if masks is None else list(masks)
+    shapes = [_shape4(v, "a residual") for v in r]
+    if len({s[0] for s in shapes}) != 1:
+        raise ValueError("the residuals differ in their number of volumes")
+    n_vol, n_slices = shapes[0][0], sum(s[1] for s in shapes)
+    if n_slices > _abi.SR_ROBUST_MAX_SLICES:
+        raise ValueError(f"at most {_abi.SR_ROBUST_MAX_SLICES} slices in total, got {n_slices}")
+    is_t = is_tensor(r[0])
+    dev = pick_device(list(r), device)
+    with torch.cuda.device(dev):
+        rt = [flat(v, dev).clone() for v in r]
+        nt = [flat(v, dev, int(np.prod(s[-3:])), "N", dtype="float64") for v, s in zip(N, shapes)]
+        mt = [_mask(m, dev, int(np.prod(s[-3:]))) for m, s in zip(masks, shapes)]
+        sums = torch.empty((n_vol, n_slices, 2), dtype=torch.float64, device=dev)
+        weights = torch.empty((n_vol, n_slices), dtype=torch.float64, device=dev)
+        sigma2 = torch.empty(n_vol, dtype=torch.float64, device=dev)
+        _robust(lib, rt, nt, mt, [s[-3:] for s in shapes], n_vol, par, sums, weights, sigma2)
+        release(*nt, *mt)
+    edges = np.cumsum([0] + [s[1] for s in shapes])
+    out = [t.reshape(tuple(v.shape)) for t, v in zip(rt, r)]
+    per_stack = [weights[:, edges[s]:edges[s + 1]] for s in range(n_s)]
+    if is_t:
+        return out, [w.contiguous() for w in per_stack], sigma2, sums
+    host = lambda t: t.cpu().numpy()
+    return [host(t) for t in out], [np.ascontiguousarray(host(w)) for w in per_stack], host(sigma2), host(sums)
+
+
 def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thickness=None, profile="box",
                    weight=_sr.DEFAULT_WEIGHT, n_iter=_sr.DEFAULT_N_ITER, prox_iter=_sr.DEFAULT_PROX_ITER, stack_masks=None,
-                   x0=None, return_info=False, device=0, slice_transforms=None):
+                   x0=None, return_info=False, device=0, slice_transforms=None, robust=None):
     """TV-regularised super-resolution reconstruction of 1 to 6 thick-slice stacks on the GPU.  Each slice is modelled as
     the slice-profile average of the ``res`` mm volume x on the ``fixed`` stack's isotropic grid, and per echo
 
@@ -272,13 +327,20 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
     stack-wise path.
     Returns ``(echoes, header)`` like :func:`reconstruct_stacks`: a float32 CUDA tensor ``(nTE, Z, Y, X)`` and a
     ``nifti.Image`` over an empty array with the grid's geometry; with ``return_info`` also ``{"tau", "column_max", "N"}``.
+    ``robust`` (None, True for :data:`_sr.ROBUST_DEFAULTS`, or a dict of them): outlier weighting.  Every iteration
+    multiplies its residuals by a weight per slice and a Huber weight per sample, both scaled by a robust noise estimate per
+    echo (:func:`sr_robust_weights`, one more launch group, still no synchronisation); the info then also holds
+    ``"slice_weights"`` (one float64 ``(nTE, lz)`` tensor per stack), ``"sigma2"`` (``(nTE,)``) and ``"robust_sums"``
+    (``(nTE, n_slices, 2)``: count and sum of squares per slice) of the last iteration.  None launches none of it.
     The step size is read back once before the loop (one synchronisation); the loop itself queues 3 + stacks launch groups
     per iteration and does not synchronise.  :func:`_sr.reconstruct_sr` states the definition in numpy; same bits."""
     import torch
 
     from . import nifti
 
-    lib = require(*(_abi.SR_SYMBOLS + _abi.TV_SYMBOLS + (() if slice_transforms is None else _abi.SR_SLICE_SYMBOLS)))
+    robust = _sr.robust_params(robust)
+    lib = require(*(_abi.SR_SYMBOLS + _abi.TV_SYMBOLS + (() if slice_transforms is None else _abi.SR_SLICE_SYMBOLS)
+                    + (() if robust is None else _abi.SR_ROBUST_SYMBOLS)))
     if not (float(weight) >= 0.0 and np.isfinite(weight)) or int(n_iter) < 0 or int(prox_iter) < 1:
         raise ValueError("weight must be finite and >= 0, n_iter >= 0, prox_iter >= 1")
     pid = _sr._profile_id(profile)
@@ -300,6 +362,10 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
     lo_size = (C.c_int32 * (3 * n_s))(*[v for s in lr_shapes for v in s])
     need = C.c_size_t(0)
     check(lib.t2fit_sr_workspace_bytes(n_s, lo_size, *hr_shape, n_vol, C.byref(need)))
+    robust_need, n_slices = C.c_size_t(0), sum(s[0] for s in lr_shapes)
+    if robust is not None:
+        check(lib.t2fit_sr_robust_workspace_bytes(n_s, lo_size, n_vol, C.byref(robust_need)))
+        robust_par = robust_struct(robust)
     n_h = int(np.prod(hr_shape))
     with torch.cuda.device(dev):
         y = [flat(stacks[o], dev) for o in order]
@@ -311,7 +377,7 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
             x = reconstruct_stacks({o: stacks[o] for o in order}, g, fixed=fixed, res=res, transforms=transforms, device=dev.index)[0].reshape(-1)
         else:
             x = resample_volume(y[0].reshape((n_vol,) + lr_shapes[0]), g[order[0]], like=hi)[0].reshape(-1)
-        ws, base = workspace(need.value, dev)
+        ws, base = workspace(need.value + robust_need.value, dev)
         off = base - ws.data_ptr()
 
         def carve(nbytes, dtype):
@@ -326,6 +392,11 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
             N.append(carve(8 * int(np.prod(s)), torch.float64))
             r.append(carve(4 * n_vol * int(np.prod(s)), torch.float32))
         assert off - (base - ws.data_ptr()) == need.value
+        if robust is not None:
+            sums = carve(16 * n_vol * n_slices, torch.float64)
+            q = carve(8 * n_vol * n_slices, torch.float64)
+            sigma2 = carve(8 * n_vol, torch.float64)
+            assert off - (base - ws.data_ptr()) == need.value + robust_need.value
         if tables is None:
             def fwd(s, xs, nv, ys, ms, out, n_out):
                 _forward(lib, xs, hr_shape, nv, B[s], boxes[s], pid, rels[s], ys, ms, lr_shapes[s], out, n_out)
@@ -361,6 +432,8 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
         for _ in range(int(n_iter)):
             for s in range(n_s):
                 fwd(s, x, n_vol, y[s], masks[s], r[s], None)
+            if robust is not None:
+                _robust(lib, r, N, masks, lr_shapes, n_vol, robust_par, sums, q, sigma2)
             if float(weight) > 0.0:
                 adj(range(n_s), r, x, tau, z, n_vol)
                 check(lib.t2fit_tv_denoise_dev(C.byref(par), z.data_ptr(), x.data_ptr(), n_vol, *hr_shape, tv_ptr, tv_need.value,
@@ -368,6 +441,13 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
             else:
                 adj(range(n_s), r, x, tau, x, n_vol)
         info = {"tau": tau, "column_max": col_max, "N": [n.clone().reshape(s) for n, s in zip(N, lr_shapes)]} if return_info else None
+        if return_info and robust is not None:
+            ran = int(n_iter) > 0
+            edges = np.cumsum([0] + [s[0] for s in lr_shapes])
+            table = q.reshape(n_vol, n_slices)
+            info["slice_weights"] = [table[:, edges[s]:edges[s + 1]].clone() for s in range(n_s)] if ran else None
+            info["sigma2"] = sigma2.clone() if ran else None
+            info["robust_sums"] = sums.reshape(n_vol, n_slices, 2).clone() if ran else None
         if float(weight) > 0.0:
             release(tv_ws)
         release(ws, *y, *[m for m in masks if m is not None], *(tables or []))

@@ -20,7 +20,11 @@ kernel.
 A stack acquired slice by slice from a moving subject has a rigid pose per slice: :func:`forward_slices`,
 :func:`adjoint_slices` and ``reconstruct_sr(slice_transforms=...)`` take an affine per slice (``(lz, 3, 4)``, from
 :func:`slice_affines`), sample ``j`` forming its weights from ``u = coord(B[j_z], v)``; the statement of
-t2fit_sr_slice_forward_dev / t2fit_sr_slice_adjoint_dev."""
+t2fit_sr_slice_forward_dev / t2fit_sr_slice_adjoint_dev.
+
+Bad slices (drop-outs, stripes, misplaced slices) are weighted down by ``reconstruct_sr(robust=...)``: every iteration
+multiplies its residuals by a weight per slice and a Huber weight per sample (:func:`robust_step`, the statement of
+t2fit_sr_robust_dev: only +, x, /, sqrt and comparisons, the slice sums in the device's tree lane by lane)."""
 from __future__ import annotations
 
 import numpy as np
@@ -511,10 +515,159 @@ def initial_volume(stacks, geoms, order, hi, res, transforms):
     return _resample.resample(np.asarray(stacks[order[0]], np.float32), _resample.index_affine(hi, g), hi.shape)
 
 
-def iterate(x, y, N, B, profile, rels, tau, weight, prox_iter, masks=None, out_dtype=np.float32):
-    """One proximal-gradient step on ``x`` ``(n, Z, Y, X)``: residuals of every stack, the update ``z``, the TV prox."""
+# ---- outlier weighting: a weight per slice and a Huber weight per sample ------------------------------------------------
+ROBUST_DEFAULTS = {"slice_threshold": 1.5, "huber": 2.5, "min_count": 16, "sigma_floor": 0.0}  # the sweep
+ROBUST_MAX_SLICES = 4096
+ROBUST_LANES, ROBUST_WAVE = 256, 64
+
+
+def robust_params(robust):
+    """None for ``None`` / ``False``, the defaults for ``True``, a checked copy of the defaults updated by a dict."""
+    if robust is None or robust is False:
+        return None
+    p = dict(ROBUST_DEFAULTS)
+    if robust is not True:
+        if not isinstance(robust, dict):
+            raise ValueError(f"robust is None, True or a dict of {sorted(ROBUST_DEFAULTS)}, got {robust!r}")
+        unknown = [k for k in robust if k not in p]
+        if unknown:
+            raise ValueError(f"robust takes {sorted(ROBUST_DEFAULTS)}, got {unknown}")
+        p.update(robust)
+    for k in ("slice_threshold", "huber"):
+        p[k] = float(p[k])
+        if not (p[k] > 0.0 and np.isfinite(p[k])):
+            raise ValueError(f"robust {k} must be finite and > 0, got {p[k]!r}")
+    p["sigma_floor"] = float(p["sigma_floor"])
+    if not (p["sigma_floor"] >= 0.0 and np.isfinite(p["sigma_floor"])):
+        raise ValueError(f"robust sigma_floor must be finite and >= 0, got {p['sigma_floor']!r}")
+    if int(p["min_count"]) != p["min_count"] or int(p["min_count"]) < 1:
+        raise ValueError(f"robust min_count must be an integer >= 1, got {p['min_count']!r}")
+    p["min_count"] = int(p["min_count"])
+    return p
+
+
+def _robust_counted(rv, N, mask):
+    """Which samples of ``rv`` ``(n, lz, ly, lx)`` are counted: ``N > 0``, the mask byte set, the residual finite."""
+    c = np.asarray(N, np.float64).reshape(rv.shape[-3:]) > 0.0
+    if mask is not None:
+        c &= np.asarray(mask).reshape(c.shape) != 0
+    return c[None] & np.isfinite(rv)
+
+
+def robust_slice_sums(r, N, mask=None):
+    """``(n, lz, 2)`` float64: per echo and slice the number ``c`` of counted samples and ``q2 = sum (double)r (double)r``
+    over them, in the device's tree, lane by lane: lane ``t`` of 256 adds the samples ``i = t, t + 256, ...`` of the
+    slice's ``ly lx`` in ascending ``i``; each wave of 64 lanes adds by the xor butterfly 32, 16, .., 1; the four waves meet
+    as ``((w0 + w1) + w2) + w3``."""
+    rv = _volumes(r)[0]
+    n_vol, lz, ly, lx = rv.shape
+    plane = ly * lx
+    rows = -(-plane // ROBUST_LANES)
+    pad = ((0, 0), (0, 0), (0, rows * ROBUST_LANES - plane))
+    ok = np.pad(_robust_counted(rv, N, mask).reshape(n_vol, lz, plane), pad).reshape(n_vol, lz, rows, ROBUST_LANES)
+    d = np.pad(rv.astype(np.float64).reshape(n_vol, lz, plane), pad).reshape(n_vol, lz, rows, ROBUST_LANES)
+    c = np.zeros((n_vol, lz, ROBUST_LANES), np.float64)
+    q2 = np.zeros((n_vol, lz, ROBUST_LANES), np.float64)
+    with np.errstate(all="ignore"):
+        for i in range(rows):
+            q2 = np.where(ok[:, :, i], q2 + d[:, :, i] * d[:, :, i], q2)
+            c = np.where(ok[:, :, i], c + 1.0, c)
+    lane = np.arange(ROBUST_LANES)
+    out = []
+    for v in (c, q2):
+        for s in (32, 16, 8, 4, 2, 1):
+            v = v + v[..., lane ^ s]
+        w = v[..., ::ROBUST_WAVE]
+        out.append(((w[..., 0] + w[..., 1]) + w[..., 2]) + w[..., 3])
+    return np.stack(out, axis=-1)
+
+
+def robust_scale(sums, params=None):
+    """``(weights (n, n_slices), sigma2 (n,))`` from the sums of every slice of every stack, ``(n, n_slices, 2)``, listed
+    stack-major and ascending in slice index.  Per echo: slice k is eligible when ``c >= min_count``, then ``m_k = q2 / c``;
+    with ``v`` the sorted eligible ``m``, ``sigma2 = max(0.5 (v[(n - 1) // 2] + v[n // 2]), sigma_floor^2)``; no eligible
+    slice or ``sigma2`` not > 0: robustness is off (weights 1, ``sigma2`` reported 0).  ``q_k = 1`` if the slice is not
+    eligible or ``m_k <= t^2 sigma2``, else ``(t^2 sigma2) / m_k``."""
+    p = robust_params(True if params is None else params)
+    sums = np.asarray(sums, np.float64)
+    n_vol, n_slices = sums.shape[:2]
+    if n_slices > ROBUST_MAX_SLICES:
+        raise ValueError(f"at most {ROBUST_MAX_SLICES} slices in total, got {n_slices}")
+    tt, floor2 = p["slice_threshold"] * p["slice_threshold"], p["sigma_floor"] * p["sigma_floor"]
+    weights, sigma2 = np.ones((n_vol, n_slices), np.float64), np.zeros(n_vol, np.float64)
+    for e in range(n_vol):
+        c, q2 = sums[e, :, 0], sums[e, :, 1]
+        eligible = c >= float(p["min_count"])
+        m = np.where(eligible, q2 / np.where(eligible, c, 1.0), -1.0)
+        v = np.sort(m[eligible])
+        n = len(v)
+        if n == 0:
+            continue
+        s2 = 0.5 * (v[(n - 1) // 2] + v[n // 2])
+        s2 = s2 if s2 > floor2 else floor2
+        if not s2 > 0.0:
+            continue
+        sigma2[e] = s2
+        limit = tt * s2
+        down = eligible & ~(m <= limit)
+        weights[e] = np.where(down, limit / np.where(down, m, 1.0), 1.0)
+    return weights, sigma2
+
+
+def robust_apply(r, N, mask, weights, sigma2, params=None):
+    """The weighted residual of one stack: ``weights`` ``(n, lz)`` are its slices' ``q``, ``sigma2`` ``(n,)``.  A counted
+    sample becomes ``(float)((q_k w_j) (double)r_j)`` with ``w_j = 1`` if ``|r_j| <= delta`` else ``delta / |r_j|``,
+    ``delta = huber sqrt(sigma2)``; a sample that is not counted becomes +0.0; an echo with ``sigma2 = 0`` stays as it is."""
+    p = robust_params(True if params is None else params)
+    rv = _volumes(r)[0]
+    ok = _robust_counted(rv, N, mask)
+    s2 = np.asarray(sigma2, np.float64).reshape(-1, 1, 1, 1)
+    q = np.asarray(weights, np.float64).reshape(rv.shape[0], rv.shape[1], 1, 1)
+    with np.errstate(all="ignore"):
+        delta = p["huber"] * np.sqrt(s2)
+        d = rv.astype(np.float64)
+        ad = np.abs(d)
+        inside = ad <= delta
+        w = np.where(inside, 1.0, delta / np.where(inside, 1.0, ad))
+        out = np.where(ok, (q * w) * d, 0.0).astype(rv.dtype)
+    out = np.where(s2 > 0.0, out, rv)
+    return out.reshape(np.shape(r))
+
+
+def robust_step(r, N, masks=None, params=None):
+    """``(weighted r, slice weights, sigma2, sums)`` of all stacks: lists over the stacks of residuals and normalisers.
+    ``slice weights``: one ``(n, lz_s)`` array per stack; ``sums``: ``(n, n_slices, 2)`` over all slices, stack-major."""
+    p = robust_params(True if params is None else params)
+    n_s = len(r)
+    if not 1 <= n_s <= MAX_STACKS or len(N) != n_s:
+        raise ValueError(f"between 1 and {MAX_STACKS} stacks with one N each, got {n_s}")
+    masks = [None] * n_s if masks is None else list(masks)
+    sums = np.concatenate([robust_slice_sums(r[s], N[s], masks[s]) for s in range(n_s)], axis=1)
+    weights, sigma2 = robust_scale(sums, p)
+    edges = np.cumsum([0] + [_volumes(v)[0].shape[1] for v in r])
+    per_stack = [weights[:, edges[s]:edges[s + 1]].copy() for s in range(n_s)]
+    out = [robust_apply(r[s], N[s], masks[s], per_stack[s], sigma2, p) for s in range(n_s)]
+    return out, per_stack, sigma2, sums
+
+
+def _reweigh(r, N, masks, robust, info):
+    """The residuals after :func:`robust_step` when ``robust`` asks for it; ``info`` (a dict or None) takes the tables."""
+    p = robust_params(robust)
+    if p is None:
+        return r
+    r, weights, sigma2, sums = robust_step(r, N, masks, p)
+    if info is not None:
+        info.update(slice_weights=weights, sigma2=sigma2, robust_sums=sums)
+    return r
+
+
+def iterate(x, y, N, B, profile, rels, tau, weight, prox_iter, masks=None, out_dtype=np.float32, robust=None, info=None):
+    """One proximal-gradient step on ``x`` ``(n, Z, Y, X)``: residuals of every stack, the update ``z``, the TV prox.
+    ``robust`` (None, True or a dict of :data:`ROBUST_DEFAULTS`): the residuals pass through :func:`robust_step` first;
+    ``info``: a dict that then receives ``slice_weights``, ``sigma2`` and ``robust_sums``."""
     r = [forward(x, B[s], y[s].shape[-3:], profile, rels[s], y=y[s], mask=None if masks is None else masks[s],
                  out_dtype=out_dtype)[0] for s in range(len(y))]
+    r = _reweigh(r, N, masks, robust, info)
     z = adjoint(r, N, B, profile, rels, x.shape[-3:], masks=masks, x=x, tau=tau, out_dtype=out_dtype)
     if not weight > 0.0:
         return z
@@ -523,10 +676,12 @@ def iterate(x, y, N, B, profile, rels, tau, weight, prox_iter, masks=None, out_d
     return np.stack([_tv.tv_problem(v, tau * weight, 0.0, prox_iter, np.float64)[0] for v in z])
 
 
-def iterate_slices(x, y, N, B, profile, rels, tau, weight, prox_iter, masks=None, out_dtype=np.float32):
+def iterate_slices(x, y, N, B, profile, rels, tau, weight, prox_iter, masks=None, out_dtype=np.float32, robust=None,
+                   info=None):
     """:func:`iterate` on the slice operators: ``B[s]`` is ``(lz_s, 3, 4)``."""
     r = [forward_slices(x, B[s], y[s].shape[-3:], profile, rels[s], y=y[s], mask=None if masks is None else masks[s],
                         out_dtype=out_dtype)[0] for s in range(len(y))]
+    r = _reweigh(r, N, masks, robust, info)
     z = adjoint_slices(r, N, B, profile, rels, x.shape[-3:], masks=masks, x=x, tau=tau, out_dtype=out_dtype)
     if not weight > 0.0:
         return z
@@ -537,14 +692,18 @@ def iterate_slices(x, y, N, B, profile, rels, tau, weight, prox_iter, masks=None
 
 def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thickness=None, profile="box",
                    weight=DEFAULT_WEIGHT, n_iter=DEFAULT_N_ITER, prox_iter=DEFAULT_PROX_ITER, stack_masks=None, x0=None,
-                   return_info=False, out_dtype=np.float32, slice_transforms=None):
+                   return_info=False, out_dtype=np.float32, slice_transforms=None, robust=None):
     """The whole reconstruction on the host, argument for argument ``t2map.reconstruct_sr``.  Returns ``(x, Geometry of H)``
     and with ``return_info`` also ``{"tau", "N", "column_max"}``.  ``slice_transforms``: ``{stack name: (lz, 4, 4)}``, a pose
     per slice (fixed point -> stack point) in place of the stack's transform; the fixed stack may have an entry, stacks
     without one carry their stack transform on every slice.  Then N, tau and the loop run on :func:`forward_slices` and
-    :func:`adjoint_slices`; ``x0`` stays the merge.  None: the stack-wise operators."""
+    :func:`adjoint_slices`; ``x0`` stays the merge.  None: the stack-wise operators.  ``robust`` (None, True for
+    :data:`ROBUST_DEFAULTS`, or a dict of them): every iteration reweighs its residuals by :func:`robust_step`; the info then
+    also holds ``"slice_weights"`` (one ``(n_vol, lz)`` array per stack) and ``"sigma2"`` (``(n_vol,)``) of the last
+    iteration (None when there was none)."""
     if not (float(weight) >= 0.0 and np.isfinite(weight)) or int(n_iter) < 0 or int(prox_iter) < 1:
         raise ValueError("weight must be finite and >= 0, n_iter >= 0, prox_iter >= 1")
+    robust = robust_params(robust)
     pid = _profile_id(profile)
     names = [o for o in geoms if o in stacks]
     shapes = {o: np.asarray(stacks[o]).shape for o in names}
@@ -567,10 +726,17 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
     x = x.reshape((-1,) + hi.shape).astype(out_dtype)
     if len(x) != len(y[0]):
         raise ValueError("x0 does not have the stacks' number of echoes")
+    last = {"slice_weights": None, "sigma2": None}
     for _ in range(int(n_iter)):
-        x = step(x, y, N, B, pid, rels, tau, float(weight), int(prox_iter), masks, out_dtype)
+        if robust is None:
+            x = step(x, y, N, B, pid, rels, tau, float(weight), int(prox_iter), masks, out_dtype)
+        else:
+            x = step(x, y, N, B, pid, rels, tau, float(weight), int(prox_iter), masks, out_dtype, robust=robust, info=last)
     if np.asarray(stacks[order[0]]).ndim == 3:
         x = x[0]
     if return_info:
-        return x, hi, {"tau": tau, "N": N, "column_max": col_max}
+        info = {"tau": tau, "N": N, "column_max": col_max}
+        if robust is not None:
+            info.update(last)
+        return x, hi, info
     return x, hi

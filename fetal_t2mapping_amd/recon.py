@@ -164,7 +164,8 @@ def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False
     whatever ``integer_cast`` says); its entry ``slice_transforms_dir`` (``--sr_slice_transforms``) names a directory of
     :func:`load_slice_transforms` files, read per echo and passed on as ``slice_transforms``; its entry ``estimate_slices``
     (``--sr_estimate_slices``) is the number of rounds of ``t2map.sr.reconstruct_svr``, which finds those poses on the first
-    echo of each call, and ``write_slice_transforms_dir`` where they are written for every echo.  Returns ``(float32 CUDA tensor
+    echo of each call, and ``write_slice_transforms_dir`` where they are written for every echo; its entry
+    ``write_slice_weights`` (``--sr_write_slice_weights``, with ``robust``) names the CSV of :func:`save_slice_weights`.  Returns ``(float32 CUDA tensor
     (n, Z, Y, X), header, transforms per echo)``."""
     import torch
 
@@ -179,11 +180,15 @@ def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False
                 save_transforms(write_transforms, acq, t)
     else:
         per_echo = [load_transforms(transforms_dir, acq, fixed) for acq in acqs]
-    slices_dir = rounds = write_slices = None
+    slices_dir = rounds = write_slices = weights_file = None
+    robust_info = []
     if sr is not None:
         sr = dict(sr)
         slices_dir, rounds = sr.pop("slice_transforms_dir", None), sr.pop("estimate_slices", None)
         write_slices = sr.pop("write_slice_transforms_dir", None)
+        weights_file = sr.pop("write_slice_weights", None)
+        if weights_file and (rounds or not sr.get("robust")):
+            raise ValueError("write_slice_weights needs robust and is not available with estimate_slices")
     per_slice = [load_slice_transforms(slices_dir, acq, geoms, fixed) for acq in acqs]
     groups = []
     for i in range(n):
@@ -203,8 +208,13 @@ def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False
                 save_slice_transforms(write_slices, acqs[i], found.transforms)
         elif sr is not None:
             poses = {"slice_transforms": per_slice[g[0]]} if slices_dir else {}
-            out, header = t2map.sr.reconstruct_sr(part, geoms, fixed=fixed, res=res, transforms=per_echo[g[0]], device=device, **sr,
-                                                  **poses)
+            if weights_file:
+                out, header, info = t2map.sr.reconstruct_sr(part, geoms, fixed=fixed, res=res, transforms=per_echo[g[0]],
+                                                            device=device, return_info=True, **sr, **poses)
+                robust_info.append((g, info))
+            else:
+                out, header = t2map.sr.reconstruct_sr(part, geoms, fixed=fixed, res=res, transforms=per_echo[g[0]], device=device,
+                                                      **sr, **poses)
         else:
             out, header = t2map.reconstruct_stacks(part, geoms, fixed=fixed, res=res, transforms=per_echo[g[0]],
                                                    integer_cast=integer_cast, device=device)
@@ -213,6 +223,16 @@ def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False
         else:
             merged = torch.empty((n,) + tuple(out.shape[1:]), dtype=out.dtype, device=out.device) if merged is None else merged
             merged[g] = out
+    if weights_file and robust_info and robust_info[0][1].get("sigma2") is not None:
+        order = [fixed] + [o for o in geoms if o in stacks and o != fixed]
+        lz = [int(stacks[o].shape[-3]) for o in order]
+        weights = [np.ones((n, k), np.float64) for k in lz]
+        sums, sigma2 = np.zeros((n, sum(lz), 2), np.float64), np.zeros(n, np.float64)
+        for g, info in robust_info:
+            for s in range(len(order)):
+                weights[s][g] = info["slice_weights"][s].cpu().numpy()
+            sums[g], sigma2[g] = info["robust_sums"].cpu().numpy(), info["sigma2"].cpu().numpy()
+        save_slice_weights(weights_file, order, weights, sums, sigma2)
     if register_echoes:
         grid = _resample.as_geometry(header, tuple(merged.shape[1:]))
         for i in range(1, n):
@@ -566,7 +586,47 @@ def reconstruct_subject(sitk, bids_path, sub_md, sub, ses, *, fixed="ax", res=1.
 
 
 SR_FLAGS = ("sr_weight", "sr_iter", "sr_profile", "sr_thickness", "sr_slice_transforms", "sr_estimate_slices",
-            "sr_write_slice_transforms")
+            "sr_write_slice_transforms", "sr_robust", "sr_robust_slice", "sr_robust_huber", "sr_write_slice_weights")
+SLICE_WEIGHT_COLUMNS = ("stack", "slice", "echo", "weight", "count", "mean_square_residual")
+
+
+def save_slice_weights(path, order, weights, sums, sigma2):
+    """The slice weights of a robust reconstruction as CSV: a row (stack, slice, echo, weight, count, mean square residual)
+    per slice and echo, then a line ``sigma,<echo>,<sigma>`` per echo.  ``weights``: per stack of ``order`` ``(n, lz)``;
+    ``sums``: ``(n, n_slices, 2)`` count and sum of squares, stack-major; ``sigma2``: ``(n,)``.  Numbers are written with
+    ``repr``, so reading them back gives the same float64."""
+    n = len(sigma2)
+    lines = [",".join(SLICE_WEIGHT_COLUMNS)]
+    k0 = 0
+    for o, w in zip(order, weights):
+        for k in range(w.shape[1]):
+            for e in range(n):
+                c, q2 = float(sums[e, k0 + k, 0]), float(sums[e, k0 + k, 1])
+                lines.append(f"{o},{k},{e},{float(w[e, k])!r},{int(c)},{(q2 / c if c > 0 else 0.0)!r}")
+        k0 += w.shape[1]
+    lines += [f"sigma,{e},{float(np.sqrt(sigma2[e]))!r}" for e in range(n)]
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def load_slice_weights(path):
+    """``(rows, sigma)`` of a :func:`save_slice_weights` file: ``rows`` a list of ``(stack, slice, echo, weight, count, mean
+    square residual)``, ``sigma`` ``{echo: sigma}``."""
+    rows, sigma = [], {}
+    with open(path) as f:
+        header = f.readline().strip().split(",")
+        if tuple(header) != SLICE_WEIGHT_COLUMNS:
+            raise ValueError(f"{path}: expected the columns {SLICE_WEIGHT_COLUMNS}, got {header}")
+        for line in f:
+            v = line.strip().split(",")
+            if v[0] == "sigma" and len(v) == 3:
+                sigma[int(v[1])] = float(v[2])
+            elif len(v) == 6:
+                rows.append((v[0], int(v[1]), int(v[2]), float(v[3]), int(v[4]), float(v[5])))
+            elif line.strip():
+                raise ValueError(f"{path}: cannot read the line {line.strip()!r}")
+    return rows, sigma
 
 
 def add_sr_arguments(p, prefix):
@@ -593,6 +653,18 @@ def add_sr_arguments(p, prefix):
                         f"stack onto the current volume and reconstruct again with the poses found (not with --{prefix}sr_slice_transforms)")
     p.add_argument(f"--{prefix}sr_write_slice_transforms", default=None, metavar="DIR",
                    help=f"sr: write the poses --{prefix}sr_estimate_slices found where --{prefix}sr_slice_transforms reads them")
+    p.add_argument(f"--{prefix}sr_robust", action="store_true",
+                   help="sr: outlier weighting: every iteration weights each slice and each sample down by its residual, scaled by "
+                        "a robust noise estimate per echo (drop-outs, stripes and misplaced slices stop writing into the volume)")
+    p.add_argument(f"--{prefix}sr_robust_slice", type=float, default=None, metavar="T",
+                   help=f"sr, with --{prefix}sr_robust: a slice is weighted down when its mean square residual exceeds T^2 sigma^2 "
+                        f"(default {_sr.ROBUST_DEFAULTS['slice_threshold']})")
+    p.add_argument(f"--{prefix}sr_robust_huber", type=float, default=None, metavar="H",
+                   help=f"sr, with --{prefix}sr_robust: a sample is weighted down when its residual exceeds H sigma "
+                        f"(default {_sr.ROBUST_DEFAULTS['huber']})")
+    p.add_argument(f"--{prefix}sr_write_slice_weights", default=None, metavar="FILE.csv",
+                   help=f"sr, with --{prefix}sr_robust: write the slice weights of the last iteration (stack, slice, echo, weight, "
+                        "count, mean square residual; then sigma per echo)")
 
 
 def sr_arguments(p, args, prefix, argv):
@@ -625,6 +697,21 @@ def sr_arguments(p, args, prefix, argv):
         if rounds is None:
             p.error(f"--{prefix}sr_write_slice_transforms needs --{prefix}sr_estimate_slices")
         out["write_slice_transforms_dir"] = write_dir
+    robust, weights_file = getattr(args, f"{prefix}sr_robust"), getattr(args, f"{prefix}sr_write_slice_weights")
+    tuned = {k: getattr(args, f"{prefix}sr_robust_{f}") for k, f in (("slice_threshold", "slice"), ("huber", "huber"))}
+    for k, f in (("slice_threshold", "slice"), ("huber", "huber")):
+        if tuned[k] is not None and not robust:
+            p.error(f"--{prefix}sr_robust_{f} needs --{prefix}sr_robust")
+        if tuned[k] is not None and not (tuned[k] > 0.0 and np.isfinite(tuned[k])):
+            p.error(f"--{prefix}sr_robust_{f} must be a finite number > 0")
+    if weights_file is not None and not robust:
+        p.error(f"--{prefix}sr_write_slice_weights needs --{prefix}sr_robust")
+    if weights_file is not None and rounds is not None:
+        p.error(f"--{prefix}sr_write_slice_weights is not available with --{prefix}sr_estimate_slices")
+    if robust:
+        out["robust"] = {k: v for k, v in tuned.items() if v is not None} or True
+    if weights_file is not None:
+        out["write_slice_weights"] = weights_file
     return out
 
 

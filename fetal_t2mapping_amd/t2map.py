@@ -47,5 +47,6 @@ from . import _gpu_register as register  # noqa: F401  (a namespace: register.re
 from ._gpu_resample import RECON_FORMS, reconstruct_stacks, resample_volume  # noqa: F401
 from ._gpu_roi import ROI_MAX_LABELS, RoiStats, dense_labels, roi_erode, roi_frame, roi_stats, roi_table  # noqa: F401
 from . import _gpu_sr as sr  # noqa: F401  (a namespace: sr.reconstruct_sr, sr.sr_forward, sr.sr_adjoint, sr.sr_box and, with a
-#                               rigid pose per slice, sr.sr_forward_slices, sr.sr_adjoint_slices, sr.sr_slice_table)
+#                               rigid pose per slice, sr.sr_forward_slices, sr.sr_adjoint_slices, sr.sr_slice_table; the
+#                               outlier weighting of reconstruct_sr(robust=...) alone: sr.sr_robust_weights)
 from ._gpu_tv import denoise_tv, tv_params  # noqa: F401

@@ -572,6 +572,60 @@ int t2fit_sr_slice_adjoint_dev(int n_stacks, const float *const *r_dev, const do
                                const int32_t *profile, const double *thickness, const float *x_dev, double tau, float *out_dev,
                                int hz, int hy, int hx, int n_vol, void *stream);
 
+/* ---- Outlier-robust super-resolution: slice weights and Huber sample weights ------------------------------------------
+ * Single-shot stacks contain bad slices (signal drop-outs, spin-history stripes, slices registered to the wrong place) and
+ * a plain least-squares data term writes them straight into the volume.  The robust loop minimises, per echo,
+ *   1/2 sum_s sum_j omega_j (A_s x - y_s)_j^2 + weight * TV(x),     omega = q (per slice) * w (per sample) in [0, 1],
+ * with omega recomputed from the current residuals at every iteration: the residuals r_s = A_s x - y_s of
+ * t2fit_sr_forward_dev / t2fit_sr_slice_forward_dev are multiplied by omega in place before the adjoint, so A^T (omega r)
+ * is the gradient of the weighted term; omega <= 1, so the step size tau stays valid.  Only +, *, /, sqrt and comparisons
+ * appear, in float64 with one rounding per operation in the order written, so fetal_t2mapping_amd/_sr.py (robust_slice_sums,
+ * robust_scale, robust_apply) states it in numpy to the same bits.  Additive to ABI 5.
+ *
+ * Every echo e on its own; the slices of all stacks are listed stack-major, ascending in slice index (n_slices = sum lz_s).
+ *   counted   sample j of stack s is counted iff N_s[j] > 0, its mask byte (when there is a mask) is not 0, and r[e][j] is
+ *             finite.
+ *   sums      of slice k: c = the number of counted samples, q2 = sum (double)r * (double)r over them, in a fixed tree:
+ *             thread t of 256 adds the samples i = t, t + 256, ... of the slice's ly lx in ascending i; a wave adds by the
+ *             xor butterfly 32, 16, .., 1; the four waves meet as ((w0 + w1) + w2) + w3.  No atomics.
+ *   scale     slice k is eligible iff c >= min_count, then m_k = q2 / c.  With v the n eligible m of the echo, sorted,
+ *             sigma2 = max(0.5 (v[(n - 1) / 2] + v[n / 2]), sigma_floor^2).  n == 0 or sigma2 not > 0: robustness is off for
+ *             the echo: every weight is 1, r stays bit for bit as it was (non-finite samples too) and sigma2 is reported 0.
+ *   q_k       1 if the slice is not eligible or m_k <= T sigma2, else (T sigma2) / m_k,   T = slice_threshold^2
+ *   w_j       1 if |r_j| <= delta, else delta / |r_j|,   delta = huber * sqrt(sigma2)
+ *   apply     a counted sample becomes (float)((q_k w_j) (double)r_j), any other sample +0.0. */
+#define T2FIT_SR_ROBUST_MAX_SLICES 4096
+typedef struct t2fit_sr_robust_params {
+  double slice_threshold; /* t > 0: a slice whose mean square residual exceeds t^2 sigma2 is weighted down */
+  double huber;           /* h > 0: a sample beyond h sigma is weighted down */
+  double sigma_floor;     /* >= 0: lower bound of sigma, in intensity units */
+  int32_t min_count;      /* >= 1: counted samples a slice needs to take part in the scale and to be weighted */
+  int32_t flags;          /* reserved, must be 0 */
+} t2fit_sr_robust_params;
+
+/* slice_threshold 1.5, huber 2.5, sigma_floor 0, min_count 16, flags 0 */
+int t2fit_sr_robust_params_default(t2fit_sr_robust_params *p);
+
+/* Bytes of one buffer that holds the three tables of t2fit_sr_robust_dev, in this order: up(16 n_vol n_slices) for the sums,
+ * up(8 n_vol n_slices) for the slice weights, up(8 n_vol) for sigma2; up(v) = v rounded up to 256.  A loop carves it after
+ * t2fit_sr_workspace_bytes, whose result does not change.  Plain arithmetic, no device; refuses what t2fit_sr_robust_dev
+ * refuses in n_stacks, lo_size and n_vol. */
+int t2fit_sr_robust_workspace_bytes(int n_stacks, const int32_t *lo_size, int n_vol, size_t *bytes);
+
+/* The weighting above on the residuals of n_stacks stacks, in place.  r_dev, N_dev, mask_dev: HOST arrays of n_stacks
+ * device pointers (r_dev[s] float32 [n_vol][lz][ly][lx], in / out; N_dev[s] float64 [lz][ly][lx] from t2fit_sr_forward_dev;
+ * mask_dev or any of its entries may be NULL); lo_size: (lz, ly, lx) per stack.  Caller buffers on the device, float64:
+ * sums_dev [n_vol][n_slices][2] = (c, q2), weights_dev [n_vol][n_slices] = q, sigma2_dev [n_vol].  Three launches are queued
+ * on `stream` (the sums: a workgroup per slice and chunk of 4 echoes, N and the mask read once per chunk; the scale: a
+ * workgroup per echo, ranks by counting in LDS; the apply: a thread per sample and chunk); no allocation, copy or
+ * synchronisation.  Checked before HIP is touched (T2FIT_E_INVALID and a message): a NULL pointer (mask_dev and its entries
+ * excepted), n_stacks outside 1 .. T2FIT_SR_MAX_STACKS, n_vol or a size < 1, a stack of more than 2^40 elements, more than
+ * T2FIT_SR_ROBUST_MAX_SLICES slices in total, slice_threshold or huber not finite or not > 0, min_count < 1, sigma_floor
+ * negative or not finite, flags != 0, a residual not aligned to 4 bytes, N or a table not aligned to 8. */
+int t2fit_sr_robust_dev(int n_stacks, float *const *r_dev, const double *const *N_dev, const uint8_t *const *mask_dev,
+                        const int32_t *lo_size, int n_vol, const t2fit_sr_robust_params *params, double *sums_dev,
+                        double *weights_dev, double *sigma2_dev, void *stream);
+
 /* ---- Masks and phantom labels: binary morphology, hole filling, seed labels, relabelling ------------------------------
  * What the reference builds on the host before a fit can start (utils/qmri_utils.py): build_mask (:223-252),
  * build_phantom_masks (:591-623), build_phantom_labels_v2 (:868-933), build_mask_from_labels (:935-951) and the lookup of
