@@ -308,7 +308,7 @@ def sr_robust_weights(r, N, *, masks=None, device=0, **params):
 
 def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thickness=None, profile="box",
                    weight=_sr.DEFAULT_WEIGHT, n_iter=_sr.DEFAULT_N_ITER, prox_iter=_sr.DEFAULT_PROX_ITER, stack_masks=None,
-                   x0=None, return_info=False, device=0, slice_transforms=None, robust=None):
+                   x0=None, return_info=False, device=0, slice_transforms=None, robust=None, tv="channel"):
     """TV-regularised super-resolution reconstruction of 1 to 6 thick-slice stacks on the GPU.  Each slice is modelled as
     the slice-profile average of the ``res`` mm volume x on the ``fixed`` stack's isotropic grid, and per echo
 
@@ -332,6 +332,9 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
     echo (:func:`sr_robust_weights`, one more launch group, still no synchronisation); the info then also holds
     ``"slice_weights"`` (one float64 ``(nTE, lz)`` tensor per stack), ``"sigma2"`` (``(nTE,)``) and ``"robust_sums"``
     (``(nTE, n_slices, 2)``: count and sum of squares per slice) of the last iteration.  None launches none of it.
+    ``tv``: ``"channel"`` (every echo's prox on its own) or ``"joint"``: the prox is the vector-valued TV across the echoes
+    (``t2fit_tv_joint_denoise_dev`` in 3-D, one problem, the same ``w = tau * weight``, ``eps = 0`` and ``prox_iter``), so
+    all echoes of the volume share one edge set; with one echo it equals ``"channel"``.
     The step size is read back once before the loop (one synchronisation); the loop itself queues 3 + stacks launch groups
     per iteration and does not synchronise.  :func:`_sr.reconstruct_sr` states the definition in numpy; same bits."""
     import torch
@@ -339,8 +342,12 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
     from . import nifti
 
     robust = _sr.robust_params(robust)
+    if tv not in ("channel", "joint"):
+        raise ValueError(f"tv must be 'channel' or 'joint', got {tv!r}")
     lib = require(*(_abi.SR_SYMBOLS + _abi.TV_SYMBOLS + (() if slice_transforms is None else _abi.SR_SLICE_SYMBOLS)
-                    + (() if robust is None else _abi.SR_ROBUST_SYMBOLS)))
+                    + (() if robust is None else _abi.SR_ROBUST_SYMBOLS) + (_abi.TVJ_SYMBOLS if tv == "joint" else ())))
+    tv_bytes, tv_call = ((lib.t2fit_tv_joint_workspace_bytes, lib.t2fit_tv_joint_denoise_dev) if tv == "joint" else
+                         (lib.t2fit_tv_workspace_bytes, lib.t2fit_tv_denoise_dev))
     if not (float(weight) >= 0.0 and np.isfinite(weight)) or int(n_iter) < 0 or int(prox_iter) < 1:
         raise ValueError("weight must be finite and >= 0, n_iter >= 0, prox_iter >= 1")
     pid = _sr._profile_id(profile)
@@ -426,7 +433,7 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
         if float(weight) > 0.0:
             par = tv_params(tau * float(weight), 0.0, int(prox_iter), 3, "f32")
             tv_need = C.c_size_t(0)
-            check(lib.t2fit_tv_workspace_bytes(C.byref(par), n_vol, *hr_shape, C.byref(tv_need)))
+            check(tv_bytes(C.byref(par), n_vol, *hr_shape, C.byref(tv_need)))
             tv_ws, tv_ptr = workspace(tv_need.value, dev)
         stream = current_stream()
         for _ in range(int(n_iter)):
@@ -436,8 +443,7 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
                 _robust(lib, r, N, masks, lr_shapes, n_vol, robust_par, sums, q, sigma2)
             if float(weight) > 0.0:
                 adj(range(n_s), r, x, tau, z, n_vol)
-                check(lib.t2fit_tv_denoise_dev(C.byref(par), z.data_ptr(), x.data_ptr(), n_vol, *hr_shape, tv_ptr, tv_need.value,
-                                               None, None, stream))
+                check(tv_call(C.byref(par), z.data_ptr(), x.data_ptr(), n_vol, *hr_shape, tv_ptr, tv_need.value, None, None, stream))
             else:
                 adj(range(n_s), r, x, tau, x, n_vol)
         info = {"tau": tau, "column_max": col_max, "N": [n.clone().reshape(s) for n, s in zip(N, lr_shapes)]} if return_info else None

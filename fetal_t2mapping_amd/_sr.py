@@ -661,8 +661,18 @@ def _reweigh(r, N, masks, robust, info):
     return r
 
 
-def iterate(x, y, N, B, profile, rels, tau, weight, prox_iter, masks=None, out_dtype=np.float32, robust=None, info=None):
-    """One proximal-gradient step on ``x`` ``(n, Z, Y, X)``: residuals of every stack, the update ``z``, the TV prox.
+def _prox_joint(z, w, prox_iter, out_dtype):
+    """The prox of ``w`` times the vector-valued TV across the echoes of ``z`` ``(n, Z, Y, X)``: the joint denoiser in 3-D,
+    one problem, ``eps = 0``, ``prox_iter`` iterations (with one echo, the per-echo prox)."""
+    if np.dtype(out_dtype) == np.float32:
+        return _tv.denoise_tv_joint(z, w, eps=0.0, max_iter=prox_iter, dims=3, precision="f32")[0]
+    return _tv.tv_joint_problem(z, w, 0.0, prox_iter, np.float64)[0]
+
+
+def iterate(x, y, N, B, profile, rels, tau, weight, prox_iter, masks=None, out_dtype=np.float32, robust=None, info=None,
+            tv="channel"):
+    """One proximal-gradient step on ``x`` ``(n, Z, Y, X)``: residuals of every stack, the update ``z``, the TV prox
+    (``tv``: ``"channel"``, every echo on its own, or ``"joint"``, one gradient norm per voxel across the echoes).
     ``robust`` (None, True or a dict of :data:`ROBUST_DEFAULTS`): the residuals pass through :func:`robust_step` first;
     ``info``: a dict that then receives ``slice_weights``, ``sigma2`` and ``robust_sums``."""
     r = [forward(x, B[s], y[s].shape[-3:], profile, rels[s], y=y[s], mask=None if masks is None else masks[s],
@@ -671,13 +681,15 @@ def iterate(x, y, N, B, profile, rels, tau, weight, prox_iter, masks=None, out_d
     z = adjoint(r, N, B, profile, rels, x.shape[-3:], masks=masks, x=x, tau=tau, out_dtype=out_dtype)
     if not weight > 0.0:
         return z
+    if tv == "joint":
+        return _prox_joint(z, tau * weight, prox_iter, out_dtype)
     if np.dtype(out_dtype) == np.float32:
         return _tv.denoise_tv(z, tau * weight, eps=0.0, max_iter=prox_iter, dims=3, precision="f32")[0]
     return np.stack([_tv.tv_problem(v, tau * weight, 0.0, prox_iter, np.float64)[0] for v in z])
 
 
 def iterate_slices(x, y, N, B, profile, rels, tau, weight, prox_iter, masks=None, out_dtype=np.float32, robust=None,
-                   info=None):
+                   info=None, tv="channel"):
     """:func:`iterate` on the slice operators: ``B[s]`` is ``(lz_s, 3, 4)``."""
     r = [forward_slices(x, B[s], y[s].shape[-3:], profile, rels[s], y=y[s], mask=None if masks is None else masks[s],
                         out_dtype=out_dtype)[0] for s in range(len(y))]
@@ -685,6 +697,8 @@ def iterate_slices(x, y, N, B, profile, rels, tau, weight, prox_iter, masks=None
     z = adjoint_slices(r, N, B, profile, rels, x.shape[-3:], masks=masks, x=x, tau=tau, out_dtype=out_dtype)
     if not weight > 0.0:
         return z
+    if tv == "joint":
+        return _prox_joint(z, tau * weight, prox_iter, out_dtype)
     if np.dtype(out_dtype) == np.float32:
         return _tv.denoise_tv(z, tau * weight, eps=0.0, max_iter=prox_iter, dims=3, precision="f32")[0]
     return np.stack([_tv.tv_problem(v, tau * weight, 0.0, prox_iter, np.float64)[0] for v in z])
@@ -692,8 +706,10 @@ def iterate_slices(x, y, N, B, profile, rels, tau, weight, prox_iter, masks=None
 
 def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thickness=None, profile="box",
                    weight=DEFAULT_WEIGHT, n_iter=DEFAULT_N_ITER, prox_iter=DEFAULT_PROX_ITER, stack_masks=None, x0=None,
-                   return_info=False, out_dtype=np.float32, slice_transforms=None, robust=None):
-    """The whole reconstruction on the host, argument for argument ``t2map.reconstruct_sr``.  Returns ``(x, Geometry of H)``
+                   return_info=False, out_dtype=np.float32, slice_transforms=None, robust=None, tv="channel"):
+    """The whole reconstruction on the host, argument for argument ``t2map.reconstruct_sr``.  ``tv``: ``"channel"`` (the
+    prox of every echo on its own) or ``"joint"`` (vector-valued TV across the echoes: :func:`_tv.denoise_tv_joint` with
+    ``w = tau * weight``, ``eps = 0``, ``prox_iter`` iterations; with one echo it equals ``"channel"``).  Returns ``(x, Geometry of H)``
     and with ``return_info`` also ``{"tau", "N", "column_max"}``.  ``slice_transforms``: ``{stack name: (lz, 4, 4)}``, a pose
     per slice (fixed point -> stack point) in place of the stack's transform; the fixed stack may have an entry, stacks
     without one carry their stack transform on every slice.  Then N, tau and the loop run on :func:`forward_slices` and
@@ -703,6 +719,9 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
     iteration (None when there was none)."""
     if not (float(weight) >= 0.0 and np.isfinite(weight)) or int(n_iter) < 0 or int(prox_iter) < 1:
         raise ValueError("weight must be finite and >= 0, n_iter >= 0, prox_iter >= 1")
+    if tv not in ("channel", "joint"):
+        raise ValueError(f"tv must be 'channel' or 'joint', got {tv!r}")
+    how = {"tv": "joint"} if tv == "joint" else {}
     robust = robust_params(robust)
     pid = _profile_id(profile)
     names = [o for o in geoms if o in stacks]
@@ -729,9 +748,10 @@ def reconstruct_sr(stacks, geoms, *, fixed="ax", res=1.0, transforms=None, thick
     last = {"slice_weights": None, "sigma2": None}
     for _ in range(int(n_iter)):
         if robust is None:
-            x = step(x, y, N, B, pid, rels, tau, float(weight), int(prox_iter), masks, out_dtype)
+            x = step(x, y, N, B, pid, rels, tau, float(weight), int(prox_iter), masks, out_dtype, **how)
         else:
-            x = step(x, y, N, B, pid, rels, tau, float(weight), int(prox_iter), masks, out_dtype, robust=robust, info=last)
+            x = step(x, y, N, B, pid, rels, tau, float(weight), int(prox_iter), masks, out_dtype, robust=robust, info=last,
+                     **how)
     if np.asarray(stacks[order[0]]).ndim == 3:
         x = x[0]
     if return_info:

@@ -3,7 +3,8 @@ the definition in include/t2fit.h (t2fit_tv_denoise_dev), which is scikit-image 
 float image (what the reference's ``run_denoising`` calls slice by slice).  Every elementwise operation is one rounding
 in the working precision, in the order written; the two energy sums are accumulated in float64 (skimage sums them in
 the image's precision, so on a float32 image its stop can fall one iteration away when ``|E_prev - E|`` lies within
-float32 rounding of the threshold).  Host code for tests and baselines: the product path is the HIP kernel."""
+float32 rounding of the threshold).  The second half states the vector-valued (joint) form across the channels of a stack
+(t2fit_tv_joint_denoise_dev) from the same steps.  Host code for tests and baselines: the product path is the HIP kernel."""
 from __future__ import annotations
 
 import numpy as np
@@ -118,3 +119,85 @@ def denoise_tv(stack, weight=DEFAULT_WEIGHT, eps=DEFAULT_EPS, max_iter=DEFAULT_M
         o, n_iter[k], energy[k] = tv_problem(f, weight, eps, max_iter, dtype)
         out[k] = o.astype(np.float32)
     return out.reshape(a.shape), n_iter, energy
+
+
+# ---- vector-valued (joint) TV across the channels of a stack: include/t2fit.h, t2fit_tv_joint_denoise_dev ---------------------
+def joint_norm(g):
+    """``sqrt(S)``, ``S = sq_0; S = S + sq_c`` for c ascending, ``sq_c`` the scalar definition's sum of squares of channel
+    c's differences ``g[c]``: one norm per voxel, shared by all channels."""
+    s = None
+    for gc in g:
+        sq = gc[0] * gc[0] + gc[1] * gc[1]
+        if len(gc) == 3:
+            sq = sq + gc[2] * gc[2]
+        s = sq if s is None else s + sq
+    return np.sqrt(s)
+
+
+def joint_energy(d, nrm, weight):
+    """``(sum_c sum_x d_c^2 + weight sum_x nrm) / N``, ``N = C`` times the voxels of a channel: squares and norms in the
+    working precision, the sums in float64, channels ascending."""
+    sd = float(np.sum((d[0] * d[0]).astype(np.float64)))
+    for dc in d[1:]:
+        sd = sd + float(np.sum((dc * dc).astype(np.float64)))
+    return (sd + float(weight) * float(np.sum(nrm.astype(np.float64)))) / (len(d) * d[0].size)
+
+
+def tv_joint_problem(f, weight=DEFAULT_WEIGHT, eps=DEFAULT_EPS, max_iter=DEFAULT_MAX_ITER, dtype=np.float32, history=None):
+    """One joint problem: ``f`` is ``(C, Y, X)`` or ``(C, Z, Y, X)``; the C channels keep a dual field each and share one
+    gradient norm per voxel, ``sqrt(sum_c |grad u_c|^2)``.  Returns ``(out like f in dtype, n_iter, E)`` as
+    :func:`tv_problem` does; with ``C = 1`` every byte, ``n_iter`` and ``E`` are :func:`tv_problem`'s.  The weight is not
+    rescaled by C: the joint norm of pure noise is about ``sqrt(C)`` times a channel's.  The steps are the module's
+    functions, looked up at every call."""
+    T = np.dtype(dtype).type
+    f = np.asarray(f).astype(T)
+    n = f.ndim - 1
+    if n not in (2, 3):
+        raise ValueError("a joint problem is (C, Y, X) or (C, Z, Y, X)")
+    chans = range(f.shape[0])
+    tau, tw = step_sizes(n, weight, T)
+    p = [[np.zeros(f.shape[1:], T) for _ in range(n)] for _ in chans]
+    e_init = e_prev = e = 0.0
+    out = f
+    n_iter = 0
+    with np.errstate(all="ignore"):
+        for i in range(int(max_iter)):
+            d = [np.zeros(f.shape[1:], T) if i == 0 else divergence(p[c]) for c in chans]
+            out = np.stack([f[c] + d[c] for c in chans])
+            g = [gradient(out[c]) for c in chans]
+            nrm = joint_norm(g)
+            e = joint_energy(d, nrm, weight)
+            if history is not None:
+                history.append(e)
+            p = [update(p[c], g[c], nrm, tau, tw) for c in chans]
+            n_iter = i
+            if i == 0:
+                e_init = e_prev = e
+            elif abs(e_prev - e) < eps * e_init:
+                break
+            else:
+                e_prev = e
+    return out, n_iter, e
+
+
+def denoise_tv_joint(stack, weight=DEFAULT_WEIGHT, eps=DEFAULT_EPS, max_iter=DEFAULT_MAX_ITER, dims=2, precision="f32"):
+    """The joint call on the host: ``stack`` is ``(C, Z, Y, X)`` float32; ``dims=2`` takes slice z of all channels as a
+    problem (Z problems), ``dims=3`` the whole stack as one.  Returns ``(out float32 like stack, n_iter int32 per problem,
+    energy float64 per problem)``."""
+    a = np.ascontiguousarray(stack, dtype=np.float32)
+    if a.ndim != 4:
+        raise ValueError("stack must be (C, Z, Y, X)")
+    if dims not in (2, 3):
+        raise ValueError("dims must be 2 or 3")
+    dtype = {"f32": np.float32, "f64": np.float64}[precision]
+    out = np.empty(a.shape, np.float32)
+    if dims == 3:
+        o, n, e = tv_joint_problem(a, weight, eps, max_iter, dtype)
+        out[...] = o.astype(np.float32)
+        return out, np.array([n], np.int32), np.array([e], np.float64)
+    n_iter = np.zeros(a.shape[1], np.int32)
+    energy = np.zeros(a.shape[1], np.float64)
+    for z in range(a.shape[1]):
+        o, n_iter[z], energy[z] = tv_joint_problem(a[:, z], weight, eps, max_iter, dtype)
+        out[:, z] = o.astype(np.float32)
+    return out, n_iter, energy

@@ -4,7 +4,7 @@
         --in_vivo --gaussian --lf --sim 1 [--TEs 114 202 299] [--no_prior] [--solver lbfgsb|lm|loglin] [--gpus N]
         [--roi_stats ho:2 --roi_stats jhu:3 --roi_stats feta] [--roi_connectivity 3] [--roi_erosion 1]
         [--bootstrap 100 [--bootstrap_seed 0] [--bootstrap_alpha 0.05] [--bootstrap_noise background|sigma_map|<float>]]
-        [--denoise tv [--denoise_weight 0.1|<c>sigma] [--denoise_dims 2|3] [--denoise_eps 2e-4] [--denoise_iter 200]]
+        [--denoise tv|tv_joint [--denoise_weight 0.1|<c>sigma] [--denoise_dims 2|3] [--denoise_eps 2e-4] [--denoise_iter 200]]
 
 --gpus N (N > 1) starts one process per GPU (torch.distributed.run, RCCL) before anything touches a GPU: with at
 least N subjects in the CSVs each rank streams its own subjects (dist.subjects_of_rank: nothing is exchanged,
@@ -25,6 +25,9 @@ T2cihimap / T2nokmap_ada-<fit>.nii.gz beside the four maps.
 --denoise tv passes the decoded echo volumes through t2map.denoise_tv (TV-Chambolle as scikit-image defines it: the
 reference's run_denoising, utils/qmri_utils.py:393-405, the last step of its reconstruction stage) before the union mask
 and the fit; masks, geometry and output file names are unchanged.
+--denoise tv_joint is vector-valued TV across the echoes (t2map.denoise_tv(joint=True)): one gradient norm per voxel,
+sqrt(sum over echoes |grad u|^2), so all echoes share one edge set.  The weight is not rescaled by the echo count: the
+joint norm of pure noise is about sqrt(nTE) times one echo's, so a weight that suits tv is about sqrt(nTE) too small.
 The convergence-study figures (:465-468) are written on request (--plots, convergence.py).  ``--csv prj-004``
 (prj-003, prj-002) stands for the session logs of that project of the reference's paper, as in
 utils/metadata_utils.py:19-85.
@@ -439,11 +442,13 @@ def parse_denoise_weight(text: str):
     return kind, v
 
 
-def denoise_subject(vols, masks, weight, dims=2, eps=2e-4, max_iter=200, device=0):
+def denoise_subject(vols, masks, weight, dims=2, eps=2e-4, max_iter=200, device=0, joint=False):
     """``--denoise tv``: the decoded echo volumes through t2map.denoise_tv on the device (what the reference's
     run_denoising does to them on the host before run_t2mapping.py reads the file), ahead of the union mask and the
     fit.  ``weight``: parse_denoise_weight's pair; the ``sigma`` form measures the noise level on the voxels outside
-    the union mask, before denoising.  Masks and geometry are untouched.  Returns the denoised volumes (float32)."""
+    the union mask, before denoising.  Masks and geometry are untouched.  Returns the denoised volumes (float32).
+    ``joint`` (``--denoise tv_joint``): vector-valued TV across the echoes, one problem per slice of all echoes
+    (``dims=2``) or one in all (``dims=3``); the weight, ``<c>sigma`` included, is not rescaled by the echo count."""
     import torch
 
     t0 = time.time()
@@ -463,10 +468,11 @@ def denoise_subject(vols, masks, weight, dims=2, eps=2e-4, max_iter=200, device=
         sigma, count = t2map.estimate_background_sigma(stack, union.astype(np.uint8), device=device)
         note = f" ({value:g} x background sigma {sigma:.4g} over {count} samples)"
         value = value * sigma
-    out, info = t2map.denoise_tv(stack, value, eps=eps, max_iter=max_iter, dims=dims, out=stack, return_info=True)
+    out, info = t2map.denoise_tv(stack, value, eps=eps, max_iter=max_iter, dims=dims, out=stack, return_info=True,
+                                 **({"joint": True} if joint else {}))
     n_iter = info["n_iter"].cpu().numpy()
     host = out.cpu().numpy()
-    print(f"Denoising: TV-Chambolle {dims}-D, weight {value:.4g}{note}, {n_iter.size} problems, n_iter mean "
+    print(f"Denoising: TV-Chambolle {dims}-D{', joint across the echoes' if joint else ''}, weight {value:.4g}{note}, {n_iter.size} problems, n_iter mean "
           f"{float(n_iter.mean()):.1f} max {int(n_iter.max())}, {time.time() - t0:.3f} s")
     return [host[i] for i in range(len(vols))]
 
@@ -838,9 +844,12 @@ def parse_arguments(argv=None):
                         "reference's build_phantom_masks and build_phantom_labels_v2; needs --phantom_seeds; off by default")
     p.add_argument("--phantom_seeds", default=None, metavar="FILE",
                    help="JSON list of [x, y, z] voxel indices, one per vial in label order")
-    p.add_argument("--denoise", choices=["tv"], default=None,
+    p.add_argument("--denoise", choices=["tv", "tv_joint"], default=None,
                    help="denoise the echo volumes on the GPU before the fit: tv = TV-Chambolle as scikit-image's "
-                        "denoise_tv_chambolle, the reference's run_denoising; off by default")
+                        "denoise_tv_chambolle, the reference's run_denoising; tv_joint = vector-valued TV across the echoes "
+                        "(one gradient norm per voxel, so all echoes share one edge set; the weight is not rescaled: the "
+                        "joint norm of pure noise is about sqrt(nTE) times one echo's, so a weight that suits tv is about "
+                        "sqrt(nTE) too small); off by default")
     p.add_argument("--denoise_weight", default="0.1", metavar="{W,<c>sigma}",
                    help="TV weight in intensity units (default 0.1, the reference's, which barely changes images with "
                         "values in the hundreds), or <c>sigma: c times the background noise level measured outside the mask")
@@ -908,6 +917,8 @@ def parse_arguments(argv=None):
             p.error("--denoise cannot be combined with --bootstrap: the replicas would not pass through the denoiser, so "
                     "their spread would not be that of the fitted maps")
         args.denoise_args = {"weight": weight, "dims": args.denoise_dims, "eps": args.denoise_eps, "max_iter": args.denoise_iter}
+        if args.denoise == "tv_joint":
+            args.denoise_args["joint"] = True
     if args.bootstrap:
         try:
             args.bootstrap_noise = parse_bootstrap_noise(args.bootstrap_noise)

@@ -586,7 +586,7 @@ def reconstruct_subject(sitk, bids_path, sub_md, sub, ses, *, fixed="ax", res=1.
 
 
 SR_FLAGS = ("sr_weight", "sr_iter", "sr_profile", "sr_thickness", "sr_slice_transforms", "sr_estimate_slices",
-            "sr_write_slice_transforms", "sr_robust", "sr_robust_slice", "sr_robust_huber", "sr_write_slice_weights")
+            "sr_write_slice_transforms", "sr_robust", "sr_robust_slice", "sr_robust_huber", "sr_write_slice_weights", "sr_tv")
 SLICE_WEIGHT_COLUMNS = ("stack", "slice", "echo", "weight", "count", "mean_square_residual")
 
 
@@ -640,6 +640,10 @@ def add_sr_arguments(p, prefix):
                         "iterative back-projection)")
     p.add_argument(f"--{prefix}sr_iter", type=int, default=_sr.DEFAULT_N_ITER,
                    help=f"sr: proximal-gradient iterations (default {_sr.DEFAULT_N_ITER})")
+    p.add_argument(f"--{prefix}sr_tv", choices=["channel", "joint"], default="channel",
+                   help="sr: the total variation of every echo on its own (channel, default), or joint: vector-valued TV across "
+                        "the echoes, one gradient norm per voxel, so the echoes of the volume share one edge set (the weight is "
+                        "not rescaled by the echo count)")
     p.add_argument(f"--{prefix}sr_profile", choices=sorted(_sr.PROFILES), default="box",
                    help="sr: slice profile, box or a cubic B-spline of that full width at half maximum (default box)")
     p.add_argument(f"--{prefix}sr_thickness", type=float, default=None, metavar="MM",
@@ -683,6 +687,8 @@ def sr_arguments(p, args, prefix, argv):
     if thick is not None and not (thick > 0.0 and np.isfinite(thick)):
         p.error(f"--{prefix}sr_thickness must be a positive number")
     out = {"weight": weight, "n_iter": n_iter, "profile": getattr(args, f"{prefix}sr_profile"), "thickness": thick}
+    if getattr(args, f"{prefix}sr_tv") == "joint":
+        out["tv"] = "joint"
     slices_dir = getattr(args, f"{prefix}sr_slice_transforms")
     if slices_dir is not None:
         out["slice_transforms_dir"] = slices_dir

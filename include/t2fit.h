@@ -383,6 +383,54 @@ int t2fit_tv_workspace_bytes(const t2fit_tv_params *p, int n_vol, int nz, int ny
 int t2fit_tv_denoise_dev(const t2fit_tv_params *p, const float *in_dev, float *out_dev, int n_vol, int nz, int ny, int nx,
                          void *workspace_dev, size_t workspace_bytes, int32_t *n_iter_dev, double *energy_dev, void *stream);
 
+/* ---- Vector-valued (joint) TV across the channels of the stack ---------------------------------------------------------
+ * The scalar call above treats every echo as an image of its own, so edges land at different voxels at different echo
+ * times.  The joint form couples the C = n_chan channels (echo times) of the float32 stack (n_chan, nz, ny, nx), the
+ * te-major stack t2fit_tv_denoise_dev and t2fit_volume_dev take, through one gradient norm per voxel,
+ * sqrt(sum_c |grad u_c|^2): all channels share one edge set.  Additive to ABI 5: two new symbols, the struct is
+ * t2fit_tv_params with flags == 0.
+ *
+ * dims = 2: a problem is slice z of all channels (nz problems; the channel stride is nz * ny * nx); dims = 3: the whole
+ * stack is one problem.  With n = dims spatial axes, N = C * (spatial voxels of a problem), working precision T and
+ * tau = 1 / (2 n) (unchanged: the bound ||div||^2 <= 4 n holds channel by channel):
+ *   p_{c,a} = 0
+ *   for i = 0 .. max_iter - 1:
+ *     d_c     = 0 if i == 0, else the scalar definition's divergence of (p_{c,0..n-1}): same order, same dropped terms
+ *     out_c   = f_c + d_c
+ *     g_{c,a}[x] = out_c[x + e_a] - out_c[x]   (0 where x + e_a is outside)
+ *     sq_c    = (g_{c,0}^2 + g_{c,1}^2) (+ g_{c,2}^2)
+ *     S       = sq_0;  S = S + sq_c for c = 1 .. C - 1, ascending
+ *     nrm     = sqrt(S)                        (one per voxel, shared by all channels)
+ *     E       = (sum_c sum_x d_c^2 + weight * sum_x nrm) / N
+ *     p_{c,a} = (p_{c,a} - T(tau) * g_{c,a}) / (1 + T(tau / weight) * nrm)
+ *     the stop rule on E and n_iter exactly as in the scalar definition
+ *   result = out_c of the last iteration executed
+ * Arithmetic as in the scalar definition: one correctly rounded operation in T per elementwise step, in the order
+ * written, no fused multiply-add; d^2 and nrm formed in T and summed in float64 in a fixed tree (channels ascending
+ * inside a tile).  With C = 1 every byte, n_iter and E are those of t2fit_tv_denoise_dev.  NaN / Inf in any channel of a
+ * problem reaches every channel of that problem through nrm and stays inside that problem.
+ * The weight is in intensity units and is NOT rescaled by C: the joint norm of pure noise is about sqrt(C) times a
+ * channel's, so a weight that suits the scalar call is about sqrt(C) too small here.
+ * fetal_t2mapping_amd/_tv.py (tv_joint_problem) restates the loop in numpy. */
+#define T2FIT_TV_JOINT_MAX_CHAN 64 /* n_chan above this is refused (the kernels loop the channels: any count up to it runs) */
+
+/* Bytes of the workspace of a joint call; plain arithmetic, no device.  With e, up() and the tiles of
+ * t2fit_tv_workspace_bytes, problems = nz (dims = 2) or 1 (dims = 3) and tiles counted per problem over its spatial
+ * extent (one tile serves all channels):
+ *   2 up(dims * n_chan * nz * ny * nx * e)  [the p pair of all channels]  +  up(16 * tiles * problems)  [partial energies]
+ *   +  up(32 * problems)  [state]
+ * Refuses what t2fit_tv_joint_denoise_dev refuses in p and the sizes. */
+int t2fit_tv_joint_workspace_bytes(const t2fit_tv_params *p, int n_chan, int nz, int ny, int nx, size_t *bytes);
+
+/* The contract of t2fit_tv_denoise_dev: in place allowed, workspace aligned to 256 and of any content, n_iter_dev /
+ * energy_dev one per problem or NULL, asynchronous on `stream` with 2 max_iter + 1 launches queued, the stop rule on the
+ * device, no allocation, copy or synchronisation inside, every argument checked before HIP is touched with the same
+ * refusals, and n_chan < 1 or > T2FIT_TV_JOINT_MAX_CHAN.  p->flags must be 0.  Per iteration a workgroup reads f and p
+ * of every channel of its tile twice (once for S, once for the update; the last channel once) and writes p once. */
+int t2fit_tv_joint_denoise_dev(const t2fit_tv_params *p, const float *in_dev, float *out_dev, int n_chan, int nz, int ny, int nx,
+                               void *workspace_dev, size_t workspace_bytes, int32_t *n_iter_dev, double *energy_dev,
+                               void *stream);
+
 /* ---- Orthogonal-stack reconstruction: resample to an isotropic grid and merge -------------------------------------
  * Steps 1 and 2 of the reference's run_qmri_reconstruction.py: every acquired thick-slice stack (ax / cor / sag, one per
  * echo time) is resampled to a 1 mm grid with linear interpolation (utils/qmri_utils.py resample_volume, :62-80), the
