@@ -18,6 +18,8 @@ from .t2map import (binary_close, binary_dilate, binary_erode, binary_open, bina
 from .t2map import sr  # the super-resolution reconstruction: sr.reconstruct_sr, sr.sr_forward, sr.sr_adjoint, sr.sr_box
 from ._gpu_sr import reconstruct_sr, sr_adjoint, sr_box, sr_forward  # the same four, by their own names
 from ._gpu_sr import sr_adjoint_slices, sr_forward_slices, sr_slice_table  # the operators with a rigid pose per slice
+from .t2map import mppca  # MP-PCA denoising and noise maps across the echoes: mppca.denoise_mppca, mppca.mppca_noise_map
+from ._gpu_mppca import denoise_mppca, mppca_noise_map  # the same two, by their own names
 
 __all__ = ["BootMaps", "BootStats", "RoiStats", "T2Maps", "bootstrap_volume", "compute_residuals", "denoise_tv", "dense_labels",
            "estimate_background_sigma", "fit_table", "fit_volume", "fit_voxel", "fit_voxels", "fit_voxels_trace", "label_stats",
@@ -25,4 +27,4 @@ __all__ = ["BootMaps", "BootStats", "RoiStats", "T2Maps", "bootstrap_volume", "c
            "stack_mask_flatten", "synth_replica", "union_mask_dev",
            "binary_close", "binary_dilate", "binary_erode", "binary_open", "binary_threshold", "build_mask", "fill_holes",
            "mask_from_labels", "phantom_labels", "phantom_mask", "relabel", "seed_labels", "synthseg_to_feta", "register",
-           "atlas", "bias", "sr"]
+           "atlas", "bias", "sr", "mppca"]

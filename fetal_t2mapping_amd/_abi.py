@@ -59,6 +59,12 @@ class T2FitTvParams(C.Structure):
 
 
 TV_JOINT_MAX_CHAN = 64
+MPPCA_MAX_TE, MPPCA_MAX_RADIUS = 16, 4
+
+
+class T2FitMppcaParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("dims", C.c_int32), ("estimator", C.c_int32), ("flags", C.c_int32)]
+
 
 INTERP_LINEAR, INTERP_NEAREST = 0, 1
 INTERPS = {"linear": INTERP_LINEAR, "nearest": INTERP_NEAREST}
@@ -118,6 +124,10 @@ SYMBOLS = [
                                                  C.POINTER(C.c_size_t)]),
     ("t2fit_tv_joint_denoise_dev", C.c_int, [C.POINTER(T2FitTvParams), _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t,
                                              _P, _P, _P]),
+    ("t2fit_mppca_params_default", C.c_int, [C.POINTER(T2FitMppcaParams)]),
+    ("t2fit_mppca_workspace_bytes", C.c_int, [C.POINTER(T2FitMppcaParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    ("t2fit_mppca_dev", C.c_int, [C.POINTER(T2FitMppcaParams), _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t,
+                                  _P]),
     ("t2fit_resample_dev", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _P, C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.c_double, C.c_int, _P]),
     ("t2fit_reconstruct_workspace_bytes", C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
@@ -211,8 +221,9 @@ SR_SLICE_SYMBOLS = ("t2fit_sr_slice_table_bytes", "t2fit_sr_slice_table_host", "
 SVR_SYMBOLS = ("t2fit_svr_table_bytes", "t2fit_svr_table_host", "t2fit_svr_workspace_bytes", "t2fit_svr_sums_dev")
 SR_ROBUST_SYMBOLS = ("t2fit_sr_robust_params_default", "t2fit_sr_robust_workspace_bytes", "t2fit_sr_robust_dev")
 TVJ_SYMBOLS = ("t2fit_tv_joint_workspace_bytes", "t2fit_tv_joint_denoise_dev")
+MPPCA_SYMBOLS = ("t2fit_mppca_params_default", "t2fit_mppca_workspace_bytes", "t2fit_mppca_dev")
 LOOKED_UP = (ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS + MI_SYMBOLS + SR_SYMBOLS + SR_SLICE_SYMBOLS + SVR_SYMBOLS
-             + SR_ROBUST_SYMBOLS + TVJ_SYMBOLS)
+             + SR_ROBUST_SYMBOLS + TVJ_SYMBOLS + MPPCA_SYMBOLS)
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

@@ -3,8 +3,10 @@
     python -m fetal_t2mapping_amd.cli --path /data/qMRI --csv 2024083017_17510000.csv \
         --in_vivo --gaussian --lf --sim 1 [--TEs 114 202 299] [--no_prior] [--solver lbfgsb|lm|loglin] [--gpus N]
         [--roi_stats ho:2 --roi_stats jhu:3 --roi_stats feta] [--roi_connectivity 3] [--roi_erosion 1]
-        [--bootstrap 100 [--bootstrap_seed 0] [--bootstrap_alpha 0.05] [--bootstrap_noise background|sigma_map|<float>]]
-        [--denoise tv|tv_joint [--denoise_weight 0.1|<c>sigma] [--denoise_dims 2|3] [--denoise_eps 2e-4] [--denoise_iter 200]]
+        [--bootstrap 100 [--bootstrap_seed 0] [--bootstrap_alpha 0.05] [--bootstrap_noise background|sigma_map|mppca|<float>]]
+        [--denoise tv|tv_joint [--denoise_weight 0.1|<c>sigma] [--denoise_dims 2|3] [--denoise_eps 2e-4] [--denoise_iter 200]
+                               [--denoise_sigma background|mppca]]
+        [--denoise mppca [--denoise_patch 2] [--denoise_dims 2|3]] [--write_noise_map]
 
 --gpus N (N > 1) starts one process per GPU (torch.distributed.run, RCCL) before anything touches a GPU: with at
 least N subjects in the CSVs each rank streams its own subjects (dist.subjects_of_rank: nothing is exchanged,
@@ -28,6 +30,12 @@ and the fit; masks, geometry and output file names are unchanged.
 --denoise tv_joint is vector-valued TV across the echoes (t2map.denoise_tv(joint=True)): one gradient norm per voxel,
 sqrt(sum over echoes |grad u|^2), so all echoes share one edge set.  The weight is not rescaled by the echo count: the
 joint norm of pure noise is about sqrt(nTE) times one echo's, so a weight that suits tv is about sqrt(nTE) too small.
+--denoise mppca is Marchenko-Pastur PCA across the echoes (t2map.denoise_mppca; Veraart et al. 2016, MRtrix's dwidenoise):
+no weight to tune; --denoise_patch R is the radius of its (2R+1)^dims window.  --write_noise_map writes the noise level and
+the number of signal components it measures in tissue, on the echoes as they were read, as ..._mppcasigmamap / mppcarankmap
+beside the four maps.  --bootstrap_noise mppca replicates from that per-voxel sigma map; --denoise_sigma mppca takes the
+sigma of a <c>sigma TV weight from its median inside the mask instead of from the background.  The noise is treated as
+Gaussian: at low SNR the Rician floor biases sigma low.
 The convergence-study figures (:465-468) are written on request (--plots, convergence.py).  ``--csv prj-004``
 (prj-003, prj-002) stands for the session logs of that project of the reference's paper, as in
 utils/metadata_utils.py:19-85.
@@ -380,13 +388,13 @@ BOOT_TAGS = ("T2std", "T2bias", "T2cilo", "T2cihi", "T2nok")
 
 
 def parse_bootstrap_noise(text: str):
-    """``--bootstrap_noise``: ``background`` / ``sigma_map`` as they are, anything else a noise level > 0."""
-    if text in ("background", "sigma_map"):
+    """``--bootstrap_noise``: ``background`` / ``sigma_map`` / ``mppca`` as they are, anything else a noise level > 0."""
+    if text in ("background", "sigma_map", "mppca"):
         return text
     try:
         level = float(text)
     except ValueError:
-        raise ValueError(f"--bootstrap_noise {text!r}: expected 'background', 'sigma_map' or a number") from None
+        raise ValueError(f"--bootstrap_noise {text!r}: expected 'background', 'sigma_map', 'mppca' or a number") from None
     if not (level > 0.0 and np.isfinite(level)):
         raise ValueError(f"--bootstrap_noise {text!r}: the noise level must be a positive number")
     return level
@@ -398,19 +406,24 @@ def boot_map_path(bids_path, acq, dirname, sim, analysis, tag):
 
 
 def save_bootstrap_maps(vols, mask, maps4, te_eff, fit, fit_params, prior, solver, precision, numpy_legacy, n_replicas, seed,
-                        alpha, noise, recon_img, bids_path, acq, dirname, sim, device=0):
+                        alpha, noise, recon_img, bids_path, acq, dirname, sim, device=0, mppca=None):
     """``--bootstrap R``: t2map.bootstrap_volume of the maps just written (the volume is not fitted again), then the
     T2 standard deviation, bias, interval bounds and replica counts as NIfTI maps with the T2 map's geometry.  Prints one
-    line: noise level, R, seconds, replicas per second.  Returns the paths written."""
+    line: noise level, R, seconds, replicas per second.  Returns the paths written.  ``noise`` ``'mppca'``: the replicas
+    take the per-voxel sigma map of t2map.mppca_noise_map of the echoes (``mppca``: its radius and dims), on the path a
+    fitted sigma map takes."""
     sitk = _sitk()
     t2_map, k_map, sigma_map, res_map = maps4
     echoes = np.stack([np.asarray(v, np.float32) for v in vols])
     t0 = time.time()
+    level_map = t2map.mppca_noise_map(echoes, device=device, **(mppca or {}))[0] if noise == "mppca" else None
     boot = t2map.bootstrap_volume(echoes, mask, te_eff, fit, fit_params, prior=prior, n_replicas=n_replicas, seed=seed,
-                                  alpha=alpha, noise_sigma=noise, solver=solver, precision=precision,
+                                  alpha=alpha, noise_sigma=noise if level_map is None else level_map, solver=solver,
+                                  precision=precision,
                                   maps=t2map.T2Maps(t2_map, k_map, sigma_map, res_map), numpy_legacy=numpy_legacy, device=device)
     dt = time.time() - t0
-    level = "the fitted sigma map" if boot.noise_sigma is None else f"{boot.noise_sigma:.6g}"
+    level = ("the MP-PCA sigma map" if level_map is not None else
+             "the fitted sigma map" if boot.noise_sigma is None else f"{boot.noise_sigma:.6g}")
     print(f"Bootstrap: noise level {level} ({noise if isinstance(noise, str) else 'given'}), {n_replicas} replicas in "
           f"{dt:.3f} sec ({n_replicas / max(dt, 1e-9):.1f} replicas/sec)")
     items = []
@@ -442,13 +455,47 @@ def parse_denoise_weight(text: str):
     return kind, v
 
 
-def denoise_subject(vols, masks, weight, dims=2, eps=2e-4, max_iter=200, device=0, joint=False):
+def save_noise_maps(sigma, rank, recon_img, bids_path, acq, dirname, sim, analysis):
+    """``--write_noise_map``: the MP-PCA noise level (float32) and signal rank (uint8) of every voxel beside the four maps,
+    with their geometry and naming rule (tags mppcasigma, mppcarank).  Returns the paths written."""
+    sitk = _sitk()
+    paths = []
+    for arr, tag in ((sigma, "mppcasigma"), (rank, "mppcarank")):
+        img = sitk.GetImageFromArray(arr)
+        img.SetSpacing(recon_img.GetSpacing())
+        img.SetOrigin(recon_img.GetOrigin())
+        img.SetDirection(recon_img.GetDirection())
+        paths.append(boot_map_path(bids_path, acq, dirname, sim, analysis, tag))
+        sitk.WriteImage(img, paths[-1])
+    return paths
+
+
+def _denoise_mppca_subject(vols, stack, radius, dims, device, maps, t0):
+    """The ``--denoise mppca`` half of :func:`denoise_subject`."""
+    out, noise = t2map.denoise_mppca(stack, radius=radius, dims=dims, out=stack, return_maps=True, device=device)
+    host = out.cpu().numpy()
+    sigma, rank = noise["sigma"].cpu().numpy(), noise["rank"].cpu().numpy()
+    if maps is not None:
+        maps["sigma"], maps["rank"] = sigma, rank
+    seen = sigma > 0
+    print(f"Denoising: MP-PCA {dims}-D, radius {radius} ({(2 * radius + 1) ** dims} voxels per window), median sigma "
+          f"{float(np.median(sigma[seen])) if seen.any() else 0.0:.4g}, mean rank {float(rank[seen].mean()) if seen.any() else 0.0:.2f}, "
+          f"{time.time() - t0:.3f} s")
+    return [host[i] for i in range(len(vols))]
+
+
+def denoise_subject(vols, masks, weight=None, dims=2, eps=2e-4, max_iter=200, device=0, joint=False, method="tv", radius=2,
+                    sigma_from="background", maps=None):
     """``--denoise tv``: the decoded echo volumes through t2map.denoise_tv on the device (what the reference's
     run_denoising does to them on the host before run_t2mapping.py reads the file), ahead of the union mask and the
     fit.  ``weight``: parse_denoise_weight's pair; the ``sigma`` form measures the noise level on the voxels outside
     the union mask, before denoising.  Masks and geometry are untouched.  Returns the denoised volumes (float32).
     ``joint`` (``--denoise tv_joint``): vector-valued TV across the echoes, one problem per slice of all echoes
-    (``dims=2``) or one in all (``dims=3``); the weight, ``<c>sigma`` included, is not rescaled by the echo count."""
+    (``dims=2``) or one in all (``dims=3``); the weight, ``<c>sigma`` included, is not rescaled by the echo count.
+    ``sigma_from`` ``'mppca'`` (``--denoise_sigma mppca``): the ``sigma`` form takes the median of the MP-PCA noise map
+    (t2map.mppca_noise_map, ``radius`` and ``dims`` as given) inside the union mask instead: a level measured in tissue.
+    ``method`` ``'mppca'`` (``--denoise mppca``): the volumes through t2map.denoise_mppca instead (no weight; ``radius`` is
+    that of its window); ``maps``, a dict, then receives the ``sigma`` and ``rank`` volumes it measured on the way."""
     import torch
 
     t0 = time.time()
@@ -459,14 +506,23 @@ def denoise_subject(vols, masks, weight, dims=2, eps=2e-4, max_iter=200, device=
     stack = torch.empty((len(vols),) + shape, dtype=torch.float32, device=dev)
     for i, v in enumerate(vols):
         stack[i] = torch.from_numpy(np.ascontiguousarray(v).astype(np.float32, copy=False)).to(dev)
+    if method == "mppca":
+        return _denoise_mppca_subject(vols, stack, radius, dims, device, maps, t0)
+    if weight is None:
+        raise ValueError("--denoise tv needs a weight (parse_denoise_weight's pair)")
     kind, value = weight
     note = ""
     if kind == "sigma":
         union = np.zeros(shape, bool)
         for m in masks:
             union |= np.asarray(m) != 0
-        sigma, count = t2map.estimate_background_sigma(stack, union.astype(np.uint8), device=device)
-        note = f" ({value:g} x background sigma {sigma:.4g} over {count} samples)"
+        if sigma_from == "mppca":
+            level = t2map.mppca_noise_map(stack, radius=radius, dims=dims, device=device)[0].cpu().numpy()[union]
+            sigma, count = (float(np.median(level)) if level.size else 0.0), int(level.size)
+            note = f" ({value:g} x MP-PCA median sigma {sigma:.4g} over {count} voxels of the mask)"
+        else:
+            sigma, count = t2map.estimate_background_sigma(stack, union.astype(np.uint8), device=device)
+            note = f" ({value:g} x background sigma {sigma:.4g} over {count} samples)"
         value = value * sigma
     out, info = t2map.denoise_tv(stack, value, eps=eps, max_iter=max_iter, dims=dims, out=stack, return_info=True,
                                  **({"joint": True} if joint else {}))
@@ -615,7 +671,7 @@ def _one_block(vols):
 def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field, prior, fast, norm, sim,
                    solver="lbfgsb", precision="f64", device=0, plots=False, plot_seed=None, numpy_legacy=False,
                    roi_specs=(), roi_connectivity=3, roi_erosion=1, bootstrap=0, bootstrap_seed=0, bootstrap_alpha=0.05,
-                   bootstrap_noise="background", denoise=None, reconstruct=None, build_mask=None):
+                   bootstrap_noise="background", denoise=None, reconstruct=None, build_mask=None, noise_map=None):
     """run_t2mapping.py:333-479 with the voxel loop on the GPU.  ``plots``: also write the reference's
     convergence-study figures (:465-468) under <prj>/ada/convergence_analysis.  ``roi_specs``: (name, tissue) pairs
     of --roi_stats; each adds a per-region table after the maps (save_roi_csvs).  ``bootstrap`` > 0: that many
@@ -625,7 +681,9 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
     from recon_1mm but reconstructed in memory from the acquired ax / cor / sag stacks, ahead of the denoiser.
     ``build_mask``: None, or the keyword arguments of build_phantom_subject (--build_mask phantom): the masks of every
     echo and the vial labels are built on the device from the volumes about to be fitted (after the reconstruction, if
-    any) and used in place of the recon_1mm_mask / recon_1mm_label files."""
+    any) and used in place of the recon_1mm_mask / recon_1mm_label files.  ``noise_map``: None, or ``{'radius', 'dims'}`` of
+    the MP-PCA noise map, with ``'write': True`` for --write_noise_map (save_noise_maps, of the echoes before any denoising);
+    --bootstrap_noise mppca reads its radius and dims."""
     sitk = _sitk()
     tes_s = [x / 1000 for x in TEs]
     metadata = metadata[metadata["EchoTime"].isin(tes_s)]
@@ -645,6 +703,11 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
                          "echoes): give at least as many subjects as ranks, or run on one GPU")
     if build_mask is not None and not phantom:
         raise ValueError("--build_mask phantom goes with --in_vitro / --in_vitro_fast")
+    write_noise = bool(noise_map and noise_map.get("write"))
+    mppca_window = {k: noise_map[k] for k in ("radius", "dims") if k in noise_map} if noise_map else {}
+    if write_noise and share_volumes:
+        raise ValueError("--write_noise_map is not run on a volume that is shared by several ranks (each rank holds a part of the "
+                         "echoes): give at least as many subjects as ranks, or run on one GPU")
     mine = set(subjects if (world == 1 or share_volumes) else
                [subjects[i] for i in dist_subjects_of_rank(len(subjects), rank, world)])
     writer = (rank == 0) or not share_volumes
@@ -693,8 +756,13 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
                 else:
                     vols, masks, label, recon_img = _read_subject(sitk, recon_paths, mask_paths, label_path)
                 keep = (label != 0) if (phantom and fast) else None  # :394-400
+                noise_maps = {}
+                if write_noise and not (denoise and denoise.get("method") == "mppca"):
+                    noise_maps["sigma"], noise_maps["rank"] = t2map.mppca_noise_map(
+                        np.stack([np.asarray(v, np.float32) for v in vols]), device=device, **mppca_window)
                 if denoise:
-                    vols = denoise_subject(vols, masks, device=device, **denoise)
+                    vols = denoise_subject(vols, masks, device=device, **denoise,
+                                           **({"maps": noise_maps} if write_noise and not noise_maps else {}))
                 t0 = time.time()
                 fitted = _fit_subject(vols, masks, keep, te_eff, fit, fit_params, prior, norm, solver, precision, device,
                                       **({"numpy_legacy": True} if numpy_legacy else {}))
@@ -737,6 +805,8 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
                                               precision=precision, device=device, seed=plot_seed, picks=picks, rows=rows,
                                               numpy_legacy=numpy_legacy)
             save_nifti_maps(t2_map, k_map, sigma_map, res_map, t2map_dirname, recon_img, bids_path, acq, sim, fit)
+            if write_noise:
+                save_noise_maps(noise_maps["sigma"], noise_maps["rank"], recon_img, bids_path, acq.iloc[0], t2map_dirname, sim, fit)
             if phantom:
                 # the reference unpacks (gt, id) as id, gt (run_t2mapping.py:27 vs :478), which swaps the
                 # CSV's `id` and `trueT2` columns; kept so the output file is identical
@@ -751,7 +821,8 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
             elif bootstrap:
                 save_bootstrap_maps(vols, mask, maps4, te_eff, fit, fit_params, prior, solver, precision, numpy_legacy,
                                     bootstrap, bootstrap_seed, bootstrap_alpha, bootstrap_noise, recon_img, bids_path,
-                                    acq.iloc[0], t2map_dirname, sim, device=device)
+                                    acq.iloc[0], t2map_dirname, sim, device=device,
+                                    **({"mppca": mppca_window} if bootstrap_noise == "mppca" else {}))
 
 
 def dist_subjects_of_rank(n_subjects, rank, world):
@@ -814,7 +885,7 @@ def parse_arguments(argv=None):
     p.add_argument("--bootstrap_seed", type=int, default=0, help="seed of the replica stream (default 0)")
     p.add_argument("--bootstrap_alpha", type=float, default=0.05,
                    help="the interval maps are the alpha/2 and 1 - alpha/2 percentiles (default 0.05: a 95 %% interval)")
-    p.add_argument("--bootstrap_noise", default="background", metavar="{background,sigma_map,<float>}",
+    p.add_argument("--bootstrap_noise", default="background", metavar="{background,sigma_map,mppca,<float>}",
                    help="noise level of the replicas: measured on the voxels outside the mask (default), the fitted sigma of "
                         "every voxel (3-parameter fits only), or a number")
     p.add_argument("--reconstruct", action="store_true",
@@ -844,12 +915,13 @@ def parse_arguments(argv=None):
                         "reference's build_phantom_masks and build_phantom_labels_v2; needs --phantom_seeds; off by default")
     p.add_argument("--phantom_seeds", default=None, metavar="FILE",
                    help="JSON list of [x, y, z] voxel indices, one per vial in label order")
-    p.add_argument("--denoise", choices=["tv", "tv_joint"], default=None,
+    p.add_argument("--denoise", choices=["tv", "tv_joint", "mppca"], default=None,
                    help="denoise the echo volumes on the GPU before the fit: tv = TV-Chambolle as scikit-image's "
                         "denoise_tv_chambolle, the reference's run_denoising; tv_joint = vector-valued TV across the echoes "
                         "(one gradient norm per voxel, so all echoes share one edge set; the weight is not rescaled: the "
                         "joint norm of pure noise is about sqrt(nTE) times one echo's, so a weight that suits tv is about "
-                        "sqrt(nTE) too small); off by default")
+                        "sqrt(nTE) too small); mppca = Marchenko-Pastur PCA across the echoes (dwidenoise's estimator): no "
+                        "weight to tune, --denoise_patch sets its window; off by default")
     p.add_argument("--denoise_weight", default="0.1", metavar="{W,<c>sigma}",
                    help="TV weight in intensity units (default 0.1, the reference's, which barely changes images with "
                         "values in the hundreds), or <c>sigma: c times the background noise level measured outside the mask")
@@ -857,6 +929,15 @@ def parse_arguments(argv=None):
                    help="2: every slice on its own (default, the reference's); 3: every volume as a whole")
     p.add_argument("--denoise_eps", type=float, default=2e-4, help="relative energy change that stops a problem (default 2e-4)")
     p.add_argument("--denoise_iter", type=int, default=200, help="iteration limit of a problem (default 200)")
+    p.add_argument("--denoise_patch", type=int, default=2, metavar="R",
+                   help="MP-PCA: radius of the (2R+1)^dims window, 1..4 (default 2); the window must hold more voxels than "
+                        "there are echoes")
+    p.add_argument("--denoise_sigma", choices=["background", "mppca"], default="background",
+                   help="where the sigma of a <c>sigma weight of tv / tv_joint comes from: background = the voxels outside "
+                        "the mask (default); mppca = the median of the MP-PCA noise map inside the mask")
+    p.add_argument("--write_noise_map", action="store_true",
+                   help="also write the MP-PCA noise level and signal rank of every voxel (of the echoes before any "
+                        "denoising) beside the maps; window by --denoise_patch / --denoise_dims")
     args = p.parse_args(argv)
     args.reconstruct_args = None
     given = [f for f in ("--recon_fixed", "--recon_res", "--recon_transforms", "--recon_register", "--recon_register_echoes",
@@ -900,11 +981,35 @@ def parse_arguments(argv=None):
         except (OSError, ValueError) as e:
             p.error(str(e))
     args.denoise_args = None
-    given = [f for f in ("--denoise_weight", "--denoise_dims", "--denoise_eps", "--denoise_iter")
+    given = [f for f in ("--denoise_weight", "--denoise_dims", "--denoise_eps", "--denoise_iter", "--denoise_patch", "--denoise_sigma")
              if any(a == f or a.startswith(f + "=") for a in (argv if argv is not None else sys.argv[1:]))]
-    if given and not args.denoise:
-        p.error(f"{given[0]} has no effect without --denoise tv")
-    if args.denoise:
+    # what runs MP-PCA: the denoiser itself, the noise map, the bootstrap's noise level, the sigma of a TV weight
+    uses_mppca = (args.denoise == "mppca" or args.write_noise_map or (args.bootstrap and args.bootstrap_noise == "mppca")
+                  or (args.denoise in ("tv", "tv_joint") and args.denoise_sigma == "mppca"))
+    window_flags = ("--denoise_patch", "--denoise_dims")
+    stray = [f for f in given if not (f in window_flags and uses_mppca)]
+    if "--denoise_patch" in given and not uses_mppca:
+        p.error("--denoise_patch is the MP-PCA window: it goes with --denoise mppca, --denoise_sigma mppca, --write_noise_map or "
+                "--bootstrap_noise mppca")
+    if stray and not args.denoise:
+        p.error(f"{stray[0]} has no effect without --denoise tv")
+    if not 1 <= args.denoise_patch <= 4:
+        p.error("--denoise_patch must be in 1..4")
+    args.noise_map_args = None
+    if uses_mppca:
+        args.noise_map_args = {"radius": args.denoise_patch, "dims": args.denoise_dims}
+        if args.write_noise_map:
+            args.noise_map_args["write"] = True
+    if args.denoise == "mppca":
+        tv_only = [f for f in given if f in ("--denoise_weight", "--denoise_eps", "--denoise_iter", "--denoise_sigma")]
+        if tv_only:
+            p.error(f"{tv_only[0]} belongs to --denoise tv / tv_joint: MP-PCA has no weight and no iteration (its window is "
+                    "--denoise_patch and --denoise_dims)")
+        if args.bootstrap:
+            p.error("--denoise cannot be combined with --bootstrap: the replicas would not pass through the denoiser, so "
+                    "their spread would not be that of the fitted maps")
+        args.denoise_args = {"method": "mppca", "radius": args.denoise_patch, "dims": args.denoise_dims}
+    elif args.denoise:
         try:
             weight = parse_denoise_weight(args.denoise_weight)
         except ValueError as e:
@@ -919,6 +1024,10 @@ def parse_arguments(argv=None):
         args.denoise_args = {"weight": weight, "dims": args.denoise_dims, "eps": args.denoise_eps, "max_iter": args.denoise_iter}
         if args.denoise == "tv_joint":
             args.denoise_args["joint"] = True
+        if args.denoise_sigma == "mppca":
+            if weight[0] != "sigma":
+                p.error("--denoise_sigma mppca has no effect on a weight in intensity units: give --denoise_weight <c>sigma")
+            args.denoise_args.update(sigma_from="mppca", radius=args.denoise_patch)
     if args.bootstrap:
         try:
             args.bootstrap_noise = parse_bootstrap_noise(args.bootstrap_noise)
@@ -1002,7 +1111,8 @@ def main(argv=None):
                        bootstrap=args.bootstrap, bootstrap_seed=args.bootstrap_seed, bootstrap_alpha=args.bootstrap_alpha,
                        bootstrap_noise=args.bootstrap_noise, **({"denoise": args.denoise_args} if args.denoise_args else {}),
                        **({"reconstruct": args.reconstruct_args} if args.reconstruct_args else {}),
-                       **({"build_mask": args.build_mask_args} if args.build_mask_args else {}))
+                       **({"build_mask": args.build_mask_args} if args.build_mask_args else {}),
+                       **({"noise_map": args.noise_map_args} if args.noise_map_args else {}))
     finally:
         if world > 1:
             import torch.distributed as dist

@@ -431,6 +431,62 @@ int t2fit_tv_joint_denoise_dev(const t2fit_tv_params *p, const float *in_dev, fl
                                void *workspace_dev, size_t workspace_bytes, int32_t *n_iter_dev, double *energy_dev,
                                void *stream);
 
+/* ---- Marchenko-Pastur PCA denoising and noise maps across the echoes (additive to ABI 5) ---------------------------
+ * Veraart et al., NeuroImage 2016, as MRtrix's dwidenoise implements it: a denoiser with no weight to tune and a noise
+ * map measured in tissue.  Over a window of N = (2 radius + 1)^dims voxels (x, y for dims = 2; x, y, z for dims = 3) the
+ * n_te echoes form an n_te x N matrix of low rank plus noise, whose noise eigenvalues follow the Marchenko-Pastur law.
+ * Input: a float32 te-major stack (n_te, nz, ny, nx), an optional uint8 mask (nz, ny, nx).  A centre is a voxel whose
+ * whole window lies inside the volume; it is processed when its own voxel is in the mask (NULL: all) and its G is finite.
+ * Everything below is float64 with one rounding per operation in the order written, nothing fused:
+ *   1. G_ij = sum over the window of x_i x_j (i <= j; samples cast first): along x in increasing offset from 0.0, those
+ *      sums along y, those along z (dims = 3).
+ *   2. Cyclic Jacobi from A = G, V = I, at most 16 sweeps.  Before a sweep off = sum_{p<q} A_pq^2 (row-major from 0.0); the
+ *      centre stops when off == 0.0.  A sweep visits (p, q), p < q, row by row: g = |A_pq|; if |A_pp| + g == |A_pp| and
+ *      |A_qq| + g == |A_qq| then A_pq = 0.0; if A_pq == 0.0 the pair is skipped; else theta = (A_qq - A_pp) / (2 A_pq),
+ *      t = sgn(theta) / (|theta| + sqrt(theta theta + 1)) with sgn(0) = +1, c = 1 / sqrt(t t + 1), s = t c; for k != p, q:
+ *      A_kp' = c A_kp - s A_kq, A_kq' = s A_kp + c A_kq; A_pp -= t A_pq, A_qq += t A_pq, A_pq = 0; columns p and q of V get
+ *      the same rotation.
+ *   3. The eigenvalues (the diagonal) in ascending order s_0 .. s_{M-1}, ties by index.
+ *   4. q = N, lam_r = max(s_0, 0) / q, clam = 0, cut = 0, sigma^2 = 0; for p = 0 .. M-1: lam = max(s_p, 0) / q, clam += lam,
+ *      gamma = (p+1) / (q - (M-p-1)) (estimator 2) or (p+1) / q (estimator 1), a = clam / (p+1),
+ *      b = (lam - lam_r) / (4 sqrt(gamma)); if b < a: sigma^2 = a, cut = p + 1.  The M - cut largest components are kept.
+ *   5. P = sum of v_j v_j^T over the kept components in ascending order from 0.0; P = 0 at an unprocessed centre.
+ *   6. For every voxel v: Pbar(v) = the ordered window sum of step 1 over the field of P (zero where there is no centre),
+ *      cnt(v) = the number of processed centres whose window holds v,
+ *      out_i(v) = float32((sum_j Pbar_ij(v) x_j(v), j ascending from 0.0) / cnt); the input sample when cnt = 0.
+ *   7. sigma(v) = float32(sqrt(sigma^2)) and rank(v) = uint8(M - cut) of the centre clamp(v, radius, n - 1 - radius) (per
+ *      windowed axis); 0 when that centre is unprocessed.
+ * The noise is treated as Gaussian: at low SNR the Rician floor of magnitude data biases sigma low.
+ * fetal_t2mapping_amd/_mppca.py states all of it in numpy; the device output is bit-identical to it. */
+#define T2FIT_MPPCA_MAX_TE 16    /* n_te outside 2 .. this is refused; 2 .. 8 run register-resident kernels, 9 .. 16 a generic one */
+#define T2FIT_MPPCA_MAX_RADIUS 4 /* radius outside 1 .. this is refused */
+
+typedef struct t2fit_mppca_params {
+  int32_t radius;    /* 1 .. T2FIT_MPPCA_MAX_RADIUS; default 2 */
+  int32_t dims;      /* 2: the window spans x, y (every slice on its own, default); 3: x, y, z */
+  int32_t estimator; /* 1 or 2 (default): gamma of step 4 */
+  int32_t flags;     /* must be 0 */
+} t2fit_mppca_params;
+
+int t2fit_mppca_params_default(t2fit_mppca_params *p);
+
+/* Bytes of the workspace of a denoising call (out_dev != NULL); plain arithmetic, no device.  With up() rounding up to
+ * 256 and centres = (nz or nz - 2 radius) (ny - 2 radius) (nx - 2 radius):
+ *   up(8 * n_te (n_te + 1) / 2 * centres)  [the projector field, pair-major]  +  up(centres)  [processed flags]
+ * Refuses what t2fit_mppca_dev refuses in p and the sizes. */
+int t2fit_mppca_workspace_bytes(const t2fit_mppca_params *p, int n_te, int nz, int ny, int nx, size_t *bytes);
+
+/* mask_dev, out_dev, sigma_dev (float32, nz ny nx), rank_dev (uint8, nz ny nx) may each be NULL, the three outputs not all
+ * at once.  out_dev == NULL is the estimate-only call: one kernel, no projector field, and workspace_dev may be NULL with
+ * workspace_bytes 0.  Otherwise the workspace is aligned to 256 bytes, of any content, and two kernels run.  out_dev may
+ * equal in_dev; sigma_dev and rank_dev must not overlap in_dev.  Asynchronous on `stream`; no allocation, copy or
+ * synchronisation inside.  Every argument is checked before HIP is touched and a refusal (T2FIT_E_INVALID) leaves a
+ * message: p NULL, dims, radius, estimator, flags, n_te outside 2 .. T2FIT_MPPCA_MAX_TE, a window that holds no more voxels
+ * than there are echoes, a windowed axis shorter than 2 radius + 1, in_dev NULL, float pointers not aligned to 4 bytes,
+ * a missing, misaligned or short workspace. */
+int t2fit_mppca_dev(const t2fit_mppca_params *p, const float *in_dev, const uint8_t *mask_dev, float *out_dev, float *sigma_dev,
+                    uint8_t *rank_dev, int n_te, int nz, int ny, int nx, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ---- Orthogonal-stack reconstruction: resample to an isotropic grid and merge -------------------------------------
  * Steps 1 and 2 of the reference's run_qmri_reconstruction.py: every acquired thick-slice stack (ax / cor / sag, one per
  * echo time) is resampled to a 1 mm grid with linear interpolation (utils/qmri_utils.py resample_volume, :62-80), the
