@@ -60,6 +60,7 @@ class T2FitTvParams(C.Structure):
 
 TV_JOINT_MAX_CHAN = 64
 MPPCA_MAX_TE, MPPCA_MAX_RADIUS = 16, 4
+SEG_MAX_CLASSES, SEG_MAX_CHANNELS, SEG_MAX_RADIUS = 8, 4, 32
 
 
 class T2FitMppcaParams(C.Structure):
@@ -128,6 +129,15 @@ SYMBOLS = [
     ("t2fit_mppca_workspace_bytes", C.c_int, [C.POINTER(T2FitMppcaParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     ("t2fit_mppca_dev", C.c_int, [C.POINTER(T2FitMppcaParams), _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t,
                                   _P]),
+    ("t2fit_seg_workspace_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    ("t2fit_seg_mask_dev", C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P]),
+    ("t2fit_seg_priors_dev", C.c_int, [_P, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int,
+                                       C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int, _P, _P, _P]),
+    ("t2fit_seg_normalise_dev", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_double, _P, _P]),
+    ("t2fit_seg_sums_dev", C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    ("t2fit_seg_estep_dev", C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_double, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, _P, _P]),
+    ("t2fit_seg_labels_dev", C.c_int, [_P, _P, C.POINTER(C.c_int32), C.c_int, C.c_int64, _P, _P]),
     ("t2fit_resample_dev", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _P, C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.c_double, C.c_int, _P]),
     ("t2fit_reconstruct_workspace_bytes", C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
@@ -222,8 +232,10 @@ SVR_SYMBOLS = ("t2fit_svr_table_bytes", "t2fit_svr_table_host", "t2fit_svr_works
 SR_ROBUST_SYMBOLS = ("t2fit_sr_robust_params_default", "t2fit_sr_robust_workspace_bytes", "t2fit_sr_robust_dev")
 TVJ_SYMBOLS = ("t2fit_tv_joint_workspace_bytes", "t2fit_tv_joint_denoise_dev")
 MPPCA_SYMBOLS = ("t2fit_mppca_params_default", "t2fit_mppca_workspace_bytes", "t2fit_mppca_dev")
+SEG_SYMBOLS = ("t2fit_seg_workspace_bytes", "t2fit_seg_mask_dev", "t2fit_seg_priors_dev", "t2fit_seg_normalise_dev", "t2fit_seg_sums_dev",
+               "t2fit_seg_estep_dev", "t2fit_seg_labels_dev")
 LOOKED_UP = (ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS + MI_SYMBOLS + SR_SYMBOLS + SR_SLICE_SYMBOLS + SVR_SYMBOLS
-             + SR_ROBUST_SYMBOLS + TVJ_SYMBOLS + MPPCA_SYMBOLS)
+             + SR_ROBUST_SYMBOLS + TVJ_SYMBOLS + MPPCA_SYMBOLS + SEG_SYMBOLS)
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _register, _resample
+from . import _register, _resample, _seg
 
 
 def extract_brain(vol, mask):
@@ -38,13 +38,21 @@ def subject_mask(subject, mask):
 
 
 def atlas_labels(subject, subject_geom, template, template_geom, atlases, *, mask=None, bins=32, dof=12, levels=(4, 2, 1),
-                 max_iter=100, init="centroids", metric="cr"):
+                 max_iter=100, init="centroids", metric="cr", tissue=None):
     """``(warped template float32, {name: int32 labels}, Registration)`` on the subject's grid: the brain is extracted
     (``mask``; None: ``build_mask``), the template (moving, its mask ``template > 0``) is registered onto it (fixed) with
     the correlation ratio (``metric`` 'cr') or Mattes mutual information ('mattes'), and the found transform resamples the
-    template (linear) and every atlas (nearest, 0 outside)."""
+    template (linear) and every atlas (nearest, 0 outside).
+
+    ``tissue``: a dict with ``labels`` (a tissue-label atlas on the template's grid), ``classes`` (its K label values),
+    ``channels`` (1 .. 4 volumes of the subject, e.g. echoes) and optionally ``sigma`` (default 2 voxels) and the keywords of
+    ``_seg.segment_em``.  The tissue atlas follows the found transform by nearest neighbour, is blurred into spatial priors
+    and refined on the channels by expectation-maximisation inside the subject mask; a fourth value is returned, a dict
+    with ``labels`` (int32), ``propagated`` (the unrefined labels), ``prior``, ``model``, ``s0_trace`` and ``n_iter``."""
     subject, template = np.asarray(subject, np.float32), np.asarray(template, np.float32)
     atlases = check_atlases(atlases, template.shape)
+    if tissue is not None:
+        t_labels, t_classes, t_channels, t_sigma, t_em = _seg.tissue_arguments(tissue, template.shape, subject.shape)
     fmask = subject_mask(subject, mask)
     brain = extract_brain(subject, fmask)
     sg, tg = _resample.as_geometry(subject_geom, subject.shape), _resample.as_geometry(template_geom, template.shape)
@@ -52,4 +60,9 @@ def atlas_labels(subject, subject_geom, template, template_geom, atlases, *, mas
                                       moving_mask=(template > 0).astype(np.uint8), levels=levels, max_iter=max_iter, init=init)
     a = _resample.index_affine(sg, tg, found.transform)
     warped = _resample.resample(template, a, subject.shape)
-    return warped, {n: _resample.resample(lab, a, subject.shape, interp="nearest", default=0) for n, lab in atlases.items()}, found
+    labels = {n: _resample.resample(lab, a, subject.shape, interp="nearest", default=0) for n, lab in atlases.items()}
+    if tissue is None:
+        return warped, labels, found
+    propagated = _resample.resample(t_labels, a, subject.shape, interp="nearest", default=0)
+    prior = _seg.priors_from_labels(propagated, t_classes, t_sigma)
+    return warped, labels, found, _seg.tissue_result(propagated, prior, _seg.segment_em(t_channels, fmask, prior, t_classes, **t_em))

@@ -2,7 +2,7 @@
 :mod:`fetal_t2mapping_amd._atlas` states the stage in numpy."""
 import numpy as np
 
-from . import _atlas, _gpu_register, _resample
+from . import _atlas, _gpu_register, _gpu_seg, _resample, _seg
 from ._gpu import is_tensor, pick_device, volume
 from ._gpu_morph import build_mask
 from ._gpu_resample import resample_volume
@@ -23,7 +23,7 @@ def extract_brain(vol, mask, *, device=0):
 
 
 def atlas_labels(subject, subject_geom, template, template_geom, atlases, *, mask=None, bins=32, dof=12, levels=(4, 2, 1),
-                 max_iter=100, init="centroids", metric="cr", device=0):  # noqa: A002
+                 max_iter=100, init="centroids", metric="cr", tissue=None, device=0):  # noqa: A002
     """The reference's ``build_jhu_ho_labels`` (utils/qmri_utils.py:1011-1037) without FSL: ``subject`` (float32
     ``(Z, Y, X)``, e.g. the first-echo reconstruction) is brain-extracted with ``mask`` (None: :func:`build_mask`), the
     ``template`` (e.g. MNI152 T1; its mask is ``template > 0``) is registered onto it by
@@ -33,13 +33,23 @@ def atlas_labels(subject, subject_geom, template, template_geom, atlases, *, mas
     template float32, {name: int32 labels}, Registration)`` as numpy arrays; ``Registration.transform`` is the 4 x 4
     (subject point -> template point, LPS mm -- not FSL's convention).  Equal to :func:`_atlas.atlas_labels`.  Parity with
     flirt is not pinned: the cost and the transform model are its, the optimizer and the (absent) search are not.
-    ``metric``: 'cr', or 'mattes' for Mattes mutual information."""
+    ``metric``: 'cr', or 'mattes' for Mattes mutual information.
+
+    ``tissue``: a dict with ``labels`` (a tissue-label atlas on the template's grid), ``classes`` (its K label values),
+    ``channels`` (1 .. 4 volumes of the subject, e.g. echoes) and optionally ``sigma`` (default 2 voxels) and the keywords of
+    ``seg.segment_em``.  The tissue atlas follows the found transform by nearest neighbour, is blurred into spatial priors
+    (``seg.priors_from_labels``) and refined on the channels by expectation-maximisation inside the subject mask
+    (``seg.segment_em``), all on the device; a fourth value is returned, a dict of numpy arrays with ``labels`` (int32),
+    ``propagated`` (the unrefined labels), ``prior``, ``model``, ``s0_trace`` and ``n_iter``.  ``tissue=None`` changes nothing."""
     import torch
 
     dev = pick_device((subject, template, mask), device)
     template_host = template.cpu().numpy() if is_tensor(template) else np.asarray(template, np.float32)
     atlases = _atlas.check_atlases({n: (a.cpu().numpy() if is_tensor(a) else a) for n, a in dict(atlases).items()}, template_host.shape)
     s, t = volume(subject, torch.float32, dev, "subject"), volume(template, torch.float32, dev, "template")
+    if tissue is not None:
+        tis = {k: (v.cpu().numpy() if is_tensor(v) else v) for k, v in dict(tissue).items()}
+        t_labels, t_classes, t_channels, t_sigma, t_em = _seg.tissue_arguments(tis, template_host.shape, tuple(s.shape))
     fmask = build_mask(s, device=dev.index) if mask is None else volume(mask, torch.uint8, dev, "mask")
     brain = extract_brain(s, fmask)
     sg, tg = _resample.as_geometry(subject_geom, tuple(s.shape)), _resample.as_geometry(template_geom, tuple(t.shape))
@@ -49,4 +59,11 @@ def atlas_labels(subject, subject_geom, template, template_geom, atlases, *, mas
     warped = resample_volume(t, tg, like=sg, transform=found.transform)[0].cpu().numpy()
     labels = {n: resample_volume(torch.from_numpy(lab).to(dev), tg, like=sg, transform=found.transform, interp="nearest",
                                  default=0)[0].cpu().numpy() for n, lab in atlases.items()}
-    return warped, labels, found
+    if tissue is None:
+        return warped, labels, found
+    propagated = resample_volume(torch.from_numpy(t_labels).to(dev), tg, like=sg, transform=found.transform, interp="nearest",
+                                 default=0)[0]
+    prior = _gpu_seg.priors_from_labels(propagated, t_classes, t_sigma)
+    res = _gpu_seg.segment_em(torch.from_numpy(t_channels).to(dev), fmask, prior, t_classes, **t_em)
+    return warped, labels, found, _seg.tissue_result(propagated.cpu().numpy(), prior.cpu().numpy(),
+                                                     res._replace(labels=res.labels.cpu().numpy()))

@@ -20,6 +20,10 @@ build_jhu_ho_labels (utils/qmri_utils.py:953-974, :1011-1037) without FSL: per (
 volume is masked by its recon_1mm_mask (``recon_1mm_bet``), the template is registered onto it on the GPU
 (``t2map.atlas.atlas_labels``: 12 degrees of freedom, correlation ratio; not flirt, parity unpinned) and written on the subject's
 grid as ``recon_1mm_mni152``, every atlas as ``recon_1mm_<NAME>`` -- the name ``cli.py --roi_stats NAME`` opens.
+With ``--tissue_atlas FILE`` a tissue-label image on the template's grid follows the same transform and is refined on the
+subject's echoes by expectation-maximisation on the GPU (``t2map.seg``), in place of the reference's SynthSeg steps 4 to 6
+(utils/qmri_utils.py:424-466, :976-1009; another method, parity impossible to pin); the labels are written as
+``recon_1mm_feta``, which ``cli.py --roi_stats feta`` and the tissue erosion read.
 
 ``--register_to_lf`` (``--hf --in_vivo``) stands for the reference's register_high_to_low_field (utils/qmri_utils.py:1039-1051,
 step 3bis of run_qmri_reconstruction.py): every 1.5 T recon_1mm volume is registered rigidly (Mattes mutual information) onto
@@ -45,7 +49,7 @@ import time
 import numpy as np
 
 from . import _resample, _sr, t2map
-from .cli import (_sitk, build_phantom_subject, get_img_path, load_seeds, mask_dirname, phantom_labels_dirname, recon_dirname,
+from .cli import (_sitk, build_phantom_subject, feta_dirname, get_img_path, load_seeds, mask_dirname, phantom_labels_dirname, recon_dirname,
                   set_metadata)
 
 in_dirname = "anat"
@@ -513,23 +517,62 @@ def process_register_to_lf(metadata, bids_path, *, write_transforms=None, device
     return written
 
 
-def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fixed="ax", dof=12, bins=32, metric="cr", device=0):  # noqa: A002
+TISSUE_DEFAULT_CLASSES = (1, 2, 3, 4, 5, 6, 7)  # the FeTA values
+tissue_prior_dirname = feta_dirname + "_prior"
+
+
+def parse_tissue_classes(text):
+    """``--tissue_classes 1,2,...`` -> a tuple of at least 2 distinct positive label values."""
+    try:
+        values = tuple(int(v) for v in str(text).split(","))
+    except ValueError:
+        raise ValueError(f"--tissue_classes {text!r}: expected integers separated by commas") from None
+    if len(values) < 2:
+        raise ValueError(f"--tissue_classes {text!r}: a segmentation needs at least 2 classes")
+    if len(values) > 8 or len(set(values)) != len(values) or min(values) < 1:
+        raise ValueError(f"--tissue_classes {text!r}: at most 8 distinct values >= 1")
+    return values
+
+
+def tissue_echo_rows(echoes, wanted_ms):
+    """The rows of the echoes [ms] the tissue segmentation reads, in the order asked for, out of ``echo_groups``' list of
+    one (sub, ses); None: the first echo.  An echo that is not among the reconstructed ones raises."""
+    if wanted_ms is None:
+        return [echoes[0][1]]
+    by_ms = {int(round(te * 1000)): rows for te, rows in echoes}
+    missing = [ms for ms in wanted_ms if ms not in by_ms]
+    if missing:
+        raise ValueError(f"--tissue_echoes: no echo of {missing[0]} ms is reconstructed (there are {', '.join(map(str, sorted(by_ms)))} ms)")
+    return [by_ms[ms] for ms in wanted_ms]
+
+
+def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fixed="ax", dof=12, bins=32, metric="cr", tissue=None,
+                         device=0):  # noqa: A002
     """``--atlas_labels``: for every (sub, ses), from the first echo's recon_1mm volume and recon_1mm_mask: the masked volume
     under recon_1mm_bet, the registered template under recon_1mm_mni152 with the 4 x 4 transform beside it (``.txt``:
     subject point -> template point, LPS millimetres, the text form of --write_transforms; not FSL's convention), and
-    every atlas (int32, nearest neighbour) under recon_1mm_<NAME>.  ``metric``: 'cr' or 'mattes'.  Returns the paths
-    written."""
+    every atlas (int32, nearest neighbour) under recon_1mm_<NAME>.  ``metric``: 'cr' or 'mattes'.
+
+    ``tissue`` (``--tissue_atlas``): a dict with ``path`` (a tissue-label image on the template's grid), ``classes``,
+    ``echoes`` (echo times [ms], None: the first echo) and optionally ``sigma``, ``beta``, ``n_iter``, ``write_prior``.  The
+    tissue atlas follows the same transform and is refined on the recon_1mm volumes of those echoes by expectation-
+    maximisation (``t2map.atlas.atlas_labels(tissue=...)``); the result goes, int32, under recon_1mm_feta, which
+    ``cli.py --roi_stats feta`` reads, and with ``write_prior`` the propagated, unrefined labels under recon_1mm_feta_prior.
+    Returns the paths written."""
     sitk = _sitk()
     template_img = sitk.ReadImage(template_path)
     template = np.asarray(sitk.GetArrayFromImage(template_img), np.float32)
-    atlases = {}
-    for name, path in atlas_specs:
+
+    def read_labels(flag, path):
         img = sitk.ReadImage(path)
         arr = np.asarray(sitk.GetArrayFromImage(img))
         if arr.shape != template.shape or any(getattr(img, get)() != getattr(template_img, get)()
                                               for get in ("GetSpacing", "GetOrigin", "GetDirection")):
-            raise ValueError(f"--atlas {name}={path}: the atlas does not lie on the template's grid")
-        atlases[name] = (arr if arr.dtype.kind in "iu" else np.rint(arr)).astype(np.int32)
+            raise ValueError(f"{flag}={path}: the atlas does not lie on the template's grid")
+        return (arr if arr.dtype.kind in "iu" else np.rint(arr)).astype(np.int32)
+
+    atlases = {name: read_labels(f"--atlas {name}", path) for name, path in atlas_specs}
+    tissue_labels = None if tissue is None else read_labels("--tissue_atlas ", tissue["path"])
     written = []
 
     def write(arr, like, path):
@@ -548,8 +591,20 @@ def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fix
         mask = np.asarray(sitk.GetArrayFromImage(sitk.ReadImage(mask_path)))
         t0 = time.time()
         subject = np.asarray(sitk.GetArrayFromImage(img), np.float32)
-        warped, labels, found = t2map.atlas.atlas_labels(subject, img, template, template_img, atlases, mask=mask, dof=dof, bins=bins,
-                                                   device=device, **({} if metric == "cr" else {"metric": metric}))
+        more = {} if metric == "cr" else {"metric": metric}
+        if tissue is not None:
+            channels = []
+            for ch_rows in tissue_echo_rows(echoes, tissue.get("echoes")):
+                ch_acq = ch_rows[fixed] if fixed in ch_rows else next(iter(ch_rows.values()))
+                ch = np.asarray(sitk.GetArrayFromImage(sitk.ReadImage(get_img_path(bids_path, ch_acq, recon_dirname).replace(" ", ""))),
+                                np.float32)
+                if ch.shape != subject.shape:
+                    raise ValueError(f"--tissue_echoes: the echoes of {sub}_{ses} do not share a grid")
+                channels.append(ch)
+            more["tissue"] = {"labels": tissue_labels, "classes": tissue["classes"], "channels": np.stack(channels),
+                              **{k: tissue[k] for k in ("sigma", "beta", "n_iter") if tissue.get(k) is not None}}
+        warped, labels, found, *refined = t2map.atlas.atlas_labels(subject, img, template, template_img, atlases, mask=mask, dof=dof,
+                                                             bins=bins, device=device, **more)
         write(t2map.atlas.extract_brain(subject, mask), img, get_img_path(bids_path, acq, atlas_bet_dirname).replace(" ", ""))
         template_out = get_img_path(bids_path, acq, atlas_template_dirname).replace(" ", "")
         write(warped, img, template_out)
@@ -557,6 +612,13 @@ def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fix
         written.append(template_out.replace(".nii.gz", ".txt"))
         for name, lab in labels.items():
             write(lab, img, get_img_path(bids_path, acq, recon_dirname + "_" + name).replace(" ", ""))
+        if refined:
+            write(np.asarray(refined[0]["labels"], np.int32), img, get_img_path(bids_path, acq, feta_dirname).replace(" ", ""))
+            if tissue.get("write_prior"):
+                write(np.asarray(refined[0]["propagated"], np.int32), img, get_img_path(bids_path, acq, tissue_prior_dirname).replace(" ", ""))
+            dead = [int(c) for c, d in zip(tissue["classes"], refined[0]["model"].dead) if d]
+            print(f"... tissue labels of {sub}_{ses}: {refined[0]['n_iter']} EM iterations over {len(channels)} echo(es)"
+                  + (f", classes without voxels: {dead}" if dead else ""))
         print(f"... atlas labels of {sub}_{ses}: {'CR' if metric == 'cr' else '-MI'} {found.metric:.4f}, iterations {found.iterations}, "
               f"{round(time.time() - t0, 4)} sec")
     return written
@@ -777,6 +839,21 @@ def parse_arguments(argv=None):
     p.add_argument("--atlas_bins", type=int, default=32, help="bins of the correlation ratio, 1..64 (default 32)")
     p.add_argument("--atlas_metric", choices=["cr", "mattes"], default="cr",
                    help="with --atlas_labels: cr = the correlation ratio (default, flirt's cost); mattes = Mattes mutual information")
+    p.add_argument("--tissue_atlas", default=None, metavar="FILE",
+                   help="with --atlas_labels: a tissue-label image on the template's grid.  It follows the found transform, is "
+                        "blurred into spatial priors and refined on the subject's own echoes by expectation-maximisation on the "
+                        "GPU (Gaussian mixture with a Potts term; stands for the reference's SynthSeg steps, parity impossible to "
+                        "pin); the labels are written under recon_1mm_feta, which cli.py --roi_stats feta reads; off by default")
+    p.add_argument("--tissue_classes", default=None, metavar="1,2,...", help="with --tissue_atlas: the label values that are tissue "
+                                                                             "classes, 2 .. 8 of them (default 1,2,3,4,5,6,7: FeTA's)")
+    p.add_argument("--tissue_echoes", type=int, nargs="+", default=None, metavar="MS",
+                   help="with --tissue_atlas: the echoes [ms] whose recon_1mm volumes are the channels, at most 4 (default: the "
+                        "first echo, which the atlas registration uses)")
+    p.add_argument("--tissue_sigma", type=float, default=None, help="with --tissue_atlas: blur of the priors in voxels (default 2)")
+    p.add_argument("--tissue_beta", type=float, default=None, help="with --tissue_atlas: weight of the Potts term (default 0.5)")
+    p.add_argument("--tissue_iter", type=int, default=None, help="with --tissue_atlas: EM iterations (default 15)")
+    p.add_argument("--write_tissue_prior", action="store_true",
+                   help="with --tissue_atlas: also write the propagated, unrefined labels under recon_1mm_feta_prior")
     p.add_argument("--n4", action="store_true",
                    help="N4 bias-field correction of the acquired stacks on the GPU before step 1 (the reference's "
                         "run_biasfield_correction2; parity with ITK unpinned): per orientation one log field, estimated on one "
@@ -821,6 +898,35 @@ def parse_arguments(argv=None):
                 p.error(f"--atlas: {path!r} does not exist")
     elif args.atlas_template is not None or args.atlas:
         p.error("--atlas_template / --atlas have no effect without --atlas_labels")
+    tissue_flags = [f for f, v in (("--tissue_classes", args.tissue_classes), ("--tissue_echoes", args.tissue_echoes),
+                                   ("--tissue_sigma", args.tissue_sigma), ("--tissue_beta", args.tissue_beta),
+                                   ("--tissue_iter", args.tissue_iter), ("--write_tissue_prior", args.write_tissue_prior or None))
+                    if v is not None]
+    args.tissue_args = None
+    if args.tissue_atlas is not None:
+        if not args.atlas_labels:
+            p.error("--tissue_atlas has no effect without --atlas_labels")
+        if not os.path.isfile(args.tissue_atlas):
+            p.error(f"--tissue_atlas: {args.tissue_atlas!r} does not exist")
+        try:
+            classes = TISSUE_DEFAULT_CLASSES if args.tissue_classes is None else parse_tissue_classes(args.tissue_classes)
+        except ValueError as e:
+            p.error(str(e))
+        if args.tissue_echoes is not None and not 1 <= len(args.tissue_echoes) <= 4:
+            p.error("--tissue_echoes takes 1 .. 4 echo times")
+        if args.tissue_echoes is not None and len(set(args.tissue_echoes)) != len(args.tissue_echoes):
+            p.error("--tissue_echoes: an echo is given twice")
+        if args.tissue_sigma is not None and not 0.0 <= args.tissue_sigma <= 8.0:
+            p.error("--tissue_sigma is in 0 .. 8 voxels")
+        if args.tissue_beta is not None and not (args.tissue_beta >= 0.0 and np.isfinite(args.tissue_beta)):
+            p.error("--tissue_beta must be a number >= 0")
+        if args.tissue_iter is not None and args.tissue_iter < 1:
+            p.error("--tissue_iter must be >= 1")
+        args.tissue_args = {"path": args.tissue_atlas, "classes": classes, "echoes": args.tissue_echoes, "sigma": args.tissue_sigma,
+                            "beta": args.tissue_beta, "n_iter": args.tissue_iter, "write_prior": args.write_tissue_prior}
+    elif tissue_flags:
+        p.error(f"{tissue_flags[0]} has no effect without --tissue_atlas")
+    args.error = p.error
     if args.phantom_masks and not args.in_vitro:
         p.error("--phantom_masks goes with --in_vitro")
     if args.phantom_seeds is not None and not args.phantom_masks:
@@ -852,6 +958,12 @@ def main(argv=None):
     bids_path = os.path.join(args.path, "projects/")
     csv_path = os.path.join(args.path, "dicom/logs/")
     metadata = set_metadata(csv_path, args.csv, bool(args.lf))
+    if args.tissue_args is not None:
+        try:
+            for _, _, _, echoes in echo_groups(metadata):
+                tissue_echo_rows(echoes, args.tissue_args["echoes"])
+        except ValueError as e:
+            args.error(str(e))
     process_recon(metadata, bids_path, fixed=args.fixed, res=args.res, transforms_dir=args.transforms,
                   write_resamp=args.write_resamp, denoise=not args.no_denoise, register=args.register,
                   write_transforms=args.write_transforms, register_echoes=args.register_echoes, n4=args.n4_args,
@@ -862,7 +974,8 @@ def main(argv=None):
         process_phantom_masks(metadata, bids_path, seeds=args.seeds, fixed=args.fixed, device=args.device)
     if args.atlas_labels:
         process_atlas_labels(metadata, bids_path, args.atlas_template, args.atlas_specs, fixed=args.fixed, dof=args.atlas_dof,
-                             bins=args.atlas_bins, metric=args.atlas_metric, device=args.device)
+                             bins=args.atlas_bins, metric=args.atlas_metric, device=args.device,
+                             **({} if args.tissue_args is None else {"tissue": args.tissue_args}))
 
 
 if __name__ == "__main__":

@@ -32,6 +32,7 @@ atlas labels           ``_gpu_atlas``      ``_atlas`` (affine registration by th
 super-resolution       ``_gpu_sr``         ``_sr`` (operator, adjoint and the proximal-gradient loop; the prox is ``_tv``); here as ``sr``
 slice-to-volume        ``_gpu_register``,  ``_svr`` (batched per-slice sums, transform model, lockstep descent and driver, which are host
 registration           ``_gpu_sr``         code); here as ``register.register_slices``, ``register.slice_sums``, ``sr.reconstruct_svr``
+tissue segmentation    ``_gpu_seg``        ``_seg`` (the steps, and the EM loop and class model, which are host code); here as ``seg``
 N4 bias field          ``_gpu_bias``       ``_bias`` (and the sharpening table, the refinement and the loop, which are host code); here as ``bias``
 =====================  ==================  ===========================================================
 
@@ -53,6 +54,8 @@ from . import _gpu_sr as sr  # noqa: F401  (a namespace: sr.reconstruct_sr, sr.s
 #                               outlier weighting of reconstruct_sr(robust=...) alone: sr.sr_robust_weights)
 from ._gpu_tv import denoise_tv, tv_params  # noqa: F401
 from . import _gpu_mppca as mppca  # noqa: F401  (a namespace: mppca.denoise_mppca, mppca.mppca_noise_map, mppca.mppca_params)
+from . import _gpu_seg as seg  # noqa: F401  (a namespace: seg.segment_em, seg.priors_from_labels, seg.moment_sums, seg.e_step,
+#                                seg.hard_labels, seg.seg_params)
 
 
 def __getattr__(name):

@@ -487,6 +487,74 @@ int t2fit_mppca_workspace_bytes(const t2fit_mppca_params *p, int n_te, int nz, i
 int t2fit_mppca_dev(const t2fit_mppca_params *p, const float *in_dev, const uint8_t *mask_dev, float *out_dev, float *sigma_dev,
                     uint8_t *rank_dev, int n_te, int nz, int ny, int nx, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ---- Atlas-prior EM tissue segmentation (additive to ABI 5) ---------------------------------------------------------
+ * A Gaussian mixture over C channels (echoes of one subject) and K classes with spatial priors and a mean-field Potts
+ * term (Van Leemput 1999; Habas 2010 for fetal brains).  The library provides the steps; the loop, the class model
+ * (means, precisions, log-determinants from the sums) and the stop rule are host code, fetal_t2mapping_amd/_seg.py, which
+ * also states every step below in numpy.  Volumes are (nz, ny, nx), x fastest; p, pi and the priors are K planes, y is C
+ * planes, float32; masks are uint8.  M is the set of voxels with mask != 0 and every channel finite: t2fit_seg_mask_dev
+ * writes it as 0 / 1, and the mask_dev of the other steps must be such a mask (they test their own voxel's channels again,
+ * but trust the mask for its neighbours).  Everything is float64 with one rounding per operation in the order written,
+ * nothing fused, and one rounding to float32 where a float32 is stored:
+ *   priors     plane k = the image labels == classes[k] (1.0 / 0.0), blurred along x, then y, then z; a pass is
+ *              float32(sum_j w_j (double)in[i + j - r], j = 0 .. 2 r ascending from 0.0, taps beyond the volume left out).
+ *   normalise  pi_ik = float32(((double)prior_ik + floor) / ((sum_l (double)prior_il, l ascending from 0.0) + K floor)) in
+ *              mask != 0, +0.0 outside.
+ *   sums       per class k, M = 1 + C + C (C + 1) / 2 values: S0 = sum p, S1_c = sum p y_c, S2_cd = sum (p y_c) y_d (c <= d,
+ *              row-major), over the voxels of M.  The tree: workgroup b takes the voxels 1024 b .. 1024 b + 1023 of the flat
+ *              volume; its lane t (0 .. 255) adds the terms of the voxels 1024 b + 256 j + t, j = 0 .. 3 in this order from
+ *              0.0, leaving out those beyond the volume or outside M; each wave of 64 lanes folds by v = v + v[lane ^ s] for
+ *              s = 32, 16, 8, 4, 2, 1; the four waves add as ((w0 + w1) + w2) + w3.  The workgroup values are then folded in
+ *              passes until one is left (at least one pass): a pass turns 256 consecutive values (zeros beyond the end)
+ *              into one by s[t] = s[t] + s[t + h] for t < h, h = 128, 64, .. 1.  sums_out[k M + m].
+ *   estep      for a voxel of M and a live class k, with model[k] = (mu_c (C), the upper triangle of the precision P_cd
+ *              row-major, c_k): t_c = (double)y_c - mu_c; d = sum over c <= d row-major from 0.0 of
+ *              (((c == d ? 1 : 2) P_cd) t_c) t_d; n = sum from 0.0 of (1 - (double)p_old_jk) over the neighbours j inside the
+ *              volume with mask != 0, in the order -z, -y, -x, +x, +y, +z; a_k = (c_k - 0.5 d) - beta n; m = max a_k;
+ *              q_k = (double)pi_ik exp(a_k - m); s = sum of q_k, k ascending from 0.0; p_new_ik = float32(q_k / s).  A class
+ *              that is not live and a voxel outside M get +0.0.  (exp is the device library's: the statement's differs in
+ *              the last bits, so this step is within 1 float32 ulp of it, not bit-identical.)
+ *   labels     classes[the first k of the largest p_ik] where mask != 0, 0 elsewhere.
+ * All entry points are asynchronous on `stream`, allocate nothing and check every argument before HIP is touched; a
+ * refusal (T2FIT_E_INVALID) leaves a message that names the argument: n_class outside 2 .. T2FIT_SEG_MAX_CLASSES, n_chan
+ * outside 1 .. T2FIT_SEG_MAX_CHANNELS, a radius outside 0 .. T2FIT_SEG_MAX_RADIUS, sizes < 1 or a volume above 2^37 voxels,
+ * NULL pointers, float pointers not aligned to 4 bytes (double ones to 8), floor or beta negative or not finite,
+ * p_new_dev == p_old_dev, no live class. */
+#define T2FIT_SEG_MAX_CLASSES 8
+#define T2FIT_SEG_MAX_CHANNELS 4
+#define T2FIT_SEG_MAX_RADIUS 32
+
+/* Bytes of the workspace that serves both t2fit_seg_priors_dev and t2fit_seg_sums_dev; plain arithmetic, no device.  With
+ * up() rounding up to 256, n = nz ny nx, b = ceil(n / 1024) and Q = n_class (1 + n_chan + n_chan (n_chan + 1) / 2):
+ *   max(up(4 n_class n)  [the y pass of the blur],  up(8 Q b) + up(8 Q ceil(b / 256))  [the partial sums, two buffers]) */
+int t2fit_seg_workspace_bytes(int n_class, int n_chan, int nz, int ny, int nx, size_t *bytes);
+
+/* m_out = 1 where mask_dev != 0 (NULL: everywhere) and all n_chan channels of y_dev are finite, else 0. */
+int t2fit_seg_mask_dev(const float *y_dev, const uint8_t *mask_dev, int n_chan, int64_t n_vox, uint8_t *m_out_dev, void *stream);
+
+/* classes and the taps (2 r + 1 doubles per axis, host memory) are read before the call returns.  The workspace (of any
+ * content, aligned to 4 bytes) must not overlap prior_out_dev. */
+int t2fit_seg_priors_dev(const int32_t *labels_dev, const int32_t *classes, int n_class, int nz, int ny, int nx, const double *taps_z,
+                         int rz, const double *taps_y, int ry, const double *taps_x, int rx, float *prior_out_dev, void *workspace_dev,
+                         void *stream);
+
+/* pi_out_dev must not overlap prior_dev. */
+int t2fit_seg_normalise_dev(const float *prior_dev, const uint8_t *mask_dev, int n_class, int64_t n_vox, double floor, float *pi_out_dev,
+                            void *stream);
+
+/* Writes n_class (1 + n_chan + n_chan (n_chan + 1) / 2) doubles to sums_out_dev (device memory).  The workspace is of any
+ * content and aligned to 8 bytes. */
+int t2fit_seg_sums_dev(const float *p_dev, const float *y_dev, const uint8_t *mask_dev, int n_class, int n_chan, int nz, int ny, int nx,
+                       double *sums_out_dev, void *workspace_dev, void *stream);
+
+/* model: n_class rows of n_chan + n_chan (n_chan + 1) / 2 + 1 doubles, live: n_class flags, both host memory, read before
+ * the call returns (they travel in the kernel's arguments). */
+int t2fit_seg_estep_dev(const float *p_old_dev, const float *pi_dev, const float *y_dev, const uint8_t *mask_dev, const double *model,
+                        const int32_t *live, double beta, int n_class, int n_chan, int nz, int ny, int nx, float *p_new_dev, void *stream);
+
+int t2fit_seg_labels_dev(const float *p_dev, const uint8_t *mask_dev, const int32_t *classes, int n_class, int64_t n_vox,
+                         int32_t *labels_out_dev, void *stream);
+
 /* ---- Orthogonal-stack reconstruction: resample to an isotropic grid and merge -------------------------------------
  * Steps 1 and 2 of the reference's run_qmri_reconstruction.py: every acquired thick-slice stack (ax / cor / sag, one per
  * echo time) is resampled to a 1 mm grid with linear interpolation (utils/qmri_utils.py resample_volume, :62-80), the
