@@ -187,6 +187,14 @@ SYMBOLS = [
     ("t2fit_register_mi_workspace_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     ("t2fit_register_mi_gradient_dev", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_double, C.c_double, _P, C.c_int, C.c_int, C.c_int,
                                                  _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _P, _P, C.c_size_t, _P]),
+    ("t2fit_ffd_workspace_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    ("t2fit_ffd_joint_hist_dev", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _P,
+                                           C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P, C.c_size_t, _P]),
+    ("t2fit_ffd_gradient_dev", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_double, C.c_double, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int,
+                                         C.c_int, C.c_int, C.POINTER(C.c_double), _P, C.c_int, _P, _P, C.c_size_t, _P]),
+    ("t2fit_ffd_warp_dev", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _P, C.c_int, _P, C.c_int, C.c_int,
+                                     C.c_int, C.c_int, C.c_double, _P, C.c_size_t, _P]),
+    ("t2fit_ffd_jacobian_dev", C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     ("t2fit_svr_table_bytes", C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
     ("t2fit_svr_table_host", C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8),
                                        C.c_int, C.POINTER(C.c_int32), _P, C.c_size_t]),
@@ -234,8 +242,10 @@ TVJ_SYMBOLS = ("t2fit_tv_joint_workspace_bytes", "t2fit_tv_joint_denoise_dev")
 MPPCA_SYMBOLS = ("t2fit_mppca_params_default", "t2fit_mppca_workspace_bytes", "t2fit_mppca_dev")
 SEG_SYMBOLS = ("t2fit_seg_workspace_bytes", "t2fit_seg_mask_dev", "t2fit_seg_priors_dev", "t2fit_seg_normalise_dev", "t2fit_seg_sums_dev",
                "t2fit_seg_estep_dev", "t2fit_seg_labels_dev")
+FFD_SYMBOLS = ("t2fit_ffd_workspace_bytes", "t2fit_ffd_joint_hist_dev", "t2fit_ffd_gradient_dev", "t2fit_ffd_warp_dev",
+               "t2fit_ffd_jacobian_dev")
 LOOKED_UP = (ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS + MI_SYMBOLS + SR_SYMBOLS + SR_SLICE_SYMBOLS + SVR_SYMBOLS
-             + SR_ROBUST_SYMBOLS + TVJ_SYMBOLS + MPPCA_SYMBOLS + SEG_SYMBOLS)
+             + SR_ROBUST_SYMBOLS + TVJ_SYMBOLS + MPPCA_SYMBOLS + SEG_SYMBOLS + FFD_SYMBOLS)
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _register, _resample, _seg
+from . import _ffd, _register, _resample, _seg
 
 
 def extract_brain(vol, mask):
@@ -38,7 +38,7 @@ def subject_mask(subject, mask):
 
 
 def atlas_labels(subject, subject_geom, template, template_geom, atlases, *, mask=None, bins=32, dof=12, levels=(4, 2, 1),
-                 max_iter=100, init="centroids", metric="cr", tissue=None):
+                 max_iter=100, init="centroids", metric="cr", tissue=None, nonrigid=None):
     """``(warped template float32, {name: int32 labels}, Registration)`` on the subject's grid: the brain is extracted
     (``mask``; None: ``build_mask``), the template (moving, its mask ``template > 0``) is registered onto it (fixed) with
     the correlation ratio (``metric`` 'cr') or Mattes mutual information ('mattes'), and the found transform resamples the
@@ -48,7 +48,13 @@ def atlas_labels(subject, subject_geom, template, template_geom, atlases, *, mas
     ``channels`` (1 .. 4 volumes of the subject, e.g. echoes) and optionally ``sigma`` (default 2 voxels) and the keywords of
     ``_seg.segment_em``.  The tissue atlas follows the found transform by nearest neighbour, is blurred into spatial priors
     and refined on the channels by expectation-maximisation inside the subject mask; a fourth value is returned, a dict
-    with ``labels`` (int32), ``propagated`` (the unrefined labels), ``prior``, ``model``, ``s0_trace`` and ``n_iter``."""
+    with ``labels`` (int32), ``propagated`` (the unrefined labels), ``prior``, ``model``, ``s0_trace`` and ``n_iter``.
+
+    ``nonrigid``: None (the affine alone), True or a dict of :func:`_ffd.register_ffd`'s keywords (``schedule``, ``weight``,
+    ``max_iter``, ``max_step``, ``bins``, ``moving_bins``).  After the affine, :func:`_ffd.register_ffd` starts from it; the
+    template is warped linearly and every atlas and the tissue atlas by nearest neighbour through :func:`_ffd.warp`, and the
+    third value is the :class:`_ffd.FFDRegistration` (its ``transform`` is the affine's).  The affine stage keeps the
+    ``metric`` the caller chose; the deformation always uses Mattes mutual information."""
     subject, template = np.asarray(subject, np.float32), np.asarray(template, np.float32)
     atlases = check_atlases(atlases, template.shape)
     if tissue is not None:
@@ -59,10 +65,19 @@ def atlas_labels(subject, subject_geom, template, template_geom, atlases, *, mas
     found = _register.register_affine(brain, template, sg, tg, metric=metric, bins=bins, dof=dof, fixed_mask=fmask,
                                       moving_mask=(template > 0).astype(np.uint8), levels=levels, max_iter=max_iter, init=init)
     a = _resample.index_affine(sg, tg, found.transform)
-    warped = _resample.resample(template, a, subject.shape)
-    labels = {n: _resample.resample(lab, a, subject.shape, interp="nearest", default=0) for n, lab in atlases.items()}
+    if nonrigid is None:
+        def carry(vol, interp="linear"):
+            return _resample.resample(vol, a, subject.shape, interp=interp, default=0)
+    else:
+        found = _ffd.register_ffd(brain, template, sg, tg, affine=found, fixed_mask=fmask, moving_mask=(template > 0).astype(np.uint8),
+                                  **_ffd.nonrigid_options(nonrigid))
+
+        def carry(vol, interp="linear"):
+            return _ffd.warp(vol, a, found.lattice, subject.shape, interp=interp, default=0)
+    warped = carry(template)
+    labels = {n: carry(lab, "nearest") for n, lab in atlases.items()}
     if tissue is None:
         return warped, labels, found
-    propagated = _resample.resample(t_labels, a, subject.shape, interp="nearest", default=0)
+    propagated = carry(t_labels, "nearest")
     prior = _seg.priors_from_labels(propagated, t_classes, t_sigma)
     return warped, labels, found, _seg.tissue_result(propagated, prior, _seg.segment_em(t_channels, fmask, prior, t_classes, **t_em))

@@ -450,3 +450,16 @@ def register_slices(stacks, geoms, volume, volume_geom, *, transforms=None, stac
     return _svr.register_with(lambda a, active: slices.sums(a, s_of, k_of, active), names, geoms, host_masks,
                               _resample.as_geometry(volume_geom, tuple(slices.moving.shape)), transforms, init,
                               max_iter=int(max_iter), step=float(step), min_step=float(min_step), min_count=int(min_count))
+
+
+# ---- non-rigid alignment ---------------------------------------------------------------------------------------------------
+_FFD_NAMES = ("register_ffd", "ffd_joint_histogram", "ffd_gradient", "ffd_warp", "ffd_min_jacobian")
+
+
+def __getattr__(name):
+    """``register.register_ffd`` and the four ``ffd_*`` steps live in :mod:`_gpu_ffd`, which builds on this module."""
+    if name in _FFD_NAMES:
+        from . import _gpu_ffd
+
+        return getattr(_gpu_ffd, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

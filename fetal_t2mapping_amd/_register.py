@@ -79,12 +79,14 @@ def workspace_bytes(shape):
     return sum((N_SUMS * 8 * n + 255) // 256 * 256 for n in pass_sizes(bz * by * bx))
 
 
-def _terms(fixed, fmask, moving, mmask, a, z0, nzc):
-    """float64 ``(43, nzc, fy, fx)``: what every voxel of the fixed planes ``z0 .. z0 + nzc`` adds to the sums."""
+def _terms(fixed, fmask, moving, mmask, a, z0, nzc, coords=None):
+    """float64 ``(43, nzc, fy, fx)``: what every voxel of the fixed planes ``z0 .. z0 + nzc`` adds to the sums.
+    ``coords``: the moving coordinates ``(c_x, c_y, c_z)`` of those planes from the caller (:mod:`_ffd`), in place of
+    ``A`` applied to the voxel index."""
     _, fy, fx = fixed.shape
     n = moving.shape[::-1]
     shape = (nzc, fy, fx)
-    c = _resample._coords(a, shape, (0, 0, z0))
+    c = _resample._coords(a, shape, (0, 0, z0)) if coords is None else coords
     counted = fmask[z0:z0 + nzc] != 0
     for k in range(3):
         counted = counted & (c[k] >= -0.5) & (c[k] < n[k] - 0.5)

@@ -102,21 +102,23 @@ def _coords(a, out_shape, start=(0, 0, 0)):
     return [np.broadcast_to(((a[k, 0] * ix + a[k, 1] * iy) + a[k, 2] * iz) + a[k, 3], out_shape) for k in range(3)]
 
 
-def resample(src, A, out_shape, interp="linear", default=0.0, integer_cast=False, start=(0, 0, 0)):
+def resample(src, A, out_shape, interp="linear", default=0.0, integer_cast=False, start=(0, 0, 0), coords=None):
     """``src`` ``(Z, Y, X)`` (or ``(n, Z, Y, X)``: volumes that share the geometry) sampled at the points of ``A`` (from
     :func:`index_affine`) for an output of ``out_shape`` (Z, Y, X).  linear: float32 result; nearest: the source's type
     (int32 or float32).  ``start`` (x, y, z): evaluate the box of ``out_shape`` whose first voxel has this output index (a
-    part of a larger output, with the very same coordinates).  See include/t2fit.h for the definition."""
+    part of a larger output, with the very same coordinates).  ``coords``: the source coordinates ``(c_x, c_y, c_z)`` of
+    every output voxel from the caller (:mod:`_ffd`: a deformation), in place of ``A`` applied to the output index.  See
+    include/t2fit.h for the definition."""
     src = np.asarray(src)
     if src.ndim == 4:
-        return np.stack([resample(v, A, out_shape, interp, default, integer_cast, start) for v in src])
+        return np.stack([resample(v, A, out_shape, interp, default, integer_cast, start, coords) for v in src])
     if src.ndim != 3:
         raise ValueError("src must be (Z, Y, X) or (n, Z, Y, X)")
     mode = INTERPS[interp] if isinstance(interp, str) else int(interp)
     a = np.asarray(A, np.float64).reshape(3, 4)
     out_shape = tuple(int(v) for v in out_shape)
     n = src.shape[::-1]  # (nx, ny, nz)
-    c = _coords(a, out_shape, tuple(int(v) for v in start))
+    c = _coords(a, out_shape, tuple(int(v) for v in start)) if coords is None else coords
     inside = np.ones(out_shape, bool)
     for k in range(3):
         inside &= (c[k] >= -0.5) & (c[k] < n[k] - 0.5)

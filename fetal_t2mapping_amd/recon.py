@@ -547,7 +547,7 @@ def tissue_echo_rows(echoes, wanted_ms):
 
 
 def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fixed="ax", dof=12, bins=32, metric="cr", tissue=None,
-                         device=0):  # noqa: A002
+                         nonrigid=None, write_warp=False, device=0):  # noqa: A002
     """``--atlas_labels``: for every (sub, ses), from the first echo's recon_1mm volume and recon_1mm_mask: the masked volume
     under recon_1mm_bet, the registered template under recon_1mm_mni152 with the 4 x 4 transform beside it (``.txt``:
     subject point -> template point, LPS millimetres, the text form of --write_transforms; not FSL's convention), and
@@ -558,6 +558,11 @@ def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fix
     tissue atlas follows the same transform and is refined on the recon_1mm volumes of those echoes by expectation-
     maximisation (``t2map.atlas.atlas_labels(tissue=...)``); the result goes, int32, under recon_1mm_feta, which
     ``cli.py --roi_stats feta`` reads, and with ``write_prior`` the propagated, unrefined labels under recon_1mm_feta_prior.
+
+    ``nonrigid`` (``--atlas_nonrigid``): None, True or a dict, ``t2map.atlas.atlas_labels(nonrigid=...)``: a B-spline free-form
+    deformation after the affine carries the template and the atlases; the transform text file still holds the affine.
+    ``write_warp`` (``--write_atlas_warp``): the affine and the lattice go beside it as ``.npz`` (``transform`` 4 x 4,
+    ``lattice`` float64 ``(3, c, c, c)`` in voxels of the subject's grid, ``min_jacobian``, ``n_folded``).
     Returns the paths written."""
     sitk = _sitk()
     template_img = sitk.ReadImage(template_path)
@@ -592,6 +597,8 @@ def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fix
         t0 = time.time()
         subject = np.asarray(sitk.GetArrayFromImage(img), np.float32)
         more = {} if metric == "cr" else {"metric": metric}
+        if nonrigid is not None:
+            more["nonrigid"] = nonrigid
         if tissue is not None:
             channels = []
             for ch_rows in tissue_echo_rows(echoes, tissue.get("echoes")):
@@ -610,6 +617,10 @@ def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fix
         write(warped, img, template_out)
         np.savetxt(template_out.replace(".nii.gz", ".txt"), found.transform, fmt="%.17g")
         written.append(template_out.replace(".nii.gz", ".txt"))
+        if nonrigid is not None and write_warp:
+            np.savez(template_out.replace(".nii.gz", ".npz"), transform=found.transform, lattice=found.lattice,
+                     min_jacobian=found.min_jacobian, n_folded=found.n_folded)
+            written.append(template_out.replace(".nii.gz", ".npz"))
         for name, lab in labels.items():
             write(lab, img, get_img_path(bids_path, acq, recon_dirname + "_" + name).replace(" ", ""))
         if refined:
@@ -619,8 +630,11 @@ def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fix
             dead = [int(c) for c, d in zip(tissue["classes"], refined[0]["model"].dead) if d]
             print(f"... tissue labels of {sub}_{ses}: {refined[0]['n_iter']} EM iterations over {len(channels)} echo(es)"
                   + (f", classes without voxels: {dead}" if dead else ""))
-        print(f"... atlas labels of {sub}_{ses}: {'CR' if metric == 'cr' else '-MI'} {found.metric:.4f}, iterations {found.iterations}, "
-              f"{round(time.time() - t0, 4)} sec")
+        affine = found if nonrigid is None else found.affine
+        warp_note = "" if nonrigid is None else (f"non-rigid side {found.side}, cost {found.cost:.4f}, iterations {found.iterations}, "
+                                                 f"min det J {found.min_jacobian:.4f}, folded {found.n_folded}, ")
+        print(f"... atlas labels of {sub}_{ses}: {'CR' if metric == 'cr' else '-MI'} {affine.metric:.4f}, iterations {affine.iterations}, "
+              f"{warp_note}{round(time.time() - t0, 4)} sec")
     return written
 
 
@@ -839,6 +853,17 @@ def parse_arguments(argv=None):
     p.add_argument("--atlas_bins", type=int, default=32, help="bins of the correlation ratio, 1..64 (default 32)")
     p.add_argument("--atlas_metric", choices=["cr", "mattes"], default="cr",
                    help="with --atlas_labels: cr = the correlation ratio (default, flirt's cost); mattes = Mattes mutual information")
+    p.add_argument("--atlas_nonrigid", action="store_true",
+                   help="with --atlas_labels: after the affine, a B-spline free-form deformation under Mattes mutual information "
+                        "(t2map.register.register_ffd) carries the template and the atlases; parity with elastix / NiftyReg / ANTs "
+                        "is unpinned")
+    p.add_argument("--atlas_nonrigid_sides", default=None, metavar="4,5,7",
+                   help="with --atlas_nonrigid: the lattice side per level, from 4,5,7,11,19, never falling; the shrink factors are "
+                        "the last of 4,2,1 (default 4,5,7)")
+    p.add_argument("--atlas_nonrigid_weight", type=float, default=None, help="with --atlas_nonrigid: weight of the bending term (default 0.05)")
+    p.add_argument("--atlas_nonrigid_iter", type=int, default=None, help="with --atlas_nonrigid: moves per level at most (default 20)")
+    p.add_argument("--write_atlas_warp", action="store_true",
+                   help="with --atlas_nonrigid: write the affine and the lattice as .npz beside the transform text file")
     p.add_argument("--tissue_atlas", default=None, metavar="FILE",
                    help="with --atlas_labels: a tissue-label image on the template's grid.  It follows the found transform, is "
                         "blurred into spatial priors and refined on the subject's own echoes by expectation-maximisation on the "
@@ -903,6 +928,33 @@ def parse_arguments(argv=None):
                                    ("--tissue_iter", args.tissue_iter), ("--write_tissue_prior", args.write_tissue_prior or None))
                     if v is not None]
     args.tissue_args = None
+    args.nonrigid_args = None
+    nonrigid_flags = [f for f, v in (("--atlas_nonrigid_sides", args.atlas_nonrigid_sides), ("--atlas_nonrigid_weight", args.atlas_nonrigid_weight),
+                                     ("--atlas_nonrigid_iter", args.atlas_nonrigid_iter), ("--write_atlas_warp", args.write_atlas_warp or None))
+                      if v is not None]
+    if args.atlas_nonrigid:
+        if not args.atlas_labels:
+            p.error("--atlas_nonrigid has no effect without --atlas_labels")
+        args.nonrigid_args = {}
+        if args.atlas_nonrigid_sides is not None:
+            try:
+                sides = [int(v) for v in args.atlas_nonrigid_sides.split(",")]
+            except ValueError:
+                p.error(f"--atlas_nonrigid_sides {args.atlas_nonrigid_sides!r}: expected integers separated by commas")
+            if not 1 <= len(sides) <= 3 or any(c not in (4, 5, 7, 11, 19) for c in sides) or sorted(sides) != sides:
+                p.error("--atlas_nonrigid_sides: one to three sides from 4,5,7,11,19 that never fall")
+            args.nonrigid_args["schedule"] = tuple(zip((4, 2, 1)[-len(sides):], sides))
+        if args.atlas_nonrigid_weight is not None:
+            if not (args.atlas_nonrigid_weight >= 0.0 and np.isfinite(args.atlas_nonrigid_weight)):
+                p.error("--atlas_nonrigid_weight is finite and >= 0")
+            args.nonrigid_args["weight"] = args.atlas_nonrigid_weight
+        if args.atlas_nonrigid_iter is not None:
+            if args.atlas_nonrigid_iter < 0:
+                p.error("--atlas_nonrigid_iter is >= 0")
+            args.nonrigid_args["max_iter"] = args.atlas_nonrigid_iter
+        args.nonrigid_args = args.nonrigid_args or True
+    elif nonrigid_flags:
+        p.error(f"{nonrigid_flags[0]} has no effect without --atlas_nonrigid")
     if args.tissue_atlas is not None:
         if not args.atlas_labels:
             p.error("--tissue_atlas has no effect without --atlas_labels")
@@ -975,7 +1027,8 @@ def main(argv=None):
     if args.atlas_labels:
         process_atlas_labels(metadata, bids_path, args.atlas_template, args.atlas_specs, fixed=args.fixed, dof=args.atlas_dof,
                              bins=args.atlas_bins, metric=args.atlas_metric, device=args.device,
-                             **({} if args.tissue_args is None else {"tissue": args.tissue_args}))
+                             **({} if args.tissue_args is None else {"tissue": args.tissue_args}),
+                             **({} if args.nonrigid_args is None else {"nonrigid": args.nonrigid_args, "write_warp": args.write_atlas_warp}))
 
 
 if __name__ == "__main__":

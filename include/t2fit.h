@@ -1038,6 +1038,69 @@ int t2fit_register_mi_gradient_dev(const uint8_t *bins_dev, const double *table_
                                    const double *A, double *sums_dev, void *workspace_dev, size_t workspace_bytes,
                                    void *stream);
 
+/* ---- Non-rigid alignment: a cubic B-spline free-form deformation under Mattes mutual information -----------------------
+ * The device half of a deformable step after the affine registration (the reference has none: build_jhu_ho_labels is
+ * flirt with 12 degrees of freedom).  The metric arithmetic, the regulariser and the descent are host code
+ * (fetal_t2mapping_amd/_ffd.py, which also restates everything here in numpy; the device results equal it bit for bit).
+ * Parity with elastix, NiftyReg or ANTs is not pinned.  Additive to ABI 5: five new symbols (look them up).
+ *
+ * THE TRANSFORM.  For the fixed voxel x = (ix, iy, iz) the moving index coordinate is c(x) = A (x + d(x), 1) with
+ *   d_k(x) = sum_z bz sum_y by sum_x bx phi_k[kz + .][ky + .][kx + .],  k = 0..2 (0 is x), in fixed-grid voxels.
+ * lattice_dev is float64 [3][c][c][c], c = side in {4, 5, 7, 11, 19}.  Along an axis of n voxels the first node k and the
+ * weights b_0..3 of voxel i are those of the N4 lattice above: p = (i (c - 3)) / (n - 1), k = floor(p), tau = p - k, the
+ * last voxel k = c - 4, tau = 1 (n = 1: k = 0, tau = 0), b = the uniform cubic B-spline basis in tau.  The taps are added
+ * z, then y, then x, each as ((w_0 v_0 + w_1 v_1) + w_2 v_2) + w_3 v_3, in float64.  With p = (ix + d_0, iy + d_1,
+ * iz + d_2), c_a = ((A[4a] p_x + A[4a+1] p_y) + A[4a+2] p_z) + A[4a+3].  A lattice of zeros gives the coordinates of the
+ * affine entry points bit for bit.  Every multiply and add rounds once, no fused multiply-add.
+ *
+ * JOINT HISTOGRAM (t2fit_ffd_joint_hist_dev): t2fit_register_joint_hist_dev with c(x) in place of A x: same counting
+ * rule, same window, integer sums (64-bit integer atomics, LDS then global), equal to the statement integer for integer.
+ * GRADIENT (t2fit_ffd_gradient_dev): float64 [3][c][c][c], the lattice gradient of -MI with the counted set held fixed.
+ * Per counted voxel s = sum_j T[b_f][i0 - 1 + j] w'_j(u) (the c_v of t2fit_register_mi_gradient_dev), the force
+ *   f_j = ((s g_0) A[j] + (s g_1) A[4 + j]) + (s g_2) A[8 + j],  s g_a rounded first,
+ * +0.0 at a voxel that does not count, and G_j[cz][cy][cx] = sum_z bz sum_y by sum_x bx f_j: along x lane l of a wave adds
+ * the terms l, l + 64, .. of the row in order from +0.0 and the 64 lanes halve (32, 16, .. 1); then y, then z in index
+ * order from +0.0.  A node outside a voxel's four receives +0.0 from it, not a product with a zero weight: a non-finite
+ * sample cannot reach a node whose support it lies outside.  No floating-point atomics; bit-identical from call to call.
+ * WARP (t2fit_ffd_warp_dev): t2fit_resample_dev's sample (linear for float32, nearest for float32 / int32, default_value
+ * outside, no flags, one volume) at c(x) on the output grid; with a lattice of zeros the bytes of t2fit_resample_dev.
+ * JACOBIAN (t2fit_ffd_jacobian_dev): det(I + dd/dx) per voxel from the analytic derivative weights -- the derivative of
+ * the basis in tau (-(om om) 0.5, 1.5 t2 - 2 tau, (-1.5 t2 + tau) + 0.5, t2 0.5), each times (c - 3) / (n - 1), 0 when
+ * n = 1 -- as (a00 (a11 a22 - a12 a21) - a01 (a10 a22 - a12 a20)) + a02 (a10 a21 - a11 a20), a[k][a] = [k == a] +
+ * dd_k/dx_a; *min_dev is the minimum over the voxels whose mask byte is not 0 (+Inf when there is none), *n_folded_dev the
+ * count of det <= 0 among them.  Minimum and count do not depend on the order.  A lattice of zeros gives exactly 1.0 and 0.
+ *
+ * All calls are asynchronous on `stream`; no allocation, copy or synchronisation; A is a HOST pointer read before the
+ * call returns.  workspace_dev: at least t2fit_ffd_workspace_bytes(fixed sizes, side) bytes, aligned to 256 (the axis
+ * tables, the row and plane sums of the gradient, the row minima and counts); calls that may overlap need one each.
+ * Checked before HIP is touched (T2FIT_E_INVALID and a message): a NULL pointer, a side that is not one of the five,
+ * n_f outside 1..64, n_m outside 5..64, a size < 1, a non-finite entry of A, lo_m or scale_m, an unknown src_type / interp,
+ * an int32 source with linear interpolation, a default_value that does not fit int32, moving_dev / src_dev / out_dev not
+ * aligned to 4 bytes, lattice_dev / hist_dev / table_dev / grad_dev / min_dev / n_folded_dev not aligned to 8, out_dev =
+ * src_dev, grad_dev = lattice_dev, a workspace that is not aligned to 256 bytes or too small. */
+int t2fit_ffd_workspace_bytes(int fz, int fy, int fx, int side, size_t *bytes);
+
+int t2fit_ffd_joint_hist_dev(const uint8_t *bins_dev, const uint8_t *fixed_mask_dev, int fz, int fy, int fx,
+                             const float *moving_dev, const uint8_t *moving_mask_dev, int mz, int my, int mx,
+                             const double *A, const double *lattice_dev, int side, int n_f, int n_m, double lo_m,
+                             double scale_m, uint64_t *hist_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+int t2fit_ffd_gradient_dev(const uint8_t *bins_dev, const double *table_dev, int n_f, int n_m, double lo_m, double scale_m,
+                           const uint8_t *fixed_mask_dev, int fz, int fy, int fx, const float *moving_dev,
+                           const uint8_t *moving_mask_dev, int mz, int my, int mx, const double *A,
+                           const double *lattice_dev, int side, double *grad_dev, void *workspace_dev,
+                           size_t workspace_bytes, void *stream);
+
+/* src_type: T2FIT_RESAMPLE_F32 / _I32; interp: T2FIT_INTERP_LINEAR / _NEAREST; (nz, ny, nx) the source, (oz, oy, ox) the
+ * output (fixed) grid the lattice spans. */
+int t2fit_ffd_warp_dev(const void *src_dev, int src_type, int nz, int ny, int nx, const double *A,
+                       const double *lattice_dev, int side, void *out_dev, int oz, int oy, int ox, int interp,
+                       double default_value, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+int t2fit_ffd_jacobian_dev(const double *lattice_dev, int side, const uint8_t *mask_dev, int fz, int fy, int fx,
+                           double *min_dev, int64_t *n_folded_dev, void *workspace_dev, size_t workspace_bytes,
+                           void *stream);
+
 /* ---- Slice-to-volume registration: the 43 sums of every slice of every stack, batched ------------------------------------
  * The device half of the step that finds the per-slice poses t2fit_sr_slice_*_dev consume: one launch evaluates the
  * correlation metric's 43 sums of K slices, each slice of each stack under an affine of its own, against one volume.  The
