@@ -61,6 +61,7 @@ class T2FitTvParams(C.Structure):
 TV_JOINT_MAX_CHAN = 64
 MPPCA_MAX_TE, MPPCA_MAX_RADIUS = 16, 4
 SEG_MAX_CLASSES, SEG_MAX_CHANNELS, SEG_MAX_RADIUS = 8, 4, 32
+DICT_MAX_ATOMS = 65536
 
 
 class T2FitMppcaParams(C.Structure):
@@ -210,6 +211,9 @@ SYMBOLS = [
                                    C.c_size_t, _P]),
     ("t2fit_n4_field_dev", C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     ("t2fit_n4_apply_dev", C.c_int, [_P, _P, C.c_int64, C.c_double, _P, _P]),
+    ("t2fit_dict_pack_bytes", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    ("t2fit_dict_pack_host", C.c_int, [C.c_int, C.c_int, _P, _P, C.c_size_t]),
+    ("t2fit_dict_match_dev", C.c_int, [_P, C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P]),
     ("t2fit_set_timing", C.c_int, [C.c_int]),
     ("t2fit_set_reserve_cus", C.c_int, [C.c_int]),
     ("t2fit_kernel_ms", C.c_double, [C.c_int]),
@@ -244,8 +248,9 @@ SEG_SYMBOLS = ("t2fit_seg_workspace_bytes", "t2fit_seg_mask_dev", "t2fit_seg_pri
                "t2fit_seg_estep_dev", "t2fit_seg_labels_dev")
 FFD_SYMBOLS = ("t2fit_ffd_workspace_bytes", "t2fit_ffd_joint_hist_dev", "t2fit_ffd_gradient_dev", "t2fit_ffd_warp_dev",
                "t2fit_ffd_jacobian_dev")
+DICT_SYMBOLS = ("t2fit_dict_pack_bytes", "t2fit_dict_pack_host", "t2fit_dict_match_dev")
 LOOKED_UP = (ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS + MI_SYMBOLS + SR_SYMBOLS + SR_SLICE_SYMBOLS + SVR_SYMBOLS
-             + SR_ROBUST_SYMBOLS + TVJ_SYMBOLS + MPPCA_SYMBOLS + SEG_SYMBOLS + FFD_SYMBOLS)
+             + SR_ROBUST_SYMBOLS + TVJ_SYMBOLS + MPPCA_SYMBOLS + SEG_SYMBOLS + FFD_SYMBOLS + DICT_SYMBOLS)
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

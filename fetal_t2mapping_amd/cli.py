@@ -1,7 +1,7 @@
 """CLI and volume driver: the reference's ``run_t2mapping.py`` surface on the MI355X fit.
 
     python -m fetal_t2mapping_amd.cli --path /data/qMRI --csv 2024083017_17510000.csv \
-        --in_vivo --gaussian --lf --sim 1 [--TEs 114 202 299] [--no_prior] [--solver lbfgsb|lm|loglin] [--gpus N]
+        --in_vivo --gaussian --lf --sim 1 [--TEs 114 202 299] [--no_prior] [--solver lbfgsb|lm|loglin|dict] [--gpus N]
         [--roi_stats ho:2 --roi_stats jhu:3 --roi_stats feta] [--roi_connectivity 3] [--roi_erosion 1]
         [--bootstrap 100 [--bootstrap_seed 0] [--bootstrap_alpha 0.05] [--bootstrap_noise background|sigma_map|mppca|<float>]]
         [--denoise tv|tv_joint [--denoise_weight 0.1|<c>sigma] [--denoise_dims 2|3] [--denoise_eps 2e-4] [--denoise_iter 200]
@@ -387,6 +387,112 @@ def save_roi_csvs(t2_map, k_map, sigma_map, specs, connectivity, erosion, bids_p
 BOOT_TAGS = ("T2std", "T2bias", "T2cilo", "T2cihi", "T2nok")
 
 
+def parse_dict_arguments(args):
+    """``--solver dict`` and its table: None without it, else ``{'t2': (lo, hi, n), 'csf': (t2_long, nf) or None}`` or
+    ``{'file': path}``.  ValueError for what does not go together."""
+    given = [f for f in ("dict_t2", "dict_csf", "dict_file") if getattr(args, f) is not None]
+    if args.solver != "dict":
+        if given:
+            raise ValueError(f"--{given[0]} has no effect without --solver dict")
+        return None
+    if not args.gaussian:
+        raise ValueError("--solver dict goes with --gaussian only: a dictionary is matched by least squares up to a scale "
+                         "(a Rician expectation depends on k / sigma, so it is not scale-free)")
+    if (args.dict_t2 is None) == (args.dict_file is None):
+        raise ValueError("--solver dict needs a dictionary: one of --dict_t2 LO:HI:N (optionally with --dict_csf T2LONG:NF) and "
+                         "--dict_file FILE.npz")
+    if args.norm:
+        raise ValueError("--solver dict cannot be combined with --norm: the match is scale-free already")
+    if args.bootstrap:
+        raise ValueError("--solver dict cannot be combined with --bootstrap: the replicas are refitted by the iterative solvers")
+    if args.gpus > 1:
+        raise ValueError("--solver dict runs on one GPU per volume: --gpus 1")
+    n_te = len(args.TEs) if args.TEs is not None else 3
+    if args.dict_file is not None:
+        if args.dict_csf is not None:
+            raise ValueError("--dict_csf goes with --dict_t2 (a --dict_file holds its own model)")
+        from ._dict import Dictionary
+
+        try:
+            d = Dictionary.load(args.dict_file)
+        except (OSError, KeyError, ValueError) as e:
+            raise ValueError(f"--dict_file {args.dict_file!r}: {e}")
+        if "t2" not in d.names:
+            raise ValueError(f"--dict_file {args.dict_file!r} has no t2 column (it has {', '.join(d.names)})")
+        if d.n_te != n_te:
+            raise ValueError(f"--dict_file {args.dict_file!r} has {d.n_te} echoes per atom, {n_te} echoes are fitted")
+        return {"file": args.dict_file}
+    try:
+        lo, hi, n = args.dict_t2.split(":")
+        lo, hi, n = float(lo), float(hi), int(n)
+    except ValueError:
+        raise ValueError(f"--dict_t2 {args.dict_t2!r}: expected LO:HI:N, for example 20:2000:512")
+    if not (0 < lo < hi and np.isfinite(hi)) or n < 2:
+        raise ValueError("--dict_t2 needs 0 < LO < HI and N >= 2")
+    csf = None
+    if args.dict_csf is not None:
+        try:
+            t2_long, nf = args.dict_csf.split(":")
+            t2_long, nf = float(t2_long), int(nf)
+        except ValueError:
+            raise ValueError(f"--dict_csf {args.dict_csf!r}: expected T2LONG:NF, for example 2000:32")
+        if not (t2_long > 0 and np.isfinite(t2_long)) or nf < 1:
+            raise ValueError("--dict_csf needs T2LONG > 0 and NF >= 1")
+        csf = (t2_long, nf)
+    if n * (csf[1] if csf else 1) > 65536:
+        raise ValueError("the dictionary would have more than 65536 atoms")
+    return {"t2": (lo, hi, n), "csf": csf}
+
+
+def build_dictionary(spec, te_ms):
+    """The dictionary of :func:`parse_dict_arguments` for these echo times [ms]."""
+    from . import _dict
+
+    if "file" in spec:
+        d = _dict.Dictionary.load(spec["file"])
+        if d.n_te != len(te_ms):
+            raise ValueError(f"{spec['file']!r} has {d.n_te} echoes per atom, {len(te_ms)} echoes are fitted")
+        return d
+    grid = _dict.log_grid(*spec["t2"])
+    if spec["csf"] is None:
+        return _dict.monoexp(te_ms, grid)
+    t2_long, nf = spec["csf"]
+    return _dict.biexp(te_ms, grid, t2_long, np.arange(nf) / nf)
+
+
+def _fit_subject_dict(vols, masks, keep, dictionary, device):
+    """:func:`_fit_subject` for ``--solver dict``: same mask, the maps of t2map.dictionary.fit_volume_dict; sigma is 0 and res
+    the RMSE of the matched atom.  Returns ``(mask, (t2, k, sigma, res), status, None, extras)`` with ``extras`` the further
+    parameter maps and the atom index (int32)."""
+    import torch
+
+    echoes, mask, _ = t2map.stack_mask_flatten(vols, masks, device=device)
+    if keep is not None:
+        mask = mask & keep
+    shape = mask.shape
+    mask_d = torch.from_numpy(mask.astype(np.uint8).reshape(-1)).to(echoes.device)
+    maps, extras = t2map.dictionary.fit_volume_dict(echoes.reshape((len(vols),) + shape), mask_d.reshape(shape), dictionary, device=device)
+    torch.cuda.synchronize()
+    out = tuple(getattr(maps, n).cpu().numpy() for n in ("t2", "k", "sigma", "res"))
+    return mask, out, maps.status.cpu().numpy(), None, {n: t.cpu().numpy() for n, t in extras.items()}
+
+
+def save_dict_maps(extras, recon_img, bids_path, acq, dirname, sim, analysis):
+    """``--solver dict``: one map per further parameter column of the dictionary (tag = the column's name) and the atom index
+    (tag dictindex, int32; -1 where nothing was matched), beside the four maps with their geometry and naming rule.  Returns
+    the paths written."""
+    sitk = _sitk()
+    paths = []
+    for name, arr in extras.items():
+        img = sitk.GetImageFromArray(arr)
+        img.SetSpacing(recon_img.GetSpacing())
+        img.SetOrigin(recon_img.GetOrigin())
+        img.SetDirection(recon_img.GetDirection())
+        paths.append(boot_map_path(bids_path, acq, dirname, sim, analysis, "dictindex" if name == "index" else name))
+        sitk.WriteImage(img, paths[-1])
+    return paths
+
+
 def parse_bootstrap_noise(text: str):
     """``--bootstrap_noise``: ``background`` / ``sigma_map`` / ``mppca`` as they are, anything else a noise level > 0."""
     if text in ("background", "sigma_map", "mppca"):
@@ -671,7 +777,7 @@ def _one_block(vols):
 def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field, prior, fast, norm, sim,
                    solver="lbfgsb", precision="f64", device=0, plots=False, plot_seed=None, numpy_legacy=False,
                    roi_specs=(), roi_connectivity=3, roi_erosion=1, bootstrap=0, bootstrap_seed=0, bootstrap_alpha=0.05,
-                   bootstrap_noise="background", denoise=None, reconstruct=None, build_mask=None, noise_map=None):
+                   bootstrap_noise="background", denoise=None, reconstruct=None, build_mask=None, noise_map=None, dictionary=None):
     """run_t2mapping.py:333-479 with the voxel loop on the GPU.  ``plots``: also write the reference's
     convergence-study figures (:465-468) under <prj>/ada/convergence_analysis.  ``roi_specs``: (name, tissue) pairs
     of --roi_stats; each adds a per-region table after the maps (save_roi_csvs).  ``bootstrap`` > 0: that many
@@ -683,8 +789,10 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
     echo and the vial labels are built on the device from the volumes about to be fitted (after the reconstruction, if
     any) and used in place of the recon_1mm_mask / recon_1mm_label files.  ``noise_map``: None, or ``{'radius', 'dims'}`` of
     the MP-PCA noise map, with ``'write': True`` for --write_noise_map (save_noise_maps, of the echoes before any denoising);
-    --bootstrap_noise mppca reads its radius and dims."""
+    --bootstrap_noise mppca reads its radius and dims.  ``dictionary``: the table of ``--solver dict`` (parse_dict_arguments)."""
     sitk = _sitk()
+    if (solver == "dict") != (dictionary is not None):
+        raise ValueError("solver 'dict' and a dictionary go together")
     tes_s = [x / 1000 for x in TEs]
     metadata = metadata[metadata["EchoTime"].isin(tes_s)]
     # more than one process (--gpus N): whole subjects are dealt to the ranks when there are enough of them, otherwise
@@ -708,6 +816,9 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
     if write_noise and share_volumes:
         raise ValueError("--write_noise_map is not run on a volume that is shared by several ranks (each rank holds a part of the "
                          "echoes): give at least as many subjects as ranks, or run on one GPU")
+    if dictionary is not None and share_volumes:
+        raise ValueError("--solver dict is not run on a volume that is shared by several ranks: give at least as many subjects "
+                         "as ranks, or run on one GPU")
     mine = set(subjects if (world == 1 or share_volumes) else
                [subjects[i] for i in dist_subjects_of_rank(len(subjects), rank, world)])
     writer = (rank == 0) or not share_volumes
@@ -764,10 +875,15 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
                     vols = denoise_subject(vols, masks, device=device, **denoise,
                                            **({"maps": noise_maps} if write_noise and not noise_maps else {}))
                 t0 = time.time()
-                fitted = _fit_subject(vols, masks, keep, te_eff, fit, fit_params, prior, norm, solver, precision, device,
-                                      **({"numpy_legacy": True} if numpy_legacy else {}))
-                mask, maps4, status = fitted[:3]
-                extras = fitted[3] if len(fitted) > 3 else None
+                dict_maps = None
+                if dictionary is not None:
+                    mask, maps4, status, extras, dict_maps = _fit_subject_dict(vols, masks, keep, build_dictionary(dictionary, te_eff),
+                                                                               device)
+                else:
+                    fitted = _fit_subject(vols, masks, keep, te_eff, fit, fit_params, prior, norm, solver, precision, device,
+                                          **({"numpy_legacy": True} if numpy_legacy else {}))
+                    mask, maps4, status = fitted[:3]
+                    extras = fitted[3] if len(fitted) > 3 else None
             t2_map, k_map, sigma_map, res_map = maps4
             print(f"Dimensions of the t2w images: {mask.shape + (te_eff.size,)} (z,y,x,necho)")
             print(f"Mask Dimension: {mask.shape} -  Number of voxels inside mask: {int(np.sum(mask))}")
@@ -805,6 +921,8 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
                                               precision=precision, device=device, seed=plot_seed, picks=picks, rows=rows,
                                               numpy_legacy=numpy_legacy)
             save_nifti_maps(t2_map, k_map, sigma_map, res_map, t2map_dirname, recon_img, bids_path, acq, sim, fit)
+            if dictionary is not None:
+                save_dict_maps(dict_maps, recon_img, bids_path, acq.iloc[0], t2map_dirname, sim, fit)
             if write_noise:
                 save_noise_maps(noise_maps["sigma"], noise_maps["rank"], recon_img, bids_path, acq.iloc[0], t2map_dirname, sim, fit)
             if phantom:
@@ -857,9 +975,18 @@ def parse_arguments(argv=None):
     p.add_argument("--TEs", nargs="+", type=int, help="echo times [ms] to fit (default 114/115, 202, 299)")
     p.add_argument("--no_prior", action="store_true", help="k >= S(TE0) instead of the table's lower bound")
     p.add_argument("--norm", action="store_true", help="divide each voxel's samples by their maximum")
-    p.add_argument("--solver", choices=["lbfgsb", "lm", "loglin"], default="lbfgsb",
+    p.add_argument("--solver", choices=["lbfgsb", "lm", "loglin", "dict"], default="lbfgsb",
                    help="lbfgsb: the reference's solver and stop rules (default); lm: converged bounded LM; "
-                        "loglin: closed-form weighted log-linear fit (--gaussian only)")
+                        "loglin: closed-form weighted log-linear fit (--gaussian only); dict: dictionary matching against "
+                        "the table of --dict_t2 / --dict_csf / --dict_file (--gaussian only; the res map is then the RMSE of "
+                        "the matched atom, sigma is 0, and every further parameter column and the atom index get a map)")
+    p.add_argument("--dict_t2", metavar="LO:HI:N", help="--solver dict: mono-exponential atoms at N T2 values from LO to HI ms, log-spaced")
+    p.add_argument("--dict_csf", metavar="T2LONG:NF",
+                   help="with --dict_t2: two compartments, (1 - f) exp(-TE/T2) + f exp(-TE/T2LONG), at NF fractions f = 0, 1/NF, .. "
+                        "in [0, 1); writes a fraction map")
+    p.add_argument("--dict_file", metavar="FILE.npz",
+                   help="--solver dict: a dictionary saved by t2map.dictionary.Dictionary.save (atoms, params, names; a t2 "
+                        "column; as many echoes as are fitted)")
     p.add_argument("--precision", choices=["f64", "f32"], default="f64", help="arithmetic of the lm solver")
     p.add_argument("--device", type=int, default=0, help="HIP device ordinal (one process; with --gpus each rank uses its own)")
     p.add_argument("--gpus", type=int, default=1,
@@ -939,6 +1066,10 @@ def parse_arguments(argv=None):
                    help="also write the MP-PCA noise level and signal rank of every voxel (of the echoes before any "
                         "denoising) beside the maps; window by --denoise_patch / --denoise_dims")
     args = p.parse_args(argv)
+    try:
+        args.dict_args = parse_dict_arguments(args)
+    except ValueError as e:
+        p.error(str(e))
     args.reconstruct_args = None
     given = [f for f in ("--recon_fixed", "--recon_res", "--recon_transforms", "--recon_register", "--recon_register_echoes",
                          "--recon_n4", "--recon_register_metric", "--recon_method")
@@ -1112,7 +1243,8 @@ def main(argv=None):
                        bootstrap_noise=args.bootstrap_noise, **({"denoise": args.denoise_args} if args.denoise_args else {}),
                        **({"reconstruct": args.reconstruct_args} if args.reconstruct_args else {}),
                        **({"build_mask": args.build_mask_args} if args.build_mask_args else {}),
-                       **({"noise_map": args.noise_map_args} if args.noise_map_args else {}))
+                       **({"noise_map": args.noise_map_args} if args.noise_map_args else {}),
+                       **({"dictionary": args.dict_args} if args.dict_args else {}))
     finally:
         if world > 1:
             import torch.distributed as dist

@@ -33,6 +33,7 @@ super-resolution       ``_gpu_sr``         ``_sr`` (operator, adjoint and the pr
 slice-to-volume        ``_gpu_register``,  ``_svr`` (batched per-slice sums, transform model, lockstep descent and driver, which are host
 registration           ``_gpu_sr``         code); here as ``register.register_slices``, ``register.slice_sums``, ``sr.reconstruct_svr``
 tissue segmentation    ``_gpu_seg``        ``_seg`` (the steps, and the EM loop and class model, which are host code); here as ``seg``
+dictionary fit         ``_gpu_dict``       ``_dict`` (and the dictionary builders, which both share); here as ``dictionary``
 N4 bias field          ``_gpu_bias``       ``_bias`` (and the sharpening table, the refinement and the loop, which are host code); here as ``bias``
 =====================  ==================  ===========================================================
 
@@ -56,6 +57,8 @@ from ._gpu_tv import denoise_tv, tv_params  # noqa: F401
 from . import _gpu_mppca as mppca  # noqa: F401  (a namespace: mppca.denoise_mppca, mppca.mppca_noise_map, mppca.mppca_params)
 from . import _gpu_seg as seg  # noqa: F401  (a namespace: seg.segment_em, seg.priors_from_labels, seg.moment_sums, seg.e_step,
 #                                seg.hard_labels, seg.seg_params)
+from . import _gpu_dict as dictionary  # noqa: F401  (a namespace: dictionary.Dictionary, .monoexp, .biexp, .log_grid, .pack, .match,
+#                                         .fit_volume_dict)
 
 
 def __getattr__(name):

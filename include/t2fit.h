@@ -1237,6 +1237,47 @@ int t2fit_n4_field_dev(const double *lattice_dev, int side, const float *u0_dev,
 /* Step 7; out_dev may be in_dev, not field_dev. */
 int t2fit_n4_apply_dev(const float *in_dev, const float *field_dev, int64_t n_vox, double scale, float *out_dev, void *stream);
 
+/* ---- Dictionary-matching fit (additive to ABI 5) ---------------------------------------------------------------------
+ * Any signal model as a table: A atoms (decay curves) of n_te samples each.  Every voxel's decay is matched against every
+ * atom; the best atom gives the parameters (the caller's table, row `index`), the projection onto it the scale.  With
+ * D the atoms as given (float32), everything below float64 with one rounding per operation in the order written, nothing
+ * fused, sums over the echoes e ascending from 0.0:
+ *   packing   n2_j = sum_e D_je D_je, n_j = sqrt(n2_j), Dh_je = float32(D_je / n_j),
+ *             dmax = float32(max_j sqrt(sum_e Dh_je Dh_je))
+ *   score     s_j = sum_e Dh_je y_e;  index = argmax_j s_j, the lowest j on a tie
+ *   scale     q = (sum_e y_e D_je) / n2_j of the matched atom, k = q if q > 0 else 0;  scale = float32(k)
+ *   rmse      float32(sqrt((sum_e (y_e - k D_je)^2) / n_te))
+ * A voxel with mask == 0 or a non-finite sample is not fitted: index -1, scale 0, rmse 0.  An all-zero voxel ties on every
+ * atom: index 0, scale 0, rmse 0.  fetal_t2mapping_amd/_dict.py states all of it in numpy; the device output is
+ * bit-identical to it.  (The device finds candidates with the float32 matrix instruction and re-scores, in float64 as
+ * above, every atom whose float32 score is within a proven error bound of the running best: DESIGN.md section 8r.)
+ *
+ * The packed dictionary is one block of t2fit_dict_pack_bytes bytes, little endian, that t2fit_dict_pack_host writes on
+ * the host and the caller copies to the device (16-byte aligned) once per dictionary:
+ *   byte  0  uint32 magic 0x54443254   int32 n_atoms   int32 n_te   int32 k_pad (n_te rounded up to even)
+ *   byte 16  int32 n_tiles (ceil(n_atoms / 32))   float32 dmax   uint32 0, 0
+ *   byte 32  uint64 off_tiles (= 64)   uint64 off_atoms   uint64 off_norm2   uint64 bytes (the whole block)
+ *   off_tiles  float32 [n_tiles][k_pad][32]: Dh of atom 32 t + r at [t][e][r]; 0.0 for e >= n_te and for 32 t + r >= n_atoms
+ *   off_atoms  float32 [n_atoms][n_te]: D as given; the section is padded with zero bytes to a multiple of 16
+ *   off_norm2  float64 [n_atoms]: n2_j; padded likewise */
+#define T2FIT_DICT_MAX_ATOMS 65536 /* n_atoms outside 1 .. this is refused; n_te outside 2 .. T2FIT_MAX_TE likewise */
+
+/* Plain arithmetic, no device. */
+int t2fit_dict_pack_bytes(int n_atoms, int n_te, size_t *bytes);
+
+/* No device.  atoms: float32 [n_atoms][n_te] on the host.  Refuses (T2FIT_E_INVALID, with a message) the sizes above, a NULL
+ * pointer, `bytes` below t2fit_dict_pack_bytes, an atom with a non-finite sample and an atom whose norm is 0. */
+int t2fit_dict_pack_host(int n_atoms, int n_te, const float *atoms, void *packed_host, size_t bytes);
+
+/* y_dev: float32, TE-major (n_te, n_vox).  mask_dev: uint8 [n_vox], 0 / not 0, or NULL (every voxel).  index_dev int32,
+ * scale_dev and rmse_dev float32, [n_vox] each, all written for every voxel.  One kernel on `stream`, no allocation.
+ * Refused before HIP is touched: a NULL y_dev, packed_dev or output, n_te outside 2 .. T2FIT_MAX_TE, n_vox < 0, y_dev or an
+ * output not aligned to 4 bytes, packed_dev not aligned to 16.  The 64-byte header is then read back from packed_dev (one
+ * copy and one wait on `stream`: the only synchronisation) and refused, before any launch, when its magic, n_te, k_pad,
+ * n_atoms, n_tiles or offsets are not what t2fit_dict_pack_host writes for this n_te.  n_vox == 0 is a no-op. */
+int t2fit_dict_match_dev(const float *y_dev, int n_te, int64_t n_vox, const uint8_t *mask_dev, const void *packed_dev,
+                         int32_t *index_dev, float *scale_dev, float *rmse_dev, void *stream);
+
 /* Kernel timing for benchmarks (no reference counterpart).  With timing enabled (t2fit_set_timing(1)) every
  * t2fit_volume_dev call of this thread records HIP events around its fit kernel on the launch stream.
  * t2fit_kernel_ms(k): duration in milliseconds of the fit kernel launched k timed calls ago (0 = the most recent;
