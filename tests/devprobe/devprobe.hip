@@ -1,7 +1,8 @@
 // devprobe.hip -- TEST INFRASTRUCTURE: the device-side mirror of tests/hostsim.  It compiles the per-lane headers for
 // gfx950 -- the side of every `#if defined(__HIP_DEVICE_COMPILE__)` that the host simulator never sees -- and wraps the
 // single sequences (exp, square roots, reciprocals, quotients, log, i0e, the wave paths of t2_log_i0e4, one evaluation of
-// the lane solver) into small kernels, one thread per element.  It is built by tests/devprobe/probe.py into
+// the lane solver) into small kernels, one thread per element; and one kernel that issues the matrix instruction of the
+// dictionary fit as DESIGN.md section 8r documents it and returns its float32 scores.  It is built by tests/devprobe/probe.py into
 // tests/devprobe/libt2fit_devprobe.so and loaded only by tests/; the product library and its ABI know nothing of it.
 //
 // Kernel rules: workgroups of exactly 64 lanes (one wave: the caller decides which elements share the wave-level
@@ -11,6 +12,7 @@
 // the launch, so an element no lane wrote cannot pass for a result.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../fetal_t2mapping_amd/csrc/t2fit_config.h"
 #include "../../fetal_t2mapping_amd/csrc/t2fit_dispatch.h"
@@ -166,6 +168,42 @@ __global__ __launch_bounds__(kWave) void k_eval(const LaneParams P, const float*
   }
 }
 
+// ---- the float32 scores of the dictionary fit on the matrix cores ------------------------------------------------------
+// What DESIGN.md section 8r documents, written from the document and not from the product kernel: one wave per 32-atom
+// tile and 32-voxel group; lane l supplies A[row l & 31][k = l >> 5] (a normalised atom, from the packed block's
+// [tile][echo][32 rows]) and B[k = l >> 5][voxel l & 31] (a sample); one v_mfma_f32_32x32x2_f32 per pair of echoes, in
+// ascending order, into one accumulator; accumulator register r of lane l is the score of row
+// (r & 3) + 8 (r >> 2) + 4 (l >> 5) for the voxel l & 31.  out: (n_vox, 32 n_tiles) float32.
+struct DictBlockHeader {  // the 64-byte header of the packed dictionary (include/t2fit.h)
+  uint32_t magic;
+  int32_t n_atoms, n_te, k_pad, n_tiles;
+  float dmax;
+  uint32_t reserved[2];
+  uint64_t off_tiles, off_atoms, off_norm2, bytes;
+};
+static_assert(sizeof(DictBlockHeader) == 64, "header layout");
+
+typedef float probe_f32x16 __attribute__((ext_vector_type(16)));
+
+__global__ __launch_bounds__(kWave) void k_dict_scores(const unsigned char* packed, const float* y, int64_t n_vox, float* out) {
+  const DictBlockHeader* h = reinterpret_cast<const DictBlockHeader*>(packed);
+  const int tile = blockIdx.x, lane = threadIdx.x, col = lane & 31, half = lane >> 5;
+  const int n_te = h->n_te, k_pad = h->k_pad;
+  const int64_t width = (int64_t)h->n_tiles * 32;
+  const float* rows = reinterpret_cast<const float*>(packed + h->off_tiles) + (size_t)tile * k_pad * 32;
+  const int64_t v = (int64_t)blockIdx.y * 32 + col;
+  probe_f32x16 acc;
+  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+  for (int s = 0; s < k_pad / 2; ++s) {  // (all 64 lanes take every step: the instruction needs the whole wave)
+    const int k = 2 * s + half;
+    const float a = rows[k * 32 + col];
+    const float b = (k < n_te && v < n_vox) ? y[(int64_t)k * n_vox + v] : 0.0f;
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+  }
+  if (v < n_vox)
+    for (int r = 0; r < 16; ++r) out[v * width + tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * half] = acc[r];
+}
+
 }  // namespace
 
 #define PROBE_CASE(K, OP, ...) \
@@ -288,6 +326,28 @@ extern "C" int devprobe_eval(const t2fit_config* cfg, const float* rows, const d
     if (P.model == T2FIT_MODEL_GAUSSIAN) go(std::integral_constant<int, T2FIT_MODEL_GAUSSIAN>{});
     else if (P.model == T2FIT_MODEL_GAUSSIAN_RICIAN) go(std::integral_constant<int, T2FIT_MODEL_GAUSSIAN_RICIAN>{});
     else go(std::integral_constant<int, T2FIT_MODEL_RICIAN>{});
+  });
+}
+
+// packed: a block as _dict.pack / t2fit_dict_pack_host writes it (`bytes` long); y: (n_te, n_vox) float32;
+// out: (n_vox, 32 n_tiles) float32, the float32 score of every (voxel, row of a tile), padded rows included.
+extern "C" int devprobe_dict_scores(const void* packed, size_t bytes, const float* y, int n_te, int64_t n_vox, float* out) {
+  if (!packed || !y || !out || bytes < sizeof(DictBlockHeader) || n_vox < 0 || n_vox > (1 << 20)) return (int)hipErrorInvalidValue;
+  DictBlockHeader h;
+  memcpy(&h, packed, sizeof(h));
+  // the header is what the kernel indexes with: nothing is launched unless it describes this block
+  if (h.magic != 0x54443254u || h.n_te != n_te || n_te < 2 || n_te > T2FIT_MAX_TE || h.k_pad != (n_te + 1) / 2 * 2 || h.n_atoms < 1 ||
+      h.n_atoms > T2FIT_DICT_MAX_ATOMS || h.n_tiles != (h.n_atoms + 31) / 32 || h.off_tiles != sizeof(DictBlockHeader) || h.bytes != bytes ||
+      h.off_tiles + (uint64_t)h.n_tiles * h.k_pad * 32 * sizeof(float) > bytes)
+    return (int)hipErrorInvalidValue;
+  if (n_vox == 0) return 0;
+  const int64_t groups = (n_vox + 31) / 32;
+  const void* in[] = {packed, y};
+  void* outp[] = {out};
+  const size_t inb[] = {bytes, (size_t)n_te * n_vox * sizeof(float)}, outb[] = {(size_t)n_vox * h.n_tiles * 32 * sizeof(float)};
+  return with_buffers(2, in, inb, 1, outp, outb, [&](void** d) {
+    hipLaunchKernelGGL(k_dict_scores, dim3((unsigned)h.n_tiles, (unsigned)groups), dim3(kWave), 0, 0, (const unsigned char*)d[0],
+                       (const float*)d[1], n_vox, (float*)d[2]);
   });
 }
 

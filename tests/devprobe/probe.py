@@ -54,6 +54,7 @@ def lib():
         L.devprobe_unary_f32.argtypes = [C.c_int, p, i64, p]
         L.devprobe_eval.argtypes = [C.POINTER(_abi.T2FitConfig), p, p, i64, C.c_int, p]
         L.devprobe_config_default.argtypes = [C.POINTER(_abi.T2FitConfig), C.c_int, C.c_int]
+        L.devprobe_dict_scores.argtypes = [p, C.c_size_t, p, C.c_int, i64, p]
         _lib = L
     return _lib
 
@@ -138,6 +139,20 @@ def eval_points(cfg, rows, xs, nte_special: bool = False):
     assert rows.shape == (len(xs), cfg.n_te) and xs.shape[1] == 3
     out = np.empty((len(xs), 4))
     _call("eval", lib().devprobe_eval, C.byref(cfg), rows.ctypes.data, xs.ctypes.data, len(xs), int(nte_special),
+          out.ctypes.data)
+    return out
+
+
+def dict_scores(packed, y):
+    """The float32 scores of the matrix instruction as the dictionary fit issues it.  packed: the
+    bytes of _dict.pack; y: (n_te, n_vox) float32 -> (n_vox, 32 * n_tiles) float32, the padded rows of a ragged last tile
+    included (they score 0)."""
+    packed = np.ascontiguousarray(packed, np.uint8)
+    y = np.ascontiguousarray(y, np.float32)
+    assert y.ndim == 2
+    n_atoms = int(packed[4:8].view(np.int32)[0])
+    out = np.empty((y.shape[1], (n_atoms + 31) // 32 * 32), np.float32)
+    _call("dict_scores", lib().devprobe_dict_scores, packed.ctypes.data, packed.size, y.ctypes.data, y.shape[0], y.shape[1],
           out.ctypes.data)
     return out
 

@@ -2,8 +2,11 @@
 (fetal_t2mapping_amd/_dict.py): index, scale and rmse bit for bit, and equal from call to call, over echo counts (odd
 padding, several k-steps), atom counts (a single atom, ragged last tiles), voxel counts (ragged groups and waves), masks
 that empty whole groups and workgroups, duplicates, the near-tie case of tests/dict_cases.py, zero / NaN / Inf voxels,
-samples over seven decades, raw calls through the C ABI, sample offsets beyond 2^31, fit_volume_dict and the CLI.  tests/test_dict_host.py holds the
-statement to a brute-force matcher."""
+samples over seven decades, raw calls through the C ABI, sample offsets beyond 2^31, fit_volume_dict and the CLI; tables
+that take several chunks (near ties, every echo count from 2 to 32 with one and with two chunks, the boundaries of waves
+that hold two groups, idle waves, ties between copies in different chunks, 65536 atoms) and magnitudes (samples next to
+the largest float, subnormal samples, -0.0, atoms far from unit norm).  tests/test_dict_host.py holds the statement to a
+brute-force matcher; tests/test_dict_scores_gpu.py holds the float32 scores of the matrix instruction to their bound."""
 import ctypes as C
 import os
 
@@ -80,7 +83,7 @@ def test_masks_that_empty_groups_waves_and_workgroups(t2):
     want = _check(t2, y, d.atoms, mask, "emptied groups")
     assert np.all(want[0][mask == 0] == -1) and np.all(want[0][mask != 0] >= 0)
     _check(t2, y, d.atoms, np.zeros(n_vox, np.uint8), "an empty mask")
-    # 9 echoes run two groups per wave: other boundaries
+    # 9 echoes are five k-steps (an odd count padded to 10), still four groups per wave: holes at other places
     d9 = K.atoms_for(40, 9)
     y9 = K.decays(9, 700, seed=79)
     m9 = K.holes_mask(700, 80)
@@ -115,6 +118,123 @@ def test_near_ties_need_the_float64_stage(t2):
     assert np.array_equal(want[0], index) and info["differ"] >= 20
     _same(t2.dictionary.match(y, atoms), want, "near ties")
     _same(t2.dictionary.match(y, atoms), want, "near ties (again)")
+
+
+@pytest.mark.parametrize("case", K.MULTI_CHUNK_CASES, ids=lambda c: f"{c[0]}x{c[1]}")
+def test_near_ties_on_tables_of_several_chunks(t2, case):
+    """The near-tie cases whose tables take 2, 7, 9, 16 and 32 chunks (tests/dict_cases.py: the builder asserts on the CPU
+    that the float32 chain picks another atom on >= 20 voxels and that the rule with T = 0 misses the statement)."""
+    atoms, y, index, info = K.near_tie_case(*case)
+    y = y.copy()
+    want = _check(t2, y, atoms, None, f"near ties, {info['n_chunks']} chunks")
+    assert np.array_equal(want[0], index) and info["n_chunks"] >= 2 and info["differ"] >= 20 and info["t0_misses"] >= 1
+    _check(t2, y, atoms, K.holes_mask(y.shape[1], case[3]), f"near ties, {info['n_chunks']} chunks, holes")
+
+
+@pytest.mark.parametrize("n_te", range(2, 33))
+def test_every_instance_with_one_and_two_chunks(t2, n_te):
+    """All 16 k-step counts, odd and even echo counts: a table of one chunk, and one of two chunks whose second is short
+    and whose last tile is ragged."""
+    want = _check(t2, K.decays(n_te, 301, seed=200 + n_te, negate_every=7), K.atoms_for(70, n_te).atoms, K.holes_mask(301, 300 + n_te),
+                  f"n_te {n_te}, 70 atoms")
+    assert len(np.unique(want[0])) > 10
+    tpc = 4096 // ((n_te + n_te % 2) * 32)
+    n_atoms = 32 * tpc + 33
+    assert K.chunks_of(n_atoms, n_te) == (tpc, 2) and n_atoms <= 2081
+    want = _check(t2, K.decays(n_te, 130, seed=400 + n_te), K.atoms_for(n_atoms, n_te).atoms, None, f"n_te {n_te}, {n_atoms} atoms")
+    assert len(np.unique(want[0])) > 10 and want[0].min() >= 0
+
+
+@pytest.mark.parametrize("n_vox", [1, 31, 33, 63, 65, 255, 257, 513])
+@pytest.mark.parametrize("n_te", [17, 32])
+def test_voxel_counts_with_two_groups_per_wave(t2, n_te, n_vox):
+    """Above 16 echoes a wave holds 64 voxels and a workgroup 256; 300 atoms are two chunks at 17 echoes, three at 32."""
+    assert K.chunks_of(300, n_te)[1] >= 2
+    want = _check(t2, K.decays(n_te, n_vox, seed=n_te * 1000 + n_vox), K.atoms_for(300, n_te).atoms, None, f"{n_te} echoes, {n_vox} voxels")
+    assert np.all(want[0] >= 0)
+
+
+@pytest.mark.parametrize("n_te", [17, 32])
+def test_masks_that_empty_groups_waves_and_workgroups_with_two_groups_per_wave(t2, n_te):
+    atoms = K.atoms_for(300, n_te).atoms
+    n_vox = 3 * 256 + 40
+    y = K.decays(n_te, n_vox, seed=500 + n_te)
+    mask = K.holes_mask(n_vox, 600 + n_te)
+    mask[32:64] = 0       # one 32-voxel group
+    mask[128:192] = 0     # a whole wave: it sits through the barriers of every chunk
+    mask[256:512] = 0     # a whole workgroup
+    mask[768:] = 0        # the ragged last workgroup
+    want = _check(t2, y, atoms, mask, f"emptied groups, {n_te} echoes")
+    assert np.all(want[0][mask == 0] == -1) and np.all(want[0][mask != 0] >= 0) and len(np.unique(want[0])) > 10
+    _check(t2, y, atoms, np.zeros(n_vox, np.uint8), f"an empty mask, {n_te} echoes")
+
+
+def test_an_idle_wave_sits_through_the_chunks_with_four_groups_per_wave(t2):
+    atoms = K.atoms_for(1000, 8).atoms
+    assert K.chunks_of(1000, 8) == (16, 2)
+    n_vox = 3 * 512 + 40
+    y = K.decays(8, n_vox, seed=91)
+    mask = K.holes_mask(n_vox, 92)
+    mask[128:256] = 0     # a whole wave of the first workgroup
+    mask[1024 + 384:1536] = 0  # the last wave of the third
+    want = _check(t2, y, atoms, mask, "an emptied wave, 8 echoes, two chunks")
+    assert np.all(want[0][mask == 0] == -1) and np.all(want[0][mask != 0] >= 0)
+
+
+def test_ties_across_chunks(t2):
+    atoms, y, index, named = K.cross_chunk_tie_case()
+    want = _check(t2, y.copy(), atoms, None, "ties across chunks")
+    assert np.array_equal(want[0], index)
+    got = t2.dictionary.match(y.copy(), atoms)[0]
+    got = got.cpu().numpy() if hasattr(got, "cpu") else np.asarray(got)
+    assert {n: int(got[v]) for n, (v, _) in named.items()} == {"copy_met_first": 40, "lower_met_first": 110, "ragged_last_tile": 295,
+                                                               "last_slot_before_the_break": 287}
+
+
+def test_samples_next_to_the_largest_float(t2):
+    """|y| dmax >= 1e38 on about half of the voxels: there the band is infinite and every atom is re-scored, whatever the
+    float32 scores are; the other voxels of the same groups keep a finite band."""
+    atoms, y, share = K.huge_case()
+    assert 0.2 <= share <= 0.8
+    want = _check(t2, y.copy(), atoms, None, "huge samples")
+    assert np.all(np.isfinite(want[1])) and np.all(np.isfinite(want[2])) and len(np.unique(want[0])) > 10
+
+
+@pytest.mark.parametrize("scale", K.TINY_SCALES)
+def test_subnormal_samples(t2, scale):
+    atoms, y, info = K.tiny_case(scale)
+    want = _check(t2, y.copy(), atoms, None, f"samples times {scale}")
+    sub = (want[2] > 0) & (want[2] < np.float32(K.SMALLEST_NORMAL))
+    assert int(sub.sum()) == info["subnormal_rmse"] and (scale > 1e-40 or sub.any()) and len(np.unique(want[0])) > 10
+
+
+def test_minus_zero_a_single_subnormal_sample_and_the_largest_float_over_8(t2):
+    atoms, y, rows = K.special_rows_case()
+    with np.errstate(over="ignore"):  # (one scale is beyond float32 and becomes inf, in the statement as on the device)
+        want = _check(t2, y.copy(), atoms, None, "special rows")
+    v = rows["minus_zero"]
+    assert want[0][v] == 0 and want[1][v].view(np.uint32) == 0 and want[2][v].view(np.uint32) == 0
+    assert np.isinf(want[1][rows["plus_minus_max_over_8"]]) and np.all(want[0] >= 0)
+
+
+@pytest.mark.parametrize("factor", [1e-18, 1e18])
+def test_atoms_far_from_unit_norm(t2, factor):
+    y = K.decays(6, 300, seed=55)
+    want = _check(t2, y, K.scaled_atoms(factor), K.holes_mask(300, 56), f"atoms times {factor}")
+    unscaled = _dict.match(y, K.atoms_for(512, 6).atoms, K.holes_mask(300, 56))
+    # (the scaled atoms are rounded to float32 once more, so a near tie may fall the other way; elsewhere the scale is the
+    # unscaled one over the factor)
+    same = (want[0] == unscaled[0]) & (want[0] >= 0)
+    assert same.mean() > 0.5 and np.allclose(want[1][same].astype(np.float64) * factor, unscaled[1][same], rtol=1e-5)
+
+
+@pytest.mark.parametrize("n_te", [2, 32])
+def test_the_largest_table(t2, n_te):
+    """65536 atoms (T2FIT_DICT_MAX_ATOMS) through the public entry: 2048 tiles in 32 chunks of 64 at 2 echoes, in 512 chunks of 4
+    at 32 echoes; atom indices beyond 2^15."""
+    atoms = K.atoms_for(_abi.DICT_MAX_ATOMS, n_te).atoms
+    want = _check(t2, K.decays(n_te, 96, seed=700 + n_te), atoms, None, f"65536 atoms, {n_te} echoes")
+    assert want[0].max() > 32767 and want[0].max() < 65536 and want[0].min() >= 0
 
 
 def test_raw_calls_and_refusals(t2):

@@ -1,7 +1,8 @@
 """The dictionary fit without a GPU: the numpy statement (fetal_t2mapping_amd/_dict.py) against a brute-force matcher in
 Python floats, the packed block against t2fit_dict_pack_host byte for byte, the refusals through both, the builders, the
-two-compartment model against the mono-exponential one, save / load, the CLI flags, and the case that shows why the
-float32 scores of the matrix instruction need the float64 re-score and that its bound holds (tests/dict_cases.py)."""
+two-compartment model against the mono-exponential one, save / load, the CLI flags, and the cases that show why the
+float32 scores of the matrix instruction need the float64 re-score and that its bound holds, on a table of one chunk and
+on tables of several, ties across chunks, and the conditions of the magnitude cases (tests/dict_cases.py)."""
 import ctypes as C
 
 import numpy as np
@@ -212,6 +213,50 @@ def test_float32_scores_need_the_float64_stage_and_the_bound_holds():
     dh, _, dmax = _dict.normalise(atoms)
     got, _ = K.candidate_rule(K.chain32(dh, y, 6), _dict.scores(dh, y), np.zeros(2000, np.float32), 6)
     assert np.any(got != index)
+
+
+@pytest.mark.parametrize("case", K.MULTI_CHUNK_CASES, ids=lambda c: f"{c[0]}x{c[1]}")
+def test_float32_scores_need_the_float64_stage_on_tables_of_several_chunks(case):
+    """The same three assertions of the builder on tables that the kernel walks in 2, 7, 9, 16 and 32 chunks (17 and 32
+    echoes: two groups per wave; 65536 atoms: the largest table), where the tiles are visited out of index order; the builder
+    also asserts that the table needs at least two chunks and that the rule with T = 0 misses the statement's atom."""
+    n_atoms, n_te, n_vox, _ = case
+    atoms, y, index, info = K.near_tie_case(*case)
+    assert atoms.shape == (n_atoms, n_te) and y.shape == (n_te, n_vox) and index.shape == (n_vox,)
+    assert info["n_chunks"] == K.chunks_of(n_atoms, n_te)[1] >= 2 and info["differ"] >= 20 and info["t0_misses"] >= 1
+    assert info["rescored_max"] < n_atoms  # the rule selects, it does not re-score everything
+    assert index.min() >= 0 and index.max() < n_atoms and len(np.unique(index)) > 10
+
+
+def test_ties_across_chunks_go_to_the_lowest_index():
+    """Duplicates whose copies sit in other chunks (the builder asserts the statement's index on the four named voxels, that
+    the scores of the copies are equal, and that the tile-by-tile rule reproduces the statement)."""
+    atoms, y, index, named = K.cross_chunk_tie_case()
+    assert atoms.shape == (300, 32) and K.chunks_of(300, 32) == (4, 3)
+    assert np.array_equal(atoms[104], atoms[40]) and np.array_equal(atoms[142], atoms[110])
+    assert {n: int(index[v]) for n, (v, _) in named.items()} == {"copy_met_first": 40, "lower_met_first": 110,
+                                                                 "ragged_last_tile": 295, "last_slot_before_the_break": 287}
+    # the walk: tile 3 (chunk 0) before tile 1 (chunk 1); tile 3 before tile 4; tile 9 is ragged; tile 8 ends chunk 2
+    order = [slot * 3 + c for c in range(3) for slot in range(4) if slot * 3 + c < 10]
+    assert order == [0, 3, 6, 9, 1, 4, 7, 2, 5, 8]
+    assert order.index(104 // 32) < order.index(40 // 32) and order.index(110 // 32) < order.index(142 // 32)
+    for v, j in named.values():  # the brute-force matcher agrees on the ties
+        assert K.brute_force(y[:, v:v + 1], atoms)[0][0] == j
+
+
+def test_magnitude_cases_reach_what_they_are_for():
+    """The builders of the magnitude cases assert their own conditions: the share of voxels beyond |y| dmax = 1e38 (between
+    20 % and 80 %, finite samples, finite scale and rmse without a numpy warning), the subnormal shares of the tiny samples
+    and a subnormal rmse, the special rows, and atoms far from unit norm with finite non-zero squared norms."""
+    assert 0.2 <= K.huge_case()[2] <= 0.8
+    shares = [K.tiny_case(s)[2] for s in K.TINY_SCALES]
+    assert shares[0]["subnormal_samples"] < 0.01 < 0.1 < shares[1]["subnormal_samples"] < 0.5 < 0.9 < shares[2]["subnormal_samples"]
+    assert any(s["subnormal_rmse"] >= 1 for s in shares)
+    atoms, y, rows = K.special_rows_case()
+    assert np.all(y[:, rows["minus_zero"]].view(np.uint32) == 0x80000000)
+    for factor in (1e-18, 1e18):
+        n2 = _dict.normalise(K.scaled_atoms(factor))[1]
+        assert n2.max() < 1e-30 if factor < 1 else n2.min() > 1e20
 
 
 def test_fma_emulation_is_exact_on_hard_roundings():
