@@ -62,6 +62,11 @@ TV_JOINT_MAX_CHAN = 64
 MPPCA_MAX_TE, MPPCA_MAX_RADIUS = 16, 4
 SEG_MAX_CLASSES, SEG_MAX_CHANNELS, SEG_MAX_RADIUS = 8, 4, 32
 DICT_MAX_ATOMS = 65536
+UNRING_MIN_N, UNRING_MAX_N, UNRING_MAX_SHIFTS, UNRING_MAX_WINDOW = 8, 512, 32, 8
+
+
+class T2FitUnringParams(C.Structure):
+    _fields_ = [("K", C.c_int32), ("min_w", C.c_int32), ("max_w", C.c_int32), ("flags", C.c_int32)]
 
 
 class T2FitMppcaParams(C.Structure):
@@ -214,6 +219,14 @@ SYMBOLS = [
     ("t2fit_dict_pack_bytes", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     ("t2fit_dict_pack_host", C.c_int, [C.c_int, C.c_int, _P, _P, C.c_size_t]),
     ("t2fit_dict_match_dev", C.c_int, [_P, C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    ("t2fit_unring_params_default", C.c_int, [C.POINTER(T2FitUnringParams)]),
+    ("t2fit_unring_tables_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    ("t2fit_unring_tables_host", C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_size_t]),
+    ("t2fit_unring_workspace_bytes", C.c_int, [C.POINTER(T2FitUnringParams), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    ("t2fit_unring_split_dev", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    ("t2fit_unring_rows_dev", C.c_int, [C.POINTER(T2FitUnringParams), _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    ("t2fit_unring_dev", C.c_int, [C.POINTER(T2FitUnringParams), _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int64), _P,
+                                   C.c_size_t, _P]),
     ("t2fit_set_timing", C.c_int, [C.c_int]),
     ("t2fit_set_reserve_cus", C.c_int, [C.c_int]),
     ("t2fit_kernel_ms", C.c_double, [C.c_int]),
@@ -249,8 +262,10 @@ SEG_SYMBOLS = ("t2fit_seg_workspace_bytes", "t2fit_seg_mask_dev", "t2fit_seg_pri
 FFD_SYMBOLS = ("t2fit_ffd_workspace_bytes", "t2fit_ffd_joint_hist_dev", "t2fit_ffd_gradient_dev", "t2fit_ffd_warp_dev",
                "t2fit_ffd_jacobian_dev")
 DICT_SYMBOLS = ("t2fit_dict_pack_bytes", "t2fit_dict_pack_host", "t2fit_dict_match_dev")
+UNRING_SYMBOLS = ("t2fit_unring_params_default", "t2fit_unring_tables_bytes", "t2fit_unring_tables_host", "t2fit_unring_workspace_bytes",
+                  "t2fit_unring_split_dev", "t2fit_unring_rows_dev", "t2fit_unring_dev")
 LOOKED_UP = (ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS + MI_SYMBOLS + SR_SYMBOLS + SR_SLICE_SYMBOLS + SVR_SYMBOLS
-             + SR_ROBUST_SYMBOLS + TVJ_SYMBOLS + MPPCA_SYMBOLS + SEG_SYMBOLS + FFD_SYMBOLS + DICT_SYMBOLS)
+             + SR_ROBUST_SYMBOLS + TVJ_SYMBOLS + MPPCA_SYMBOLS + SEG_SYMBOLS + FFD_SYMBOLS + DICT_SYMBOLS + UNRING_SYMBOLS)
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

@@ -1033,9 +1033,10 @@ def parse_arguments(argv=None):
                         "with its defaults)")
     p.add_argument("--recon_register_echoes", action="store_true",
                    help="with --reconstruct: register every merged echo onto the first one (recon.py --register_echoes)")
-    from .recon import add_sr_arguments, sr_arguments
+    from .recon import add_sr_arguments, add_unring_arguments, sr_arguments, unring_arguments
 
     add_sr_arguments(p, "recon_")
+    add_unring_arguments(p, "recon_")
     p.add_argument("--build_mask", choices=["phantom"], default=None,
                    help="build the masks of every echo and the vial labels on the GPU from the volumes about to be fitted "
                         "(after --reconstruct if given) instead of reading recon_1mm_mask / recon_1mm_label: phantom = the "
@@ -1072,7 +1073,7 @@ def parse_arguments(argv=None):
         p.error(str(e))
     args.reconstruct_args = None
     given = [f for f in ("--recon_fixed", "--recon_res", "--recon_transforms", "--recon_register", "--recon_register_echoes",
-                         "--recon_n4", "--recon_register_metric", "--recon_method")
+                         "--recon_n4", "--recon_register_metric", "--recon_method", "--recon_unring")
              if any(a == f or a.startswith(f + "=") for a in (argv if argv is not None else sys.argv[1:]))]
     if given and not args.reconstruct:
         p.error(f"{given[0]} has no effect without --reconstruct")
@@ -1096,6 +1097,9 @@ def parse_arguments(argv=None):
             from .recon import N4_DEFAULTS
 
             args.reconstruct_args["n4"] = dict(N4_DEFAULTS)
+    unring = unring_arguments(p, args, "recon_", argv)  # (after the check above: --recon_unring needs --reconstruct)
+    if unring is not None:
+        args.reconstruct_args["unring"] = unring
     sr = sr_arguments(p, args, "recon_", argv)  # after the check above: --recon_method needs --reconstruct
     if sr is not None:
         args.reconstruct_args["sr"] = sr

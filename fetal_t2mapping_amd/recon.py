@@ -37,7 +37,13 @@ as the reference sets them; parity with ITK unpinned), inside the stack's ``<run
 directory ``mask`` when it exists, else inside ``build_mask`` of the stack, and every echo's stack of that orientation is
 divided by that one field before step 1 -- the decay curve keeps its shape.  ``--write_n4`` writes the corrected stacks under
 the derivative directory ``n4``.  The reference takes both directory names as arguments and never fixes them: ``mask`` and
-``n4`` are this driver's choice."""
+``n4`` are this driver's choice.
+
+``--unring`` (no reference counterpart) removes the Gibbs ringing of every raw stack of every echo on the GPU
+(``t2map.unring.unring_volume``: local sub-voxel shifts, Kellner et al. 2016) before ``--n4`` and step 1.  A stack arrives
+as ``(Z, Y, X)`` with Z the slice index whatever its orientation, so the acquired plane, which is what gets filtered, is
+always (Y, X).  The stacks stop being integers: the pixel type is treated as under ``--n4``.  ``--write_unring`` writes them
+under the derivative directory ``unring``."""
 from __future__ import annotations
 
 import argparse
@@ -55,6 +61,7 @@ from .cli import (_sitk, build_phantom_subject, feta_dirname, get_img_path, load
 in_dirname = "anat"
 resamp_dirname = "resamp_1mm"
 n4_dirname = "n4"             # --write_n4: the corrected stacks (a choice: the reference passes the name in)
+unring_dirname = "unring"     # --write_unring: the unrung stacks, <sub>_<ses>_<run>_T2w_unring.nii.gz
 stack_mask_dirname = "mask"   # --n4: <sub>_<ses>_<run>_T2w_mask.nii.gz of an acquired stack, when there is one
 N4_DEFAULTS = {"fwhm_cor": 0.25, "fwhm": 0.5, "echo": None, "scale": 1.0}
 N4_ECHO_MS = 255
@@ -352,17 +359,46 @@ def n4_batch(sitk, bids_path, batch, stacks, n4, device=0):
     return correct_stacks(stacks, masks, echo_ms, device=device, **n4)[0]
 
 
+UNRING_DEFAULTS = {"K": 20, "min_w": 1, "max_w": 3}
+
+
+def unring_batch(stacks, unring, device=0):
+    """The stacks of a batch after ``--unring`` (`unring`: K, min_w, max_w): every (Y, X) slice of every echo of every
+    orientation, Z being the slice index of a raw stack."""
+    out = {}
+    for o in _resample.ORIENTATIONS:
+        info = {}
+        out[o] = np.asarray(t2map.unring.unring_volume(np.ascontiguousarray(stacks[o], dtype=np.float32), slice_axis=0, info=info,
+                                                       device=device, **unring), np.float32)
+        skipped = f", {info['skipped']} slices with non-finite samples left as they are" if info.get("skipped") else ""
+        print(f"Gibbs-ringing removal: {o.upper()}, {stacks[o].shape[0]} echoes of {stacks[o].shape[1]} slices{skipped}")
+    return out
+
+
+def write_stacks(sitk, bids_path, batch, stacks, geoms, dirname):
+    """The stacks of a batch under the derivative directory `dirname`, named after the raw stacks (:func:`get_img_path`)."""
+    for o in _resample.ORIENTATIONS:
+        for it, vol in zip(batch, stacks[o]):
+            img = sitk.GetImageFromArray(vol)
+            g = geoms[o]
+            img.SetSpacing(g.GetSpacing()), img.SetOrigin(g.GetOrigin()), img.SetDirection(g.GetDirection())
+            path = get_img_path(bids_path, it[1][o], dirname)
+            sitk.WriteImage(img, path)
+            print(f"Image saved in : {path}")
+
+
 def process_recon(metadata, bids_path, *, fixed="ax", res=1.0, transforms_dir=None, write_resamp=False, denoise=True,
                   integer_cast=None, register=False, write_transforms=None, register_echoes=False, n4=None, write_n4=False,
-                  register_metric="corr", sr=None, device=0):
+                  register_metric="corr", sr=None, unring=None, write_unring=False, device=0):
     """Reconstruct every echo of every (prj, sub, ses) of `metadata` that has the three orientations and write it.
     The echoes of a subject whose stacks share their geometry per orientation go through one call.  ``integer_cast``:
     None keeps the pixel type as the reference does (cast when the stacks are int16 on disk).  ``register`` /
     ``write_transforms`` / ``register_echoes`` / ``register_metric``: see :func:`merge_echoes`.  ``n4``: None, or the keyword arguments of
     :func:`correct_stacks` (``--n4``): the stacks are bias-corrected before step 1 and are no longer integers, so the
     pixel type is not kept unless ``integer_cast`` says so; ``write_n4`` writes them under ``n4``.  ``sr``: see
-    :func:`merge_echoes` (same file names).  Returns the paths
-    written under ``recon_1mm``."""
+    :func:`merge_echoes` (same file names).  ``unring``: None, or K, min_w, max_w of :func:`unring_batch` (``--unring``): the
+    raw stacks are unrung first, before ``n4``, and the pixel type is treated as under ``n4``; ``write_unring`` writes them
+    under ``unring``.  Returns the paths written under ``recon_1mm``."""
     import torch
 
     sitk = _sitk()
@@ -371,6 +407,10 @@ def process_recon(metadata, bids_path, *, fixed="ax", res=1.0, transforms_dir=No
         for batch in batches_of(read_echoes(sitk, bids_path, echoes, sub, ses)):
             t0 = time.time()
             stacks, geoms, cast = batch_inputs(sitk, batch, integer_cast)
+            if unring is not None:
+                stacks, cast = unring_batch(stacks, unring, device), bool(integer_cast)
+                if write_unring:
+                    write_stacks(sitk, bids_path, batch, stacks, geoms, unring_dirname)
             if n4 is not None:
                 stacks, cast = n4_batch(sitk, bids_path, batch, stacks, n4, device), bool(integer_cast)
                 if write_n4:
@@ -639,9 +679,10 @@ def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fix
 
 
 def reconstruct_subject(sitk, bids_path, sub_md, sub, ses, *, fixed="ax", res=1.0, transforms_dir=None, integer_cast=None,
-                        register=False, register_echoes=False, n4=None, register_metric="corr", sr=None, device=0):
+                        register=False, register_echoes=False, n4=None, register_metric="corr", sr=None, unring=None, device=0):
     """cli.py --reconstruct: the echoes of one (sub, ses) (`sub_md`: its metadata rows) reconstructed in memory.  Every
-    echo must have the three orientations and the echoes must share their grids.  ``n4``, ``sr``: as :func:`process_recon`.
+    echo must have the three orientations and the echoes must share their grids.  ``n4``, ``sr``, ``unring``: as
+    :func:`process_recon`.
     Returns ``(volumes: list of (Z, Y, X) float32 arrays in EchoTime order, header)``."""
     echoes = [(float(te), {acq["ImageOrientationPatientSTR"]: acq for _, acq in te_md.iterrows()})
               for te, te_md in sub_md.groupby("EchoTime")]
@@ -652,6 +693,8 @@ def reconstruct_subject(sitk, bids_path, sub_md, sub, ses, *, fixed="ax", res=1.
     if len(batches) != 1:
         raise ValueError(f"--reconstruct: the stacks of {sub}_{ses} do not lie on the same grids at every echo time")
     stacks, geoms, cast = batch_inputs(sitk, batches[0], integer_cast)
+    if unring is not None:
+        stacks, cast = unring_batch(stacks, unring, device), bool(integer_cast)
     if n4 is not None:
         stacks, cast = n4_batch(sitk, bids_path, batches[0], stacks, n4, device), bool(integer_cast)
     merged, header, _ = merge_echoes(stacks, geoms, [it[1][fixed] for it in ready], fixed=fixed, res=res, integer_cast=cast,
@@ -892,10 +935,12 @@ def parse_arguments(argv=None):
     p.add_argument("--n4_scale", type=float, default=N4_DEFAULTS["scale"],
                    help="with --n4: factor on the corrected stacks (default 1; run_biasfield_correction's 0.25 is --n4_scale 0.25)")
     p.add_argument("--write_n4", action="store_true", help="with --n4: also write the corrected stacks under derivatives/n4/")
+    add_unring_arguments(p, "")
     add_sr_arguments(p, "")
     p.add_argument("--device", type=int, default=0, help="HIP device ordinal")
     args = p.parse_args(argv)
     args.sr_args = sr_arguments(p, args, "", argv)
+    args.unring_args = unring_arguments(p, args, "", argv)
     given = [f for f in ("--n4_fwhm_cor", "--n4_fwhm", "--n4_echo", "--n4_scale", "--write_n4")
              if any(a == f or a.startswith(f + "=") for a in (argv if argv is not None else sys.argv[1:]))]
     if given and not args.n4:
@@ -1002,6 +1047,48 @@ def parse_arguments(argv=None):
     return args
 
 
+def add_unring_arguments(p, prefix):
+    """``--unring`` and its sub-flags (recon.py), or ``--recon_unring`` .. (cli.py, `prefix` "recon_")."""
+    with_ = f"with --{prefix}unring"
+    p.add_argument(f"--{prefix}unring", action="store_true",
+                   help="Gibbs-ringing removal (local sub-voxel shifts, Kellner et al. 2016) of every acquired slice of every raw "
+                        "stack of every echo on the GPU, before --n4 and step 1; off by default")
+    p.add_argument(f"--{prefix}unring_shifts", type=int, default=None, metavar="K",
+                   help=f"{with_}: sub-voxel shifts per side, 1 .. 32 (default 20: 41 candidates)")
+    p.add_argument(f"--{prefix}unring_window", default=None, metavar="MIN,MAX",
+                   help=f"{with_}: the window of the total variation in samples, 1 <= MIN <= MAX <= 8 (default 1,3)")
+    if not prefix:
+        p.add_argument("--write_unring", action="store_true", help="with --unring: also write the unrung stacks under derivatives/unring/")
+
+
+def unring_arguments(p, args, prefix, argv):
+    """None without ``--unring``, else K, min_w, max_w for :func:`unring_batch`; a sub-flag without the flag is an error."""
+    from ._unring import MAX_K, MAX_W
+
+    flags = [f"--{prefix}unring_shifts", f"--{prefix}unring_window"] + ([] if prefix else ["--write_unring"])
+    given = [f for f in flags if any(a == f or a.startswith(f + "=") for a in (argv if argv is not None else sys.argv[1:]))]
+    on = getattr(args, f"{prefix}unring")
+    if given and not on:
+        p.error(f"{given[0]} has no effect without --{prefix}unring")
+    if not on:
+        return None
+    out = dict(UNRING_DEFAULTS)
+    shifts, window = getattr(args, f"{prefix}unring_shifts"), getattr(args, f"{prefix}unring_window")
+    if shifts is not None:
+        if not 1 <= shifts <= MAX_K:
+            p.error(f"--{prefix}unring_shifts is in 1 .. {MAX_K}")
+        out["K"] = shifts
+    if window is not None:
+        try:
+            lo, hi = (int(v) for v in window.split(","))
+        except ValueError:
+            p.error(f"--{prefix}unring_window {window!r}: expected MIN,MAX")
+        if not 1 <= lo <= hi <= MAX_W:
+            p.error(f"--{prefix}unring_window: 1 <= MIN <= MAX <= {MAX_W}")
+        out["min_w"], out["max_w"] = lo, hi
+    return out
+
+
 def main(argv=None):
     args = parse_arguments(argv)
     if not os.path.exists(args.path):
@@ -1019,7 +1106,8 @@ def main(argv=None):
     process_recon(metadata, bids_path, fixed=args.fixed, res=args.res, transforms_dir=args.transforms,
                   write_resamp=args.write_resamp, denoise=not args.no_denoise, register=args.register,
                   write_transforms=args.write_transforms, register_echoes=args.register_echoes, n4=args.n4_args,
-                  write_n4=args.write_n4, register_metric=args.register_metric, sr=args.sr_args, device=args.device)
+                  write_n4=args.write_n4, register_metric=args.register_metric, sr=args.sr_args, unring=args.unring_args,
+                  write_unring=args.write_unring, device=args.device)
     if args.register_to_lf:
         process_register_to_lf(metadata, bids_path, write_transforms=args.write_transforms, device=args.device)
     if args.phantom_masks:

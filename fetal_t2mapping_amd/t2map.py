@@ -34,6 +34,7 @@ slice-to-volume        ``_gpu_register``,  ``_svr`` (batched per-slice sums, tra
 registration           ``_gpu_sr``         code); here as ``register.register_slices``, ``register.slice_sums``, ``sr.reconstruct_svr``
 tissue segmentation    ``_gpu_seg``        ``_seg`` (the steps, and the EM loop and class model, which are host code); here as ``seg``
 dictionary fit         ``_gpu_dict``       ``_dict`` (and the dictionary builders, which both share); here as ``dictionary``
+Gibbs-ringing removal  ``_gpu_unring``     ``_unring`` (and the tables, which both read); here as ``unring``
 N4 bias field          ``_gpu_bias``       ``_bias`` (and the sharpening table, the refinement and the loop, which are host code); here as ``bias``
 =====================  ==================  ===========================================================
 
@@ -59,6 +60,8 @@ from . import _gpu_seg as seg  # noqa: F401  (a namespace: seg.segment_em, seg.p
 #                                seg.hard_labels, seg.seg_params)
 from . import _gpu_dict as dictionary  # noqa: F401  (a namespace: dictionary.Dictionary, .monoexp, .biexp, .log_grid, .pack, .match,
 #                                         .fit_volume_dict)
+from . import _gpu_unring as unring  # noqa: F401  (a namespace: unring.unring_volume, .unring_slices, .unring_split, .unring_rows,
+#                                       .unring_tables)
 
 
 def __getattr__(name):

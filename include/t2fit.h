@@ -1278,6 +1278,94 @@ int t2fit_dict_pack_host(int n_atoms, int n_te, const float *atoms, void *packed
 int t2fit_dict_match_dev(const float *y_dev, int n_te, int64_t n_vox, const uint8_t *mask_dev, const void *packed_dev,
                          int32_t *index_dev, float *scale_dev, float *rmse_dev, void *stream);
 
+/* ---- Gibbs-ringing removal by local sub-voxel shifts (additive to ABI 5) ----------------------------------------------
+ * Kellner et al. 2016 on float32 slices (S, ny, nx), every slice on its own, the in-plane axes last.  Refused:
+ * nx or ny outside T2FIT_UNRING_MIN_N .. T2FIT_UNRING_MAX_N, K outside 1 .. T2FIT_UNRING_MAX_SHIFTS, a window outside
+ * 1 <= min_w <= max_w <= T2FIT_UNRING_MAX_WINDOW, min(nx, ny) < 2 (max_w + 1) + 1.  fetal_t2mapping_amd/_unring.py states
+ * everything below in numpy; the device output is bit-identical to it and equal from call to call.
+ *
+ * Tables: built on the host in float64 and rounded once to float32 (t2fit_unring_tables_host; _unring.Tables.pack writes
+ * the same block).  The device calls read them, so a caller may pass either.  The block, little endian, 16-byte aligned
+ * on the device:
+ *   byte   0  uint32 magic 0x52553254   int32 nx   int32 ny   int32 K   16 bytes 0
+ *   byte  32  uint64 offsets of cx, sx, cy, sy, g, hx, hy, ab   uint64 bytes (the whole block)   24 bytes 0
+ *   cx, sx    float32 [nx][nx]: C[k][m] = cos(2 pi ((k m) mod nx) / nx), S likewise with sin;  cy, sy: the same for ny
+ *   g         float32 [ny][nx]: G = cy / (cx + cy) with cx = 1 + cos(2 pi kx / nx), cy = 1 + cos(2 pi ky / ny), 0.5 where
+ *             cx + cy = 0; stored as float32(G / (nx ny))
+ *   hx, hy    float32 [2K+1][n]: the taps of the shifts s_0 = 0, s_j = j / (2K+1), s_{K+j} = -j / (2K+1) (j = 1 .. K):
+ *             h_j[d] = (1/n) [1 + 2 sum_{k=1}^{ceil(n/2)-1} cos(2 pi k (d + s_j) / n) + (n even) cos(pi d) cos(pi s_j)];
+ *             row 0 is (1, 0, 0, ..) and is never read
+ *   ab        float32 [2][2K+1]: a_j = float32(1 - |s_j|), then b_j = float32(|s_j|)
+ *   every table is padded with zero bytes to a multiple of 16.
+ *
+ * Arithmetic: every product of a table and data is a float32 fma chain over the contracted index, ascending, from 0.0f
+ * (what v_mfma_f32_32x32x2_f32 computes; an odd length is padded with exact zeros).  Everything else is float32 with one
+ * rounding per operation, nothing fused.
+ *
+ * Step 1, split (t2fit_unring_split_dev).  Planes are indexed [y or ky][x or kx]; stacked operands hold the cosine or
+ * real part first, the sine or imaginary part second, and the contracted index of a stacked operand runs through the
+ * first part, then the second:
+ *   [P; Q] = [Cx; Sx] . X^T (over x);   [A; B] = [[Cy, -Sy], [Sy, Cy]] . [P; Q] (over (part, y));   A, B <- fl(A G), fl(B G);
+ *   [Vr; Vi] = [[Cy, Sy], [Sy, -Cy]] . [A; B] (over (part, ky));   I1 = [Cx, -Sx] . [Vr; Vi]^T (over (part, kx));   I2 = fl(X - I1).
+ * I1 keeps the ringing along x, I2 the ringing along y.
+ * Step 2, rows (t2fit_unring_rows_dev, along x or along y).  The shifts are visited in the order j = 0, 1, .., 2K.  Y_0 is
+ * the row itself; Y_j[l] = sum_m h_j[(l - m) mod n] x[m] (the chain, over m).  d[l] = |Y_j[l] - Y_j[l-1]| (indices circular),
+ * tvl[l] = sum_{t=min_w..max_w} d[l-t], tvr[l] = sum_t d[l+t+1], both ascending in t from 0.0f, tv = min(tvl, tvr).  A shift
+ * replaces the running best only when its tv is strictly smaller.  The output of the winner j: Y_0[l] for j = 0,
+ * fl(fl(Y_j[l] a_j) + fl(Y_j[l-1] b_j)) for s_j > 0, fl(fl(Y_j[l] a_j) + fl(Y_j[l+1] b_j)) for s_j < 0.
+ * Step 3: out = rows along x of I1 + rows along y of I2, one float32 addition.
+ * t2fit_unring_dev copies a slice with a non-finite sample through unchanged and counts it in *skipped; a slice whose
+ * samples are all equal is copied through too (it comes back bit for bit) and is not counted.  The split and the rows on
+ * their own do not look for non-finite samples: what they give on a row that holds one is not defined bit for bit. */
+#define T2FIT_UNRING_MIN_N 8
+#define T2FIT_UNRING_MAX_N 512
+#define T2FIT_UNRING_MAX_SHIFTS 32
+#define T2FIT_UNRING_MAX_WINDOW 8
+
+typedef struct t2fit_unring_params {
+  int32_t K;     /* shifts per side: 2K+1 candidates.  Default 20 */
+  int32_t min_w; /* the window of the total variation, in samples.  Default 1 */
+  int32_t max_w; /* default 3 */
+  int32_t flags; /* 0 */
+} t2fit_unring_params;
+
+int t2fit_unring_params_default(t2fit_unring_params *params);
+
+/* Plain arithmetic, no device. */
+int t2fit_unring_tables_bytes(int ny, int nx, int K, size_t *bytes);
+
+/* No device.  Writes the block described above; refuses the sizes above, a NULL pointer, `bytes` below
+ * t2fit_unring_tables_bytes. */
+int t2fit_unring_tables_host(int ny, int nx, int K, void *tables_host, size_t bytes);
+
+/* One workspace serves t2fit_unring_split_dev and t2fit_unring_dev for up to n_slices slices: six float32 images of at
+ * most 64 slices (the calls work through the slices 64 at a time) and two bytes per slice.  It does not depend on K: the
+ * shifted copies never reach global memory.  Plain arithmetic, no device.  The calls keep nothing in it between calls. */
+int t2fit_unring_workspace_bytes(const t2fit_unring_params *params, int n_slices, int ny, int nx, size_t *bytes);
+
+/* X -> I1, I2, float32 [n_slices][ny][nx] each; the three must differ.  Four launches per 64 slices on `stream`.  Refused
+ * before HIP is touched: a NULL pointer, the sizes above, n_slices < 0, an image not aligned to 4 bytes, tables_dev not
+ * aligned to 16, a workspace that is NULL, not aligned to 256 bytes or too small.  The 128-byte header is then read back
+ * from tables_dev (one copy and one wait on `stream`) and refused, before any launch, when it is not what
+ * t2fit_unring_tables_host writes for this nx and ny.  n_slices == 0 is a no-op. */
+int t2fit_unring_split_dev(const void *tables_dev, const float *in_dev, int n_slices, int ny, int nx, float *i1_dev, float *i2_dev,
+                           void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* Step 2 on every row (axis 0: along x) or every column (axis 1: along y, by addressing) of in_dev.  out_dev float32,
+ * shift_dev int8 (the winning j) and tv_dev float32 (the winning tv), [n_slices][ny][nx] each; shift_dev and tv_dev may be
+ * NULL.  out_dev must not be in_dev.  One launch, no workspace.  Refusals as above, except that the size limits and the
+ * window's hold for the axis the rows run along only (across it any size from 1 to T2FIT_UNRING_MAX_N goes, and the tables
+ * need to match along the axis only); params.K must be the tables' K. */
+int t2fit_unring_rows_dev(const t2fit_unring_params *params, const void *tables_dev, const float *in_dev, int n_slices, int ny, int nx,
+                          int axis, float *out_dev, int8_t *shift_dev, float *tv_dev, void *stream);
+
+/* The whole stage.  shift_dev int8 and tv_dev float32, [2][n_slices][ny][nx] (axis x first), or NULL; they hold what the
+ * rows gave, also for a slice that is copied through.  skipped (host) receives the number of slices with a non-finite
+ * sample, or is NULL (the call then does not wait for the stream a second time).  out_dev must not be in_dev. */
+int t2fit_unring_dev(const t2fit_unring_params *params, const void *tables_dev, const float *in_dev, int n_slices, int ny, int nx,
+                     float *out_dev, int8_t *shift_dev, float *tv_dev, int64_t *skipped, void *workspace_dev, size_t workspace_bytes,
+                     void *stream);
+
 /* Kernel timing for benchmarks (no reference counterpart).  With timing enabled (t2fit_set_timing(1)) every
  * t2fit_volume_dev call of this thread records HIP events around its fit kernel on the launch stream.
  * t2fit_kernel_ms(k): duration in milliseconds of the fit kernel launched k timed calls ago (0 = the most recent;
