@@ -166,9 +166,27 @@ def _above(threshold):
     return float(f) if float(f) > float(threshold) else float(np.nextafter(f, np.float32(np.inf)))
 
 
-def build_mask(vol, threshold=1.0, slice_axis=2, size=5, *, device=0):
+def _clean(m, keep_largest, min_size, connectivity, device):
+    """The island removal of build_mask / phantom_mask on the 3-D result; with the defaults the mask itself, untouched."""
+    keep_largest, min_size = int(keep_largest), int(min_size)
+    if keep_largest < 0 or min_size < 0:
+        raise ValueError("keep_largest and min_size must not be negative")
+    if not keep_largest and not min_size:
+        return m
+    from . import _gpu_components
+
+    if min_size:
+        m = _gpu_components.remove_small(m, min_size, connectivity, device=device)
+    if keep_largest:
+        m = _gpu_components.keep_largest(m, keep_largest, connectivity, device=device)
+    return m
+
+
+def build_mask(vol, threshold=1.0, slice_axis=2, size=5, *, device=0, keep_largest=0, min_size=0, connectivity=1):
     """The reference's ``build_mask``: ``vol > threshold``, then per plane perpendicular to ``slice_axis`` of the
-    (z, y, x) array: fill holes, dilate and erode with a ``size x size`` square (scipy's borders).  uint8 CUDA tensor."""
+    (z, y, x) array: fill holes, dilate and erode with a ``size x size`` square (scipy's borders).  uint8 CUDA tensor.
+    Not the reference's: ``min_size`` > 0 drops the 3-D components (``connectivity`` 1, 2, 3) of fewer voxels from the
+    result, ``keep_largest`` = k > 0 keeps its k largest (``t2map.components``); with the defaults neither runs."""
     if size < 1 or size % 2 == 0:
         raise ValueError("size must be odd")
     fp_shape = [size, size, size]
@@ -177,17 +195,18 @@ def build_mask(vol, threshold=1.0, slice_axis=2, size=5, *, device=0):
     m = binary_threshold(np.asarray(vol, np.float32) if not is_tensor(vol) else vol.float(), _above(threshold), device=device)
     m = fill_holes(m, slice_axis=slice_axis, out=m)
     m = binary_dilate(m, square, out=m)
-    return binary_erode(m, square, out=m)
+    return _clean(binary_erode(m, square, out=m), keep_largest, min_size, connectivity, device)
 
 
-def phantom_mask(vol, threshold=100, close_radius=15, dilate_radius=10, *, device=0):
+def phantom_mask(vol, threshold=100, close_radius=15, dilate_radius=10, *, device=0, keep_largest=0, min_size=0, connectivity=1):
     """The reference's ``build_phantom_masks`` for one echo volume: ``vol >= threshold``, 3-D fill holes, closing with
     the radius-``close_radius`` ball on the unbounded domain, dilation with the radius-``dilate_radius`` ball
-    (:func:`_morph.ball`).  uint8 CUDA tensor."""
+    (:func:`_morph.ball`).  uint8 CUDA tensor.  ``keep_largest``, ``min_size``, ``connectivity``: as in
+    :func:`build_mask`, off by default."""
     m = binary_threshold(np.asarray(vol, np.float32) if not is_tensor(vol) else vol.float(), float(threshold), device=device)
     m = fill_holes(m, out=m)
     m = binary_close(m, _morph.ball(close_radius), unbounded=True, out=m)
-    return binary_dilate(m, _morph.ball(dilate_radius), out=m)
+    return _clean(binary_dilate(m, _morph.ball(dilate_radius), out=m), keep_largest, min_size, connectivity, device)
 
 
 def phantom_labels(shape, seeds, radius=6, *, device=0):

@@ -41,7 +41,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _morph, _resample
+from . import _components, _morph, _resample
 
 BX, BY, BZ = 64, 4, 8
 FAN = 256
@@ -279,13 +279,19 @@ def shrink_mask(mask, s):
     return m[:nz * s, :ny * s, :nx * s].reshape(nz, s, ny, s, nx, s).any(axis=(1, 3, 5)).astype(np.uint8)
 
 
-def build_mask(vol, threshold=1.0, slice_axis=2, size=5):
-    """The reference's ``build_mask`` (utils/qmri_utils.py:223-252) with :mod:`_morph`, as ``_gpu_morph.build_mask``."""
+def build_mask(vol, threshold=1.0, slice_axis=2, size=5, *, keep_largest=0, min_size=0, connectivity=1):
+    """The reference's ``build_mask`` (utils/qmri_utils.py:223-252) with :mod:`_morph`, as ``_gpu_morph.build_mask``;
+    ``min_size`` and ``keep_largest`` (off by default) clean the 3-D result with :mod:`_components`."""
     fp = [size, size, size]
     fp[slice_axis] = 1
     square = np.ones(fp, bool)
     m = _morph.fill_holes(np.asarray(vol, np.float32) > np.float32(threshold), slice_axis=slice_axis)
-    return _morph.erode(_morph.dilate(m, square), square).astype(np.uint8)
+    m = _morph.erode(_morph.dilate(m, square), square).astype(np.uint8)
+    if min_size:
+        m = _components.remove_small(m, min_size, connectivity)
+    if keep_largest:
+        m = _components.keep_largest(m, keep_largest, connectivity)
+    return m
 
 
 def check_levels(levels, fixed_shape, moving_shape):

@@ -26,6 +26,7 @@ enum ScratchUse : int {
   kScratchRing,      // fit: global part of the correction-pair ring (one-wave-workgroup kernels, Rician likelihood)
   kScratchRoiErode,  // ROI statistics: the erosion's second buffer
   kScratchRoiStats,  // ROI statistics: the sort's tables and segments
+  kScratchComponents,  // component selection table: the best key, the counts of the kept per chunk
 };
 struct ScratchCache {
   struct Entry { int device; hipStream_t stream; int use; void* p; size_t bytes; };

@@ -43,10 +43,16 @@ the derivative directory ``n4``.  The reference takes both directory names as ar
 (``t2map.unring.unring_volume``: local sub-voxel shifts, Kellner et al. 2016) before ``--n4`` and step 1.  A stack arrives
 as ``(Z, Y, X)`` with Z the slice index whatever its orientation, so the acquired plane, which is what gets filtered, is
 always (Y, X).  The stacks stop being integers: the pixel type is treated as under ``--n4``.  ``--write_unring`` writes them
-under the derivative directory ``unring``."""
+under the derivative directory ``unring``.
+
+``--mask_keep_largest K`` / ``--mask_min_size N`` (no reference counterpart) clean every mask that ``build_mask`` makes
+here -- the registrations' and, without a mask file, the N4's -- of islands on the GPU (``t2map.components``).
+``--phantom_find_seeds FILE.json`` (with ``--phantom_masks``) proposes the seeds of ``--phantom_seeds`` from the connected
+components of an intensity window of the first echo's reconstruction (:func:`process_find_seeds`)."""
 from __future__ import annotations
 
 import argparse
+import json
 import os
 import re
 import sys
@@ -54,7 +60,7 @@ import time
 
 import numpy as np
 
-from . import _resample, _sr, t2map
+from . import _morph, _resample, _sr, t2map
 from .cli import (_sitk, build_phantom_subject, feta_dirname, get_img_path, load_seeds, mask_dirname, phantom_labels_dirname, recon_dirname,
                   set_metadata)
 
@@ -146,12 +152,27 @@ def save_slice_transforms(transforms_dir, acq, slice_transforms):
     return paths
 
 
-def register_stacks(stacks, geoms, *, fixed="ax", res=1.0, integer_cast=False, device=0, **register_args):
+def _clean_args(mask_clean):
+    """The keyword that hands ``mask_clean`` down; none without it, so that a run without the flags makes the calls it made."""
+    return {"mask_clean": mask_clean} if mask_clean else {}
+
+
+def cleaned_masks(fixed, moving, mask_clean, device=0):
+    """The ``fixed_mask`` / ``moving_mask`` keywords of a registration under ``--mask_keep_largest`` / ``--mask_min_size``
+    (`mask_clean`: the keywords of ``t2map.build_mask``); none without them: the registration then builds its own."""
+    if not mask_clean:
+        return {}
+    return {"fixed_mask": t2map.build_mask(fixed, device=device, **mask_clean),
+            "moving_mask": t2map.build_mask(moving, device=device, **mask_clean)}
+
+
+def register_stacks(stacks, geoms, *, fixed="ax", res=1.0, integer_cast=False, mask_clean=None, device=0, **register_args):
     """{moving orientation: 4 x 4} of one echo: every stack ``(Z, Y, X)`` is resampled to its own ``res`` mm grid (stage 1)
     and each moving volume ``H_m`` is registered onto the fixed one ``H_0`` (``t2map.register.register_rigid``)."""
     order = [fixed] + _resample.moving_order(fixed)
     hi = {o: t2map.resample_volume(stacks[o], geoms[o], res=res, integer_cast=integer_cast, device=device) for o in order}
-    return {o: t2map.register.register_rigid(hi[fixed][0], hi[o][0], hi[fixed][1], hi[o][1], device=device, **register_args).transform
+    return {o: t2map.register.register_rigid(hi[fixed][0], hi[o][0], hi[fixed][1], hi[o][1], device=device, **register_args,
+                                             **cleaned_masks(hi[fixed][0], hi[o][0], mask_clean, device)).transform
             for o in order[1:]}
 
 
@@ -165,7 +186,7 @@ def _metric_args(register_metric):
 
 
 def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False, transforms_dir=None, register=False,
-                 write_transforms=None, register_echoes=False, register_metric="corr", sr=None, device=0):
+                 write_transforms=None, register_echoes=False, register_metric="corr", sr=None, mask_clean=None, device=0):
     """Stages 1 and 2 and the merge of the echoes of one batch (`acqs`: the fixed orientation's metadata row of every
     echo).  The transforms of an echo are read (``transforms_dir``) or found (``register``); echoes with the same
     transforms share a call, so without either the batch is one call.  ``register_echoes``: every merged echo but the
@@ -176,7 +197,8 @@ def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False
     :func:`load_slice_transforms` files, read per echo and passed on as ``slice_transforms``; its entry ``estimate_slices``
     (``--sr_estimate_slices``) is the number of rounds of ``t2map.sr.reconstruct_svr``, which finds those poses on the first
     echo of each call, and ``write_slice_transforms_dir`` where they are written for every echo; its entry
-    ``write_slice_weights`` (``--sr_write_slice_weights``, with ``robust``) names the CSV of :func:`save_slice_weights`.  Returns ``(float32 CUDA tensor
+    ``write_slice_weights`` (``--sr_write_slice_weights``, with ``robust``) names the CSV of :func:`save_slice_weights`.
+    ``mask_clean``: see :func:`cleaned_masks`, for both registrations.  Returns ``(float32 CUDA tensor
     (n, Z, Y, X), header, transforms per echo)``."""
     import torch
 
@@ -185,7 +207,7 @@ def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False
     if register:
         stacks = {o: torch.from_numpy(np.ascontiguousarray(stacks[o], np.float32)).to(dev) for o in stacks}
         per_echo = [register_stacks({o: stacks[o][i] for o in stacks}, geoms, fixed=fixed, res=res, integer_cast=integer_cast,
-                                    device=device, **_metric_args(register_metric)) for i in range(n)]
+                                    device=device, **_metric_args(register_metric), **_clean_args(mask_clean)) for i in range(n)]
         if write_transforms:
             for acq, t in zip(acqs, per_echo):
                 save_transforms(write_transforms, acq, t)
@@ -247,7 +269,8 @@ def merge_echoes(stacks, geoms, acqs, *, fixed="ax", res=1.0, integer_cast=False
     if register_echoes:
         grid = _resample.as_geometry(header, tuple(merged.shape[1:]))
         for i in range(1, n):
-            found = t2map.register.register_rigid(merged[0], merged[i], grid, grid, device=device, **_metric_args(register_metric))
+            found = t2map.register.register_rigid(merged[0], merged[i], grid, grid, device=device, **_metric_args(register_metric),
+                                                  **cleaned_masks(merged[0], merged[i], mask_clean, device))
             merged[i] = t2map.resample_volume(merged[i], grid, like=grid, transform=found.transform,
                                               integer_cast=integer_cast, device=device)[0]
     return merged, header, per_echo
@@ -324,14 +347,18 @@ def n4_echo_index(echo_ms, echo=None):
     return echo_ms.index(N4_ECHO_MS) if N4_ECHO_MS in echo_ms else 0
 
 
-def correct_stacks(stacks, masks, echo_ms, *, fwhm_cor=0.25, fwhm=0.5, echo=None, scale=1.0, device=0):
+def correct_stacks(stacks, masks, echo_ms, *, fwhm_cor=0.25, fwhm=0.5, echo=None, scale=1.0, mask_clean=None, device=0):
     """run_biasfield_correction2 on the stacks of a batch: ``stacks`` {orientation: float32 ``(n, Z, Y, X)``}, ``masks``
     {orientation: mask or None (``build_mask``)}.  Per orientation ONE log field, estimated on the echo of
-    :func:`n4_echo_index`, divides every echo.  Returns ``(corrected stacks, {orientation: log field})``."""
+    :func:`n4_echo_index`, divides every echo.  ``mask_clean``: the keywords of ``t2map.build_mask`` for a mask that is
+    built (``--mask_keep_largest`` / ``--mask_min_size``).  Returns ``(corrected stacks, {orientation: log field})``."""
     at = n4_echo_index(echo_ms, echo)
     out, fields = {}, {}
     for o in _resample.ORIENTATIONS:
-        found = t2map.bias.n4_correct(stacks[o][at], masks.get(o), fwhm=fwhm_cor if o == "cor" else fwhm, device=device)
+        mask = masks.get(o)
+        if mask is None and mask_clean:
+            mask = t2map.build_mask(np.asarray(stacks[o][at], np.float32), device=device, **mask_clean)
+        found = t2map.bias.n4_correct(stacks[o][at], mask, fwhm=fwhm_cor if o == "cor" else fwhm, device=device)
         fields[o] = np.asarray(found.log_field, np.float32)
         out[o] = np.stack([np.asarray(t2map.bias.apply_field(v, fields[o], scale, device=device), np.float32) for v in stacks[o]])
         print(f"N4 bias field correction: {o.upper()}, TE {int(round(float(echo_ms[at])))} ms, iterations {found.iterations}")
@@ -351,12 +378,12 @@ def read_stack_masks(sitk, bids_path, rows, shapes):
     return masks
 
 
-def n4_batch(sitk, bids_path, batch, stacks, n4, device=0):
+def n4_batch(sitk, bids_path, batch, stacks, n4, device=0, mask_clean=None):
     """The stacks of a batch after ``--n4`` (`n4`: the keyword arguments of :func:`correct_stacks`)."""
     echo_ms = [it[0] * 1000.0 for it in batch]
     at = n4_echo_index(echo_ms, n4.get("echo"))
     masks = read_stack_masks(sitk, bids_path, batch[at][1], {o: stacks[o].shape[1:] for o in _resample.ORIENTATIONS})
-    return correct_stacks(stacks, masks, echo_ms, device=device, **n4)[0]
+    return correct_stacks(stacks, masks, echo_ms, device=device, **_clean_args(mask_clean), **n4)[0]
 
 
 UNRING_DEFAULTS = {"K": 20, "min_w": 1, "max_w": 3}
@@ -389,7 +416,7 @@ def write_stacks(sitk, bids_path, batch, stacks, geoms, dirname):
 
 def process_recon(metadata, bids_path, *, fixed="ax", res=1.0, transforms_dir=None, write_resamp=False, denoise=True,
                   integer_cast=None, register=False, write_transforms=None, register_echoes=False, n4=None, write_n4=False,
-                  register_metric="corr", sr=None, unring=None, write_unring=False, device=0):
+                  register_metric="corr", sr=None, unring=None, write_unring=False, mask_clean=None, device=0):
     """Reconstruct every echo of every (prj, sub, ses) of `metadata` that has the three orientations and write it.
     The echoes of a subject whose stacks share their geometry per orientation go through one call.  ``integer_cast``:
     None keeps the pixel type as the reference does (cast when the stacks are int16 on disk).  ``register`` /
@@ -398,7 +425,8 @@ def process_recon(metadata, bids_path, *, fixed="ax", res=1.0, transforms_dir=No
     pixel type is not kept unless ``integer_cast`` says so; ``write_n4`` writes them under ``n4``.  ``sr``: see
     :func:`merge_echoes` (same file names).  ``unring``: None, or K, min_w, max_w of :func:`unring_batch` (``--unring``): the
     raw stacks are unrung first, before ``n4``, and the pixel type is treated as under ``n4``; ``write_unring`` writes them
-    under ``unring``.  Returns the paths written under ``recon_1mm``."""
+    under ``unring``.  ``mask_clean``: None, or ``keep_largest`` / ``min_size`` of ``t2map.build_mask`` for every mask that is built
+    here (the registrations', the N4's).  Returns the paths written under ``recon_1mm``."""
     import torch
 
     sitk = _sitk()
@@ -412,7 +440,7 @@ def process_recon(metadata, bids_path, *, fixed="ax", res=1.0, transforms_dir=No
                 if write_unring:
                     write_stacks(sitk, bids_path, batch, stacks, geoms, unring_dirname)
             if n4 is not None:
-                stacks, cast = n4_batch(sitk, bids_path, batch, stacks, n4, device), bool(integer_cast)
+                stacks, cast = n4_batch(sitk, bids_path, batch, stacks, n4, device, **_clean_args(mask_clean)), bool(integer_cast)
                 if write_n4:
                     for o in _resample.ORIENTATIONS:
                         for it, vol in zip(batch, stacks[o]):
@@ -436,7 +464,7 @@ def process_recon(metadata, bids_path, *, fixed="ax", res=1.0, transforms_dir=No
             merged, header, _ = merge_echoes(stacks, geoms, [it[1][fixed] for it in batch], fixed=fixed, res=res,
                                              integer_cast=cast, transforms_dir=transforms_dir, register=register,
                                              write_transforms=write_transforms, register_echoes=register_echoes,
-                                             register_metric=register_metric, sr=sr, device=device)
+                                             register_metric=register_metric, sr=sr, device=device, **_clean_args(mask_clean))
             if denoise:
                 merged = t2map.denoise_tv(merged, out=merged)
             torch.cuda.synchronize(merged.device)
@@ -488,6 +516,44 @@ def process_phantom_masks(metadata, bids_path, *, seeds=None, fixed="ax", thresh
             if seeds:
                 label_dir = os.path.dirname(get_img_path(bids_path, acq, phantom_labels_dirname))
                 write(label, img, os.path.join(label_dir, label_file_name(name)))
+    return written
+
+
+def seeds_file_name(path, sub, ses, several):
+    """The file ``--phantom_find_seeds`` writes: `path`, or with several subjects `path` with ``_<sub>_<ses>`` before its
+    extension."""
+    if not several:
+        return path
+    root, ext = os.path.splitext(path)
+    return f"{root}_{sub}_{ses}{ext}"
+
+
+def process_find_seeds(metadata, bids_path, path, *, window, erode=2, size=(1, 0), fixed="ax", device=0):
+    """``--phantom_find_seeds FILE``: per subject, the vials of the first echo's recon_1mm volume as connected components
+    -- ``window[0] <= volume <= window[1]``, eroded by the ball of radius ``erode``, labelled (6 neighbours), the sizes
+    ``size[0]..size[1]`` kept (0: no upper limit) -- and their centroids as the JSON list of ``[x, y, z]`` that
+    ``--phantom_seeds`` reads, in label order.  A proposal: nothing is labelled here, and which vial is which is the
+    user's to check.  Returns the paths written."""
+    sitk = _sitk()
+    groups = echo_groups(metadata)
+    written = []
+    for prj, sub, ses, echoes in groups:
+        rows = echoes[0][1]
+        acq = rows[fixed] if fixed in rows else next(iter(rows.values()))
+        recon_path = get_img_path(bids_path, acq, recon_dirname).replace(" ", "")
+        vol = np.asarray(sitk.GetArrayFromImage(sitk.ReadImage(recon_path)), np.float32)
+        m = t2map.binary_threshold(vol, window[0], window[1], device=device)
+        if erode > 0:
+            m = t2map.binary_erode(m, _morph.ball(erode), out=m, device=device)
+        seeds = t2map.components.seeds(m, 1, size[0], size[1], device=device)
+        if not 1 <= len(seeds) <= 255:
+            raise ValueError(f"--phantom_find_seeds: {len(seeds)} components of {recon_path} lie in the window {window[0]:g}..{window[1]:g} "
+                             f"with a size in {size[0]}..{size[1] or 'inf'} after the erosion; --phantom_seeds takes 1..255")
+        out = seeds_file_name(path, sub, ses, len(groups) > 1)
+        with open(out, "w") as f:
+            json.dump(seeds, f)
+        written.append(out)
+        print(f"Vial seeds proposed: {len(seeds)} from {recon_path} -> {out}")
     return written
 
 
@@ -883,6 +949,22 @@ def parse_arguments(argv=None):
     p.add_argument("--phantom_seeds", default=None, metavar="FILE",
                    help="with --phantom_masks: JSON list of [x, y, z] voxel indices, one per vial; the vial labels are written "
                         "under recon_1mm_label/ (the reference's build_phantom_labels_v2)")
+    p.add_argument("--phantom_find_seeds", default=None, metavar="FILE.json",
+                   help="with --phantom_masks: propose the seeds.  The first echo's reconstruction is thresholded into "
+                        "--phantom_vial_window, eroded, split into connected components on the GPU, and the centroids of those "
+                        "with a size in --phantom_vial_size are written as the JSON --phantom_seeds reads (with several subjects: "
+                        "FILE_<sub>_<ses>.json).  Nothing is labelled from it in this run; check the order of the vials")
+    p.add_argument("--phantom_vial_window", default=None, metavar="LO,HI",
+                   help="with --phantom_find_seeds: the intensity window of the vials, both ends included (needed)")
+    p.add_argument("--phantom_vial_erode", type=int, default=None, metavar="R",
+                   help="with --phantom_find_seeds: radius of the ball that erodes the window's mask, 0..32 (default 2)")
+    p.add_argument("--phantom_vial_size", default=None, metavar="MIN,MAX",
+                   help="with --phantom_find_seeds: voxels of a vial after the erosion; MAX 0 is no upper limit (default 1,0)")
+    p.add_argument("--mask_keep_largest", type=int, default=0, metavar="K",
+                   help="keep the K largest connected components of every mask build_mask makes here (--register, "
+                        "--register_echoes, --n4 without a mask file); 0, the default, keeps the mask as it is")
+    p.add_argument("--mask_min_size", type=int, default=0, metavar="N",
+                   help="drop the connected components of fewer than N voxels from every such mask; 0, the default, drops none")
     p.add_argument("--atlas_labels", action="store_true",
                    help="after the reconstruction: register --atlas_template onto the first echo's recon_1mm volume masked by "
                         "recon_1mm_mask (affine, correlation ratio, on the GPU; stands for the reference's flirt call, parity "
@@ -1034,6 +1116,38 @@ def parse_arguments(argv=None):
             args.seeds = load_seeds(args.phantom_seeds)
         except (OSError, ValueError) as e:
             p.error(str(e))
+    vial_flags = [f for f, v in (("--phantom_vial_window", args.phantom_vial_window), ("--phantom_vial_erode", args.phantom_vial_erode),
+                                 ("--phantom_vial_size", args.phantom_vial_size)) if v is not None]
+    args.find_seeds = None
+    if args.phantom_find_seeds is not None:
+        if not args.phantom_masks:
+            p.error("--phantom_find_seeds has no effect without --phantom_masks")
+        if args.phantom_vial_window is None:
+            p.error("--phantom_find_seeds needs --phantom_vial_window LO,HI (the intensities of the vials)")
+        try:
+            lo, hi = (float(v) for v in args.phantom_vial_window.split(","))
+        except ValueError:
+            p.error(f"--phantom_vial_window {args.phantom_vial_window!r}: expected LO,HI")
+        if not lo <= hi:  # (also a NaN)
+            p.error("--phantom_vial_window: LO must not be above HI")
+        erode = 2 if args.phantom_vial_erode is None else args.phantom_vial_erode
+        if not 0 <= erode <= 32:
+            p.error("--phantom_vial_erode is in 0..32")
+        try:
+            smin, smax = (int(v) for v in (args.phantom_vial_size or "1,0").split(","))
+        except ValueError:
+            p.error(f"--phantom_vial_size {args.phantom_vial_size!r}: expected MIN,MAX")
+        if smin < 1 or smax < 0 or (smax and smax < smin):
+            p.error("--phantom_vial_size: MIN is at least 1 and MAX is 0 (no limit) or at least MIN")
+        args.find_seeds = {"window": (lo, hi), "erode": erode, "size": (smin, smax)}
+    elif vial_flags:
+        p.error(f"{vial_flags[0]} has no effect without --phantom_find_seeds")
+    if args.mask_keep_largest < 0 or args.mask_min_size < 0:
+        p.error("--mask_keep_largest and --mask_min_size must not be negative")
+    if (args.mask_keep_largest or args.mask_min_size) and not (args.register or args.register_echoes or args.n4):
+        p.error("--mask_keep_largest / --mask_min_size have no effect without --register, --register_echoes or --n4")
+    args.mask_clean = ({"keep_largest": args.mask_keep_largest, "min_size": args.mask_min_size}
+                       if args.mask_keep_largest or args.mask_min_size else None)
     if not (args.res > 0.0 and np.isfinite(args.res)):
         p.error("--res must be a positive number")
     if args.transforms is not None and not os.path.isdir(args.transforms):
@@ -1107,9 +1221,14 @@ def main(argv=None):
                   write_resamp=args.write_resamp, denoise=not args.no_denoise, register=args.register,
                   write_transforms=args.write_transforms, register_echoes=args.register_echoes, n4=args.n4_args,
                   write_n4=args.write_n4, register_metric=args.register_metric, sr=args.sr_args, unring=args.unring_args,
-                  write_unring=args.write_unring, device=args.device)
+                  write_unring=args.write_unring, mask_clean=args.mask_clean, device=args.device)
     if args.register_to_lf:
         process_register_to_lf(metadata, bids_path, write_transforms=args.write_transforms, device=args.device)
+    if args.find_seeds is not None:
+        try:
+            process_find_seeds(metadata, bids_path, args.phantom_find_seeds, fixed=args.fixed, device=args.device, **args.find_seeds)
+        except ValueError as e:
+            args.error(str(e))
     if args.phantom_masks:
         process_phantom_masks(metadata, bids_path, seeds=args.seeds, fixed=args.fixed, device=args.device)
     if args.atlas_labels:

@@ -35,6 +35,7 @@ registration           ``_gpu_sr``         code); here as ``register.register_sl
 tissue segmentation    ``_gpu_seg``        ``_seg`` (the steps, and the EM loop and class model, which are host code); here as ``seg``
 dictionary fit         ``_gpu_dict``       ``_dict`` (and the dictionary builders, which both share); here as ``dictionary``
 Gibbs-ringing removal  ``_gpu_unring``     ``_unring`` (and the tables, which both read); here as ``unring``
+connected components   ``_gpu_components`` ``_components``; here as ``components``
 N4 bias field          ``_gpu_bias``       ``_bias`` (and the sharpening table, the refinement and the loop, which are host code); here as ``bias``
 =====================  ==================  ===========================================================
 
@@ -62,6 +63,8 @@ from . import _gpu_dict as dictionary  # noqa: F401  (a namespace: dictionary.Di
 #                                         .fit_volume_dict)
 from . import _gpu_unring as unring  # noqa: F401  (a namespace: unring.unring_volume, .unring_slices, .unring_split, .unring_rows,
 #                                       .unring_tables)
+from . import _gpu_components as components  # noqa: F401  (a namespace: components.label, .stats, .lut, .select, .keep_largest,
+#                                               .remove_small, .seeds, .TILE)
 
 
 def __getattr__(name):

@@ -878,6 +878,64 @@ int t2fit_seed_labels_dev(const int32_t *seeds, const int32_t *labels, int n_see
  * allowed).  n_vox in 1..2^39-1.  Asynchronous on `stream`. */
 int t2fit_relabel_dev(const int32_t *in_dev, int64_t n_vox, const int32_t *lut_dev, int n_lut, int32_t *out_dev, void *stream);
 
+/* ---- Connected components: labels, sizes, boxes, centroid sums, selection tables -------------------------------------------
+ * No reference counterpart (the reference never asks which voxels belong together); the definition is
+ * scipy.ndimage.label's.  Additive to ABI 5: four new symbols (look them up to detect them).
+ * fetal_t2mapping_amd/_components.py states every result in numpy; all of it is integer arithmetic and the device
+ * results equal the statement in every element.
+ *
+ * A volume is (nz, ny, nx) with x fastest and fewer than 2^31 voxels; v = (z ny + y) nx + x is a voxel's linear index.
+ * Input T2FIT_MORPH_U8: foreground = not 0.  Input T2FIT_MORPH_I32: classes -- two voxels are connected only when they
+ * are neighbours AND hold the same value, which is not 0 (one labelling of a whole multi-class volume).  connectivity
+ * 1, 2, 3: the 6, 18, 26 neighbours that differ in at most that many coordinates (scipy's
+ * generate_binary_structure(3, connectivity)); a 2-D problem is a volume with nz = 1.  Labels: int32, 0 on the
+ * background, 1..n on the components, numbered in ascending order of each component's smallest linear index (scipy's
+ * numbering).
+ *
+ * The labelling is a lock-free union-find in which a parent is never larger than its child: tiles of
+ * T2FIT_COMPONENTS_TILE_Z x _Y x _X voxels are solved in LDS, the tile faces are merged with atomic minima, the trees
+ * are flattened and the roots ranked by a fixed prefix sum.  No wave waits for another and every loop is bounded, so
+ * the result does not depend on how the device schedules the work. */
+#define T2FIT_COMPONENTS_TILE_Z 4
+#define T2FIT_COMPONENTS_TILE_Y 8
+#define T2FIT_COMPONENTS_TILE_X 64
+
+/* Bytes of the workspace of t2fit_components_label_dev; plain arithmetic, no device.  With up(v) = v rounded up to 256:
+ *   256 [the count] + up(4 ceil(nz ny nx / 1024)) [roots per 1024 voxels]
+ * Refuses a size < 1 and a volume of 2^31 voxels or more. */
+int t2fit_components_workspace_bytes(int nz, int ny, int nx, size_t *bytes);
+
+/* in_dev (device uint8 or int32 [nz ny nx], in_type T2FIT_MORPH_U8 or T2FIT_MORPH_I32) -> labels_dev (device int32
+ * [nz ny nx], not the input; it serves as the parent array on the way).  Seven launches on `stream`, asynchronous.  The
+ * number of components n is left in the first int32 of the workspace; with n_out (HOST pointer, may be NULL) the call
+ * also waits for `stream` once and returns n there, through pinned memory.  Checked before HIP is touched
+ * (T2FIT_E_INVALID and a message): NULL in_dev / labels_dev / workspace_dev, an unknown in_type, a size < 1, 2^31 voxels
+ * or more, a connectivity outside 1..3, an int32 volume not aligned to 4 bytes, labels_dev == in_dev, a workspace that
+ * is too small or not aligned to 256 bytes. */
+int t2fit_components_label_dev(const void *in_dev, int in_type, int nz, int ny, int nx, int connectivity, int32_t *labels_dev,
+                               int32_t *n_out, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* Per value i = 0..n of an int32 label volume (other values are ignored; row 0 is the background), n + 1 rows each:
+ *   sizes_dev int64 [n + 1]       the number of voxels
+ *   bbox_dev  int32 [n + 1][6]    (z0, y0, x0, z1, y1, x1), inclusive; of a value that does not occur (nz, ny, nx, -1, -1, -1)
+ *   sums_dev  int64 [n + 1][3]    (sum of z, sum of y, sum of x): the centroid times the size
+ * Any of the three may be NULL.  Integers, hence exact in any order: one pass with 64-bit atomics; the lanes of a wave
+ * that hold the same value combine first.  Asynchronous on `stream`.  Refused before HIP is touched: NULL labels_dev, a
+ * size < 1, 2^31 voxels or more, n < 0, a misaligned pointer. */
+int t2fit_components_stats_dev(const int32_t *labels_dev, int nz, int ny, int nx, int n, int64_t *sizes_dev, int32_t *bbox_dev,
+                               int64_t *sums_dev, void *stream);
+
+/* The selection table lut_dev (device int32 [n + 1], lut[0] = 0) for t2fit_relabel_dev, from sizes_dev (device int64
+ * [n + 1], row 0 ignored).  Component i passes when min_size <= size[i] and (max_size == 0 or size[i] <= max_size).
+ * largest = 0: what passes is kept.  largest = 1: of what passes only the largest is kept, on a tie the lowest label (the sizes
+ * of t2fit_components_stats_dev lie in 0..2^31-1; `largest` compares a size outside 0..2^32-1 as clamped to that range).
+ * renumber = 0: a kept component maps to its own label; renumber = 1: to its rank (1..) among the kept.  What is not
+ * kept maps to 0.  *n_kept_out (HOST pointer, or NULL): the number kept; the call then waits for `stream` once.  The
+ * temporaries live in the library's per-stream scratch.  Refused before HIP is touched: NULL sizes_dev / lut_dev, n < 0,
+ * min_size < 0, max_size < 0, largest or renumber other than 0 / 1, a misaligned pointer. */
+int t2fit_components_lut_dev(const int64_t *sizes_dev, int n, int64_t min_size, int64_t max_size, int largest, int renumber,
+                             int32_t *lut_dev, int32_t *n_kept_out, void *stream);
+
 /* ---- Rigid registration: the correlation metric's sums and the pyramid levels -------------------------------------------
  * The device half of a rigid registration built from the ingredients of the reference's registration_itk
  * (utils/qmri_utils.py:167-221): correlation metric, fixed and moving masks, linear interpolator.  The metric's
