@@ -22,7 +22,8 @@ from .t2map import mppca  # MP-PCA denoising and noise maps across the echoes: m
 from ._gpu_mppca import denoise_mppca, mppca_noise_map  # the same two, by their own names
 from .t2map import seg  # atlas-prior EM tissue segmentation: seg.segment_em, seg.priors_from_labels (not in __all__, as t2map's own names are)
 from .t2map import dictionary  # the dictionary-matching fit: dictionary.Dictionary, .monoexp, .biexp, .match, .fit_volume_dict (not in __all__)
-from .t2map import components  # connected components: components.label, .stats, .select, .keep_largest, .remove_small, .seeds (not in __all__)
+from .t2map import components  # connected components: components.label, .stats, .select, .keep_largest, .remove_small, .reassign_small, .seeds (not in __all__)
+from .t2map import distance  # the exact Euclidean distance transform: distance.nearest, .edt, .fill_nearest, .dilate_mm, .erode_mm, .surface, .surface_distances (not in __all__)
 from .t2map import unring  # Gibbs-ringing removal: unring.unring_volume, .unring_slices, .unring_split, .unring_rows, .unring_tables (not in __all__)
 
 __all__ = ["BootMaps", "BootStats", "RoiStats", "T2Maps", "bootstrap_volume", "compute_residuals", "denoise_tv", "dense_labels",

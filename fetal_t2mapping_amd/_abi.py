@@ -64,6 +64,7 @@ SEG_MAX_CLASSES, SEG_MAX_CHANNELS, SEG_MAX_RADIUS = 8, 4, 32
 DICT_MAX_ATOMS = 65536
 UNRING_MIN_N, UNRING_MAX_N, UNRING_MAX_SHIFTS, UNRING_MAX_WINDOW = 8, 512, 32, 8
 COMPONENTS_TILE = (4, 8, 64)  # (z, y, x) voxels of the tile a workgroup labels in LDS
+EDT_MAX_AXIS = 2048  # voxels per axis of the distance transform
 
 
 class T2FitUnringParams(C.Structure):
@@ -183,6 +184,9 @@ SYMBOLS = [
                                              _P]),
     ("t2fit_components_stats_dev", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     ("t2fit_components_lut_dev", C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, C.POINTER(C.c_int32), _P]),
+    ("t2fit_edt_workspace_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    ("t2fit_edt_dev", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _P, _P, _P, C.c_size_t, _P]),
+    ("t2fit_edt_fill_dev", C.c_int, [_P, _P, _P, C.c_int64, _P, _P]),
     ("t2fit_register_workspace_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     ("t2fit_register_sums_dev", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
                                           C.POINTER(C.c_double), _P, _P, C.c_size_t, _P]),
@@ -272,9 +276,10 @@ UNRING_SYMBOLS = ("t2fit_unring_params_default", "t2fit_unring_tables_bytes", "t
                   "t2fit_unring_split_dev", "t2fit_unring_rows_dev", "t2fit_unring_dev")
 COMPONENT_SYMBOLS = ("t2fit_components_workspace_bytes", "t2fit_components_label_dev", "t2fit_components_stats_dev",
                      "t2fit_components_lut_dev")
+EDT_SYMBOLS = ("t2fit_edt_workspace_bytes", "t2fit_edt_dev", "t2fit_edt_fill_dev")
 LOOKED_UP = (ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS + MI_SYMBOLS + SR_SYMBOLS + SR_SLICE_SYMBOLS + SVR_SYMBOLS
              + SR_ROBUST_SYMBOLS + TVJ_SYMBOLS + MPPCA_SYMBOLS + SEG_SYMBOLS + FFD_SYMBOLS + DICT_SYMBOLS + UNRING_SYMBOLS
-             + COMPONENT_SYMBOLS)
+             + COMPONENT_SYMBOLS + EDT_SYMBOLS)
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

@@ -184,3 +184,33 @@ def seeds(mask, connectivity=1, min_size=1, max_size=0, *, device=0):
     table, kept = lut(sizes, min_size=min_size, max_size=max_size, renumber=True, device=device)
     sizes, _, sums = _tables(_relabel(lab, table), kept, ("sizes", "sums"))
     return [[int(v) for v in row] for row in _components.centroids(sizes.cpu().numpy(), sums.cpu().numpy())]
+
+
+def reassign_small(classes, min_size, connectivity=1, spacing=None, *, device=0):
+    """``(classes, n_changed)``: every island of fewer than ``min_size`` voxels takes, voxel by voxel, the class at its
+    nearest site -- the sites being the voxels that are not 0 and not in a small island -- instead of leaving a hole as
+    :func:`remove_small` does (:func:`_edt.reassign_small`).  ``classes``: an integer volume (bool: a mask); ``spacing``:
+    ``(sz, sy, sx)`` of the distance, default 1.  Class 0 stays 0; one round; with no site nothing changes.  A speck
+    surrounded by class 0 takes a class but stays a speck: that is :func:`remove_small`'s job.  int32 CUDA tensor and the
+    number of voxels changed (the call waits for the stream for the counts)."""
+    import torch
+
+    from . import _gpu_edt
+
+    if int(min_size) < 0:
+        raise ValueError("min_size must not be negative")
+    dev = pick_device((classes,), device)
+    if is_tensor(classes) and classes.dtype == torch.uint8:
+        classes = classes.to(torch.int32)
+    elif not is_tensor(classes) and np.asarray(classes).dtype == np.uint8:
+        classes = np.asarray(classes).astype(np.int32)
+    t, _ = _input(classes, dev)
+    t = t.to(torch.int32)
+    lab, n = label(t, connectivity, device=device)
+    sizes = _tables(lab, n, ("sizes",))[0]
+    table, _ = lut(sizes, min_size=int(min_size), device=device)
+    kept = _relabel(lab, table) != 0
+    small = (lab != 0) & ~kept
+    index = _gpu_edt._nearest(kept, 0, spacing, dev, want_d2=False)[1]
+    out = _gpu_edt.fill_nearest(t, small, index, device=device)
+    return out, int((out != t).sum())

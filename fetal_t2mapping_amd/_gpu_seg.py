@@ -194,12 +194,14 @@ DEVICE_STEPS = _seg.SegSteps(effective_mask, normalise_priors, functools.partial
 
 
 def segment_em(y, mask, prior, classes, *, beta=0.5, prior_floor=1e-3, var_floor=1e-6, n_iter=15, tol=0.0, return_posteriors=False,
-               device=0):
+               min_island=0, device=0):
     """EM tissue segmentation on the GPU: ``_seg.segment_em``'s loop (``_seg.run_em``) with the device steps, the volumes
     staying on the device between them.  ``y``: float32 ``(C, Z, Y, X)`` (or one ``(Z, Y, X)`` volume), 1 .. 4 channels;
     ``prior``: ``(K, Z, Y, X)`` from :func:`priors_from_labels`; ``classes``: the K label values; numpy arrays (numpy results)
     or CUDA tensors (tensor results).  Each iteration synchronises once: the class model is host arithmetic on the K x 15
-    sums.  Returns a ``_seg.SegResult``.  The defaults come from a sweep on one synthetic phantom."""
+    sums.  Returns a ``_seg.SegResult``.  The defaults come from a sweep on one synthetic phantom.
+    ``min_island`` > 0: the islands of the hard labels with fewer voxels take the class of their surroundings
+    (``components.reassign_small``) and ``n_reassigned`` counts the voxels changed; 0 runs nothing new."""
     import torch
 
     require(*_abi.SEG_SYMBOLS)
@@ -210,11 +212,16 @@ def segment_em(y, mask, prior, classes, *, beta=0.5, prior_floor=1e-3, var_floor
     if tuple(prior.shape) != (len(classes), nz, ny, nx):
         raise ValueError(f"segment_em needs prior as (K, Z, Y, X) on y's grid, got {tuple(prior.shape)} for y {tuple(y.shape)}")
     _seg.check_em_arguments(len(classes), Cn, beta, prior_floor, var_floor, n_iter, tol)
+    min_island = _seg.check_min_island(min_island)
     dev = pick_device((y, prior, mask), device)
     with torch.cuda.device(dev):
         yd = flat(y, dev).reshape(Cn, nz, ny, nx)
         M = effective_mask(yd, mask)
         pi = normalise_priors(flat(prior, dev).reshape(len(classes), nz, ny, nx), M, prior_floor)
         p, model, trace, it = _seg.run_em(pi, yd, M, Cn, DEVICE_STEPS, beta=beta, var_floor=var_floor, n_iter=n_iter, tol=tol)
-        labels = hard_labels(p, classes, M)
-    return _seg.SegResult(_host(labels, y), model, trace, it, _host(p, y) if return_posteriors else None)
+        labels, changed = hard_labels(p, classes, M), 0
+        if min_island:
+            from ._gpu_components import reassign_small
+
+            labels, changed = reassign_small(labels, min_island, device=dev.index)
+    return _seg.SegResult(_host(labels, y), model, trace, it, _host(p, y) if return_posteriors else None, changed)

@@ -28,7 +28,7 @@ VOX_PER_BLOCK = VOX_PER_LANE * LANES
 
 SegSteps = namedtuple("SegSteps", "effective_mask normalise_priors moment_sums e_step hard_labels")
 SegModel = namedtuple("SegModel", "mean cov precision logc dead")
-SegResult = namedtuple("SegResult", "labels model s0_trace n_iter posteriors")
+SegResult = namedtuple("SegResult", "labels model s0_trace n_iter posteriors n_reassigned", defaults=(0,))
 
 
 def n_moments(n_chan):
@@ -327,11 +327,13 @@ def run_em(pi, y, M, n_chan, steps, *, beta, var_floor, n_iter, tol):
 
 
 def segment_em(y, mask, prior, classes, *, beta=0.5, prior_floor=1e-3, var_floor=1e-6, n_iter=15, tol=0.0, steps=None,
-               return_posteriors=False):
+               return_posteriors=False, min_island=0):
     """Segment ``y`` ``(C, Z, Y, X)`` inside ``mask`` into the ``classes`` from spatial priors ``prior`` ``(K, Z, Y, X)``
     (:func:`priors_from_labels`) by expectation-maximisation.  Returns a :class:`SegResult`: int32 labels (0 outside ``M``),
     the last model (:class:`SegModel`: means, covariances, precisions, dead flags), the ``S0`` of every iteration, the
-    number of iterations run and, with ``return_posteriors``, the posteriors."""
+    number of iterations run and, with ``return_posteriors``, the posteriors.  ``min_island`` > 0: the islands of the hard
+    labels with fewer voxels take the class of their surroundings (``_edt.reassign_small``, 6 neighbours, unit spacing)
+    and ``n_reassigned`` counts the voxels changed; the posteriors are not touched."""
     steps = NUMPY_STEPS if steps is None else steps
     y = np.asarray(y, np.float32)
     if y.ndim == 3:
@@ -344,10 +346,22 @@ def segment_em(y, mask, prior, classes, *, beta=0.5, prior_floor=1e-3, var_floor
     M = steps.effective_mask(y, mask)
     pi = steps.normalise_priors(prior, M, prior_floor)
     p, model, trace, it = run_em(pi, y, M, y.shape[0], steps, beta=beta, var_floor=var_floor, n_iter=n_iter, tol=tol)
-    return SegResult(steps.hard_labels(p, classes, M), model, trace, it, p if return_posteriors else None)
+    labels, changed = steps.hard_labels(p, classes, M), 0
+    if check_min_island(min_island):
+        from . import _edt
+
+        labels, changed = _edt.reassign_small(np.asarray(labels), min_island)
+    return SegResult(labels, model, trace, it, p if return_posteriors else None, changed)
 
 
-TISSUE_KEYS = ("labels", "classes", "channels", "sigma", "beta", "prior_floor", "var_floor", "n_iter", "tol")
+def check_min_island(min_island):
+    """``min_island`` as an int >= 0 (0: off)."""
+    if isinstance(min_island, bool) or int(min_island) != min_island or int(min_island) < 0:
+        raise ValueError(f"min_island must be an integer >= 0, got {min_island!r}")
+    return int(min_island)
+
+
+TISSUE_KEYS = ("labels", "classes", "channels", "sigma", "beta", "prior_floor", "var_floor", "n_iter", "tol", "min_island")
 
 
 def tissue_arguments(tissue, template_shape, subject_shape):
@@ -378,7 +392,7 @@ def tissue_arguments(tissue, template_shape, subject_shape):
 def tissue_result(propagated, prior, res):
     """The fourth value of ``atlas_labels(tissue=...)``."""
     return {"labels": res.labels, "propagated": propagated, "prior": prior, "model": res.model, "s0_trace": res.s0_trace,
-            "n_iter": res.n_iter}
+            "n_iter": res.n_iter, "n_reassigned": res.n_reassigned}
 
 
 def dice(a, b, classes):

@@ -715,7 +715,7 @@ def process_atlas_labels(metadata, bids_path, template_path, atlas_specs, *, fix
                     raise ValueError(f"--tissue_echoes: the echoes of {sub}_{ses} do not share a grid")
                 channels.append(ch)
             more["tissue"] = {"labels": tissue_labels, "classes": tissue["classes"], "channels": np.stack(channels),
-                              **{k: tissue[k] for k in ("sigma", "beta", "n_iter") if tissue.get(k) is not None}}
+                              **{k: tissue[k] for k in ("sigma", "beta", "n_iter", "min_island") if tissue.get(k) is not None}}
         warped, labels, found, *refined = t2map.atlas.atlas_labels(subject, img, template, template_img, atlases, mask=mask, dof=dof,
                                                              bins=bins, device=device, **more)
         write(t2map.atlas.extract_brain(subject, mask), img, get_img_path(bids_path, acq, atlas_bet_dirname).replace(" ", ""))
@@ -1002,6 +1002,9 @@ def parse_arguments(argv=None):
     p.add_argument("--tissue_sigma", type=float, default=None, help="with --tissue_atlas: blur of the priors in voxels (default 2)")
     p.add_argument("--tissue_beta", type=float, default=None, help="with --tissue_atlas: weight of the Potts term (default 0.5)")
     p.add_argument("--tissue_iter", type=int, default=None, help="with --tissue_atlas: EM iterations (default 15)")
+    p.add_argument("--tissue_min_island", type=int, default=None, metavar="N",
+                   help="with --tissue_atlas: islands of the tissue labels with fewer than N voxels take the class of their "
+                        "surroundings (the class at the nearest voxel of a larger region; default 0: off)")
     p.add_argument("--write_tissue_prior", action="store_true",
                    help="with --tissue_atlas: also write the propagated, unrefined labels under recon_1mm_feta_prior")
     p.add_argument("--n4", action="store_true",
@@ -1052,7 +1055,8 @@ def parse_arguments(argv=None):
         p.error("--atlas_template / --atlas have no effect without --atlas_labels")
     tissue_flags = [f for f, v in (("--tissue_classes", args.tissue_classes), ("--tissue_echoes", args.tissue_echoes),
                                    ("--tissue_sigma", args.tissue_sigma), ("--tissue_beta", args.tissue_beta),
-                                   ("--tissue_iter", args.tissue_iter), ("--write_tissue_prior", args.write_tissue_prior or None))
+                                   ("--tissue_iter", args.tissue_iter), ("--tissue_min_island", args.tissue_min_island),
+                                   ("--write_tissue_prior", args.write_tissue_prior or None))
                     if v is not None]
     args.tissue_args = None
     args.nonrigid_args = None
@@ -1101,8 +1105,12 @@ def parse_arguments(argv=None):
             p.error("--tissue_beta must be a number >= 0")
         if args.tissue_iter is not None and args.tissue_iter < 1:
             p.error("--tissue_iter must be >= 1")
+        if args.tissue_min_island is not None and args.tissue_min_island < 0:
+            p.error("--tissue_min_island must be >= 0")
         args.tissue_args = {"path": args.tissue_atlas, "classes": classes, "echoes": args.tissue_echoes, "sigma": args.tissue_sigma,
                             "beta": args.tissue_beta, "n_iter": args.tissue_iter, "write_prior": args.write_tissue_prior}
+        if args.tissue_min_island:  # (the key is there only when the flag asks for something)
+            args.tissue_args["min_island"] = args.tissue_min_island
     elif tissue_flags:
         p.error(f"{tissue_flags[0]} has no effect without --tissue_atlas")
     args.error = p.error

@@ -36,6 +36,7 @@ tissue segmentation    ``_gpu_seg``        ``_seg`` (the steps, and the EM loop 
 dictionary fit         ``_gpu_dict``       ``_dict`` (and the dictionary builders, which both share); here as ``dictionary``
 Gibbs-ringing removal  ``_gpu_unring``     ``_unring`` (and the tables, which both read); here as ``unring``
 connected components   ``_gpu_components`` ``_components``; here as ``components``
+distance transform     ``_gpu_edt``        ``_edt`` (and the surface measures' reductions, which are host code); here as ``distance``
 N4 bias field          ``_gpu_bias``       ``_bias`` (and the sharpening table, the refinement and the loop, which are host code); here as ``bias``
 =====================  ==================  ===========================================================
 
@@ -64,7 +65,9 @@ from . import _gpu_dict as dictionary  # noqa: F401  (a namespace: dictionary.Di
 from . import _gpu_unring as unring  # noqa: F401  (a namespace: unring.unring_volume, .unring_slices, .unring_split, .unring_rows,
 #                                       .unring_tables)
 from . import _gpu_components as components  # noqa: F401  (a namespace: components.label, .stats, .lut, .select, .keep_largest,
-#                                               .remove_small, .seeds, .TILE)
+#                                               .remove_small, .reassign_small, .seeds, .TILE)
+from . import _gpu_edt as distance  # noqa: F401  (a namespace: distance.nearest, .edt, .fill_nearest, .dilate_mm, .erode_mm, .surface,
+#                                      .surface_distances)
 
 
 def __getattr__(name):

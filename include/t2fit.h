@@ -936,6 +936,44 @@ int t2fit_components_stats_dev(const int32_t *labels_dev, int nz, int ny, int nx
 int t2fit_components_lut_dev(const int64_t *sizes_dev, int n, int64_t min_size, int64_t max_size, int largest, int renumber,
                              int32_t *lut_dev, int32_t *n_kept_out, void *stream);
 
+/* ---- Exact Euclidean distance transform: squared distances and nearest sites -----------------------------------------------
+ * No reference counterpart; the distances are scipy.ndimage.distance_transform_edt's.  Additive to ABI 5: three new
+ * symbols (look them up to detect them).  fetal_t2mapping_amd/_edt.py states every result in numpy and the device
+ * results equal the statement in every bit of d2 (inf included) and every index.
+ *
+ * A volume is (nz, ny, nx) with x fastest, each axis in 1..T2FIT_EDT_MAX_AXIS and fewer than 2^31 voxels;
+ * v = (z ny + y) nx + x is a voxel's linear index.  The sites are the voxels equal to 0 (invert = 1, scipy's convention
+ * for a mask) or not equal to 0 (invert = 0).  spacing = (sz, sy, sx).  The definition is three passes in the order z, y, x:
+ *   start:   g = 0.0 at a site, +inf elsewhere; key = the site's linear index, -1 elsewhere
+ *   pass a:  g'[i] = min over j along axis a of g[j] + t t, t = (double)(i - j) s_a (a multiply, a square, an add);
+ *            key'[i] = key[j] of the minimising j, among equal values the LOWEST key; a j with key -1 never wins
+ * so d2 = ((dz sz)^2 + (dy sy)^2) + (dx sx)^2 of the nearest site, exact for unit and dyadic spacing, and index is the
+ * lowest linear index among the nearest sites where the arithmetic is exact.  With no site: d2 = +inf, index = -1.
+ * (Spacings whose squares overflow or underflow a double are outside this guarantee.) */
+#define T2FIT_EDT_MAX_AXIS 2048
+
+/* Bytes of the workspace of t2fit_edt_dev; plain arithmetic, no device.  With up(v) = v rounded up to 256 and
+ * n = nz ny nx:   2 up(8 n) [g of two passes] + 2 up(4 n) [their keys]
+ * Refuses an axis outside 1..T2FIT_EDT_MAX_AXIS and a volume of 2^31 voxels or more. */
+int t2fit_edt_workspace_bytes(int nz, int ny, int nx, size_t *bytes);
+
+/* vol_dev (device uint8 [nz ny nx]) -> d2_dev (device double [nz ny nx], may be NULL) and index_dev (device int32
+ * [nz ny nx], may be NULL; not both).  spacing: HOST pointer to 3 doubles, NULL = 1.  Three launches on `stream`,
+ * asynchronous: the z pass sweeps each column twice, the y pass scans outward through L2, the x pass scans outward over
+ * rows staged in LDS; the work of a scan is proportional to the distance found.  Refused before HIP is touched
+ * (T2FIT_E_INVALID and a message, nothing launched): NULL vol_dev, both outputs NULL, invert not 0 / 1, an axis out of
+ * range, 2^31 voxels or more, a spacing that is not finite or <= 0, a misaligned d2_dev / index_dev, a NULL, misaligned
+ * (256 bytes) or too small workspace. */
+int t2fit_edt_dev(const uint8_t *vol_dev, int invert, int nz, int ny, int nx, const double *spacing, double *d2_dev, int32_t *index_dev,
+                  void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* out[v] = labels[index[v]] where where[v] != 0 and 0 <= index[v] < n, else labels[v] (v in 0..n-1; an index outside
+ * the volume counts as no site).  All device pointers; out_dev must not be labels_dev.  n in 1..2^31-1.  One launch,
+ * asynchronous.  Refused before HIP is touched: a NULL pointer, n out of range, an int32 buffer not aligned to 4 bytes,
+ * out_dev == labels_dev. */
+int t2fit_edt_fill_dev(const int32_t *labels_dev, const uint8_t *where_dev, const int32_t *index_dev, int64_t n, int32_t *out_dev,
+                       void *stream);
+
 /* ---- Rigid registration: the correlation metric's sums and the pyramid levels -------------------------------------------
  * The device half of a rigid registration built from the ingredients of the reference's registration_itk
  * (utils/qmri_utils.py:167-221): correlation metric, fixed and moving masks, linear interpolator.  The metric's
