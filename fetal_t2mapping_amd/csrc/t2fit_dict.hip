@@ -30,6 +30,7 @@ namespace {
 using t2fit::align_up;
 using t2fit::ceil_div;
 using t2fit::fail;
+using t2fit::misaligned;
 
 constexpr uint32_t kMagic = 0x54443254u;
 constexpr int kTile = 32;           // atoms of a tile: the rows of one matrix instruction
@@ -329,7 +330,6 @@ int t2fit_dict_match_dev(const float* y_dev, int n_te, int64_t n_vox, const uint
   if (n_te < 2 || n_te > T2FIT_MAX_TE)
     return fail(T2FIT_E_INVALID, "t2fit_dict_match_dev: n_te must be 2 .. " + std::to_string(T2FIT_MAX_TE) + ", got " + std::to_string(n_te));
   if (n_vox < 0) return fail(T2FIT_E_INVALID, "t2fit_dict_match_dev: n_vox is negative");
-  auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
   if (misaligned(y_dev, 4) || misaligned(index_dev, 4) || misaligned(scale_dev, 4) || misaligned(rmse_dev, 4))
     return fail(T2FIT_E_INVALID, "t2fit_dict_match_dev: y_dev, index_dev, scale_dev and rmse_dev must be aligned to 4 bytes");
   if (misaligned(packed_dev, 16)) return fail(T2FIT_E_INVALID, "t2fit_dict_match_dev: packed_dev must be aligned to 16 bytes");

@@ -18,9 +18,12 @@
 //                       weights, no indexed register array, no scratch), then 3 C xor butterflies.  A node outside the
 //                       voxel's four gets +0.0, selected after the product, so nothing non-finite crosses a support.
 //   ffd_y_kernel, ffd_z_kernel   the y and z contractions in index order from +0.0, a thread per output.
-//   ffd_warp_kernel     the sample of t2fit_resample.hip (linear with the zero-weight skip, or nearest) at c(x).
+//   ffd_warp_kernel     the resampling sample of t2fit_affine.h (linear with the zero-weight skip, or nearest) at c(x).
 //   ffd_jac_kernel      det(I + dd/dx) from the derivative weights, per row the minimum over the mask and the count of
 //                       det <= 0; ffd_jac_final_kernel reduces the rows (minimum and count: exact in any order).
+// What the affine stages compute at A (x, 1) is computed here at c(x) by the same functions, so a zero lattice gives their
+// bytes: the metric's sample and the resampling sample (t2fit_affine.h), the Parzen window, the bin and the histogram
+// deposit (t2fit_mattes.h).  The node and weights of a voxel index and the selected tap are t2fit_n4.hip's (t2fit_bspline.h).
 // No floating-point atomics; the order of every floating-point addition is a function of the sizes alone.  Compiled with
 // -ffp-contract=off: every multiply and add rounds once, as numpy's do.
 #include <hip/hip_runtime.h>
@@ -30,13 +33,17 @@
 #include <string>
 
 #include "t2fit_affine.h"
+#include "t2fit_bspline.h"
 #include "t2fit_error.h"
+#include "t2fit_mattes.h"
 #include "t2fit_support.h"
 
 namespace {
 
-using t2fit::align_up, t2fit::ceil_div, t2fit::kBlock;
-using t2fit::Affine, t2fit::Dims, t2fit::inside_axis, t2fit::clamp_index;
+using t2fit::align_up, t2fit::ceil_div, t2fit::kBlock, t2fit::misaligned;
+using t2fit::Affine, t2fit::Dims, t2fit::MemFetch, t2fit::sample_metric, t2fit::sample_linear, t2fit::sample_nearest;
+using t2fit::bspline_node, t2fit::bspline_weights, t2fit::select_tap;
+using t2fit::bin_of, t2fit::parzen, t2fit::deposit, t2fit::zero_u64_kernel, t2fit::wave_butterfly;
 
 constexpr int kWaves = kBlock / 64;  // rows a workgroup takes
 constexpr size_t kAlign = 256;
@@ -60,37 +67,18 @@ struct Lat {
   int n_tiles;        // nz * tiles_y
 };
 
-__device__ inline double wave_butterfly(double v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_xor(v, s, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(kBlock) void ffd_axis_kernel(int nz, int ny, int nx, int side, int* __restrict__ k_out, double* __restrict__ w_out) {
   const int v = blockIdx.x * kBlock + threadIdx.x;
   if (v >= nz + ny + nx) return;
   const int n = v < nz ? nz : (v < nz + ny ? ny : nx);
   const int i = v < nz ? v : (v < nz + ny ? v - nz : v - nz - ny);
-  const int s = side - 3;
-  double kf = 0.0, tau = 0.0, scale = 0.0;
-  if (n > 1) {
-    scale = (double)s / (double)(n - 1);
-    if (i == n - 1) {
-      kf = (double)(s - 1), tau = 1.0;
-    } else {
-      const double p = ((double)i * (double)s) / (double)(n - 1);
-      kf = floor(p);
-      tau = p - kf;
-      kf = kf > (double)(s - 1) ? (double)(s - 1) : kf;  // (never taken: p < s; keeps k + 3 inside the lattice whatever)
-    }
-  }
-  const double t2 = tau * tau, t3 = t2 * tau, om = 1.0 - tau;
+  double kf, tau, scale = 0.0;  // scale: cells per voxel, d tau / d index
+  if (n > 1) scale = (double)(side - 3) / (double)(n - 1);
+  bspline_node(i, n, side, kf, tau);
+  const double t2 = tau * tau, om = 1.0 - tau;
   k_out[v] = (int)kf;
   double* w = w_out + (int64_t)v * kTab;
-  w[0] = ((om * om) * om) / 6.0;
-  w[1] = ((3.0 * t3 - 6.0 * t2) + 4.0) / 6.0;
-  w[2] = (((-3.0 * t3 + 3.0 * t2) + 3.0 * tau) + 1.0) / 6.0;
-  w[3] = t3 / 6.0;
+  bspline_weights(tau, w);
   w[4] = (-((om * om) * 0.5)) * scale;
   w[5] = (1.5 * t2 - 2.0 * tau) * scale;
   w[6] = ((-1.5 * t2 + tau) + 0.5) * scale;
@@ -134,68 +122,6 @@ __device__ inline void deformed(const Lat& L, const Affine& A, const double (*t2
   for (int a = 0; a < 3; ++a) c[a] = ((A.m[4 * a] * px + A.m[4 * a + 1] * py) + A.m[4 * a + 2] * pz) + A.m[4 * a + 3];
 }
 
-// ---- the metric's sample: t2fit_register.hip's, at a coordinate the caller made --------------------------------------------
-__device__ inline double lerp_metric(double p, double q, double w) { return w == 0.0 ? p : p + w * (q - p); }
-
-template <bool kGrad>
-__device__ inline bool sample_metric(const float* moving, const uint8_t* moving_mask, const Dims n, const double* c, double& m, double* g) {
-  const double cx = c[0], cy = c[1], cz = c[2];
-  if (!(inside_axis(cx, n.nx) && inside_axis(cy, n.ny) && inside_axis(cz, n.nz))) return false;
-  const int qx = clamp_index(floor(cx + 0.5), n.nx), qy = clamp_index(floor(cy + 0.5), n.ny), qz = clamp_index(floor(cz + 0.5), n.nz);
-  if (moving_mask[((int64_t)qz * n.ny + qy) * n.nx + qx] == 0) return false;
-  const int x0 = clamp_index(floor(cx), n.nx), y0 = clamp_index(floor(cy), n.ny), z0 = clamp_index(floor(cz), n.nz);
-  double dx = cx - (double)x0, dy = cy - (double)y0, dz = cz - (double)z0;
-  dx = dx < 0.0 ? 0.0 : dx;
-  dy = dy < 0.0 ? 0.0 : dy;
-  dz = dz < 0.0 ? 0.0 : dz;
-  const int x1 = x0 + 1 < n.nx ? x0 + 1 : n.nx - 1, y1 = y0 + 1 < n.ny ? y0 + 1 : n.ny - 1, z1 = z0 + 1 < n.nz ? z0 + 1 : n.nz - 1;
-  const float* r00 = moving + ((int64_t)z0 * n.ny + y0) * n.nx;
-  const float* r01 = moving + ((int64_t)z0 * n.ny + y1) * n.nx;
-  const float* r10 = moving + ((int64_t)z1 * n.ny + y0) * n.nx;
-  const float* r11 = moving + ((int64_t)z1 * n.ny + y1) * n.nx;
-  const double v000 = r00[x0], v001 = r00[x1], v010 = r01[x0], v011 = r01[x1];
-  const double v100 = r10[x0], v101 = r10[x1], v110 = r11[x0], v111 = r11[x1];
-  const double l00 = lerp_metric(v000, v001, dx), l01 = lerp_metric(v010, v011, dx), l10 = lerp_metric(v100, v101, dx),
-               l11 = lerp_metric(v110, v111, dx);
-  const double p0 = lerp_metric(l00, l01, dy), p1 = lerp_metric(l10, l11, dy);
-  m = lerp_metric(p0, p1, dz);
-  if (!kGrad) return true;
-  g[0] = lerp_metric(lerp_metric(v001 - v000, v011 - v010, dy), lerp_metric(v101 - v100, v111 - v110, dy), dz);
-  g[1] = lerp_metric(l01 - l00, l11 - l10, dz);
-  g[2] = p1 - p0;
-  if (x1 == x0 || cx < 0.0) g[0] = 0.0;
-  if (y1 == y0 || cy < 0.0) g[1] = 0.0;
-  if (z1 == z0 || cz < 0.0) g[2] = 0.0;
-  return true;
-}
-
-// the cubic B-spline Parzen window of t2fit_register.hip: i0 and the four weights (<false>) or their derivatives (<true>)
-template <bool kDeriv>
-__device__ inline int parzen(double m, double lo, double scale, int n_m, double* w) {
-  double t = (m - lo) * scale + 2.0;
-  const double top = (double)(n_m - 2), last = (double)(n_m - 3);
-  t = t >= 2.0 ? t : 2.0;
-  t = t <= top ? t : top;
-  double base = floor(t);
-  base = base < last ? base : last;
-  const double u = t - base, v = 1.0 - u, u2 = u * u, v2 = v * v;
-  if (kDeriv) {
-    w[0] = -(v2 * 0.5);
-    w[1] = 1.5 * u2 - 2.0 * u;
-    w[2] = (-1.5 * u2 + u) + 0.5;
-    w[3] = u2 * 0.5;
-  } else {
-    const double u3 = u2 * u, v3 = v2 * v;
-    w[0] = v3 / 6.0;
-    w[1] = ((3.0 * u3 - 6.0 * u2) + 4.0) / 6.0;
-    w[2] = (((-3.0 * u3 + 3.0 * u2) + 3.0 * u) + 1.0) / 6.0;
-    w[3] = u3 / 6.0;
-  }
-  return (int)base;
-}
-
-__device__ inline int bin_of(uint8_t b, int n_bins) { return (int)b < n_bins ? (int)b : n_bins - 1; }
-
 struct MetricArgs {
   Lat L;
   const uint8_t* bins;
@@ -210,11 +136,6 @@ struct MetricArgs {
   Affine A;
   double* xs;                // the gradient: [rows][3][C]
 };
-
-__global__ __launch_bounds__(kBlock) void ffd_zero_hist_kernel(unsigned long long* __restrict__ hist, int n) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i < n) hist[i] = 0ull;
-}
 
 __global__ __launch_bounds__(kBlock) void ffd_hist_kernel(const MetricArgs a) {
   __shared__ double t1[3 * kMaxSide * kMaxSide];
@@ -240,14 +161,10 @@ __global__ __launch_bounds__(kBlock) void ffd_hist_kernel(const MetricArgs a) {
       if (a.fixed_mask[at] == 0) continue;
       double c[3], m, w[4];
       deformed(a.L, a.A, t2[wave], x, y, z, c);
-      if (!sample_metric<false>(a.moving, a.moving_mask, a.m, c, m, nullptr)) continue;
+      if (!sample_metric<false>(a.moving, a.moving_mask, a.m, c[0], c[1], c[2], m, nullptr)) continue;
       const int i0 = parzen<false>(m, a.lo_m, a.scale_m, a.n_m, w);
       unsigned long long* hrow = ffd_hist + bin_of(a.bins[at], a.n_f) * a.n_m + (i0 - 1);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const unsigned long long q = (unsigned long long)floor(w[j] * 1073741824.0 + 0.5);
-        if (q != 0ull) atomicAdd(&hrow[j], q);
-      }
+      deposit(hrow, w);
     }
   }
   __syncthreads();
@@ -284,7 +201,7 @@ __global__ __launch_bounds__(kBlock) void ffd_rows_kernel(const MetricArgs a) {
     if (a.fixed_mask[at] == 0) continue;  // the term is +0.0
     double cc[3], m, g[3], dw[4];
     deformed(a.L, a.A, t2[wave], x, y, z, cc);
-    if (!sample_metric<true>(a.moving, a.moving_mask, a.m, cc, m, g)) continue;
+    if (!sample_metric<true>(a.moving, a.moving_mask, a.m, cc[0], cc[1], cc[2], m, g)) continue;
     const int i0 = parzen<true>(m, a.lo_m, a.scale_m, a.n_m, dw);
     const double* trow = ffd_table + bin_of(a.bins[at], a.n_f) * a.n_m + (i0 - 1);
     double s = 0.0;
@@ -300,11 +217,7 @@ __global__ __launch_bounds__(kBlock) void ffd_rows_kernel(const MetricArgs a) {
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       const int d = c - k;
-      double wc = 0.0;
-      wc = d == 0 ? w0 : wc;
-      wc = d == 1 ? w1 : wc;
-      wc = d == 2 ? w2 : wc;
-      wc = d == 3 ? w3 : wc;
+      const double wc = select_tap(d, w0, w1, w2, w3);
       const bool in = (unsigned)d < 4u;
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
@@ -352,51 +265,12 @@ __global__ __launch_bounds__(kBlock) void ffd_z_kernel(const double* __restrict_
   out[v] = acc;
 }
 
-// ---- the warp: t2fit_resample.hip's sample at c(x) -------------------------------------------------------------------------
-__device__ inline double lerp_resample(double lo, double hi, double w) {
-  const double r = lo + w * (hi - lo);
-  return __builtin_expect(r != r, 0) ? lo + hi : r;
-}
-
-__device__ inline float warp_linear(const float* v, const Dims n, const double* c, float default_value) {
-  const double cx = c[0], cy = c[1], cz = c[2];
-  if (!(inside_axis(cx, n.nx) && inside_axis(cy, n.ny) && inside_axis(cz, n.nz))) return default_value;
-  const int x0 = clamp_index(floor(cx), n.nx), y0 = clamp_index(floor(cy), n.ny), z0 = clamp_index(floor(cz), n.nz);
-  double dx = cx - (double)x0, dy = cy - (double)y0, dz = cz - (double)z0;
-  dx = dx < 0.0 ? 0.0 : dx;
-  dy = dy < 0.0 ? 0.0 : dy;
-  dz = dz < 0.0 ? 0.0 : dz;
-  const int x1 = x0 + 1 < n.nx ? x0 + 1 : n.nx - 1, y1 = y0 + 1 < n.ny ? y0 + 1 : n.ny - 1, z1 = z0 + 1 < n.nz ? z0 + 1 : n.nz - 1;
-  auto fetch = [&](int x, int y, int z) { return (double)v[((int64_t)z * n.ny + y) * n.nx + x]; };
-  auto row = [&](int z, int y) {
-    double r = fetch(x0, y, z);
-    if (dx != 0.0) {
-      const double hi = fetch(x1, y, z);
-      r = lerp_resample(r, hi, dx);
-    }
-    return r;
-  };
-  auto plane = [&](int z) {
-    double r = row(z, y0);
-    if (dy != 0.0) {
-      const double hi = row(z, y1);
-      r = lerp_resample(r, hi, dy);
-    }
-    return r;
-  };
-  double r = plane(z0);
-  if (dz != 0.0) {
-    const double hi = plane(z1);
-    r = lerp_resample(r, hi, dz);
-  }
+// ---- the warp: t2fit_affine.h's resampling sample at c(x) -------------------------------------------------------------
+// the linear sample as a float32 (the warp has no integer pixel type); outside the volume, default_value
+__device__ inline float warp_linear(const MemFetch& fetch, const Dims n, const double* c, float default_value) {
+  double r;
+  if (!sample_linear(fetch, n, c[0], c[1], c[2], r)) return default_value;
   return (float)r;
-}
-
-__device__ inline uint32_t warp_nearest(const uint32_t* v, const Dims n, const double* c, uint32_t default_bits) {
-  const double cx = c[0], cy = c[1], cz = c[2];
-  if (!(inside_axis(cx, n.nx) && inside_axis(cy, n.ny) && inside_axis(cz, n.nz))) return default_bits;
-  const int x = clamp_index(floor(cx + 0.5), n.nx), y = clamp_index(floor(cy + 0.5), n.ny), z = clamp_index(floor(cz + 0.5), n.nz);
-  return v[((int64_t)z * n.ny + y) * n.nx + x];
 }
 
 struct WarpArgs {
@@ -422,12 +296,13 @@ __global__ __launch_bounds__(kBlock) void ffd_warp_kernel(const WarpArgs a) {
   __syncthreads();
   if (!valid) return;  // (the whole wave)
   const int64_t row = (int64_t)z * ny + y;
+  const MemFetch fetch{reinterpret_cast<const float*>(a.src), a.n.ny, a.n.nx};
 #pragma unroll 1
   for (int x = lane; x < nx; x += 64) {
     double c[3];
     deformed(a.L, a.A, t2[wave], x, y, z, c);
-    a.out[row * nx + x] = a.nearest ? warp_nearest(a.src, a.n, c, a.default_bits)
-                                    : __float_as_uint(warp_linear(reinterpret_cast<const float*>(a.src), a.n, c, __uint_as_float(a.default_bits)));
+    a.out[row * nx + x] = a.nearest ? sample_nearest(a.src, a.n, c[0], c[1], c[2], a.default_bits)
+                                    : __float_as_uint(warp_linear(fetch, a.n, c, __uint_as_float(a.default_bits)));
   }
 }
 
@@ -518,7 +393,6 @@ struct Plan {
 };
 
 bool side_ok(int side) { return side == 4 || side == 5 || side == 7 || side == 11 || side == 19; }
-bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 int make_plan(const std::string& w, int nz, int ny, int nx, int side, Plan* p) {
   if (t2fit::count_voxels(1, nz, ny, nx) < 0)
@@ -549,11 +423,7 @@ int make_plan(const std::string& w, int nz, int ny, int nx, int side, Plan* p) {
 // the lattice and the workspace: what every entry point checks after its own NULL checks and the plan
 int check_common(const std::string& w, const double* lattice_dev, const void* ws, size_t bytes, const Plan& p) {
   if (misaligned(lattice_dev, 8)) return t2fit::fail(T2FIT_E_INVALID, w + ": lattice_dev is not aligned to 8 bytes");
-  if (misaligned(ws, kAlign)) return t2fit::fail(T2FIT_E_INVALID, w + ": workspace_dev is not aligned to 256 bytes");
-  if (bytes < p.total)
-    return t2fit::fail(T2FIT_E_INVALID, w + ": workspace too small: " + std::to_string(bytes) + " bytes given, " + std::to_string(p.total) +
-                                            " needed (t2fit_ffd_workspace_bytes)");
-  return T2FIT_OK;
+  return t2fit::check_workspace(w, ws, bytes, p.total, "t2fit_ffd_workspace_bytes");
 }
 
 int check_metric(const std::string& w, int n_f, int n_m, double lo_m, double scale_m, const float* moving_dev, int mz, int my, int mx,
@@ -630,7 +500,7 @@ int t2fit_ffd_joint_hist_dev(const uint8_t* bins_dev, const uint8_t* fixed_mask_
   a.hist = reinterpret_cast<unsigned long long*>(hist_dev);
   const int n_entries = n_f * n_m;
   const unsigned grid = (unsigned)(a.L.n_tiles < kHistGrid ? a.L.n_tiles : kHistGrid);
-  hipLaunchKernelGGL(ffd_zero_hist_kernel, dim3((unsigned)ceil_div(n_entries, kBlock)), dim3(kBlock), 0, st, a.hist, n_entries);
+  hipLaunchKernelGGL(zero_u64_kernel, dim3((unsigned)ceil_div(n_entries, kBlock)), dim3(kBlock), 0, st, a.hist, n_entries);
   hipLaunchKernelGGL(ffd_hist_kernel, dim3(grid), dim3(kBlock), (size_t)n_entries * sizeof(unsigned long long), st, a);
   T2_HIP(hipGetLastError());
   return T2FIT_OK;

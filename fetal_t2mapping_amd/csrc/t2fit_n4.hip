@@ -9,7 +9,8 @@
 //   n4_minmax_kernel    min and max of u over M per workgroup (grid-stride), n4_minmax_final_kernel over the partials.
 //   n4_hist_kernel      a uint64 histogram per workgroup in LDS (integer LDS atomics), then one integer atomic per
 //                       non-empty bin to global memory.  Integer adds are exact in any order.
-//   n4_axis_kernel      per axis and voxel index: the first lattice node k and the weights b, a = b^3 / S, q = b^2.
+//   n4_axis_kernel      per axis and voxel index: the first lattice node k and the weights b (t2fit_bspline.h, shared with
+//                       t2fit_ffd.hip), a = b^3 / S, q = b^2.
 //   n4_rows_kernel      THE HOT ONE.  A wave per row (z, y): reads u and M once, forms the residual from the table E in
 //                       LDS and contracts x: lane l adds terms l, l + 64, .. from +0.0 into C accumulators (C = the
 //                       lattice side, a template argument: the four weights of a voxel are selected into place, there
@@ -20,7 +21,7 @@
 //   n4_field_kernel     a workgroup per slice z and four rows: T1[z] (C x C) and the rows' T2 (C) in LDS, a wave per row;
 //                       writes the new field and u, the row's sum d and sum d^2 (d = expm1(new - old) over M, same lane
 //                       order and butterfly) and the row's min and max of the new u.
-//   n4_reduce_kernel    a pass of the tree over the rows: 256 consecutive values by halving in LDS.
+//   tree_reduce_kernel  (t2fit_reduce.h) a pass of the tree over the rows: 256 consecutive values by halving in LDS.
 //   n4_apply_kernel     out = (float)((double)in / exp((double)field) * scale).
 // No floating-point atomics; the order of every floating-point addition is a function of the sizes alone.  Compiled with
 // -ffp-contract=off: every multiply and add rounds once, as numpy's do.
@@ -30,29 +31,26 @@
 #include <cstdint>
 #include <string>
 
+#include "t2fit_bspline.h"
 #include "t2fit_error.h"
+#include "t2fit_mattes.h"
+#include "t2fit_reduce.h"
 #include "t2fit_support.h"
 
 namespace {
 
-using t2fit::align_up, t2fit::ceil_div, t2fit::kBlock;
+using t2fit::align_up, t2fit::ceil_div, t2fit::kBlock, t2fit::misaligned, t2fit::check_workspace;
+using t2fit::bspline_node, t2fit::bspline_weights, t2fit::select_tap, t2fit::zero_u64_kernel;
+using t2fit::wave_butterfly, t2fit::TreePasses, t2fit::tree_plan, t2fit::tree_launch;
 
 constexpr int kWaves = kBlock / 64;  // rows a workgroup takes
-constexpr int kFan = 256;
 constexpr size_t kAlign = 256;
+constexpr const char* kBytesFn = "t2fit_n4_workspace_bytes";  // what reports the workspace every entry point here takes
 constexpr int kMaxBins = 1024;
 constexpr int kMaxSide = 19;
-constexpr int kMaxPasses = 8;
 constexpr int kMaxGrid = 1024;       // workgroups of the grid-stride kernels (min/max, histogram)
 constexpr int kTab = 12;             // doubles per voxel index of an axis table: b0..3, a0..3, q0..3
 constexpr unsigned long long kFix = 1ull << 24;
-static_assert(kFan == kBlock, "a value per thread");
-
-__device__ inline double wave_butterfly(double v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_xor(v, s, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(kBlock) void n4_log_kernel(const float* __restrict__ in, const uint8_t* __restrict__ mask, int64_t n,
                                                         float* __restrict__ u0, uint8_t* __restrict__ m) {
@@ -119,11 +117,6 @@ __device__ inline void bin_coord(float u, double lo, double slope, int bins, int
   t = c - f;
 }
 
-__global__ __launch_bounds__(kBlock) void n4_zero_hist_kernel(unsigned long long* __restrict__ hist, int bins) {
-  const int b = blockIdx.x * kBlock + threadIdx.x;
-  if (b < bins) hist[b] = 0ull;
-}
-
 __global__ __launch_bounds__(kBlock) void n4_hist_kernel(const float* __restrict__ u, const uint8_t* __restrict__ m, int64_t n, double lo,
                                                          double slope, int bins, unsigned long long* __restrict__ hist) {
   __shared__ unsigned long long h[kMaxBins];
@@ -155,23 +148,9 @@ __global__ __launch_bounds__(kBlock) void n4_axis_kernel(int nz, int ny, int nx,
   if (v >= nz + ny + nx) return;
   const int n = v < nz ? nz : (v < nz + ny ? ny : nx);
   const int i = v < nz ? v : (v < nz + ny ? v - nz : v - nz - ny);
-  const int s = side - 3;
-  double kf = 0.0, tau = 0.0;
-  if (n > 1) {
-    if (i == n - 1) {
-      kf = (double)(s - 1), tau = 1.0;
-    } else {
-      const double p = ((double)i * (double)s) / (double)(n - 1);
-      kf = floor(p);
-      tau = p - kf;
-    }
-  }
-  const double t2 = tau * tau, t3 = t2 * tau, om = 1.0 - tau;
-  double b[4];
-  b[0] = ((om * om) * om) / 6.0;
-  b[1] = ((3.0 * t3 - 6.0 * t2) + 4.0) / 6.0;
-  b[2] = (((-3.0 * t3 + 3.0 * t2) + 3.0 * tau) + 1.0) / 6.0;
-  b[3] = t3 / 6.0;
+  double kf, tau, b[4];
+  bspline_node(i, n, side, kf, tau);
+  bspline_weights(tau, b);
   double q[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) q[j] = b[j] * b[j];
@@ -234,13 +213,7 @@ __global__ __launch_bounds__(kBlock) void n4_rows_kernel(const RowsArgs a) {
     const double w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-      const int d = c - k;
-      double wc = 0.0;
-      wc = d == 0 ? w0 : wc;
-      wc = d == 1 ? w1 : wc;
-      wc = d == 2 ? w2 : wc;
-      wc = d == 3 ? w3 : wc;
-      acc[c] = acc[c] + wc * r;
+      acc[c] = acc[c] + select_tap(c - k, w0, w1, w2, w3) * r;
     }
   }
 #pragma unroll
@@ -367,21 +340,6 @@ __global__ __launch_bounds__(kBlock) void n4_field_kernel(const FieldArgs a) {
   }
 }
 
-// out[q][b] = the halving sum of in[q][256 b .. 256 b + 255] (zeros beyond n); grid (n_out, the number of sums)
-__global__ __launch_bounds__(kBlock) void n4_reduce_kernel(const double* __restrict__ in, int64_t n, double* __restrict__ out, int64_t n_out) {
-  __shared__ double s[kFan];
-  const int tid = threadIdx.x;
-  const int64_t q = blockIdx.y, i = (int64_t)blockIdx.x * kFan + tid;
-  s[tid] = i < n ? in[q * n + i] : 0.0;
-  __syncthreads();
-#pragma unroll
-  for (int h = kFan / 2; h >= 1; h >>= 1) {
-    if (tid < h) s[tid] = s[tid] + s[tid + h];
-    __syncthreads();
-  }
-  if (tid == 0) out[q * n_out + blockIdx.x] = s[0];
-}
-
 __global__ __launch_bounds__(kBlock) void n4_apply_kernel(const float* __restrict__ in, const float* __restrict__ field, int64_t n, double scale,
                                                           float* __restrict__ out) {
   const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -395,9 +353,7 @@ struct Plan {
   int nz, ny, nx, side;
   int64_t rows, n_vox;
   size_t k_at, w_at, xs_at, ys_at, min_at, max_at;
-  int n_pass;
-  int64_t pass_n[kMaxPasses];  // values per sum that enter pass p; pass_n[0] = rows
-  size_t pass_at[kMaxPasses];
+  TreePasses tree;  // over the two row sums of the field kernel; pass_n[0] = rows
   size_t total;
 };
 
@@ -424,27 +380,10 @@ int make_plan(const std::string& w, int nz, int ny, int nx, int side, Plan* p) {
   p->ys_at = take((size_t)nz * side * side * sizeof(double));
   p->min_at = take((size_t)(rows > kMaxGrid ? rows : kMaxGrid) * sizeof(float));
   p->max_at = take((size_t)(rows > kMaxGrid ? rows : kMaxGrid) * sizeof(float));
-  p->n_pass = 0;
-  for (int64_t n = rows;; n = ceil_div(n, (int64_t)kFan)) {
-    p->pass_n[p->n_pass] = n;
-    p->pass_at[p->n_pass] = take((size_t)n * 2 * sizeof(double));
-    ++p->n_pass;
-    if (n <= kFan) break;
-  }
+  tree_plan(&p->tree, rows, [&](int64_t n) { return take((size_t)n * 2 * sizeof(double)); });
   p->total = at;
   return T2FIT_OK;
 }
-
-int check_workspace(const std::string& w, const void* ws, size_t bytes, size_t need) {
-  if (!ws) return t2fit::fail(T2FIT_E_INVALID, w + ": workspace_dev is NULL");
-  if (reinterpret_cast<uintptr_t>(ws) & (kAlign - 1)) return t2fit::fail(T2FIT_E_INVALID, w + ": workspace_dev is not aligned to 256 bytes");
-  if (bytes < need)
-    return t2fit::fail(T2FIT_E_INVALID, w + ": workspace too small: " + std::to_string(bytes) + " bytes given, " + std::to_string(need) +
-                                            " needed (t2fit_n4_workspace_bytes)");
-  return T2FIT_OK;
-}
-
-bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 int check_count(const std::string& w, int64_t n_vox) {
   if (n_vox < 1 || n_vox >= ((int64_t)1 << 39)) return t2fit::fail(T2FIT_E_INVALID, w + ": n_vox is outside 1..2^39-1");
@@ -531,7 +470,7 @@ int t2fit_n4_minmax_dev(const float* u_dev, const uint8_t* m_dev, int64_t n_vox,
   if (misaligned(u_dev, 4) || misaligned(range_dev, 4)) return t2fit::fail(T2FIT_E_INVALID, w + ": u_dev / range_dev is not aligned to 4 bytes");
   // the partials: kMaxGrid minima at the place of the row minima, kMaxGrid maxima 256-aligned after them
   const size_t part = align_up((size_t)kMaxGrid * sizeof(float), kAlign);
-  if ((rc = check_workspace(w, workspace_dev, workspace_bytes, 2 * part)) != T2FIT_OK) return rc;
+  if ((rc = check_workspace(w, workspace_dev, workspace_bytes, 2 * part, kBytesFn)) != T2FIT_OK) return rc;
   float* mins = static_cast<float*>(workspace_dev);
   float* maxs = reinterpret_cast<float*>(static_cast<char*>(workspace_dev) + part);
   const unsigned grid = stride_grid(n_vox);
@@ -553,7 +492,7 @@ int t2fit_n4_histogram_dev(const float* u_dev, const uint8_t* m_dev, int64_t n_v
   if (misaligned(hist_dev, 8)) return t2fit::fail(T2FIT_E_INVALID, w + ": hist_dev is not aligned to 8 bytes");
   hipStream_t st = (hipStream_t)stream;
   unsigned long long* hist = reinterpret_cast<unsigned long long*>(hist_dev);
-  hipLaunchKernelGGL(n4_zero_hist_kernel, dim3((unsigned)ceil_div(bins, kBlock)), dim3(kBlock), 0, st, hist, bins);
+  hipLaunchKernelGGL(zero_u64_kernel, dim3((unsigned)ceil_div(bins, kBlock)), dim3(kBlock), 0, st, hist, bins);
   hipLaunchKernelGGL(n4_hist_kernel, dim3(stride_grid(n_vox)), dim3(kBlock), 0, st, u_dev, m_dev, n_vox, lo, slope, bins, hist);
   T2_HIP(hipGetLastError());
   return T2FIT_OK;
@@ -567,7 +506,7 @@ int t2fit_n4_weights_dev(const uint8_t* m_dev, int nz, int ny, int nx, int side,
   int rc = make_plan(w, nz, ny, nx, side, &p);
   if (rc != T2FIT_OK) return rc;
   if (misaligned(omega_dev, 8)) return t2fit::fail(T2FIT_E_INVALID, w + ": omega_dev is not aligned to 8 bytes");
-  if ((rc = check_workspace(w, workspace_dev, workspace_bytes, p.total)) != T2FIT_OK) return rc;
+  if ((rc = check_workspace(w, workspace_dev, workspace_bytes, p.total, kBytesFn)) != T2FIT_OK) return rc;
   RowsArgs a{};
   a.m = m_dev;
   launch_contractions(p, static_cast<char*>(workspace_dev), a, true, omega_dev, nullptr, nullptr, nullptr, (hipStream_t)stream);
@@ -590,7 +529,7 @@ int t2fit_n4_fit_dev(const float* u_dev, const uint8_t* m_dev, int nz, int ny, i
     return t2fit::fail(T2FIT_E_INVALID, w + ": table_dev / omega_dev / lattice_dev / delta_dev is not aligned to 8 bytes");
   if (delta_dev == lattice_dev || delta_dev == omega_dev || lattice_dev == omega_dev)
     return t2fit::fail(T2FIT_E_INVALID, w + ": omega_dev, lattice_dev and delta_dev must be three arrays");
-  if ((rc = check_workspace(w, workspace_dev, workspace_bytes, p.total)) != T2FIT_OK) return rc;
+  if ((rc = check_workspace(w, workspace_dev, workspace_bytes, p.total, kBytesFn)) != T2FIT_OK) return rc;
   RowsArgs a{};
   a.u = u_dev, a.m = m_dev, a.table = table_dev, a.lo = lo, a.slope = slope, a.bins = table_dev ? bins : 2;
   launch_contractions(p, static_cast<char*>(workspace_dev), a, false, nullptr, omega_dev, delta_dev, lattice_dev, (hipStream_t)stream);
@@ -613,23 +552,18 @@ int t2fit_n4_field_dev(const double* lattice_dev, int side, const float* u0_dev,
     return t2fit::fail(T2FIT_E_INVALID, w + ": u0_dev, field_dev and u_dev must be three arrays");
   const int tiles_y = ceil_div(ny, kWaves);
   if ((int64_t)nz * tiles_y > INT32_MAX) return t2fit::fail(T2FIT_E_INVALID, w + ": more than 2^31-1 workgroups");
-  if ((rc = check_workspace(w, workspace_dev, workspace_bytes, p.total)) != T2FIT_OK) return rc;
+  if ((rc = check_workspace(w, workspace_dev, workspace_bytes, p.total, kBytesFn)) != T2FIT_OK) return rc;
   char* ws = static_cast<char*>(workspace_dev);
   hipStream_t st = (hipStream_t)stream;
   FieldArgs a;
   a.lattice = lattice_dev, a.side = side, a.u0 = u0_dev, a.m = m_dev;
   a.ax = launch_axes(p, ws, st);
   a.tiles_y = tiles_y, a.field = field_dev, a.u = u_dev;
-  a.row_sums = reinterpret_cast<double*>(ws + p.pass_at[0]);
+  a.row_sums = reinterpret_cast<double*>(ws + p.tree.pass_at[0]);
   a.row_min = reinterpret_cast<float*>(ws + p.min_at), a.row_max = reinterpret_cast<float*>(ws + p.max_at);
   a.rows = p.rows;
   hipLaunchKernelGGL(n4_field_kernel, dim3((unsigned)(nz * tiles_y)), dim3(kBlock), 0, st, a);
-  for (int q = 0; q < p.n_pass; ++q) {
-    const bool last = q + 1 == p.n_pass;
-    const int64_t n_out = last ? 1 : p.pass_n[q + 1];
-    double* out = last ? sums_dev : reinterpret_cast<double*>(ws + p.pass_at[q + 1]);
-    hipLaunchKernelGGL(n4_reduce_kernel, dim3((unsigned)n_out, 2), dim3(kBlock), 0, st, (const double*)(ws + p.pass_at[q]), p.pass_n[q], out, n_out);
-  }
+  tree_launch(p.tree, 2, ws, sums_dev, st);
   hipLaunchKernelGGL(n4_minmax_final_kernel, dim3(1), dim3(kBlock), 0, st, (const float*)a.row_min, (const float*)a.row_max, p.rows, range_dev);
   T2_HIP(hipGetLastError());
   return T2FIT_OK;

@@ -26,8 +26,8 @@
 //                           wave are one 64-bit word (an OR butterfly of 1 << bin); only those run the sum's butterfly --
 //                           an absent bin's column values are all +0.0 and so is their tree.  The counts are whole
 //                           numbers below 2^53, exact in any order: popcounts of ballots stand for their tree.
-//   register_reduce_kernel  one pass of the tree over the slabs: a workgroup adds 256 consecutive values of one sum by
-//                           halving in LDS.  Passes repeat until one value per sum is left.
+//   tree_reduce_kernel      (t2fit_reduce.h) one pass of the tree over the slabs: a workgroup adds 256 consecutive values
+//                           of one sum by halving in LDS.  Passes repeat until one value per sum is left.
 //   shrink kernels          a pyramid level: the mean (the "any") of s^3 blocks, one thread per output voxel.
 // The order of every floating-point addition is a function of the sizes alone; there is no floating-point atomic
 // anywhere (the histogram's integer atomics are the only atomics).  Compiled with
@@ -41,19 +41,21 @@
 
 #include "t2fit_affine.h"
 #include "t2fit_error.h"
+#include "t2fit_mattes.h"
+#include "t2fit_reduce.h"
 #include "t2fit_support.h"
 
 namespace {
 
 using t2fit::align_up, t2fit::ceil_div, t2fit::kBlock;
-using t2fit::Affine, t2fit::Dims, t2fit::coord, t2fit::inside_axis, t2fit::clamp_index;
+using t2fit::Affine, t2fit::Dims, t2fit::coord, t2fit::sample_metric;
+using t2fit::bin_of, t2fit::parzen, t2fit::deposit, t2fit::zero_u64_kernel;
+using t2fit::wave_butterfly, t2fit::TreePasses, t2fit::tree_plan, t2fit::tree_launch;
 
 constexpr int kBX = 64, kBY = 4, kBZ = 8;  // the brick; kBX lanes of a wave, kBY waves
 constexpr int kSums = T2FIT_REGISTER_SUMS;
-constexpr int kFan = 256;                  // values a workgroup of the reduction adds
 constexpr size_t kAlign = 256;
 static_assert(kBX == 64 && kBX * kBY == kBlock, "a wave per row of the brick");
-static_assert(kFan == kBlock, "a value per thread");
 
 constexpr int kMaxBins = 64;  // the bins of a wave fit one 64-bit presence word
 constexpr int kMinMovingBins = 5;
@@ -80,76 +82,12 @@ struct SumsArgs {
   double* slabs;  // [kSums][n_bricks], the binned kernel: [2 n_bins][n_bricks]
 };
 
-// a bin byte above n_bins - 1 counts as n_bins - 1 (t2fit_register_bin_dev writes none)
-__device__ inline int bin_of(uint8_t b, int n_bins) { return (int)b < n_bins ? (int)b : n_bins - 1; }
-
-__device__ inline double lerp(double p, double q, double w) { return w == 0.0 ? p : p + w * (q - p); }
-
-__device__ inline double wave_butterfly(double v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_xor(v, s, 64);
-  return v;
-}
-
-// whether the fixed voxel (x, y, z), whose mask byte is set, counts; if so its interpolant m and, <true>, dm/dc.
-// <.., true>: moving_mask may be NULL (all ones)
+// whether the fixed voxel (x, y, z), whose mask byte is set, counts; if so its interpolant m and, <true>, dm/dc:
+// t2fit_affine.h's sample_metric at the voxel's image under A.  <.., true>: moving_mask may be NULL (all ones)
 template <bool kGrad, bool kMaskOptional = false>
 __device__ inline bool sample(const float* moving, const uint8_t* moving_mask, const Dims n, const Affine& A, int x, int y, int z,
                               double& m, double* g) {
-  const double cx = coord(A, 0, x, y, z), cy = coord(A, 1, x, y, z), cz = coord(A, 2, x, y, z);
-  if (!(inside_axis(cx, n.nx) && inside_axis(cy, n.ny) && inside_axis(cz, n.nz))) return false;
-  const int qx = clamp_index(floor(cx + 0.5), n.nx), qy = clamp_index(floor(cy + 0.5), n.ny), qz = clamp_index(floor(cz + 0.5), n.nz);
-  if ((!kMaskOptional || moving_mask) && moving_mask[((int64_t)qz * n.ny + qy) * n.nx + qx] == 0) return false;
-  const int x0 = clamp_index(floor(cx), n.nx), y0 = clamp_index(floor(cy), n.ny), z0 = clamp_index(floor(cz), n.nz);
-  double dx = cx - (double)x0, dy = cy - (double)y0, dz = cz - (double)z0;
-  dx = dx < 0.0 ? 0.0 : dx;
-  dy = dy < 0.0 ? 0.0 : dy;
-  dz = dz < 0.0 ? 0.0 : dz;
-  const int x1 = x0 + 1 < n.nx ? x0 + 1 : n.nx - 1, y1 = y0 + 1 < n.ny ? y0 + 1 : n.ny - 1, z1 = z0 + 1 < n.nz ? z0 + 1 : n.nz - 1;
-  const float* r00 = moving + ((int64_t)z0 * n.ny + y0) * n.nx;
-  const float* r01 = moving + ((int64_t)z0 * n.ny + y1) * n.nx;
-  const float* r10 = moving + ((int64_t)z1 * n.ny + y0) * n.nx;
-  const float* r11 = moving + ((int64_t)z1 * n.ny + y1) * n.nx;
-  const double v000 = r00[x0], v001 = r00[x1], v010 = r01[x0], v011 = r01[x1];
-  const double v100 = r10[x0], v101 = r10[x1], v110 = r11[x0], v111 = r11[x1];
-  const double l00 = lerp(v000, v001, dx), l01 = lerp(v010, v011, dx), l10 = lerp(v100, v101, dx), l11 = lerp(v110, v111, dx);
-  const double p0 = lerp(l00, l01, dy), p1 = lerp(l10, l11, dy);
-  m = lerp(p0, p1, dz);
-  if (!kGrad) return true;
-  g[0] = lerp(lerp(v001 - v000, v011 - v010, dy), lerp(v101 - v100, v111 - v110, dy), dz);
-  g[1] = lerp(l01 - l00, l11 - l10, dz);
-  g[2] = p1 - p0;
-  if (x1 == x0 || cx < 0.0) g[0] = 0.0;
-  if (y1 == y0 || cy < 0.0) g[1] = 0.0;
-  if (z1 == z0 || cz < 0.0) g[2] = 0.0;
-  return true;
-}
-
-// The cubic B-spline Parzen window of a moving sample (include/t2fit.h has the order of operations): returns i0, and the
-// four weights (<false>) or their derivatives with respect to t (<true>) on the bins i0 - 1 .. i0 + 2.  2 <= i0 <= n_m - 3
-// whatever m is (a NaN lands at t = 2), so the bins stay inside a row of n_m.
-template <bool kDeriv>
-__device__ inline int parzen(double m, double lo, double scale, int n_m, double* w) {
-  double t = (m - lo) * scale + 2.0;
-  const double top = (double)(n_m - 2), last = (double)(n_m - 3);
-  t = t >= 2.0 ? t : 2.0;
-  t = t <= top ? t : top;
-  double base = floor(t);
-  base = base < last ? base : last;
-  const double u = t - base, v = 1.0 - u, u2 = u * u, v2 = v * v;
-  if (kDeriv) {
-    w[0] = -(v2 * 0.5);
-    w[1] = 1.5 * u2 - 2.0 * u;
-    w[2] = (-1.5 * u2 + u) + 0.5;
-    w[3] = u2 * 0.5;
-  } else {
-    const double u3 = u2 * u, v3 = v2 * v;
-    w[0] = v3 / 6.0;
-    w[1] = ((3.0 * u3 - 6.0 * u2) + 4.0) / 6.0;
-    w[2] = (((-3.0 * u3 + 3.0 * u2) + 3.0 * u) + 1.0) / 6.0;
-    w[3] = u3 / 6.0;
-  }
-  return (int)base;
+  return sample_metric<kGrad, kMaskOptional>(moving, moving_mask, n, coord(A, 0, x, y, z), coord(A, 1, x, y, z), coord(A, 2, x, y, z), m, g);
 }
 
 template <int kMode>
@@ -348,21 +286,12 @@ __global__ __launch_bounds__(kBlock) void register_joint_hist_kernel(const SumsA
       if (!sample<false>(a.moving, a.moving_mask, a.m, a.A, x, y, z, m, nullptr)) continue;
       const int i0 = parzen<false>(m, a.lo_m, a.scale_m, a.n_m, w);
       unsigned long long* row = mi_hist + bin_of(a.bins[at], a.n_bins) * a.n_m + (i0 - 1);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const unsigned long long q = (unsigned long long)floor(w[j] * 1073741824.0 + 0.5);
-        if (q != 0ull) atomicAdd(&row[j], q);
-      }
+      deposit(row, w);
     }
   }
   __syncthreads();
   for (int i = threadIdx.x; i < n_entries; i += kBlock)
     if (mi_hist[i] != 0ull) atomicAdd(&a.hist[i], mi_hist[i]);
-}
-
-__global__ __launch_bounds__(kBlock) void register_zero_hist_kernel(unsigned long long* __restrict__ hist, int n) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i < n) hist[i] = 0ull;
 }
 
 // slabs[b] = N_b and slabs[n_bins + b] = S_b of the brick, by the tree of the 43 sums
@@ -439,22 +368,6 @@ __global__ void register_lut_kernel(const double* __restrict__ binned, int n_bin
   if (b < n_bins) lut[b] = binned[b] > 0.0 ? binned[n_bins + b] / binned[b] : 0.0;
 }
 
-// out[q][b] = the halving sum of in[q][256 b .. 256 b + 255] (zeros beyond n); grid (n_out, the number of sums)
-__global__ __launch_bounds__(kBlock) void register_reduce_kernel(const double* __restrict__ in, int64_t n, double* __restrict__ out,
-                                                                 int64_t n_out) {
-  __shared__ double s[kFan];
-  const int tid = threadIdx.x;
-  const int64_t q = blockIdx.y, i = (int64_t)blockIdx.x * kFan + tid;
-  s[tid] = i < n ? in[q * n + i] : 0.0;
-  __syncthreads();
-#pragma unroll
-  for (int h = kFan / 2; h >= 1; h >>= 1) {
-    if (tid < h) s[tid] = s[tid] + s[tid + h];
-    __syncthreads();
-  }
-  if (tid == 0) out[q * n_out + blockIdx.x] = s[0];
-}
-
 __global__ __launch_bounds__(kBlock) void shrink_kernel(const float* __restrict__ src, Dims n, int s, Dims o, float* __restrict__ out) {
   const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (v >= (int64_t)o.nz * o.ny * o.nx) return;
@@ -487,14 +400,11 @@ __global__ __launch_bounds__(kBlock) void shrink_mask_kernel(const uint8_t* __re
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------
-constexpr int kMaxPasses = 8;
 constexpr int kMaxShrink = 32;
 
 struct Plan {
   int bricks_x, bricks_y, bricks_z;
-  int n_pass;
-  int64_t pass_n[kMaxPasses];   // values per sum that enter pass p; pass_n[0] = the slabs
-  size_t pass_at[kMaxPasses];   // where they lie in the workspace
+  TreePasses tree;  // pass_n[0] = the slabs
   size_t total;
 };
 
@@ -504,15 +414,12 @@ int sums_plan(const std::string& w, int fz, int fy, int fx, Plan* plan, int n_su
   plan->bricks_x = ceil_div(fx, kBX), plan->bricks_y = ceil_div(fy, kBY), plan->bricks_z = ceil_div(fz, kBZ);
   const int64_t bricks = (int64_t)plan->bricks_x * plan->bricks_y * plan->bricks_z;
   if (bricks > INT32_MAX) return t2fit::fail(T2FIT_E_INVALID, w + ": the fixed volume has more than 2^31-1 bricks (the launch index is 32-bit)");
-  plan->n_pass = 0;
   plan->total = 0;
-  for (int64_t n = bricks;; n = ceil_div(n, (int64_t)kFan)) {
-    plan->pass_n[plan->n_pass] = n;
-    plan->pass_at[plan->n_pass] = plan->total;
+  tree_plan(&plan->tree, bricks, [&](int64_t n) {
+    const size_t here = plan->total;
     plan->total += align_up((size_t)n * n_sums * sizeof(double), kAlign);
-    ++plan->n_pass;
-    if (n <= kFan) break;
-  }
+    return here;
+  });
   return T2FIT_OK;
 }
 
@@ -523,12 +430,7 @@ int sums_check(const std::string& w, const float* moving_dev, int mz, int my, in
     return t2fit::fail(T2FIT_E_INVALID, w + ": the moving sizes must all be >= 1 and the volume at most 2^40 elements");
   if (!t2fit::finite12(A)) return t2fit::fail(T2FIT_E_INVALID, w + ": A has a non-finite entry");
   if (reinterpret_cast<uintptr_t>(moving_dev) & 3) return t2fit::fail(T2FIT_E_INVALID, w + ": moving_dev is not aligned to 4 bytes");
-  if (reinterpret_cast<uintptr_t>(workspace_dev) & (kAlign - 1))
-    return t2fit::fail(T2FIT_E_INVALID, w + ": workspace_dev is not aligned to 256 bytes");
-  if (workspace_bytes < plan.total)
-    return t2fit::fail(T2FIT_E_INVALID, w + ": workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " +
-                                            std::to_string(plan.total) + " needed (" + bytes_fn + ")");
-  return T2FIT_OK;
+  return t2fit::check_workspace(w, workspace_dev, workspace_bytes, plan.total, bytes_fn);
 }
 
 SumsArgs sums_args(const uint8_t* fixed_mask_dev, int fz, int fy, int fx, const float* moving_dev, const uint8_t* moving_mask_dev, int mz,
@@ -540,21 +442,9 @@ SumsArgs sums_args(const uint8_t* fixed_mask_dev, int fz, int fy, int fx, const 
   a.f = Dims{fz, fy, fx}, a.m = Dims{mz, my, mx};
   for (int i = 0; i < 12; ++i) a.A.m[i] = A[i];
   a.bricks_x = plan.bricks_x, a.bricks_y = plan.bricks_y;
-  a.n_bricks = plan.pass_n[0];
-  a.slabs = reinterpret_cast<double*>(static_cast<char*>(workspace_dev) + plan.pass_at[0]);
+  a.n_bricks = plan.tree.pass_n[0];
+  a.slabs = reinterpret_cast<double*>(static_cast<char*>(workspace_dev) + plan.tree.pass_at[0]);
   return a;
-}
-
-// the passes of the tree over the n_sums rows of slabs, the last one into out_dev
-void reduce_passes(const Plan& plan, int n_sums, void* workspace_dev, double* out_dev, hipStream_t st) {
-  char* ws = static_cast<char*>(workspace_dev);
-  for (int p = 0; p < plan.n_pass; ++p) {
-    const bool last = p + 1 == plan.n_pass;
-    const int64_t n_out = last ? 1 : plan.pass_n[p + 1];
-    double* out = last ? out_dev : reinterpret_cast<double*>(ws + plan.pass_at[p + 1]);
-    hipLaunchKernelGGL(register_reduce_kernel, dim3((unsigned)n_out, n_sums), dim3(kBlock), 0, st, (const double*)(ws + plan.pass_at[p]),
-                       plan.pass_n[p], out, n_out);
-  }
 }
 
 // the checks the two Mattes entry points share, after the NULL checks
@@ -583,9 +473,7 @@ struct SvrPlan {
   int bricks_x[kSvrMaxStacks], n_bricks[kSvrMaxStacks];
   int max_bricks;
   int64_t rows;  // 43 n_slices
-  int n_pass;
-  int64_t pass_n[kMaxPasses];
-  size_t pass_at[kMaxPasses];
+  TreePasses tree;
   size_t total;
 };
 
@@ -606,15 +494,12 @@ int svr_plan(const std::string& w, int n_stacks, const int32_t* lo_size, int n_s
   if ((int64_t)n_slices * plan->max_bricks > INT32_MAX)
     return t2fit::fail(T2FIT_E_INVALID, w + ": more than 2^31-1 workgroups (n_slices times the largest brick count of a slice)");
   plan->rows = (int64_t)kSums * n_slices;
-  plan->n_pass = 0;
   plan->total = 0;
-  for (int64_t n = plan->max_bricks;; n = ceil_div(n, (int64_t)kFan)) {
-    plan->pass_n[plan->n_pass] = n;
-    plan->pass_at[plan->n_pass] = plan->total;
+  tree_plan(&plan->tree, plan->max_bricks, [&](int64_t n) {
+    const size_t here = plan->total;
     plan->total += align_up((size_t)n * (size_t)plan->rows * sizeof(double), kAlign);
-    ++plan->n_pass;
-    if (n <= kFan) break;
-  }
+    return here;
+  });
   return T2FIT_OK;
 }
 
@@ -688,29 +573,14 @@ int t2fit_svr_sums_dev(int n_stacks, const float* const* fixed_dev, const uint8_
   if (reinterpret_cast<uintptr_t>(moving_dev) & 3) return t2fit::fail(T2FIT_E_INVALID, w + ": moving_dev is not aligned to 4 bytes");
   if ((reinterpret_cast<uintptr_t>(sums_dev) & 7) || (reinterpret_cast<uintptr_t>(table_dev) & 7))
     return t2fit::fail(T2FIT_E_INVALID, w + ": sums_dev / table_dev is not aligned to 8 bytes");
-  if (reinterpret_cast<uintptr_t>(workspace_dev) & (kAlign - 1))
-    return t2fit::fail(T2FIT_E_INVALID, w + ": workspace_dev is not aligned to 256 bytes");
-  if (workspace_bytes < plan.total)
-    return t2fit::fail(T2FIT_E_INVALID, w + ": workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " +
-                                            std::to_string(plan.total) + " needed (t2fit_svr_workspace_bytes)");
+  const int ws_rc = t2fit::check_workspace(w, workspace_dev, workspace_bytes, plan.total, "t2fit_svr_workspace_bytes");
+  if (ws_rc != T2FIT_OK) return ws_rc;
   hipStream_t st = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace_dev);
   a.n_stacks = n_stacks, a.moving = moving_dev, a.moving_mask = moving_mask_dev, a.m = Dims{mz, my, mx};
   a.table = static_cast<const SvrRec*>(table_dev), a.max_bricks = plan.max_bricks;
-  a.slabs = reinterpret_cast<double*>(ws + plan.pass_at[0]);
+  a.slabs = reinterpret_cast<double*>(static_cast<char*>(workspace_dev) + plan.tree.pass_at[0]);
   hipLaunchKernelGGL(svr_sums_kernel, dim3((unsigned)((int64_t)n_slices * plan.max_bricks)), dim3(kBlock), 0, st, a);
-  constexpr int64_t kRowsPerLaunch = 65535;  // the y extent of a grid
-  for (int p = 0; p < plan.n_pass; ++p) {
-    const bool last = p + 1 == plan.n_pass;
-    const int64_t n = plan.pass_n[p], n_out = last ? 1 : plan.pass_n[p + 1];
-    const double* in = reinterpret_cast<const double*>(ws + plan.pass_at[p]);
-    double* out = last ? sums_dev : reinterpret_cast<double*>(ws + plan.pass_at[p + 1]);
-    for (int64_t q0 = 0; q0 < plan.rows; q0 += kRowsPerLaunch) {
-      const int64_t q_n = plan.rows - q0 < kRowsPerLaunch ? plan.rows - q0 : kRowsPerLaunch;
-      hipLaunchKernelGGL(register_reduce_kernel, dim3((unsigned)n_out, (unsigned)q_n), dim3(kBlock), 0, st, in + q0 * n, n, out + q0 * n_out,
-                         n_out);
-    }
-  }
+  tree_launch(plan.tree, plan.rows, workspace_dev, sums_dev, st);
   T2_HIP(hipGetLastError());
   return T2FIT_OK;
 }
@@ -739,15 +609,12 @@ int t2fit_register_sums_dev(const float* fixed_dev, const uint8_t* fixed_mask_de
   if ((reinterpret_cast<uintptr_t>(fixed_dev) & 3) || (reinterpret_cast<uintptr_t>(moving_dev) & 3))
     return t2fit::fail(T2FIT_E_INVALID, w + ": fixed_dev / moving_dev is not aligned to 4 bytes");
   if (reinterpret_cast<uintptr_t>(sums_dev) & 7) return t2fit::fail(T2FIT_E_INVALID, w + ": sums_dev is not aligned to 8 bytes");
-  if (reinterpret_cast<uintptr_t>(workspace_dev) & (kAlign - 1))
-    return t2fit::fail(T2FIT_E_INVALID, w + ": workspace_dev is not aligned to 256 bytes");
-  if (workspace_bytes < plan.total)
-    return t2fit::fail(T2FIT_E_INVALID, w + ": workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " +
-                                            std::to_string(plan.total) + " needed (t2fit_register_workspace_bytes)");
+  const int ws_rc = t2fit::check_workspace(w, workspace_dev, workspace_bytes, plan.total, "t2fit_register_workspace_bytes");
+  if (ws_rc != T2FIT_OK) return ws_rc;
   SumsArgs a = sums_args(fixed_mask_dev, fz, fy, fx, moving_dev, moving_mask_dev, mz, my, mx, A, plan, workspace_dev);
   a.fixed = fixed_dev;
   hipLaunchKernelGGL(HIP_KERNEL_NAME(register_sums_kernel<kFromFixed>), dim3((unsigned)a.n_bricks), dim3(kBlock), 0, (hipStream_t)stream, a);
-  reduce_passes(plan, kSums, workspace_dev, sums_dev, (hipStream_t)stream);
+  tree_launch(plan.tree, kSums, workspace_dev, sums_dev, (hipStream_t)stream);
   T2_HIP(hipGetLastError());
   return T2FIT_OK;
 }
@@ -794,7 +661,7 @@ int t2fit_register_binned_sums_dev(const uint8_t* bins_dev, const uint8_t* fixed
   SumsArgs a = sums_args(fixed_mask_dev, fz, fy, fx, moving_dev, moving_mask_dev, mz, my, mx, A, plan, workspace_dev);
   a.bins = bins_dev, a.n_bins = n_bins;
   hipLaunchKernelGGL(register_binned_kernel, dim3((unsigned)a.n_bricks), dim3(kBlock), 0, st, a);
-  reduce_passes(plan, 2 * n_bins, workspace_dev, binned_dev, st);
+  tree_launch(plan.tree, 2 * n_bins, workspace_dev, binned_dev, st);
   if (lut_dev) hipLaunchKernelGGL(register_lut_kernel, dim3(1), dim3(kMaxBins), 0, st, (const double*)binned_dev, n_bins, lut_dev);
   T2_HIP(hipGetLastError());
   return T2FIT_OK;
@@ -818,7 +685,7 @@ int t2fit_register_sums_lut_dev(const uint8_t* bins_dev, const double* lut_dev, 
   SumsArgs a = sums_args(fixed_mask_dev, fz, fy, fx, moving_dev, moving_mask_dev, mz, my, mx, A, plan, workspace_dev);
   a.bins = bins_dev, a.lut = lut_dev, a.n_bins = n_bins;
   hipLaunchKernelGGL(HIP_KERNEL_NAME(register_sums_kernel<kFromLut>), dim3((unsigned)a.n_bricks), dim3(kBlock), 0, (hipStream_t)stream, a);
-  reduce_passes(plan, kSums, workspace_dev, sums_dev, (hipStream_t)stream);
+  tree_launch(plan.tree, kSums, workspace_dev, sums_dev, (hipStream_t)stream);
   T2_HIP(hipGetLastError());
   return T2FIT_OK;
 }
@@ -847,7 +714,7 @@ int t2fit_register_joint_hist_dev(const uint8_t* bins_dev, const uint8_t* fixed_
   a.hist = reinterpret_cast<unsigned long long*>(hist_dev);
   const int n_entries = n_f * n_m;
   const unsigned grid = (unsigned)(a.n_bricks < kHistGrid ? a.n_bricks : kHistGrid);
-  hipLaunchKernelGGL(register_zero_hist_kernel, dim3((unsigned)ceil_div(n_entries, kBlock)), dim3(kBlock), 0, st, a.hist, n_entries);
+  hipLaunchKernelGGL(zero_u64_kernel, dim3((unsigned)ceil_div(n_entries, kBlock)), dim3(kBlock), 0, st, a.hist, n_entries);
   hipLaunchKernelGGL(register_joint_hist_kernel, dim3(grid), dim3(kBlock), (size_t)n_entries * sizeof(unsigned long long), st, a);
   T2_HIP(hipGetLastError());
   return T2FIT_OK;
@@ -882,7 +749,7 @@ int t2fit_register_mi_gradient_dev(const uint8_t* bins_dev, const double* table_
   a.bins = bins_dev, a.lut = table_dev, a.n_bins = n_f, a.n_m = n_m, a.lo_m = lo_m, a.scale_m = scale_m;
   hipLaunchKernelGGL(HIP_KERNEL_NAME(register_sums_kernel<kFromMi>), dim3((unsigned)a.n_bricks), dim3(kBlock),
                      (size_t)n_f * n_m * sizeof(double), (hipStream_t)stream, a);
-  reduce_passes(plan, kMiSums, workspace_dev, sums_dev, (hipStream_t)stream);
+  tree_launch(plan.tree, kMiSums, workspace_dev, sums_dev, (hipStream_t)stream);
   T2_HIP(hipGetLastError());
   return T2FIT_OK;
 }

@@ -3,8 +3,9 @@
 // reference's run_qmri_reconstruction.py (utils/qmri_utils.py: resample_volume :62-80 through SimpleITK on the host,
 // reconstruct_vol_trilinear :82-136 through scipy's RegularGridInterpolator) with the rigid transforms as an input.
 //
-// One definition of a sample (sample_linear / sample_nearest below, restated in numpy in fetal_t2mapping_amd/_resample.py)
-// serves three kernels:
+// One definition of a sample (sample_linear / sample_nearest of t2fit_affine.h, restated in numpy in
+// fetal_t2mapping_amd/_resample.py; the wrappers below form the coordinate and apply the pixel type's cast) serves three
+// kernels here and t2fit_ffd.hip's warp:
 //   resample_kernel     one stage: the output brick of a workgroup is walked along the output axis that maps most
 //                       nearly onto the source's fastest axis, so that consecutive lanes read consecutive source
 //                       elements whichever way the stack is oriented; the results cross an LDS tile and leave along
@@ -30,8 +31,7 @@
 namespace {
 
 using t2fit::align_up, t2fit::ceil_div, t2fit::kBlock;
-using t2fit::Affine, t2fit::Dims, t2fit::coord, t2fit::inside_axis, t2fit::clamp_index, t2fit::finite12,
-    t2fit::count_voxels;
+using t2fit::Affine, t2fit::Dims, t2fit::coord, t2fit::MemFetch, t2fit::finite12, t2fit::count_voxels;
 constexpr int kPerThread = 2;
 constexpr int kBrick = kBlock * kPerThread;  // voxels of a workgroup's output brick
 constexpr size_t kAlign = 256;
@@ -43,64 +43,19 @@ __device__ inline float integer_cast(double r) {  // an int16 pixel type: toward
   return (float)r;
 }
 
-// One level of the interpolation, weight w in (0, 1): lo + w (hi - lo).  An infinite lo makes that the NaN of Inf - Inf,
-// where the weighted mean it stands for is that Inf (NaN only against the opposite Inf): lo + hi is just that, and is NaN
-// wherever lo or hi is.  Finite values never take the branch.
-__device__ inline double lerp(double lo, double hi, double w) {
-  const double r = lo + w * (hi - lo);
-  return __builtin_expect(r != r, 0) ? lo + hi : r;
-}
-
-// Linear sample of a volume of `n` at output index (ix, iy, iz); fetch(x, y, z) returns the node as a double.
-// Outside the volume the result is default_value and nothing is fetched.
+// Linear sample of a volume of `n` at output index (ix, iy, iz): t2fit_affine.h's sample_linear at the index's image under A,
+// then the pixel type's cast.  Outside the volume the result is default_value as it stands and nothing is fetched.
 template <typename Fetch>
 __device__ inline float sample_linear(const Fetch& fetch, const Dims n, const Affine& A, int ix, int iy, int iz, bool icast,
                                       float default_value) {
-  const double cx = coord(A, 0, ix, iy, iz), cy = coord(A, 1, ix, iy, iz), cz = coord(A, 2, ix, iy, iz);
-  if (!(inside_axis(cx, n.nx) && inside_axis(cy, n.ny) && inside_axis(cz, n.nz))) return default_value;
-  const int x0 = clamp_index(floor(cx), n.nx), y0 = clamp_index(floor(cy), n.ny), z0 = clamp_index(floor(cz), n.nz);
-  double dx = cx - (double)x0, dy = cy - (double)y0, dz = cz - (double)z0;
-  dx = dx < 0.0 ? 0.0 : dx;
-  dy = dy < 0.0 ? 0.0 : dy;
-  dz = dz < 0.0 ? 0.0 : dz;
-  const int x1 = x0 + 1 < n.nx ? x0 + 1 : n.nx - 1, y1 = y0 + 1 < n.ny ? y0 + 1 : n.ny - 1, z1 = z0 + 1 < n.nz ? z0 + 1 : n.nz - 1;
-  auto row = [&](int z, int y) {
-    double r = fetch(x0, y, z);
-    if (dx != 0.0) {
-      const double hi = fetch(x1, y, z);
-      r = lerp(r, hi, dx);
-    }
-    return r;
-  };
-  auto plane = [&](int z) {
-    double r = row(z, y0);
-    if (dy != 0.0) {
-      const double hi = row(z, y1);
-      r = lerp(r, hi, dy);
-    }
-    return r;
-  };
-  double r = plane(z0);
-  if (dz != 0.0) {
-    const double hi = plane(z1);
-    r = lerp(r, hi, dz);
-  }
+  double r;
+  if (!t2fit::sample_linear(fetch, n, coord(A, 0, ix, iy, iz), coord(A, 1, ix, iy, iz), coord(A, 2, ix, iy, iz), r)) return default_value;
   return icast ? integer_cast(r) : (float)r;
 }
 
-struct MemFetch {  // a float32 volume in memory
-  const float* v;
-  int ny, nx;
-  __device__ inline double operator()(int x, int y, int z) const { return (double)v[((int64_t)z * ny + y) * nx + x]; }
-};
-
-// nearest: the 32-bit pattern of the node floor(c + 0.5), clamped into the volume
 __device__ inline uint32_t sample_nearest(const uint32_t* v, const Dims n, const Affine& A, int ix, int iy, int iz,
                                           uint32_t default_bits) {
-  const double cx = coord(A, 0, ix, iy, iz), cy = coord(A, 1, ix, iy, iz), cz = coord(A, 2, ix, iy, iz);
-  if (!(inside_axis(cx, n.nx) && inside_axis(cy, n.ny) && inside_axis(cz, n.nz))) return default_bits;
-  const int x = clamp_index(floor(cx + 0.5), n.nx), y = clamp_index(floor(cy + 0.5), n.ny), z = clamp_index(floor(cz + 0.5), n.nz);
-  return v[((int64_t)z * n.ny + y) * n.nx + x];
+  return t2fit::sample_nearest(v, n, coord(A, 0, ix, iy, iz), coord(A, 1, ix, iy, iz), coord(A, 2, ix, iy, iz), default_bits);
 }
 
 // ---- one stage -------------------------------------------------------------------------------------------------
@@ -352,11 +307,8 @@ int t2fit_reconstruct_dev(const float* const* stacks_dev, const int32_t* lo_size
   const bool chain = (flags & T2FIT_RECON_CHAIN) != 0;
   if (chain) {
     if (!workspace_dev) return t2fit::fail(T2FIT_E_INVALID, w + ": T2FIT_RECON_CHAIN needs workspace_dev");
-    if (reinterpret_cast<uintptr_t>(workspace_dev) & (kAlign - 1))
-      return t2fit::fail(T2FIT_E_INVALID, w + ": workspace_dev is not aligned to 256 bytes");
-    if (workspace_bytes < plan.chain_total)
-      return t2fit::fail(T2FIT_E_INVALID, w + ": workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " +
-                                              std::to_string(plan.chain_total) + " needed (t2fit_reconstruct_workspace_bytes)");
+    const int ws_rc = t2fit::check_workspace(w, workspace_dev, workspace_bytes, plan.chain_total, "t2fit_reconstruct_workspace_bytes");
+    if (ws_rc != T2FIT_OK) return ws_rc;
   }
   Dims lo[3], hi[3];
   for (int s = 0; s < 3; ++s) {

@@ -8,7 +8,7 @@
 //   seg_normalise_kernel  pi from the priors and the floor; streaming, one lane per voxel.
 //   seg_sums_kernel       the moments of one class per blockIdx.y: a lane keeps its 4 voxels' channel values of the current
 //                         class walk in registers, 1 + C + C (C + 1) / 2 float64 accumulators, the wave butterfly and the
-//                         four-wave LDS step; per-workgroup partials, then seg_reduce_kernel in a fixed tree.
+//                         four-wave LDS step; per-workgroup partials, then the fixed tree of t2fit_reduce.h.
 //   seg_estep_kernel<C>   one E-step: lanes along x, a 4 x 4 x 64 tile per workgroup (a lane walks 4 slices), the model in the
 //                         kernel arguments (scalar loads), a_k and q_k of the 8 possible classes in registers behind a
 //                         compile-time loop bound; the six neighbours of p_old come through the vector cache.
@@ -22,29 +22,22 @@
 
 #include "t2fit_affine.h"
 #include "t2fit_error.h"
+#include "t2fit_reduce.h"
 #include "t2fit_support.h"
 
 namespace {
 
-using t2fit::align_up, t2fit::kBlock, t2fit::count_voxels;
+using t2fit::align_up, t2fit::kBlock, t2fit::count_voxels, t2fit::misaligned;
+using t2fit::finite_bits, t2fit::wave_butterfly, t2fit::TreePasses, t2fit::tree_plan, t2fit::tree_launch;
 
 constexpr int kMaxClass = T2FIT_SEG_MAX_CLASSES, kMaxChan = T2FIT_SEG_MAX_CHANNELS, kMaxRadius = T2FIT_SEG_MAX_RADIUS;
 constexpr int kMaxMoments = 1 + kMaxChan + kMaxChan * (kMaxChan + 1) / 2;  // 15
 constexpr int kVoxPerLane = 4, kVoxPerBlock = kVoxPerLane * kBlock;        // the sums kernel: 1024 voxels per workgroup
-constexpr int kFan = 256;                                                  // values one workgroup of a reduce pass folds
+constexpr int kFan = t2fit::kTreeFan;                                      // values one workgroup of a reduce pass folds
 constexpr int kWaves = kBlock / 64;
 constexpr int kTileZ = 4, kTileY = 4, kTileX = 64;  // the E-step: lanes (64, 4), each walking kTileZ slices
 constexpr size_t kAlign = 256;
 static_assert(kWaves == 4, "the header fixes the tree of four waves");
-static_assert(kFan == kBlock, "a reduce pass folds one value per lane");
-
-__device__ inline bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-__device__ inline double wave_butterfly(double v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_xor(v, s, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(kBlock) void seg_mask_kernel(const float* __restrict__ y, const uint8_t* __restrict__ mask, int n_chan, int64_t n,
                                                           uint8_t* __restrict__ out) {
@@ -142,21 +135,6 @@ template <int C> __global__ __launch_bounds__(kBlock) void seg_sums_kernel(const
     const int m = threadIdx.x;
     partials[((int64_t)k * M + m) * n_blocks + blockIdx.x] = ((rows[0][m] + rows[1][m]) + rows[2][m]) + rows[3][m];
   }
-}
-
-// out[q][b] = the halving sum of in[q][256 b .. 256 b + 255] (zeros beyond n_in); grid (n_out, the number of sums)
-__global__ __launch_bounds__(kBlock) void seg_reduce_kernel(const double* __restrict__ in, int64_t n_in, double* __restrict__ out, int64_t n_out) {
-  __shared__ double s[kFan];
-  const int tid = threadIdx.x;
-  const int64_t q = blockIdx.y, i = (int64_t)blockIdx.x * kFan + tid;
-  s[tid] = i < n_in ? in[q * n_in + i] : 0.0;
-  __syncthreads();
-#pragma unroll
-  for (int h = kFan / 2; h >= 1; h >>= 1) {
-    if (tid < h) s[tid] = s[tid] + s[tid + h];
-    __syncthreads();
-  }
-  if (tid == 0) out[q * n_out + blockIdx.x] = s[0];
 }
 
 struct EstepArgs {
@@ -281,8 +259,6 @@ int flat_check(const std::string& w, int n_class, int64_t n_vox) {
   return T2FIT_OK;
 }
 
-bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 size_t sums_bytes(int n_class, int n_chan, int64_t n_vox) {
   const size_t q = (size_t)n_class * (size_t)(1 + n_chan + n_chan * (n_chan + 1) / 2);
   const size_t nb = (size_t)t2fit::ceil_div<int64_t>(n_vox, kVoxPerBlock);
@@ -384,28 +360,23 @@ int t2fit_seg_sums_dev(const float* p_dev, const float* y_dev, const uint8_t* ma
   const int M = 1 + n_chan + n_chan * (n_chan + 1) / 2, Q = n_class * M;
   const int64_t nb = t2fit::ceil_div<int64_t>(n, kVoxPerBlock);
   hipStream_t st = (hipStream_t)stream;
-  double* buf[2];
-  buf[0] = static_cast<double*>(workspace_dev);
-  buf[1] = reinterpret_cast<double*>(static_cast<char*>(workspace_dev) + align_up((size_t)Q * (size_t)nb * 8, kAlign));
+  double* part = static_cast<double*>(workspace_dev);
   const dim3 grid((unsigned)nb, (unsigned)n_class);
   switch (n_chan) {
-    case 1: launch_sums<1>(grid, st, p_dev, y_dev, mask_dev, n, nb, buf[0]); break;
-    case 2: launch_sums<2>(grid, st, p_dev, y_dev, mask_dev, n, nb, buf[0]); break;
-    case 3: launch_sums<3>(grid, st, p_dev, y_dev, mask_dev, n, nb, buf[0]); break;
-    default: launch_sums<4>(grid, st, p_dev, y_dev, mask_dev, n, nb, buf[0]); break;
+    case 1: launch_sums<1>(grid, st, p_dev, y_dev, mask_dev, n, nb, part); break;
+    case 2: launch_sums<2>(grid, st, p_dev, y_dev, mask_dev, n, nb, part); break;
+    case 3: launch_sums<3>(grid, st, p_dev, y_dev, mask_dev, n, nb, part); break;
+    default: launch_sums<4>(grid, st, p_dev, y_dev, mask_dev, n, nb, part); break;
   }
   T2_HIP(hipGetLastError());
-  // the tree over the partials: passes of 256 until one value is left, at least one; the last one writes the result
-  int64_t n_in = nb;
-  int from = 0;
-  for (;;) {
-    const int64_t n_out = t2fit::ceil_div<int64_t>(n_in, kFan);
-    double* out = n_out == 1 ? sums_out_dev : buf[1 - from];
-    hipLaunchKernelGGL(seg_reduce_kernel, dim3((unsigned)n_out, (unsigned)Q), dim3(kBlock), 0, st, (const double*)buf[from], n_in, out, n_out);
-    T2_HIP(hipGetLastError());
-    if (n_out == 1) break;
-    n_in = n_out, from = 1 - from;
-  }
+  // the tree over the partials: passes of 256 until one value is left, at least one; the last one writes the result.  The
+  // passes read and write the two parts of the workspace (sums_bytes) in turn
+  const size_t second = align_up((size_t)Q * (size_t)nb * 8, kAlign);
+  TreePasses tree;
+  int pass = 0;
+  tree_plan(&tree, nb, [&](int64_t) { return pass++ % 2 == 0 ? (size_t)0 : second; });
+  tree_launch(tree, Q, workspace_dev, sums_out_dev, st);
+  T2_HIP(hipGetLastError());
   return T2FIT_OK;
 }
 

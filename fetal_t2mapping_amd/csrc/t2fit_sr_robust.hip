@@ -23,7 +23,7 @@
 
 namespace {
 
-using t2fit::align_up, t2fit::kBlock, t2fit::count_voxels;
+using t2fit::align_up, t2fit::kBlock, t2fit::count_voxels, t2fit::wave_butterfly, t2fit::finite_bits;
 
 constexpr int kRobustChunk = 4;  // echoes per read of N and the mask, as kSrChunk of the operators
 constexpr int kWaves = kBlock / 64;
@@ -47,14 +47,6 @@ struct RobustArgs {
   double tt, huber, floor2;
   int n_stacks, n_vol, n_slices, min_count;
 };
-
-__device__ inline double wave_butterfly(double v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_xor(v, s, 64);
-  return v;
-}
-
-__device__ inline bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 __global__ __launch_bounds__(kBlock) void sr_robust_sums_kernel(const RobustArgs a) {
   __shared__ double rows[kWaves][2 * kRobustChunk];

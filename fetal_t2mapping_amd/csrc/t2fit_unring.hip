@@ -33,6 +33,7 @@ namespace {
 using t2fit::align_up;
 using t2fit::ceil_div;
 using t2fit::fail;
+using t2fit::misaligned;
 
 constexpr uint32_t kMagic = 0x52553254u;
 constexpr int kTile = 32;        // rows and columns of one matrix instruction
@@ -456,8 +457,6 @@ __global__ __launch_bounds__(t2fit::kBlock) void unring_copy_kernel(const float*
   if (flags[s] == 0 && flags[n_slices + s] != 0) return;
   for (int64_t i = threadIdx.x; i < plane; i += t2fit::kBlock) out[int64_t(s) * plane + i] = x[int64_t(s) * plane + i];
 }
-
-bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 // reads the header back from the device (one copy and one wait on the stream) and checks it against the call (a size or K
 // of 0 is not compared: the rows along one axis read the tables of that axis only)
