@@ -14,7 +14,8 @@ SOURCES = [os.path.join(CSRC, f) for f in ("t2fit_kernels.hip", "t2fit_host.hip"
                                            "t2fit_boot.hip", "t2fit_denoise.hip", "t2fit_resample.hip",
                                            "t2fit_morph.hip", "t2fit_register.hip", "t2fit_n4.hip", "t2fit_sr.hip",
                                            "t2fit_sr_robust.hip", "t2fit_mppca.hip", "t2fit_seg.hip", "t2fit_ffd.hip",
-                                           "t2fit_dict.hip", "t2fit_unring.hip", "t2fit_components.hip", "t2fit_edt.hip")]
+                                           "t2fit_dict.hip", "t2fit_unring.hip", "t2fit_components.hip", "t2fit_edt.hip",
+                                           "t2fit_nnls.hip")]
 ARCH = "gfx950"
 
 

@@ -1,7 +1,7 @@
 """CLI and volume driver: the reference's ``run_t2mapping.py`` surface on the MI355X fit.
 
     python -m fetal_t2mapping_amd.cli --path /data/qMRI --csv 2024083017_17510000.csv \
-        --in_vivo --gaussian --lf --sim 1 [--TEs 114 202 299] [--no_prior] [--solver lbfgsb|lm|loglin|dict] [--gpus N]
+        --in_vivo --gaussian --lf --sim 1 [--TEs 114 202 299] [--no_prior] [--solver lbfgsb|lm|loglin|dict|nnls] [--gpus N]
         [--roi_stats ho:2 --roi_stats jhu:3 --roi_stats feta] [--roi_connectivity 3] [--roi_erosion 1]
         [--bootstrap 100 [--bootstrap_seed 0] [--bootstrap_alpha 0.05] [--bootstrap_noise background|sigma_map|mppca|<float>]]
         [--denoise tv|tv_joint [--denoise_weight 0.1|<c>sigma] [--denoise_dims 2|3] [--denoise_eps 2e-4] [--denoise_iter 200]
@@ -493,6 +493,101 @@ def save_dict_maps(extras, recon_img, bids_path, acq, dirname, sim, analysis):
     return paths
 
 
+NNLS_DEFAULT_MU = 0.03  # t2map.spectrum.DEFAULT_MU: one sweep of the CPU statement on synth.py's phantom (README, "T2 spectra")
+
+
+def parse_nnls_arguments(args):
+    """``--solver nnls`` and its grid: None without it, else ``{'t2': (lo, hi, n), 'mu': mu, 'windows': {name: (lo, hi)},
+    'write_spectrum': bool}``.  ValueError for what does not go together."""
+    given = [f for f in ("nnls_t2", "nnls_mu", "nnls_window") if getattr(args, f) is not None] + (["write_spectrum"] if args.write_spectrum else [])
+    if args.solver != "nnls":
+        if given:
+            raise ValueError(f"--{given[0]} has no effect without --solver nnls")
+        return None
+    if not args.gaussian:
+        raise ValueError("--solver nnls goes with --gaussian only: the spectrum is fitted by (regularised) least squares, which is the "
+                         "Gaussian likelihood")
+    if args.nnls_t2 is None:
+        raise ValueError("--solver nnls needs a T2 grid: --nnls_t2 LO:HI:N, for example 10:2000:40")
+    if args.norm:
+        raise ValueError("--solver nnls cannot be combined with --norm: --nnls_mu is absolute, in the units of the signal basis, and "
+                         "the fractions are scale-free already")
+    if args.bootstrap:
+        raise ValueError("--solver nnls cannot be combined with --bootstrap: the replicas are refitted by the iterative solvers")
+    if args.gpus > 1:
+        raise ValueError("--solver nnls runs on one GPU per volume: --gpus 1")
+    try:
+        lo, hi, n = args.nnls_t2.split(":")
+        lo, hi, n = float(lo), float(hi), int(n)
+    except ValueError:
+        raise ValueError(f"--nnls_t2 {args.nnls_t2!r}: expected LO:HI:N, for example 10:2000:40")
+    if not (0 < lo < hi and np.isfinite(hi)) or not (2 <= n <= 64):
+        raise ValueError("--nnls_t2 needs 0 < LO < HI and N in 2 .. 64")
+    mu = NNLS_DEFAULT_MU if args.nnls_mu is None else float(args.nnls_mu)
+    if not (mu >= 0 and np.isfinite(mu)):
+        raise ValueError("--nnls_mu must be a number that is not negative")
+    windows = {}
+    for text in args.nnls_window or ():
+        try:
+            name, span = text.split("=")
+            wlo, whi = (float(v) for v in span.split(":"))
+        except ValueError:
+            raise ValueError(f"--nnls_window {text!r}: expected NAME=LO:HI, for example csf=1000:2000")
+        if not name.isalnum() or name == "lnT2" or name in windows:
+            raise ValueError(f"--nnls_window {text!r}: NAME must be letters and digits, not lnT2, and given once")
+        if not (0 < wlo <= whi and np.isfinite(whi)):
+            raise ValueError(f"--nnls_window {text!r} needs 0 < LO <= HI")
+        windows[name] = (wlo, whi)
+    if len(windows) > 7:
+        raise ValueError("--nnls_window can be given 7 times at most (the library takes 8 functionals, one is ln T2)")
+    return {"t2": (lo, hi, n), "mu": mu, "windows": windows, "write_spectrum": bool(args.write_spectrum)}
+
+
+def build_spectrum_basis(spec, te_ms):
+    """The basis of :func:`parse_nnls_arguments` for these echo times [ms]."""
+    return t2map.spectrum.spectrum_basis(te_ms, t2map.spectrum.log_grid(*spec["t2"]), spec["mu"], spec["windows"])
+
+
+def _fit_subject_nnls(vols, masks, keep, basis, device, write_spectrum):
+    """:func:`_fit_subject` for ``--solver nnls``: same mask, the maps of t2map.spectrum.fit_volume_nnls; t2 is the
+    geometric-mean T2, k the total amplitude, sigma 0 and res the RMSE.  Returns ``(mask, (t2, k, sigma, res), status, None,
+    extras)`` with ``extras`` the window fractions, nnlsiter, nnlsstatus and, when asked for, t2spectrum."""
+    import torch
+
+    echoes, mask, _ = t2map.stack_mask_flatten(vols, masks, device=device)
+    if keep is not None:
+        mask = mask & keep
+    shape = mask.shape
+    mask_d = torch.from_numpy(mask.astype(np.uint8).reshape(-1)).to(echoes.device)
+    maps, extras = t2map.spectrum.fit_volume_nnls(echoes.reshape((len(vols),) + shape), mask_d.reshape(shape), basis, device=device,
+                                                  spectrum=write_spectrum)
+    torch.cuda.synchronize()
+    out = tuple(getattr(maps, n).cpu().numpy() for n in ("t2", "k", "sigma", "res"))
+    return mask, out, maps.status.cpu().numpy(), None, {n: t.cpu().numpy() for n, t in extras.items()}
+
+
+def save_nnls_maps(extras, recon_img, bids_path, acq, dirname, sim, analysis):
+    """``--solver nnls``: one map per window (tag <NAME>fraction), the outer steps (tag nnlsiter, int32), the solver's status
+    (tag nnlsstatus, int32: -1 outside the mask, 0 done, 1 step limit, 2 breakdown, 3 non-finite sample) and, with
+    --write_spectrum, the 4-D volume of the coefficients (tag t2spectrum: one volume per grid T2, written as NIfTI by this
+    package's own writer), beside the four maps with their geometry and naming rule.  Returns the paths written."""
+    sitk = _sitk()
+    paths = []
+    for name, arr in extras.items():
+        paths.append(boot_map_path(bids_path, acq, dirname, sim, analysis, name))
+        if arr.ndim == 4:
+            from . import nifti
+
+            nifti.WriteImage(nifti.Image(arr, recon_img.GetSpacing(), recon_img.GetOrigin(), recon_img.GetDirection()), paths[-1])
+            continue
+        img = sitk.GetImageFromArray(arr)
+        img.SetSpacing(recon_img.GetSpacing())
+        img.SetOrigin(recon_img.GetOrigin())
+        img.SetDirection(recon_img.GetDirection())
+        sitk.WriteImage(img, paths[-1])
+    return paths
+
+
 def parse_bootstrap_noise(text: str):
     """``--bootstrap_noise``: ``background`` / ``sigma_map`` / ``mppca`` as they are, anything else a noise level > 0."""
     if text in ("background", "sigma_map", "mppca"):
@@ -777,7 +872,8 @@ def _one_block(vols):
 def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field, prior, fast, norm, sim,
                    solver="lbfgsb", precision="f64", device=0, plots=False, plot_seed=None, numpy_legacy=False,
                    roi_specs=(), roi_connectivity=3, roi_erosion=1, bootstrap=0, bootstrap_seed=0, bootstrap_alpha=0.05,
-                   bootstrap_noise="background", denoise=None, reconstruct=None, build_mask=None, noise_map=None, dictionary=None):
+                   bootstrap_noise="background", denoise=None, reconstruct=None, build_mask=None, noise_map=None, dictionary=None,
+                   spectrum=None):
     """run_t2mapping.py:333-479 with the voxel loop on the GPU.  ``plots``: also write the reference's
     convergence-study figures (:465-468) under <prj>/ada/convergence_analysis.  ``roi_specs``: (name, tissue) pairs
     of --roi_stats; each adds a per-region table after the maps (save_roi_csvs).  ``bootstrap`` > 0: that many
@@ -789,10 +885,13 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
     echo and the vial labels are built on the device from the volumes about to be fitted (after the reconstruction, if
     any) and used in place of the recon_1mm_mask / recon_1mm_label files.  ``noise_map``: None, or ``{'radius', 'dims'}`` of
     the MP-PCA noise map, with ``'write': True`` for --write_noise_map (save_noise_maps, of the echoes before any denoising);
-    --bootstrap_noise mppca reads its radius and dims.  ``dictionary``: the table of ``--solver dict`` (parse_dict_arguments)."""
+    --bootstrap_noise mppca reads its radius and dims.  ``dictionary``: the table of ``--solver dict`` (parse_dict_arguments).
+    ``spectrum``: the grid of ``--solver nnls`` (parse_nnls_arguments)."""
     sitk = _sitk()
     if (solver == "dict") != (dictionary is not None):
         raise ValueError("solver 'dict' and a dictionary go together")
+    if (solver == "nnls") != (spectrum is not None):
+        raise ValueError("solver 'nnls' and a spectrum grid go together")
     tes_s = [x / 1000 for x in TEs]
     metadata = metadata[metadata["EchoTime"].isin(tes_s)]
     # more than one process (--gpus N): whole subjects are dealt to the ranks when there are enough of them, otherwise
@@ -818,6 +917,9 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
                          "echoes): give at least as many subjects as ranks, or run on one GPU")
     if dictionary is not None and share_volumes:
         raise ValueError("--solver dict is not run on a volume that is shared by several ranks: give at least as many subjects "
+                         "as ranks, or run on one GPU")
+    if spectrum is not None and share_volumes:
+        raise ValueError("--solver nnls is not run on a volume that is shared by several ranks: give at least as many subjects "
                          "as ranks, or run on one GPU")
     mine = set(subjects if (world == 1 or share_volumes) else
                [subjects[i] for i in dist_subjects_of_rank(len(subjects), rank, world)])
@@ -879,6 +981,9 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
                 if dictionary is not None:
                     mask, maps4, status, extras, dict_maps = _fit_subject_dict(vols, masks, keep, build_dictionary(dictionary, te_eff),
                                                                                device)
+                elif spectrum is not None:
+                    mask, maps4, status, extras, dict_maps = _fit_subject_nnls(vols, masks, keep, build_spectrum_basis(spectrum, te_eff),
+                                                                               device, spectrum["write_spectrum"])
                 else:
                     fitted = _fit_subject(vols, masks, keep, te_eff, fit, fit_params, prior, norm, solver, precision, device,
                                           **({"numpy_legacy": True} if numpy_legacy else {}))
@@ -923,6 +1028,8 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
             save_nifti_maps(t2_map, k_map, sigma_map, res_map, t2map_dirname, recon_img, bids_path, acq, sim, fit)
             if dictionary is not None:
                 save_dict_maps(dict_maps, recon_img, bids_path, acq.iloc[0], t2map_dirname, sim, fit)
+            if spectrum is not None:
+                save_nnls_maps(dict_maps, recon_img, bids_path, acq.iloc[0], t2map_dirname, sim, fit)
             if write_noise:
                 save_noise_maps(noise_maps["sigma"], noise_maps["rank"], recon_img, bids_path, acq.iloc[0], t2map_dirname, sim, fit)
             if phantom:
@@ -975,11 +1082,21 @@ def parse_arguments(argv=None):
     p.add_argument("--TEs", nargs="+", type=int, help="echo times [ms] to fit (default 114/115, 202, 299)")
     p.add_argument("--no_prior", action="store_true", help="k >= S(TE0) instead of the table's lower bound")
     p.add_argument("--norm", action="store_true", help="divide each voxel's samples by their maximum")
-    p.add_argument("--solver", choices=["lbfgsb", "lm", "loglin", "dict"], default="lbfgsb",
+    p.add_argument("--solver", choices=["lbfgsb", "lm", "loglin", "dict", "nnls"], default="lbfgsb",
                    help="lbfgsb: the reference's solver and stop rules (default); lm: converged bounded LM; "
                         "loglin: closed-form weighted log-linear fit (--gaussian only); dict: dictionary matching against "
                         "the table of --dict_t2 / --dict_csf / --dict_file (--gaussian only; the res map is then the RMSE of "
                         "the matched atom, sigma is 0, and every further parameter column and the atom index get a map)")
+    p.add_argument("--nnls_t2", metavar="LO:HI:N",
+                   help="--solver nnls (--gaussian only): a non-negative T2 spectrum over N (2..64) T2 values from LO to HI ms, "
+                        "log-spaced, by regularised non-negative least squares; the t2 map is then the geometric-mean T2, k the "
+                        "total amplitude, sigma 0 and res the RMSE")
+    p.add_argument("--nnls_mu", type=float, metavar="MU",
+                   help=f"--solver nnls: Tikhonov weight, absolute, in the units of the basis exp(-TE/T2) (default {NNLS_DEFAULT_MU})")
+    p.add_argument("--nnls_window", action="append", metavar="NAME=LO:HI",
+                   help="--solver nnls: also write the signal fraction with LO <= T2 <= HI ms as the map <NAME>fraction (up to 7)")
+    p.add_argument("--write_spectrum", action="store_true",
+                   help="--solver nnls: also write the coefficients as a 4-D volume, one volume per grid T2 (tag t2spectrum)")
     p.add_argument("--dict_t2", metavar="LO:HI:N", help="--solver dict: mono-exponential atoms at N T2 values from LO to HI ms, log-spaced")
     p.add_argument("--dict_csf", metavar="T2LONG:NF",
                    help="with --dict_t2: two compartments, (1 - f) exp(-TE/T2) + f exp(-TE/T2LONG), at NF fractions f = 0, 1/NF, .. "
@@ -1069,6 +1186,7 @@ def parse_arguments(argv=None):
     args = p.parse_args(argv)
     try:
         args.dict_args = parse_dict_arguments(args)
+        args.nnls_args = parse_nnls_arguments(args)
     except ValueError as e:
         p.error(str(e))
     args.reconstruct_args = None
@@ -1248,7 +1366,8 @@ def main(argv=None):
                        **({"reconstruct": args.reconstruct_args} if args.reconstruct_args else {}),
                        **({"build_mask": args.build_mask_args} if args.build_mask_args else {}),
                        **({"noise_map": args.noise_map_args} if args.noise_map_args else {}),
-                       **({"dictionary": args.dict_args} if args.dict_args else {}))
+                       **({"dictionary": args.dict_args} if args.dict_args else {}),
+                       **({"spectrum": args.nnls_args} if args.nnls_args else {}))
     finally:
         if world > 1:
             import torch.distributed as dist

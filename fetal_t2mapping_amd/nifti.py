@@ -90,7 +90,7 @@ def _matrix_to_quaternion(R):
     return b, c, d
 
 
-def _parse_header(raw: bytes) -> _Header:
+def _parse_header(raw: bytes, series: bool = False) -> _Header:
     if len(raw) < _HDR:
         raise ValueError("not a NIfTI-1 file: header shorter than 348 bytes")
     for endian in ("<", ">"):
@@ -115,15 +115,17 @@ def _parse_header(raw: bytes) -> _Header:
     shape = [int(d) for d in dim[1:1 + nd]]
     while len(shape) > 3 and shape[-1] == 1:
         shape.pop()
-    if len(shape) > 3:
+    if len(shape) > 3 and not series:
         raise ValueError(f"expected a 3-D volume, file has dimensions {shape}")
+    if len(shape) > 4:
+        raise ValueError(f"expected a 3-D volume or a 4-D series, file has dimensions {shape}")
     while len(shape) < 3:
         shape.append(1)
     if datatype not in _DTYPES:
         raise ValueError(f"unsupported NIfTI datatype code {datatype}")
     h = _Header()
     h.endian = endian
-    h.shape = tuple(shape[::-1])  # (Z, Y, X)
+    h.shape = tuple(shape[::-1])  # (Z, Y, X), or (T, Z, Y, X) for a series
     h.dtype = np.dtype(_DTYPES[datatype]).newbyteorder(endian)
     h.vox_offset = int(vox_offset) if vox_offset >= _HDR else 352
     h.slope, h.inter = (float(slope), float(inter)) if slope not in (0.0,) and np.isfinite(slope) else (1.0, 0.0)
@@ -150,7 +152,8 @@ def _parse_header(raw: bytes) -> _Header:
 
 
 def _build_header(img: Image, dtype: np.dtype) -> bytes:
-    z, y, x = img.arr.shape
+    t_len = img.arr.shape[0] if img.arr.ndim == 4 else 1  # a 4-D array is (T, Z, Y, X): the volumes of a series
+    z, y, x = img.arr.shape[-3:]
     sp = np.array(img.GetSpacing(), np.float64)
     D = np.array(img.GetDirection(), np.float64).reshape(3, 3)
     lps = np.diag([-1.0, -1.0, 1.0])
@@ -164,9 +167,9 @@ def _build_header(img: Image, dtype: np.dtype) -> bytes:
     qb, qc, qd = _matrix_to_quaternion(R)
     hdr = bytearray(352)
     struct.pack_into("<i", hdr, 0, _HDR)
-    struct.pack_into("<8h", hdr, 40, 3, x, y, z, 1, 1, 1, 1)
+    struct.pack_into("<8h", hdr, 40, 4 if img.arr.ndim == 4 else 3, x, y, z, t_len, 1, 1, 1)
     struct.pack_into("<hh", hdr, 70, _CODES[dtype.str[1:]], dtype.itemsize * 8)
-    struct.pack_into("<8f", hdr, 76, qfac, sp[0], sp[1], sp[2], 0.0, 0.0, 0.0, 0.0)
+    struct.pack_into("<8f", hdr, 76, qfac, sp[0], sp[1], sp[2], 1.0 if img.arr.ndim == 4 else 0.0, 0.0, 0.0, 0.0)
     struct.pack_into("<3f", hdr, 108, 352.0, 1.0, 0.0)
     hdr[123] = 2  # xyzt_units: millimetres
     struct.pack_into("<hh", hdr, 252, 1, 1)  # qform_code, sform_code: scanner anatomical
@@ -182,7 +185,7 @@ def _is_gz(path: str) -> bool:
         return f.read(2) == b"\x1f\x8b"
 
 
-def _decode_into(path: str, out: Optional[np.ndarray], want_dtype=None):
+def _decode_into(path: str, out: Optional[np.ndarray], want_dtype=None, series: bool = False):
     """Decode `path`; voxel values go to `out` (flat view, converted to its dtype with the header's
     scaling applied) or to a fresh array of the file's dtype.  Streaming: the compressed file is never
     held decompressed as a whole next to the destination."""
@@ -212,7 +215,7 @@ def _decode_into(path: str, out: Optional[np.ndarray], want_dtype=None):
                 return f.read(nbytes)
 
         head = pull(352)
-        h = _parse_header(head)
+        h = _parse_header(head, series)
         skip = h.vox_offset - len(head)
         if skip > 0:
             pull(skip)
@@ -240,8 +243,11 @@ def _decode_into(path: str, out: Optional[np.ndarray], want_dtype=None):
     return h, out
 
 
-def ReadImage(path: str) -> Image:
-    h, data = _decode_into(path, None)
+def ReadImage(path: str, series: bool = False) -> Image:
+    """The volume at `path`.  A file with more than three dimensions is refused unless ``series=True``, which also reads
+    a 4-D series as ``(T, Z, Y, X)`` (what ``WriteImage`` writes for a 4-D array; the echoes and masks of the pipeline are
+    volumes and never take this path)."""
+    h, data = _decode_into(path, None, series=series)
     return Image(data.reshape(h.shape), h.spacing, h.origin, h.direction)
 
 
@@ -263,8 +269,8 @@ def GetArrayFromImage(img: Image) -> np.ndarray:
 
 def GetImageFromArray(arr) -> Image:
     arr = np.asarray(arr)
-    if arr.ndim != 3:
-        raise ValueError("expected a (Z, Y, X) array")
+    if arr.ndim not in (3, 4):
+        raise ValueError("expected a (Z, Y, X) array or a (T, Z, Y, X) series")
     return Image(arr)
 
 

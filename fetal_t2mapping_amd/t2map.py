@@ -37,6 +37,7 @@ dictionary fit         ``_gpu_dict``       ``_dict`` (and the dictionary builder
 Gibbs-ringing removal  ``_gpu_unring``     ``_unring`` (and the tables, which both read); here as ``unring``
 connected components   ``_gpu_components`` ``_components``; here as ``components``
 distance transform     ``_gpu_edt``        ``_edt`` (and the surface measures' reductions, which are host code); here as ``distance``
+T2 spectra (NNLS)      ``_gpu_nnls``       ``_nnls`` (and the basis and functional builders, which both share); here as ``spectrum``
 N4 bias field          ``_gpu_bias``       ``_bias`` (and the sharpening table, the refinement and the loop, which are host code); here as ``bias``
 =====================  ==================  ===========================================================
 
@@ -68,6 +69,8 @@ from . import _gpu_components as components  # noqa: F401  (a namespace: compone
 #                                               .remove_small, .reassign_small, .seeds, .TILE)
 from . import _gpu_edt as distance  # noqa: F401  (a namespace: distance.nearest, .edt, .fill_nearest, .dilate_mm, .erode_mm, .surface,
 #                                      .surface_distances)
+from . import _gpu_nnls as spectrum  # noqa: F401  (a namespace: spectrum.Basis, .spectrum_basis, .monoexp_basis, .window_functionals,
+#                                        .ln_t2_functional, .log_grid, .pack, .solve, .fit_volume_nnls)
 
 
 def __getattr__(name):

@@ -1462,6 +1462,88 @@ int t2fit_unring_dev(const t2fit_unring_params *params, const void *tables_dev, 
                      float *out_dev, int8_t *shift_dev, float *tv_dev, int64_t *skipped, void *workspace_dev, size_t workspace_bytes,
                      void *stream);
 
+/* ---- Multi-component T2 spectra: regularised non-negative least squares (additive to ABI 5) ---------------------------
+ * A decay y (n_te samples) is decomposed over a basis A[n_te][n_basis] (any table; exp(-TE_i / T2_j) for a T2 spectrum):
+ *   min |A x - y|^2 + mu^2 |x|^2,  x >= 0     (Whittall & MacKay 1989; mu absolute, in the units of A)
+ * by Lawson-Hanson's active-set method on the normal equations (Bro & de Jong 1997).  fetal_t2mapping_amd/_nnls.py states
+ * all of it in numpy; the device output is bit-identical to it.  Everything is float64 with one rounding per operation in
+ * the order written, nothing fused; division and square root are IEEE.  With G = A^T A + mu^2 I (every element a sum over
+ * i ascending from 0.0, then mu * mu added to the diagonal; formed once by t2fit_nnls_pack_host) and the passive set P an
+ * ORDERED LIST, in order of insertion, per voxel:
+ *   1  h_j = sum_i A[i][j] y_i, i ascending from 0.0;  tol = tol_rel max_j |h_j|;  x = 0, P empty, nit = 0
+ *   2  w_j = h_j - sum_{k in P, list order} G[j][P_k] x_k, one product subtracted at a time.  The candidate is the j not in P
+ *      and not banned with the largest w_j > tol, the lowest j on a tie.  None: done.  nit == max_iter: status MAXITER,
+ *      done.  Else nit += 1.
+ *   3  Append j to P (position r).  L[r][c] = (G[P_r][P_c] - sum_{k<c, ascending} L[r][k] L[c][k]) / L[c][c];
+ *      d = G[P_r][P_r] - sum_{k<r} L[r][k]^2.  Unless d > piv_rel G[P_r][P_r]: drop j from P, ban it until the next
+ *      successful insertion, go to 2.  Else L[r][r] = sqrt(d) and the ban list is cleared.
+ *   4  L z = h_P, k ascending: z_r = (h_{P_r} - sum_{k<r} L[r][k] z_k) / L[r][r];  L^T s = z, k DESCENDING:
+ *      s_r = (z_r - sum_{k = p-1 .. r+1} L[k][r] s_k) / L[r][r].
+ *   5  Every s_r > 0: x_P = s, go to 2.
+ *   6  Else alpha = min over {r: not s_r > 0} of x_r / (x_r - s_r) (a 0 / 0 counts as 0), q the first list position that
+ *      attains it.  x_q = 0 exactly, every other x_r + alpha (s_r - x_r); every entry not above 0 leaves P, the order of the
+ *      rest is kept.  P empty: go to 2.  Else the factor of the new list (rows before the first removed position are
+ *      unchanged); a pivot failure here: status BREAKDOWN, done with the current x.  Go to 4.
+ * Outputs, float32 unless noted: x (n_basis planes, optional);  func_m = sum_j W[m][j] x_j and amp = sum_j x_j, all j
+ * ascending from 0.0;  rmse = sqrt((sum_i r_i^2) / n_te) with r_i = y_i - sum_{k in P, list order} A[i][P_k] x_k, one product
+ * at a time, i ascending;  nit and status, int32.  A voxel with mask == 0: all 0, status MASKED.  A voxel with a non-finite
+ * sample: all 0, status NONFINITE.
+ *
+ * The packed basis is one block of t2fit_nnls_pack_bytes bytes, little endian, that t2fit_nnls_pack_host writes on the
+ * host and the caller copies to the device (16-byte aligned) once per basis:
+ *   byte  0  uint32 magic 0x4C4E3254   int32 n_te   int32 n_basis   int32 n_func
+ *   byte 16  float64 mu   uint64 off_a (= 64)   uint64 off_g   uint64 off_w   uint64 bytes (the whole block)   uint64 0
+ *   off_a  float64 [n_te][n_basis]: A as given      off_g  float64 [n_basis][n_basis]: G      off_w  float64 [n_func][n_basis]: W
+ *   every section is padded with zero bytes to a multiple of 16 */
+#define T2FIT_NNLS_MAX_BASIS 64 /* n_basis outside 2 .. this is refused; n_te outside 2 .. T2FIT_MAX_TE likewise */
+#define T2FIT_NNLS_MAX_FUNC 8   /* n_func outside 0 .. this is refused */
+/* Informational, not part of the interface: how this build of the kernel is tuned.  No argument and no result depends on
+ * them; a later build may change them (and what t2fit_nnls_workgroup reports) without an ABI change.  The tests and the
+ * benchmark tool read them to name the voxel counts at which the persistent grid changes behaviour. */
+#define T2FIT_NNLS_CHUNK 64     /* consecutive voxels a wave of the persistent grid takes at a time */
+#define T2FIT_NNLS_MAX_WAVES 8  /* waves of a workgroup at most; each has one voxel in flight */
+#define T2FIT_NNLS_MASKED (-1)
+#define T2FIT_NNLS_OK 0
+#define T2FIT_NNLS_MAXITER 1
+#define T2FIT_NNLS_BREAKDOWN 2
+#define T2FIT_NNLS_NONFINITE 3
+
+typedef struct t2fit_nnls_params {
+    double tol_rel;     /* 1e-10 */
+    double piv_rel;     /* 1e-12 */
+    int32_t max_iter;   /* 0: 3 n_basis */
+    int32_t max_blocks; /* 0: as many workgroups as the device holds; > 0 caps the persistent grid (never changes a result) */
+} t2fit_nnls_params;
+
+int t2fit_nnls_params_default(t2fit_nnls_params *params);
+
+/* Plain arithmetic, no device, informational like the two constants above: the launch shape t2fit_nnls_dev uses for this
+ * n_basis: the waves of a workgroup, its LDS bytes, and the workgroups a CU holds (by 160 KiB of LDS and 32 wave slots).
+ * Refused: a NULL pointer, n_basis outside 2 .. T2FIT_NNLS_MAX_BASIS. */
+int t2fit_nnls_workgroup(int n_basis, int *waves, size_t *lds_bytes, int *workgroups_per_cu);
+
+/* Plain arithmetic, no device. */
+int t2fit_nnls_pack_bytes(int n_te, int n_basis, int n_func, size_t *bytes);
+
+/* No device.  basis: float64 [n_te][n_basis], functionals: float64 [n_func][n_basis] (NULL goes with n_func == 0), on the
+ * host.  Refuses (T2FIT_E_INVALID, with a message) the sizes above, a NULL pointer, `bytes` below t2fit_nnls_pack_bytes, a
+ * mu that is negative or not finite, and a non-finite entry of the basis or of a functional. */
+int t2fit_nnls_pack_host(int n_te, int n_basis, int n_func, const double *basis, double mu, const double *functionals,
+                         void *packed_host, size_t bytes);
+
+/* y_dev: float32, TE-major (n_te, n_vox).  mask_dev: uint8 [n_vox], 0 / not 0, or NULL (every voxel).  x_dev: float32
+ * (n_basis, n_vox) or NULL (not written); func_dev: float32 (n_func, n_vox), may be NULL when the basis has no functional;
+ * amp_dev, rmse_dev float32, nit_dev, status_dev int32, [n_vox] each.  All are written for every voxel.  One kernel on
+ * `stream` (a persistent grid that takes voxels from a counter, allocated and freed in stream order).  Refused before HIP is
+ * touched: a NULL params, y_dev, packed_dev or mandatory output, n_te outside 2 .. T2FIT_MAX_TE, n_vox < 0, a tol_rel or
+ * piv_rel that is negative or not finite, a negative max_iter or max_blocks, y_dev or an output not aligned to 4 bytes,
+ * packed_dev not aligned to 16.  The 64-byte header is then read back from packed_dev (one copy and one wait on `stream`:
+ * the only synchronisation) and refused, before any launch, when its magic, n_te, sizes, mu or offsets are not what
+ * t2fit_nnls_pack_host writes for this n_te.  n_vox == 0 is a no-op. */
+int t2fit_nnls_dev(const t2fit_nnls_params *params, const float *y_dev, int n_te, int64_t n_vox, const uint8_t *mask_dev,
+                   const void *packed_dev, float *x_dev, float *func_dev, float *amp_dev, float *rmse_dev, int32_t *nit_dev,
+                   int32_t *status_dev, void *stream);
+
 /* Kernel timing for benchmarks (no reference counterpart).  With timing enabled (t2fit_set_timing(1)) every
  * t2fit_volume_dev call of this thread records HIP events around its fit kernel on the launch stream.
  * t2fit_kernel_ms(k): duration in milliseconds of the fit kernel launched k timed calls ago (0 = the most recent;
