@@ -24,7 +24,7 @@ from .t2map import seg  # atlas-prior EM tissue segmentation: seg.segment_em, se
 from .t2map import dictionary  # the dictionary-matching fit: dictionary.Dictionary, .monoexp, .biexp, .match, .fit_volume_dict (not in __all__)
 from .t2map import components  # connected components: components.label, .stats, .select, .keep_largest, .remove_small, .reassign_small, .seeds (not in __all__)
 from .t2map import distance  # the exact Euclidean distance transform: distance.nearest, .edt, .fill_nearest, .dilate_mm, .erode_mm, .surface, .surface_distances (not in __all__)
-from .t2map import spectrum  # T2 spectra by regularised NNLS: spectrum.Basis, .spectrum_basis, .solve, .fit_volume_nnls (not in __all__)
+from .t2map import spectrum  # T2 spectra by regularised NNLS: spectrum.Basis, .spectrum_basis, .solve, .solve_chi2, .fit_volume_nnls (not in __all__)
 from .t2map import unring  # Gibbs-ringing removal: unring.unring_volume, .unring_slices, .unring_split, .unring_rows, .unring_tables (not in __all__)
 
 __all__ = ["BootMaps", "BootStats", "RoiStats", "T2Maps", "bootstrap_volume", "compute_residuals", "denoise_tv", "dense_labels",

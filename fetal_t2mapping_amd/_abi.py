@@ -68,10 +68,16 @@ EDT_MAX_AXIS = 2048  # voxels per axis of the distance transform
 NNLS_MAX_BASIS, NNLS_MAX_FUNC = 64, 8
 NNLS_CHUNK, NNLS_MAX_WAVES = 64, 8  # voxels a wave takes at a time; waves of a workgroup at most
 NNLS_MASKED, NNLS_OK, NNLS_MAXITER, NNLS_BREAKDOWN, NNLS_NONFINITE = -1, 0, 1, 2, 3
+NNLS_RULE_FOUND, NNLS_RULE_EXACT, NNLS_RULE_LOW, NNLS_RULE_HIGH = 0, 1, 2, 3  # the chi^2 rule; -1: masked or non-finite
 
 
 class T2FitNnlsParams(C.Structure):
     _fields_ = [("tol_rel", C.c_double), ("piv_rel", C.c_double), ("max_iter", C.c_int32), ("max_blocks", C.c_int32)]
+
+
+class T2FitNnlsChi2Params(C.Structure):
+    _fields_ = [("factor", C.c_double), ("mu_first", C.c_double), ("grow", C.c_double), ("exact_rel", C.c_double), ("mu_exact", C.c_double),
+                ("n_grow", C.c_int32), ("n_bisect", C.c_int32)]
 
 
 class T2FitUnringParams(C.Structure):
@@ -249,6 +255,9 @@ SYMBOLS = [
     ("t2fit_nnls_pack_bytes", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     ("t2fit_nnls_pack_host", C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_double, _P, _P, C.c_size_t]),
     ("t2fit_nnls_dev", C.c_int, [C.POINTER(T2FitNnlsParams), _P, C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("t2fit_nnls_chi2_params_default", C.c_int, [C.POINTER(T2FitNnlsChi2Params)]),
+    ("t2fit_nnls_chi2_dev", C.c_int, [C.POINTER(T2FitNnlsParams), C.POINTER(T2FitNnlsChi2Params), _P, C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P,
+                                      _P, _P, _P, _P, _P, _P, _P]),
     ("t2fit_set_timing", C.c_int, [C.c_int]),
     ("t2fit_set_reserve_cus", C.c_int, [C.c_int]),
     ("t2fit_kernel_ms", C.c_double, [C.c_int]),
@@ -290,9 +299,10 @@ COMPONENT_SYMBOLS = ("t2fit_components_workspace_bytes", "t2fit_components_label
                      "t2fit_components_lut_dev")
 EDT_SYMBOLS = ("t2fit_edt_workspace_bytes", "t2fit_edt_dev", "t2fit_edt_fill_dev")
 NNLS_SYMBOLS = ("t2fit_nnls_params_default", "t2fit_nnls_workgroup", "t2fit_nnls_pack_bytes", "t2fit_nnls_pack_host", "t2fit_nnls_dev")
+NNLS_CHI2_SYMBOLS = ("t2fit_nnls_chi2_params_default", "t2fit_nnls_chi2_dev")
 LOOKED_UP = (ADDITIVE + REGISTER_SYMBOLS + ATLAS_SYMBOLS + N4_SYMBOLS + MI_SYMBOLS + SR_SYMBOLS + SR_SLICE_SYMBOLS + SVR_SYMBOLS
              + SR_ROBUST_SYMBOLS + TVJ_SYMBOLS + MPPCA_SYMBOLS + SEG_SYMBOLS + FFD_SYMBOLS + DICT_SYMBOLS + UNRING_SYMBOLS
-             + COMPONENT_SYMBOLS + EDT_SYMBOLS + NNLS_SYMBOLS)
+             + COMPONENT_SYMBOLS + EDT_SYMBOLS + NNLS_SYMBOLS + NNLS_CHI2_SYMBOLS)
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

@@ -3,7 +3,8 @@
 distribution over a grid of T2 values by Tikhonov-regularised non-negative least squares (Whittall & MacKay 1989),
 ``min |A x - y|^2 + mu^2 |x|^2, x >= 0``, solved by Lawson-Hanson's active-set method on the normal equations (Bro & de Jong
 1997).  Everything is float64 with one rounding per operation in the order written, nothing fused; the device equals it bit
-for bit.  Used by the tests as the definition and by nobody on the hot path.
+for bit.  Used by the tests as the definition and by nobody on the hot path.  The chi^2 rule at the end (``solve_voxel_chi2``,
+``solve_chi2``: what ``t2fit_nnls_chi2_dev`` computes) chooses ``mu`` per voxel by a short, deterministic loop of such solves.
 
 The passive set P is an ordered list (order of insertion) and the Cholesky factor L of G_PP is taken in that order.  Row r
 of L reads only the rows before it, so the factor does not depend on whether a row is kept or recomputed: after a removal
@@ -303,6 +304,137 @@ def solve(echoes, basis, mask=None, tol_rel=TOL_REL, piv_rel=PIV_REL, max_iter=0
             out["x"][:, v] = x.astype(np.float32)
         out["func"][:, v], out["amp"][v], out["rmse"][v] = outputs_voxel(y[:, v], basis, x, P)
         out["nit"][v] = nit
+        if stats is not None:
+            stats.append(st)
+    for k in out:
+        out[k] = out[k].reshape(out[k].shape[:-1] + spatial)
+    return out
+
+
+# ---- the chi^2 rule: the regularisation chosen per voxel ----------------------------------------------------------------
+
+RULE_NONE, RULE_FOUND, RULE_EXACT, RULE_LOW, RULE_HIGH = -1, 0, 1, 2, 3
+CHI2_DEFAULTS = {"factor": 1.02, "mu_first": 1e-3, "grow": 4.0, "n_grow": 6, "n_bisect": 5, "exact_rel": 1e-12, "mu_exact": 0.03}
+
+
+def misfit(y, basis, x, P):
+    """``sum_i r_i^2`` exactly as :func:`outputs_voxel` forms it for the RMSE: ``r = y - sum_{k in P, list order} A[:, k] x_k``,
+    one product at a time, then the squares summed with i ascending from 0.0."""
+    A = basis.A
+    r = np.asarray(y, np.float32).astype(np.float64)
+    for k in P:
+        r = r - A[:, k] * x[k]
+    ss = 0.0
+    for i in range(basis.n_te):
+        ss = ss + r[i] * r[i]
+    return float(ss)
+
+
+def check_chi2(factor, mu_first, grow, n_grow, n_bisect, exact_rel, mu_exact):
+    """The refusals of ``t2fit_nnls_chi2_dev`` for the rule's numbers."""
+    if not (math.isfinite(factor) and factor > 1):
+        raise ValueError(f"factor must be finite and above 1, got {factor}")
+    if not (math.isfinite(grow) and grow > 1):
+        raise ValueError(f"grow must be finite and above 1, got {grow}")
+    if not (math.isfinite(mu_first) and mu_first > 0):
+        raise ValueError(f"mu_first must be finite and above 0, got {mu_first}")
+    if not (math.isfinite(exact_rel) and exact_rel >= 0) or not (math.isfinite(mu_exact) and mu_exact >= 0):
+        raise ValueError(f"exact_rel and mu_exact must be finite and not negative, got {exact_rel} and {mu_exact}")
+    if not (0 <= int(n_grow) <= 64 and 0 <= int(n_bisect) <= 64):
+        raise ValueError(f"n_grow and n_bisect must be 0 .. 64, got {n_grow} and {n_bisect}")
+
+
+def solve_voxel_chi2(y, basis, tol_rel=TOL_REL, piv_rel=PIV_REL, max_iter=0, factor=1.02, mu_first=1e-3, grow=4.0, n_grow=6, n_bisect=5,
+                     exact_rel=1e-12, mu_exact=0.03, stats=None):
+    """One voxel under the chi^2 rule (Whittall & MacKay 1989; include/t2fit.h writes the steps out): ``(x, P, nit, status, mu,
+    ratio, solves, rule)`` with ``x``, ``P`` of the final solve, ``nit`` summed and ``status`` the largest over the ``solves``
+    runs of :func:`solve_voxel`, ``mu`` the chosen weight and ``ratio`` its misfit over the unregularised one (float64 both;
+    0 for EXACT).  ``basis`` must have ``mu == 0``.  ``stats`` (a dict) receives ``ss0``, ``target``, the final bracket ``lo``,
+    ``hi`` and ``trace``, the ``(mu, ss)`` of every run in order."""
+    if basis.mu != 0:
+        raise ValueError(f"the rule owns the weight: the basis must have mu 0, got {basis.mu}")
+    check_chi2(factor, mu_first, grow, n_grow, n_bisect, exact_rel, mu_exact)
+    y32 = np.asarray(y, np.float32)
+    y = y32.astype(np.float64)
+    if not np.all(np.isfinite(y)):
+        return np.zeros(basis.n_basis), [], 0, ST_NONFINITE, 0.0, 0.0, 0, RULE_NONE
+    runs = []
+
+    def S(mu):
+        x, P, nit, status = solve_voxel(y32, basis.with_mu(mu), tol_rel, piv_rel, max_iter)
+        runs.append((mu, misfit(y32, basis, x, P), x, P, nit, status))
+        return runs[-1][1]
+
+    ss0 = S(0.0)
+    yy = 0.0
+    for i in range(basis.n_te):
+        yy = yy + y[i] * y[i]
+    target, lo, hi = float("nan"), 0.0, 0.0
+    if not ss0 > exact_rel * yy:
+        rule, mu = RULE_EXACT, float(mu_exact)
+        S(mu)
+    else:
+        target = factor * ss0
+        mu, hit, g = float(mu_first), False, 0
+        for g in range(int(n_grow) + 1):
+            if S(mu) >= target:
+                hit = True
+                break
+            lo = mu
+            if g < n_grow:
+                mu = mu * grow
+        if not hit:
+            rule = RULE_HIGH
+        elif g == 0:
+            rule = RULE_LOW
+        else:
+            rule, hi = RULE_FOUND, mu
+            for _ in range(int(n_bisect)):
+                mid = math.sqrt(lo * hi)
+                if S(mid) < target:
+                    lo = mid
+                else:
+                    hi = mid
+            mu = math.sqrt(lo * hi)
+            S(mu)
+    _, ss, x, P = runs[-1][:4]
+    if stats is not None:
+        stats.update(ss0=ss0, target=target, lo=lo, hi=hi, trace=[(r[0], r[1]) for r in runs])
+    return (x, P, sum(r[4] for r in runs), max(r[5] for r in runs), mu, 0.0 if rule == RULE_EXACT else ss / ss0, len(runs), rule)
+
+
+def solve_chi2(echoes, basis, mask=None, tol_rel=TOL_REL, piv_rel=PIV_REL, max_iter=0, stats=None, **chi2):
+    """The definition of ``t2fit_nnls_chi2_dev``: the dict of :func:`solve` (from each voxel's final solve; ``nit`` summed and
+    ``status`` the largest over its solves) plus ``mu``, ``ratio`` float32 and ``solves``, ``rule`` int32.  Outside the mask
+    and for a non-finite sample everything is 0, the status MASKED / NONFINITE and the rule -1.  ``chi2``: the rule's numbers
+    (``CHI2_DEFAULTS``).  ``stats`` (a list) receives one dict per fitted voxel."""
+    y = np.ascontiguousarray(echoes, dtype=np.float32)
+    if y.ndim < 1 or y.shape[0] != basis.n_te:
+        raise ValueError(f"the echoes are TE-major with {y.shape[0] if y.ndim else 0} echoes, the basis has {basis.n_te}")
+    unknown = set(chi2) - set(CHI2_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown numbers of the rule: {sorted(unknown)}")
+    spatial = y.shape[1:]
+    y = y.reshape(basis.n_te, -1)
+    n_vox = y.shape[1]
+    m = np.ones(n_vox, bool) if mask is None else np.asarray(mask).reshape(-1) != 0
+    if m.size != n_vox:
+        raise ValueError("mask shape does not match the echoes")
+    out = {"x": np.zeros((basis.n_basis, n_vox), np.float32), "func": np.zeros((basis.n_func, n_vox), np.float32),
+           "amp": np.zeros(n_vox, np.float32), "rmse": np.zeros(n_vox, np.float32), "nit": np.zeros(n_vox, np.int32),
+           "status": np.full(n_vox, ST_MASKED, np.int32), "mu": np.zeros(n_vox, np.float32), "ratio": np.zeros(n_vox, np.float32),
+           "solves": np.zeros(n_vox, np.int32), "rule": np.full(n_vox, RULE_NONE, np.int32)}
+    for v in np.flatnonzero(m):
+        st = {} if stats is not None else None
+        x, P, nit, status, mu, ratio, solves, rule = solve_voxel_chi2(y[:, v], basis, tol_rel, piv_rel, max_iter, stats=st, **chi2)
+        out["status"][v] = status
+        if status == ST_NONFINITE:
+            continue
+        with np.errstate(over="ignore"):
+            out["x"][:, v] = x.astype(np.float32)
+            out["mu"][v], out["ratio"][v] = np.float32(mu), np.float32(ratio)
+        out["func"][:, v], out["amp"][v], out["rmse"][v] = outputs_voxel(y[:, v], basis, x, P)
+        out["nit"][v], out["solves"][v], out["rule"][v] = nit, solves, rule
         if stats is not None:
             stats.append(st)
     for k in out:

@@ -494,12 +494,15 @@ def save_dict_maps(extras, recon_img, bids_path, acq, dirname, sim, analysis):
 
 
 NNLS_DEFAULT_MU = 0.03  # t2map.spectrum.DEFAULT_MU: one sweep of the CPU statement on synth.py's phantom (README, "T2 spectra")
+NNLS_CHI2_FACTOR = 1.02  # --nnls_chi2 without a value: the literature's factor (Whittall & MacKay 1989; DECAES's Chi2Factor)
 
 
 def parse_nnls_arguments(args):
     """``--solver nnls`` and its grid: None without it, else ``{'t2': (lo, hi, n), 'mu': mu, 'windows': {name: (lo, hi)},
-    'write_spectrum': bool}``.  ValueError for what does not go together."""
-    given = [f for f in ("nnls_t2", "nnls_mu", "nnls_window") if getattr(args, f) is not None] + (["write_spectrum"] if args.write_spectrum else [])
+    'write_spectrum': bool}`` and, with ``--nnls_chi2`` only, ``'chi2': {'factor', 'mu_exact'}`` (``'mu'`` is then 0: the rule
+    owns the weight).  ValueError for what does not go together."""
+    given = ([f for f in ("nnls_t2", "nnls_mu", "nnls_window", "nnls_chi2", "nnls_chi2_fallback") if getattr(args, f, None) is not None]
+             + (["write_spectrum"] if args.write_spectrum else []))
     if args.solver != "nnls":
         if given:
             raise ValueError(f"--{given[0]} has no effect without --solver nnls")
@@ -540,7 +543,21 @@ def parse_nnls_arguments(args):
         windows[name] = (wlo, whi)
     if len(windows) > 7:
         raise ValueError("--nnls_window can be given 7 times at most (the library takes 8 functionals, one is ln T2)")
-    return {"t2": (lo, hi, n), "mu": mu, "windows": windows, "write_spectrum": bool(args.write_spectrum)}
+    spec = {"t2": (lo, hi, n), "mu": mu, "windows": windows, "write_spectrum": bool(args.write_spectrum)}
+    factor, fallback = getattr(args, "nnls_chi2", None), getattr(args, "nnls_chi2_fallback", None)
+    if factor is None:
+        if fallback is not None:
+            raise ValueError("--nnls_chi2_fallback has no effect without --nnls_chi2")
+        return spec
+    if args.nnls_mu is not None:
+        raise ValueError("--nnls_chi2 chooses the weight per voxel and cannot be combined with --nnls_mu")
+    if not (factor > 1 and np.isfinite(factor)):
+        raise ValueError("--nnls_chi2 FACTOR must be a number above 1, for example 1.02")
+    if fallback is not None and not (fallback >= 0 and np.isfinite(fallback)):
+        raise ValueError("--nnls_chi2_fallback must be a number that is not negative")
+    spec["mu"] = 0.0  # the rule owns the weight
+    spec["chi2"] = {"factor": float(factor), "mu_exact": NNLS_DEFAULT_MU if fallback is None else float(fallback)}
+    return spec
 
 
 def build_spectrum_basis(spec, te_ms):
@@ -548,10 +565,11 @@ def build_spectrum_basis(spec, te_ms):
     return t2map.spectrum.spectrum_basis(te_ms, t2map.spectrum.log_grid(*spec["t2"]), spec["mu"], spec["windows"])
 
 
-def _fit_subject_nnls(vols, masks, keep, basis, device, write_spectrum):
+def _fit_subject_nnls(vols, masks, keep, basis, device, write_spectrum, chi2=None):
     """:func:`_fit_subject` for ``--solver nnls``: same mask, the maps of t2map.spectrum.fit_volume_nnls; t2 is the
     geometric-mean T2, k the total amplitude, sigma 0 and res the RMSE.  Returns ``(mask, (t2, k, sigma, res), status, None,
-    extras)`` with ``extras`` the window fractions, nnlsiter, nnlsstatus and, when asked for, t2spectrum."""
+    extras)`` with ``extras`` the window fractions, nnlsiter, nnlsstatus, when asked for t2spectrum and, with ``chi2`` (the
+    rule's numbers), nnlsmu, nnlschi2, nnlsrule and nnlssolves."""
     import torch
 
     echoes, mask, _ = t2map.stack_mask_flatten(vols, masks, device=device)
@@ -560,7 +578,7 @@ def _fit_subject_nnls(vols, masks, keep, basis, device, write_spectrum):
     shape = mask.shape
     mask_d = torch.from_numpy(mask.astype(np.uint8).reshape(-1)).to(echoes.device)
     maps, extras = t2map.spectrum.fit_volume_nnls(echoes.reshape((len(vols),) + shape), mask_d.reshape(shape), basis, device=device,
-                                                  spectrum=write_spectrum)
+                                                  spectrum=write_spectrum, **({"chi2": chi2} if chi2 else {}))
     torch.cuda.synchronize()
     out = tuple(getattr(maps, n).cpu().numpy() for n in ("t2", "k", "sigma", "res"))
     return mask, out, maps.status.cpu().numpy(), None, {n: t.cpu().numpy() for n, t in extras.items()}
@@ -568,7 +586,9 @@ def _fit_subject_nnls(vols, masks, keep, basis, device, write_spectrum):
 
 def save_nnls_maps(extras, recon_img, bids_path, acq, dirname, sim, analysis):
     """``--solver nnls``: one map per window (tag <NAME>fraction), the outer steps (tag nnlsiter, int32), the solver's status
-    (tag nnlsstatus, int32: -1 outside the mask, 0 done, 1 step limit, 2 breakdown, 3 non-finite sample) and, with
+    (tag nnlsstatus, int32: -1 outside the mask, 0 done, 1 step limit, 2 breakdown, 3 non-finite sample), with --nnls_chi2 the
+    chosen weight (tag nnlsmu), the misfit ratio reached (nnlschi2), the rule's code (nnlsrule, int32) and the solves (nnlssolves,
+    int32) and, with
     --write_spectrum, the 4-D volume of the coefficients (tag t2spectrum: one volume per grid T2, written as NIfTI by this
     package's own writer), beside the four maps with their geometry and naming rule.  Returns the paths written."""
     sitk = _sitk()
@@ -983,7 +1003,7 @@ def process_t2maps(metadata, bids_path, TEs, fit, fit_params, phantom, low_field
                                                                                device)
                 elif spectrum is not None:
                     mask, maps4, status, extras, dict_maps = _fit_subject_nnls(vols, masks, keep, build_spectrum_basis(spectrum, te_eff),
-                                                                               device, spectrum["write_spectrum"])
+                                                                               device, spectrum["write_spectrum"], spectrum.get("chi2"))
                 else:
                     fitted = _fit_subject(vols, masks, keep, te_eff, fit, fit_params, prior, norm, solver, precision, device,
                                           **({"numpy_legacy": True} if numpy_legacy else {}))
@@ -1093,6 +1113,13 @@ def parse_arguments(argv=None):
                         "total amplitude, sigma 0 and res the RMSE")
     p.add_argument("--nnls_mu", type=float, metavar="MU",
                    help=f"--solver nnls: Tikhonov weight, absolute, in the units of the basis exp(-TE/T2) (default {NNLS_DEFAULT_MU})")
+    p.add_argument("--nnls_chi2", type=float, nargs="?", const=NNLS_CHI2_FACTOR, metavar="FACTOR",
+                   help="--solver nnls: choose the Tikhonov weight per voxel by the chi^2 rule: the weight at which the misfit is "
+                        f"FACTOR (default {NNLS_CHI2_FACTOR}) times the unregularised misfit; not with --nnls_mu.  Also writes the maps "
+                        "nnlsmu (the weight), nnlschi2 (the misfit ratio reached), nnlsrule (0 found, 1 exact fit: the fallback "
+                        "weight, 2 the first weight is already above, 3 the last weight is still below) and nnlssolves")
+    p.add_argument("--nnls_chi2_fallback", type=float, metavar="MU",
+                   help=f"--nnls_chi2: the weight of a voxel whose unregularised fit is exact (default {NNLS_DEFAULT_MU})")
     p.add_argument("--nnls_window", action="append", metavar="NAME=LO:HI",
                    help="--solver nnls: also write the signal fraction with LO <= T2 <= HI ms as the map <NAME>fraction (up to 7)")
     p.add_argument("--write_spectrum", action="store_true",

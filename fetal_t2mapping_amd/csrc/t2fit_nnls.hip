@@ -1,6 +1,6 @@
 // t2fit_nnls.hip -- multi-component T2 spectra by regularised non-negative least squares (include/t2fit.h:
-// t2fit_nnls_params_default, t2fit_nnls_workgroup, t2fit_nnls_pack_bytes, t2fit_nnls_pack_host, t2fit_nnls_dev; fetal_t2mapping_amd/_nnls.py states
-// the result in numpy and the kernel equals it bit for bit).
+// t2fit_nnls_params_default, t2fit_nnls_workgroup, t2fit_nnls_pack_bytes, t2fit_nnls_pack_host, t2fit_nnls_dev, t2fit_nnls_chi2_params_default,
+// t2fit_nnls_chi2_dev; fetal_t2mapping_amd/_nnls.py states the result in numpy and the kernel equals it bit for bit).
 //
 // A wave per voxel.  In the outer step lane j is basis function j (h_j, w_j); in the factor, the two substitutions and the
 // partial step lane r is position r of the passive list (P_r, x_r, row r of L).  G is staged once per workgroup in LDS (its
@@ -17,6 +17,12 @@
 // The grid is persistent: a wave takes 64 consecutive voxels per increment of a counter, writes the voxels outside the
 // mask and the non-finite ones lane-parallel, then fits the rest one after the other.  After the staging barrier no wave
 // waits on another.  No floating-point atomics; every register index is a constant (no scratch).
+//
+// The chi^2 rule (t2fit_nnls_chi2_dev) is the same kernel compiled a second time (nnls_kernel<true>): the wave keeps its
+// voxel -- y, h, tol and sum y^2 -- through a short, bounded sequence of such solves whose weight it chooses from the
+// misfit of the solve before.  G in LDS is A^T A (the header's mu is 0); the weight enters as the wave-uniform mu * mu added
+// to the diagonal element where factor_row reads it, which is the rounding of the packed G of that weight.  Every decision
+// of the rule is taken on values read from one lane, so the control flow stays wave-uniform.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -96,6 +102,12 @@ __device__ __forceinline__ double bcast(double v, int lane) {
   return __hiloint2double(hi, lo);
 }
 
+// a value every lane holds alike, read from the first lane: it, and what is computed from it, can live in scalar registers
+__device__ __forceinline__ double uniform(double v) {
+  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+
 // orders this wave's LDS writes before its later LDS reads by other lanes (LDS serves one wave's accesses in order)
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -119,10 +131,15 @@ __device__ __forceinline__ uint64_t below(int p) { return p >= 64 ? ~uint64_t(0)
 
 // Row r of the factor of G_PP in list order, from the rows before it; j = P_r.  Lane c <= r holds t_c = G[j][P_c]; step k
 // turns t_k into L[r][k] and subtracts its product from every later lane (lane r subtracts the square: the pivot).  False,
-// with L untouched, unless the pivot passes.
+// with L untouched, unless the pivot passes.  kChi2: G is A^T A and m2 = mu * mu is added to its diagonal element as read (lane
+// r's t and the pivot's bound); the lanes before r read G[j][P_c] with P_c != j.
+template <bool kChi2>
 __device__ __forceinline__ bool factor_row(const double* __restrict__ G, double* __restrict__ L, int nb, int lane, int r, int j, int P,
-                                           double piv_rel) {
+                                           double piv_rel, double m2) {
   double t = lane <= r ? G[j * nb + P] : 0.0;
+  if constexpr (kChi2) {
+    if (lane == r) t = t + m2;
+  }
   const int row = tri(lane);
   for (int k = 0; k < r; ++k) {
     const double lk = bcast(t, k) / L[tri(k) + k];
@@ -131,7 +148,9 @@ __device__ __forceinline__ bool factor_row(const double* __restrict__ G, double*
     else if (lane == r) t = t - lk * lk;
   }
   const double d = bcast(t, r);
-  if (!(d > piv_rel * G[j * nb + j])) return false;
+  double gjj = G[j * nb + j];
+  if constexpr (kChi2) gjj = gjj + m2;
+  if (!(d > piv_rel * gjj)) return false;
   if (lane < r) L[tri(r) + lane] = t;
   else if (lane == r) L[tri(r) + r] = sqrt(d);
   wave_lds_sync();
@@ -147,10 +166,22 @@ struct Out {
   int32_t* status;
 };
 
+struct Chi2 {  // the rule's numbers and outputs (nnls_kernel<true>; unused, all zero, by nnls_kernel<false>)
+  double factor, mu_first, grow, exact_rel, mu_exact;
+  int n_grow, n_bisect;
+  float* mu;
+  float* ratio;
+  int32_t* solves;
+  int32_t* rule;
+};
+
+enum : int { kUnregularised, kExactFit, kBracket, kBisect, kChosen };  // what the solve just run was for
+
+template <bool kChi2>
 __global__ __launch_bounds__(64 * kMaxWaves) void nnls_kernel(const float* __restrict__ y, int n_te, int64_t n_vox,
                                                              const uint8_t* __restrict__ mask, const unsigned char* __restrict__ packed,
                                                              double tol_rel, double piv_rel, int max_iter, Out out,
-                                                             unsigned long long* __restrict__ counter) {
+                                                             unsigned long long* __restrict__ counter, Chi2 c2) {
   extern __shared__ double lds[];
   const NnlsHeader* hd = reinterpret_cast<const NnlsHeader*>(packed);
   const int nb = hd->n_basis, n_func = hd->n_func;
@@ -192,6 +223,12 @@ __global__ __launch_bounds__(64 * kMaxWaves) void nnls_kernel(const float* __res
         out.rmse[v] = 0.0f;
         out.nit[v] = 0;
         out.status[v] = masked ? T2FIT_NNLS_MASKED : T2FIT_NNLS_NONFINITE;
+        if constexpr (kChi2) {
+          c2.mu[v] = 0.0f;
+          c2.ratio[v] = 0.0f;
+          c2.solves[v] = 0;
+          c2.rule[v] = -1;
+        }
       }
       todo = __ballot(in && !masked && finite);
     }
@@ -203,127 +240,185 @@ __global__ __launch_bounds__(64 * kMaxWaves) void nnls_kernel(const float* __res
 
       // step 1: lane i holds y_i; h_j = sum_i A[i][j] y_i, tol = tol_rel max |h|
       const double yl = lane < n_te ? double(y[int64_t(lane) * n_vox + v]) : 0.0;
-      double h = 0.0;
+      double h = 0.0, yy = 0.0;
       for (int i = 0; i < n_te; ++i) {
         const double yi = bcast(yl, i);
         if (lane < nb) h = h + A[i * nb + lane] * yi;
+        if constexpr (kChi2) yy = yy + yi * yi;
       }
       const double tol = tol_rel * wave_max(fabs(h));
+      if constexpr (kChi2) yy = uniform(yy);
 
-      int P = 0;        // lane r: the basis function at list position r
-      double xl = 0.0;  // lane r: its coefficient
-      int p = 0, nit = 0, status = T2FIT_NNLS_OK;
-      uint64_t pmask = 0, banned = 0;  // by basis function: in P, banned
+      int P, p, nit, status;  // lane r of P: the basis function at list position r
+      double xl, xj, ss;      // lane r of xl: its coefficient; after a solve x_j on lane j and the misfit
+      // the rule (kChi2): the weight of the solve about to run and what it is for, the bracket, the sums over the solves
+      double mu = 0.0, ss0 = 0.0, target = 0.0, lo = 0.0, hi = 0.0;
+      int stage = kUnregularised, rule = T2FIT_NNLS_RULE_FOUND, g = 0, bisected = 0, solves = 0, nit_sum = 0, status_max = T2FIT_NNLS_OK;
 
-      for (;;) {
-        // step 2: w_j = h_j - sum_{k in P} G[j][P_k] x_k, the largest w_j > tol off P and off the ban list, lowest j on a tie
-        double w = h;
+      for (;;) {  // a solve per pass: one for nnls_kernel<false>, at most n_grow + n_bisect + 3 under the rule
+        const double m2 = kChi2 ? uniform(mu * mu) : 0.0;
+        P = 0;
+        xl = 0.0;
+        p = 0, nit = 0, status = T2FIT_NNLS_OK;
+        uint64_t pmask = 0, banned = 0;  // by basis function: in P, banned
+
+        for (;;) {
+          // step 2: w_j = h_j - sum_{k in P} G[j][P_k] x_k, the largest w_j > tol off P and off the ban list, lowest j on a tie
+          double w = h;
+          for (int k = 0; k < p; ++k) {
+            const int pk = __builtin_amdgcn_readlane(P, k);
+            const double xk = bcast(xl, k);
+            if (lane < nb) w = w - G[pk * nb + lane] * xk;
+          }
+          const bool cand = lane < nb && !((pmask | banned) >> lane & 1) && w > tol;
+          const uint64_t cands = __ballot(cand);
+          if (!cands) break;
+          const double wmax = wave_max(cand ? w : -std::numeric_limits<double>::infinity());
+          const int j = __ffsll(static_cast<unsigned long long>(__ballot(cand && w == wmax))) - 1;
+          if (nit == limit) {
+            status = T2FIT_NNLS_MAXITER;
+            break;
+          }
+          ++nit;
+          // step 3: append j; a failed pivot bans it until the next successful insertion
+          if (lane == p) {
+            P = j;
+            xl = 0.0;
+          }
+          if (!factor_row<kChi2>(G, L, nb, lane, p, j, P, piv_rel, m2)) {
+            banned |= uint64_t(1) << j;
+            continue;
+          }
+          ++p;
+          pmask |= uint64_t(1) << j;
+          banned = 0;
+
+          bool broke = false;
+          for (;;) {
+            // step 4: L z = h_P, k ascending; L^T s = z, k descending
+            double t = __shfl(h, P, 64);
+            const int row = tri(lane);
+            for (int k = 0; k < p; ++k) {
+              const double zk = bcast(t, k) / L[tri(k) + k];
+              if (lane == k) t = zk;
+              else if (lane > k && lane < p) t = t - L[row + k] * zk;
+            }
+            for (int k = p - 1; k >= 0; --k) {
+              const double sk = bcast(t, k) / L[tri(k) + k];
+              if (lane == k) t = sk;
+              else if (lane < k) t = t - L[tri(k) + lane] * sk;
+            }
+            // step 5
+            const bool neg = lane < p && !(t > 0.0);
+            if (!__ballot(neg)) {
+              if (lane < p) xl = t;
+              break;
+            }
+            // step 6: the partial step; the first position that attains alpha becomes 0 exactly, whatever is not above 0 leaves
+            double a = std::numeric_limits<double>::infinity();
+            if (neg) {
+              a = xl / (xl - t);
+              if (a != a) a = 0.0;  // 0 / 0: a new entry whose solution is exactly 0 does not move
+            }
+            const double alpha = wave_min(a);
+            const int q = __ffsll(static_cast<unsigned long long>(__ballot(neg && a == alpha))) - 1;
+            double xn = xl + alpha * (t - xl);
+            if (lane == q) xn = 0.0;
+            const bool keep = lane < p && xn > 0.0;
+            const uint64_t keepmask = __ballot(keep);
+            uint64_t gone = below(p) & ~keepmask;
+            const int first = __ffsll(static_cast<unsigned long long>(gone)) - 1;
+            if (!gone) {  // (cannot happen: position q leaves; keeps the loop bounded whatever the arithmetic does)
+              broke = true;
+              break;
+            }
+            while (gone) {
+              const int r = __ffsll(static_cast<unsigned long long>(gone)) - 1;
+              gone &= gone - 1;
+              pmask &= ~(uint64_t(1) << __builtin_amdgcn_readlane(P, r));
+            }
+            if (keep) {
+              const int at = __popcll(keepmask & below(lane));
+              sx[at] = xn;
+              sp[at] = P;
+            }
+            wave_lds_sync();
+            p = __popcll(keepmask);
+            xl = lane < p ? sx[lane] : 0.0;
+            P = lane < p ? sp[lane] : 0;
+            wave_lds_sync();
+            if (p == 0) break;
+            // the rows before the first removed position are the factor's still: recompute the others in list order
+            for (int r = first; r < p && !broke; ++r)
+              if (!factor_row<kChi2>(G, L, nb, lane, r, __builtin_amdgcn_readlane(P, r), P, piv_rel, m2)) broke = true;
+            if (broke) break;
+          }
+          if (broke) {
+            status = T2FIT_NNLS_BREAKDOWN;
+            break;
+          }
+        }
+
+        // outputs: x_j on lane j, r_i on lane i; the functionals on lanes 0 .. n_func - 1 and amp on lane n_func
+        double ri = yl;
+        xj = 0.0;
         for (int k = 0; k < p; ++k) {
           const int pk = __builtin_amdgcn_readlane(P, k);
           const double xk = bcast(xl, k);
-          if (lane < nb) w = w - G[pk * nb + lane] * xk;
+          if (lane == pk) xj = xk;
+          if (lane < n_te) ri = ri - A[lane * nb + pk] * xk;
         }
-        const bool cand = lane < nb && !((pmask | banned) >> lane & 1) && w > tol;
-        const uint64_t cands = __ballot(cand);
-        if (!cands) break;
-        const double wmax = wave_max(cand ? w : -std::numeric_limits<double>::infinity());
-        const int j = __ffsll(static_cast<unsigned long long>(__ballot(cand && w == wmax))) - 1;
-        if (nit == limit) {
-          status = T2FIT_NNLS_MAXITER;
-          break;
+        ss = 0.0;
+        for (int i = 0; i < n_te; ++i) {
+          const double r = bcast(ri, i);
+          ss = ss + r * r;
         }
-        ++nit;
-        // step 3: append j; a failed pivot bans it until the next successful insertion
-        if (lane == p) {
-          P = j;
-          xl = 0.0;
-        }
-        if (!factor_row(G, L, nb, lane, p, j, P, piv_rel)) {
-          banned |= uint64_t(1) << j;
+        if constexpr (!kChi2) break;
+
+        // the rule: what this solve's misfit decides.  Every lane holds the same ss; lane 0's is read so that the branches
+        // below are the wave's, not the lanes'
+        ss = uniform(ss);
+        ++solves;
+        nit_sum += nit;
+        status_max = status > status_max ? status : status_max;
+        if (stage == kChosen || stage == kExactFit) break;
+        if (stage == kUnregularised) {
+          ss0 = ss;
+          if (!(ss0 > c2.exact_rel * yy)) {  // an exact fit (or a NaN misfit): no target, the fallback weight
+            rule = T2FIT_NNLS_RULE_EXACT;
+            stage = kExactFit;
+            mu = c2.mu_exact;
+            continue;
+          }
+          target = uniform(c2.factor * ss0);
+          mu = c2.mu_first;
+          stage = kBracket;
           continue;
         }
-        ++p;
-        pmask |= uint64_t(1) << j;
-        banned = 0;
-
-        bool broke = false;
-        for (;;) {
-          // step 4: L z = h_P, k ascending; L^T s = z, k descending
-          double t = __shfl(h, P, 64);
-          const int row = tri(lane);
-          for (int k = 0; k < p; ++k) {
-            const double zk = bcast(t, k) / L[tri(k) + k];
-            if (lane == k) t = zk;
-            else if (lane > k && lane < p) t = t - L[row + k] * zk;
+        if (stage == kBracket) {
+          if (!(ss >= target)) {  // (a NaN misfit is no hit)
+            lo = mu;
+            if (g == c2.n_grow) {
+              rule = T2FIT_NNLS_RULE_HIGH;
+              break;
+            }
+            ++g;
+            mu = uniform(mu * c2.grow);
+            continue;
           }
-          for (int k = p - 1; k >= 0; --k) {
-            const double sk = bcast(t, k) / L[tri(k) + k];
-            if (lane == k) t = sk;
-            else if (lane < k) t = t - L[tri(k) + lane] * sk;
-          }
-          // step 5
-          const bool neg = lane < p && !(t > 0.0);
-          if (!__ballot(neg)) {
-            if (lane < p) xl = t;
+          if (g == 0) {
+            rule = T2FIT_NNLS_RULE_LOW;
             break;
           }
-          // step 6: the partial step; the first position that attains alpha becomes 0 exactly, whatever is not above 0 leaves
-          double a = std::numeric_limits<double>::infinity();
-          if (neg) {
-            a = xl / (xl - t);
-            if (a != a) a = 0.0;  // 0 / 0: a new entry whose solution is exactly 0 does not move
-          }
-          const double alpha = wave_min(a);
-          const int q = __ffsll(static_cast<unsigned long long>(__ballot(neg && a == alpha))) - 1;
-          double xn = xl + alpha * (t - xl);
-          if (lane == q) xn = 0.0;
-          const bool keep = lane < p && xn > 0.0;
-          const uint64_t keepmask = __ballot(keep);
-          uint64_t gone = below(p) & ~keepmask;
-          const int first = __ffsll(static_cast<unsigned long long>(gone)) - 1;
-          if (!gone) {  // (cannot happen: position q leaves; keeps the loop bounded whatever the arithmetic does)
-            broke = true;
-            break;
-          }
-          while (gone) {
-            const int r = __ffsll(static_cast<unsigned long long>(gone)) - 1;
-            gone &= gone - 1;
-            pmask &= ~(uint64_t(1) << __builtin_amdgcn_readlane(P, r));
-          }
-          if (keep) {
-            const int at = __popcll(keepmask & below(lane));
-            sx[at] = xn;
-            sp[at] = P;
-          }
-          wave_lds_sync();
-          p = __popcll(keepmask);
-          xl = lane < p ? sx[lane] : 0.0;
-          P = lane < p ? sp[lane] : 0;
-          wave_lds_sync();
-          if (p == 0) break;
-          // the rows before the first removed position are the factor's still: recompute the others in list order
-          for (int r = first; r < p && !broke; ++r)
-            if (!factor_row(G, L, nb, lane, r, __builtin_amdgcn_readlane(P, r), P, piv_rel)) broke = true;
-          if (broke) break;
+          hi = mu;
+          stage = kBisect;
+        } else {  // kBisect: the solve was at the bracket's geometric middle
+          if (ss < target) lo = mu;
+          else hi = mu;
+          ++bisected;
         }
-        if (broke) {
-          status = T2FIT_NNLS_BREAKDOWN;
-          break;
-        }
-      }
-
-      // outputs: x_j on lane j, r_i on lane i; the functionals on lanes 0 .. n_func - 1 and amp on lane n_func
-      double xj = 0.0, ri = yl;
-      for (int k = 0; k < p; ++k) {
-        const int pk = __builtin_amdgcn_readlane(P, k);
-        const double xk = bcast(xl, k);
-        if (lane == pk) xj = xk;
-        if (lane < n_te) ri = ri - A[lane * nb + pk] * xk;
-      }
-      double ss = 0.0;
-      for (int i = 0; i < n_te; ++i) {
-        const double r = bcast(ri, i);
-        ss = ss + r * r;
+        mu = uniform(sqrt(lo * hi));
+        if (bisected == c2.n_bisect) stage = kChosen;
       }
       double acc = 0.0;
       for (int jj = 0; jj < nb; ++jj) {
@@ -336,11 +431,97 @@ __global__ __launch_bounds__(64 * kMaxWaves) void nnls_kernel(const float* __res
       else if (lane == n_func) out.amp[v] = float(acc);
       if (lane == 0) {
         out.rmse[v] = float(sqrt(ss / double(n_te)));
-        out.nit[v] = nit;
-        out.status[v] = status;
+        if constexpr (kChi2) {
+          out.nit[v] = nit_sum;
+          out.status[v] = status_max;
+          c2.mu[v] = float(mu);
+          c2.ratio[v] = rule == T2FIT_NNLS_RULE_EXACT ? 0.0f : float(ss / ss0);
+          c2.solves[v] = solves;
+          c2.rule[v] = rule;
+        } else {
+          out.nit[v] = nit;
+          out.status[v] = status;
+        }
       }
     }
   }
+}
+
+// Both entry points: `chi2` NULL is the fixed weight of the packed block (nnls_kernel<false>), else the rule
+// (nnls_kernel<true>) with its four outputs.  Same refusals, same launch shape, same counter.
+int fit_dev(const std::string& who, const t2fit_nnls_params* params, const t2fit_nnls_chi2_params* chi2, const float* y_dev, int n_te,
+            int64_t n_vox, const uint8_t* mask_dev, const void* packed_dev, const Out& out, float* mu_dev, float* ratio_dev, int32_t* solves_dev,
+            int32_t* rule_dev, void* stream) {
+  if (!params || !y_dev || !packed_dev || !out.amp || !out.rmse || !out.nit || !out.status)
+    return fail(T2FIT_E_INVALID, who + ": params, y_dev, packed_dev, amp_dev, rmse_dev, nit_dev or status_dev is NULL");
+  if (n_te < 2 || n_te > T2FIT_MAX_TE)
+    return fail(T2FIT_E_INVALID, who + ": n_te must be 2 .. " + std::to_string(T2FIT_MAX_TE) + ", got " + std::to_string(n_te));
+  if (n_vox < 0) return fail(T2FIT_E_INVALID, who + ": n_vox is negative");
+  if (!(params->tol_rel >= 0.0 && std::isfinite(params->tol_rel)) || !(params->piv_rel >= 0.0 && std::isfinite(params->piv_rel)))
+    return fail(T2FIT_E_INVALID, who + ": tol_rel and piv_rel must be finite and not negative");
+  if (params->max_iter < 0 || params->max_blocks < 0) return fail(T2FIT_E_INVALID, who + ": max_iter and max_blocks must not be negative");
+  if (chi2) {
+    if (!(std::isfinite(chi2->factor) && chi2->factor > 1.0)) return fail(T2FIT_E_INVALID, who + ": factor must be finite and above 1");
+    if (!(std::isfinite(chi2->grow) && chi2->grow > 1.0)) return fail(T2FIT_E_INVALID, who + ": grow must be finite and above 1");
+    if (!(std::isfinite(chi2->mu_first) && chi2->mu_first > 0.0)) return fail(T2FIT_E_INVALID, who + ": mu_first must be finite and above 0");
+    if (!(std::isfinite(chi2->exact_rel) && chi2->exact_rel >= 0.0) || !(std::isfinite(chi2->mu_exact) && chi2->mu_exact >= 0.0))
+      return fail(T2FIT_E_INVALID, who + ": exact_rel and mu_exact must be finite and not negative");
+    if (chi2->n_grow < 0 || chi2->n_grow > 64 || chi2->n_bisect < 0 || chi2->n_bisect > 64)
+      return fail(T2FIT_E_INVALID, who + ": n_grow and n_bisect must be 0 .. 64");
+  }
+  if (misaligned(y_dev, 4) || misaligned(out.x, 4) || misaligned(out.func, 4) || misaligned(out.amp, 4) || misaligned(out.rmse, 4) ||
+      misaligned(out.nit, 4) || misaligned(out.status, 4) || misaligned(mu_dev, 4) || misaligned(ratio_dev, 4) || misaligned(solves_dev, 4) ||
+      misaligned(rule_dev, 4))
+    return fail(T2FIT_E_INVALID, who + ": y_dev and the outputs must be aligned to 4 bytes");
+  if (misaligned(packed_dev, 16)) return fail(T2FIT_E_INVALID, who + ": packed_dev must be aligned to 16 bytes");
+  if (n_vox == 0) return T2FIT_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  NnlsHeader h;
+  T2_HIP(hipMemcpyAsync(&h, packed_dev, sizeof(h), hipMemcpyDeviceToHost, st));
+  T2_HIP(hipStreamSynchronize(st));
+  if (h.magic != kMagic) return fail(T2FIT_E_INVALID, who + ": packed_dev does not hold a packed basis (magic)");
+  if (h.n_te != n_te)
+    return fail(T2FIT_E_INVALID, who + ": the basis was packed for n_te " + std::to_string(h.n_te) + ", the call has " + std::to_string(n_te));
+  if (!sizes_ok(h.n_te, h.n_basis, h.n_func)) return fail(T2FIT_E_INVALID, who + ": the basis header has sizes out of range");
+  const NnlsHeader want = header_for(h.n_te, h.n_basis, h.n_func);
+  if (h.off_a != want.off_a || h.off_g != want.off_g || h.off_w != want.off_w || h.bytes != want.bytes || !(std::isfinite(h.mu) && h.mu >= 0.0))
+    return fail(T2FIT_E_INVALID, who + ": the basis header is not what t2fit_nnls_pack_host writes");
+  if (h.n_func > 0 && !out.func) return fail(T2FIT_E_INVALID, who + ": func_dev is NULL and the basis has functionals");
+  if (chi2 && h.mu != 0.0)
+    return fail(T2FIT_E_INVALID, who + ": the basis was packed with mu " + std::to_string(h.mu) + "; the rule chooses the weight and needs mu 0");
+
+  int dev = 0, cus = 0;
+  T2_HIP(hipGetDevice(&dev));
+  T2_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  const int waves = waves_for(h.n_basis);
+  const size_t lds = lds_bytes(h.n_basis, waves);
+  const int64_t n_chunks = ceil_div<int64_t>(n_vox, kChunk);
+  int64_t blocks = std::min<int64_t>(ceil_div<int64_t>(n_chunks, waves), int64_t(cus) * per_cu(h.n_basis, waves));
+  if (params->max_blocks > 0) blocks = std::min<int64_t>(blocks, params->max_blocks);
+  const auto kernel = chi2 ? &nnls_kernel<true> : &nnls_kernel<false>;
+  T2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+  unsigned long long* counter = nullptr;
+  T2_HIP(hipMallocAsync(reinterpret_cast<void**>(&counter), sizeof(unsigned long long), st));
+  if (const hipError_t zeroed = hipMemsetAsync(counter, 0, sizeof(unsigned long long), st); zeroed != hipSuccess) {
+    (void)hipFreeAsync(counter, st);
+    T2_HIP(zeroed);
+  }
+  Chi2 c2;
+  std::memset(&c2, 0, sizeof(c2));
+  if (chi2) c2 = Chi2{chi2->factor, chi2->mu_first, chi2->grow, chi2->exact_rel, chi2->mu_exact, chi2->n_grow, chi2->n_bisect,
+                      mu_dev,       ratio_dev,      solves_dev, rule_dev};
+  const dim3 grid(static_cast<unsigned>(blocks)), block(64 * waves);
+  const unsigned char* packed = static_cast<const unsigned char*>(packed_dev);
+  if (chi2)
+    hipLaunchKernelGGL(nnls_kernel<true>, grid, block, lds, st, y_dev, n_te, n_vox, mask_dev, packed, params->tol_rel, params->piv_rel,
+                       params->max_iter, out, counter, c2);
+  else
+    hipLaunchKernelGGL(nnls_kernel<false>, grid, block, lds, st, y_dev, n_te, n_vox, mask_dev, packed, params->tol_rel, params->piv_rel,
+                       params->max_iter, out, counter, c2);
+  const hipError_t e = hipGetLastError();
+  (void)hipFreeAsync(counter, st);
+  T2_HIP(e);
+  return T2FIT_OK;
 }
 
 }  // namespace
@@ -409,57 +590,33 @@ int t2fit_nnls_pack_host(int n_te, int n_basis, int n_func, const double* basis,
   return T2FIT_OK;
 }
 
+int t2fit_nnls_chi2_params_default(t2fit_nnls_chi2_params* chi2) {
+  if (!chi2) return fail(T2FIT_E_INVALID, "t2fit_nnls_chi2_params_default: chi2 is NULL");
+  chi2->factor = 1.02;
+  chi2->mu_first = 1e-3;
+  chi2->grow = 4.0;
+  chi2->exact_rel = 1e-12;
+  chi2->mu_exact = 0.03;
+  chi2->n_grow = 6;
+  chi2->n_bisect = 5;
+  return T2FIT_OK;
+}
+
 int t2fit_nnls_dev(const t2fit_nnls_params* params, const float* y_dev, int n_te, int64_t n_vox, const uint8_t* mask_dev,
                    const void* packed_dev, float* x_dev, float* func_dev, float* amp_dev, float* rmse_dev, int32_t* nit_dev,
                    int32_t* status_dev, void* stream) {
-  if (!params || !y_dev || !packed_dev || !amp_dev || !rmse_dev || !nit_dev || !status_dev)
-    return fail(T2FIT_E_INVALID, "t2fit_nnls_dev: params, y_dev, packed_dev, amp_dev, rmse_dev, nit_dev or status_dev is NULL");
-  if (n_te < 2 || n_te > T2FIT_MAX_TE)
-    return fail(T2FIT_E_INVALID, "t2fit_nnls_dev: n_te must be 2 .. " + std::to_string(T2FIT_MAX_TE) + ", got " + std::to_string(n_te));
-  if (n_vox < 0) return fail(T2FIT_E_INVALID, "t2fit_nnls_dev: n_vox is negative");
-  if (!(params->tol_rel >= 0.0 && std::isfinite(params->tol_rel)) || !(params->piv_rel >= 0.0 && std::isfinite(params->piv_rel)))
-    return fail(T2FIT_E_INVALID, "t2fit_nnls_dev: tol_rel and piv_rel must be finite and not negative");
-  if (params->max_iter < 0 || params->max_blocks < 0) return fail(T2FIT_E_INVALID, "t2fit_nnls_dev: max_iter and max_blocks must not be negative");
-  if (misaligned(y_dev, 4) || misaligned(x_dev, 4) || misaligned(func_dev, 4) || misaligned(amp_dev, 4) || misaligned(rmse_dev, 4) ||
-      misaligned(nit_dev, 4) || misaligned(status_dev, 4))
-    return fail(T2FIT_E_INVALID, "t2fit_nnls_dev: y_dev and the outputs must be aligned to 4 bytes");
-  if (misaligned(packed_dev, 16)) return fail(T2FIT_E_INVALID, "t2fit_nnls_dev: packed_dev must be aligned to 16 bytes");
-  if (n_vox == 0) return T2FIT_OK;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  NnlsHeader h;
-  T2_HIP(hipMemcpyAsync(&h, packed_dev, sizeof(h), hipMemcpyDeviceToHost, st));
-  T2_HIP(hipStreamSynchronize(st));
-  if (h.magic != kMagic) return fail(T2FIT_E_INVALID, "t2fit_nnls_dev: packed_dev does not hold a packed basis (magic)");
-  if (h.n_te != n_te)
-    return fail(T2FIT_E_INVALID, "t2fit_nnls_dev: the basis was packed for n_te " + std::to_string(h.n_te) + ", the call has " + std::to_string(n_te));
-  if (!sizes_ok(h.n_te, h.n_basis, h.n_func)) return fail(T2FIT_E_INVALID, "t2fit_nnls_dev: the basis header has sizes out of range");
-  const NnlsHeader want = header_for(h.n_te, h.n_basis, h.n_func);
-  if (h.off_a != want.off_a || h.off_g != want.off_g || h.off_w != want.off_w || h.bytes != want.bytes || !(std::isfinite(h.mu) && h.mu >= 0.0))
-    return fail(T2FIT_E_INVALID, "t2fit_nnls_dev: the basis header is not what t2fit_nnls_pack_host writes");
-  if (h.n_func > 0 && !func_dev) return fail(T2FIT_E_INVALID, "t2fit_nnls_dev: func_dev is NULL and the basis has functionals");
+  return fit_dev("t2fit_nnls_dev", params, nullptr, y_dev, n_te, n_vox, mask_dev, packed_dev, Out{x_dev, func_dev, amp_dev, rmse_dev, nit_dev, status_dev},
+                 nullptr, nullptr, nullptr, nullptr, stream);
+}
 
-  int dev = 0, cus = 0;
-  T2_HIP(hipGetDevice(&dev));
-  T2_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const int waves = waves_for(h.n_basis);
-  const size_t lds = lds_bytes(h.n_basis, waves);
-  const int64_t n_chunks = ceil_div<int64_t>(n_vox, kChunk);
-  int64_t blocks = std::min<int64_t>(ceil_div<int64_t>(n_chunks, waves), int64_t(cus) * per_cu(h.n_basis, waves));
-  if (params->max_blocks > 0) blocks = std::min<int64_t>(blocks, params->max_blocks);
-  T2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&nnls_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-  unsigned long long* counter = nullptr;
-  T2_HIP(hipMallocAsync(reinterpret_cast<void**>(&counter), sizeof(unsigned long long), st));
-  if (const hipError_t zeroed = hipMemsetAsync(counter, 0, sizeof(unsigned long long), st); zeroed != hipSuccess) {
-    (void)hipFreeAsync(counter, st);
-    T2_HIP(zeroed);
-  }
-  const Out out{x_dev, func_dev, amp_dev, rmse_dev, nit_dev, status_dev};
-  hipLaunchKernelGGL(nnls_kernel, dim3(static_cast<unsigned>(blocks)), dim3(64 * waves), lds, st, y_dev, n_te, n_vox, mask_dev,
-                     static_cast<const unsigned char*>(packed_dev), params->tol_rel, params->piv_rel, params->max_iter, out, counter);
-  const hipError_t e = hipGetLastError();
-  (void)hipFreeAsync(counter, st);
-  T2_HIP(e);
-  return T2FIT_OK;
+int t2fit_nnls_chi2_dev(const t2fit_nnls_params* params, const t2fit_nnls_chi2_params* chi2, const float* y_dev, int n_te, int64_t n_vox,
+                        const uint8_t* mask_dev, const void* packed_dev, float* x_dev, float* func_dev, float* amp_dev, float* rmse_dev,
+                        int32_t* nit_dev, int32_t* status_dev, float* mu_dev, float* ratio_dev, int32_t* solves_dev, int32_t* rule_dev,
+                        void* stream) {
+  if (!chi2 || !mu_dev || !ratio_dev || !solves_dev || !rule_dev)
+    return fail(T2FIT_E_INVALID, "t2fit_nnls_chi2_dev: chi2, mu_dev, ratio_dev, solves_dev or rule_dev is NULL");
+  return fit_dev("t2fit_nnls_chi2_dev", params, chi2, y_dev, n_te, n_vox, mask_dev, packed_dev,
+                 Out{x_dev, func_dev, amp_dev, rmse_dev, nit_dev, status_dev}, mu_dev, ratio_dev, solves_dev, rule_dev, stream);
 }
 
 }  // extern "C"

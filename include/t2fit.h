@@ -1544,6 +1544,54 @@ int t2fit_nnls_dev(const t2fit_nnls_params *params, const float *y_dev, int n_te
                    const void *packed_dev, float *x_dev, float *func_dev, float *amp_dev, float *rmse_dev, int32_t *nit_dev,
                    int32_t *status_dev, void *stream);
 
+/* ---- The chi^2 rule: the regularisation chosen per voxel (additive to ABI 5) ------------------------------------------------
+ * The weight that suits a voxel depends on its signal-to-noise ratio, so mu is raised per voxel until the misfit is a set
+ * factor above the unregularised misfit (Whittall & MacKay 1989; Prasloski 2012; DECAES's Chi2Factor).  Below, S(mu) is
+ * the fit above with G = A^T A + mu^2 I (mu * mu added to the diagonal elements of A^T A: the G that t2fit_nnls_pack_host
+ * forms for that mu, bit for bit) and ss its misfit sum_i r_i^2 as formed for the RMSE.  Everything is float64, one rounding
+ * per operation in the order written; fetal_t2mapping_amd/_nnls.py (solve_voxel_chi2) states it and the device output is
+ * bit-identical.  Per voxel inside the mask, with finite samples:
+ *   1  S(0) gives ss0;  yy = sum_i y_i^2, i ascending from 0.0.  Unless ss0 > exact_rel yy (an exact fit has no target):
+ *      rule EXACT, the result is that of S(mu_exact), the weight mu_exact, the ratio 0.
+ *   2  target = factor ss0, lo = 0, mu = mu_first.  For g = 0 .. n_grow: run S(mu); ss >= target is a hit and ends the
+ *      loop (a NaN ss is none); else lo = mu and, if g < n_grow, mu = mu grow.  A hit at g == 0: rule LOW, the result is
+ *      that of S(mu_first).  No hit: rule HIGH, the result is that of the last S run.
+ *   3  Any other hit: hi = mu.  n_bisect times: mid = sqrt(lo hi), run S(mid), ss < target gives lo = mid, otherwise
+ *      hi = mid.  The weight is sqrt(lo hi), the result that of S at it, rule FOUND.
+ * x, func, amp and rmse are those of the final S;  mu_dev float32 of the weight;  ratio_dev float32 of ss_final / ss0 (0 for
+ * EXACT);  solves_dev int32, the S runs above (2 for EXACT and LOW, n_grow + 2 for HIGH, g + n_bisect + 3 for FOUND);
+ * nit_dev the sum of nit and status_dev the largest status over those runs;  rule_dev int32.  A voxel outside the mask or
+ * with a non-finite sample: everything 0, status MASKED / NONFINITE, rule -1.
+ *
+ * The kernel is t2fit_nnls_dev's compiled a second time: same launch shape and LDS (t2fit_nnls_workgroup), same persistent
+ * grid; a wave keeps its voxel through all its solves. */
+#define T2FIT_NNLS_RULE_FOUND 0 /* the target was bracketed and bisected */
+#define T2FIT_NNLS_RULE_EXACT 1 /* the unregularised fit is exact: mu_exact */
+#define T2FIT_NNLS_RULE_LOW 2   /* mu_first exceeds the target already: mu_first */
+#define T2FIT_NNLS_RULE_HIGH 3  /* the largest weight of the bracket stays below the target: that weight */
+
+typedef struct t2fit_nnls_chi2_params {
+    double factor;    /* 1.02: the misfit aimed at, over the unregularised one */
+    double mu_first;  /* 1e-3: the first weight of the bracket */
+    double grow;      /* 4: the bracket's growth per step */
+    double exact_rel; /* 1e-12: ss0 <= exact_rel sum y^2 is an exact fit */
+    double mu_exact;  /* 0.03: the weight of an exact fit */
+    int32_t n_grow;   /* 6: growth steps at most (the bracket ends at mu_first grow^n_grow) */
+    int32_t n_bisect; /* 5: bisections of the bracket, geometric */
+} t2fit_nnls_chi2_params;
+
+int t2fit_nnls_chi2_params_default(t2fit_nnls_chi2_params *chi2);
+
+/* Arguments as t2fit_nnls_dev; mu_dev, ratio_dev float32 and solves_dev, rule_dev int32, [n_vox] each, are mandatory and
+ * written for every voxel.  Refused before HIP is touched: everything t2fit_nnls_dev refuses, a NULL chi2 or new output
+ * (or one not aligned to 4 bytes), a factor or grow that is not finite and above 1, a mu_first that is not finite and above
+ * 0, an exact_rel or mu_exact that is negative or not finite, n_grow or n_bisect outside 0 .. 64.  After the header
+ * read-back also a header whose mu is not 0: the rule owns the weight and the block's G must be A^T A. */
+int t2fit_nnls_chi2_dev(const t2fit_nnls_params *params, const t2fit_nnls_chi2_params *chi2, const float *y_dev, int n_te,
+                        int64_t n_vox, const uint8_t *mask_dev, const void *packed_dev, float *x_dev, float *func_dev,
+                        float *amp_dev, float *rmse_dev, int32_t *nit_dev, int32_t *status_dev, float *mu_dev, float *ratio_dev,
+                        int32_t *solves_dev, int32_t *rule_dev, void *stream);
+
 /* Kernel timing for benchmarks (no reference counterpart).  With timing enabled (t2fit_set_timing(1)) every
  * t2fit_volume_dev call of this thread records HIP events around its fit kernel on the launch stream.
  * t2fit_kernel_ms(k): duration in milliseconds of the fit kernel launched k timed calls ago (0 = the most recent;
