@@ -58,6 +58,47 @@ def case(shape, kind="rows"):
     return vol, mask
 
 
+# The min/max and histogram kernels stride over the voxels with at most kMaxGrid = 1024 workgroups of 256 threads, sized
+# for 8 voxels per thread (csrc/t2fit_n4.hip: stride_grid).  Past 1024 x 2048 voxels the grid stops growing, a thread
+# makes a ninth trip, and the final kernel reads all 1024 partials.
+CAPPED_GRID_VOXELS = 1024 * 2048
+CAPPED_N = CAPPED_GRID_VOXELS + 2049
+
+
+@functools.lru_cache(maxsize=None)
+def capped_case():
+    """``(u, M)`` of a flat volume of CAPPED_N voxels, as ``log_image`` makes them from a volume with some voxels <= 0 and a
+    mask of about 1 %: the smallest and the largest value inside M, and the last voxel, lie past CAPPED_GRID_VOXELS, where
+    only a ninth trip of the kernels' loops reads them."""
+    n = CAPPED_N
+    rng = np.random.default_rng(n)
+    vol = (200.0 + 100.0 * rng.random(n)).astype(np.float32)
+    vol[rng.random(n) < 0.05] = 0.0
+    mask = (rng.random(n) < 0.01).astype(np.uint8)
+    vol[CAPPED_GRID_VOXELS + 7], vol[n - 1] = 150.0, 350.0
+    mask[CAPPED_GRID_VOXELS + 7], mask[n - 1] = 1, 1
+    u, m = _bias.log_image(vol.reshape(1, 1, n), mask.reshape(1, 1, n))
+    for a in (u, m):
+        a.setflags(write=False)
+    return u, m
+
+
+@functools.lru_cache(maxsize=None)
+def check_capped():
+    """The conditions on :func:`capped_case`, with numpy alone; returns ``(lo, hi, slope)`` of the statement."""
+    u, m = capped_case()
+    inside = np.flatnonzero(m.ravel())
+    values = u.ravel()[inside]
+    assert u.shape == (1, 1, CAPPED_N) and -(-CAPPED_N // 2048) > 1024 and 15000 < inside.size < 25000
+    assert inside[-1] == CAPPED_N - 1 and np.count_nonzero(inside >= CAPPED_GRID_VOXELS) >= 10
+    lo, hi = _bias.minmax(u, m)
+    for extreme in (lo, hi):  # one voxel holds it, in the tail
+        at = inside[values == extreme]
+        assert at.size == 1 and at[0] >= CAPPED_GRID_VOXELS
+    assert (lo, hi) == (np.float32(np.log(150.0)), np.float32(np.log(350.0))) and np.all(u.ravel()[m.ravel() == 0] == 0)
+    return lo, hi, _bias.slope_of(lo, hi)
+
+
 def lattice_of(side, seed=0):
     return np.random.default_rng(1000 + side + seed).normal(0.0, 0.1, (side,) * 3)
 

@@ -35,14 +35,50 @@ def named(name, n_f, n_m):
     return MI.inputs(name, n_f) + MI.moving_range(name, n_m)
 
 
+# More tiles than the histogram kernel launches workgroups (mi_cases.HIST_GRID = 2048): a workgroup walks ``tile +=
+# gridDim.x``, and as 2048 is no multiple of 17 (or 1) rows of tiles, its next tile lies in another plane and another group
+# of rows.  130 x 17 = 2210 tiles whose last one per plane holds a single row; 8840: four trips, five for some; ny = 1:
+# three of the four waves idle on every trip.
+CAPPED_SHAPES = ((130, 65, 5), (520, 65, 5), (2100, 1, 3))
+
+
+def tile_index(shape):
+    """int64 ``[nz, ny, 1]``: the tile of four rows of one plane every fixed voxel lies in, as the kernels count them."""
+    tiles_y = -(-shape[1] // 4)
+    return (np.arange(shape[0])[:, None] * tiles_y + np.arange(shape[1])[None, :] // 4)[:, :, None]
+
+
 @functools.lru_cache(maxsize=None)
-def shaped(shape, n_f=32):
+def shaped(shape, n_f=32, cover=False):
     """A random case on a fixed grid of ``shape`` against a moving volume two voxels larger, slightly turned: ``(bins,
-    moving, A, fixed mask, moving mask)``."""
-    mshape = tuple(n + 2 for n in shape)
-    _, moving, a, fmask, mmask = K._centred_case(51 + sum(shape), shape, mshape, angles=(1.0, -0.8, 1.2), shift=(0.2, -0.3, 0.1))
+    moving, A, fixed mask, moving mask)``.  ``cover``: for a long thin grid.  The moving grid's voxels are 0.9 mm against
+    1.2 mm along z and it stands 4 degrees about y to the fixed one, so two voxels more and a turn of a degree leave the
+    far planes outside; here the moving volume covers the fixed one in millimetres with a margin of one to two voxels, and
+    the transform turns by those 4 degrees and a fiftieth of a degree more."""
+    mshape, angles = tuple(n + 2 for n in shape), (1.0, -0.8, 1.2)
+    if cover:
+        mshape = (int(np.ceil(shape[0] * 1.2 / 0.9)) + 2, int(np.ceil(shape[1] * 1.1 / 1.0)) + 3, int(np.ceil(shape[2] * 1.0 / 1.1)) + 3)
+        angles = (0.02, 4.01, -0.02)
+    _, moving, a, fmask, mmask = K._centred_case(51 + sum(shape), shape, mshape, angles=angles, shift=(0.2, -0.3, 0.1))
     bins = np.random.default_rng(7 + sum(shape)).integers(0, n_f, shape).astype(np.uint8)
     return bins, moving, a, fmask, mmask
+
+
+@functools.lru_cache(maxsize=None)
+def check_capped(shape, side, n_f=7, n_m=9):
+    """What makes a capped shape worth running, asserted with the statement alone: more tiles than workgroups, and with the
+    fixed mask zeroed in the tiles of the first trip the statement's histogram is neither zero nor the whole one.  Returns
+    the number of tiles."""
+    bins, moving, a, fmask, mmask = shaped(shape, cover=True)
+    lo_m, scale_m = G.moving_bin_range(moving, mmask, n_m)
+    phi = lattice(side, 0, 1.2)
+    n_tiles = shape[0] * -(-shape[1] // 4)
+    assert n_tiles > MI.HIST_GRID
+    late = np.where(tile_index(shape) < MI.HIST_GRID, 0, fmask).astype(np.uint8)
+    assert 0 < np.count_nonzero(late) < np.count_nonzero(fmask)
+    h = F.joint_histogram(bins, moving, a, phi, n_f, n_m, lo_m, scale_m, late, mmask)
+    assert h.any() and not np.array_equal(h, F.joint_histogram(bins, moving, a, phi, n_f, n_m, lo_m, scale_m, fmask, mmask))
+    return n_tiles
 
 
 def normal_table(n_f, n_m):

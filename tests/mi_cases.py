@@ -12,22 +12,29 @@ from fetal_t2mapping_amd import _register as G
 from fetal_t2mapping_amd import _resample as R
 
 BIN_PAIRS = ((1, 5), (7, 9), (32, 32), (64, 64))  # (n_f, n_m): the smallest, two odd ones, the default, the largest
-HOST_CASES = ("prime", "bricks", "empty_bricks", "outside", "nothing", "fixed_1x1x1", "fixed_9x6x65", "half_rim", "integer")
+HOST_CASES = ("prime", "bricks", "empty_bricks", "outside", "nothing", "fixed_1x1x1", "fixed_9x6x65", "half_rim", "integer",
+              "capped2_thin")  # ("capped2" with a fixed mask of 4 %: the reference is a Python loop per voxel)
 GPU_CASES = ("prime", "bricks", "empty_bricks", "outside", "nothing", "fixed_1x1x1", "fixed_8x4x64", "fixed_9x6x65", "half_rim",
              "tail257")
 CONTENTION = ("constant", "lanes", "brick")
 ONE = 1 << 30  # a weight of 1.0 in the histogram's units
+# More bricks than workgroups: the histogram kernel walks ``brick += gridDim.x`` and flushes its table once at the end.
+# {name: (bricks along z, y, x)}; 'capped2_constant' is "capped2" with a moving volume of one value (below).
+CAPPED = {"capped2": (9, 258, 1), "capped5": (33, 258, 1)}
+HIST_GRID = 2048  # kHistGrid of csrc/t2fit_register.hip, and the kHistGrid of csrc/t2fit_ffd.hip over its tiles
 
 
 @functools.lru_cache(maxsize=None)
 def inputs(name, n_f):
     """``(bins, moving, A, fixed mask, moving mask)`` of a named case, a layout case of atlas_cases (64 fixed bins, whatever
-    ``n_f``: a byte above n_f - 1 counts as n_f - 1) or 'constant' (the "bricks" case with a moving volume of one value)."""
+    ``n_f``: a byte above n_f - 1 counts as n_f - 1), 'constant' (the "bricks" case with a moving volume of one value) or
+    'capped2_constant' (the same on "capped2")."""
     if name in ("lanes", "brick"):
         return AC.layout_case(name)
-    if name == "constant":
-        _, moving, a, fmask, mmask = K.case("bricks")
-        return AC.bins_of("bricks", n_f), np.full(moving.shape, 417.25, np.float32), a, fmask, mmask
+    if name in ("constant", "capped2_constant"):
+        of = "bricks" if name == "constant" else "capped2"
+        _, moving, a, fmask, mmask = K.case(of)
+        return AC.bins_of(of, n_f), np.full(moving.shape, 417.25, np.float32), a, fmask, mmask
     _, moving, a, fmask, mmask = K.case(name)
     return AC.bins_of(name, n_f), moving, a, fmask, mmask
 
@@ -46,6 +53,41 @@ def statement_hist(name, n_f, n_m):
     h = G.joint_histogram(bins, moving, a, n_f, n_m, lo_m, scale_m, fmask, mmask)
     h.setflags(write=False)
     return h
+
+
+def brick_index(shape):
+    """int64 ``shape``: the brick every fixed voxel lies in, bricks counted in ``(bz, by, bx)`` order as the kernels do."""
+    _, nby, nbx = G.brick_counts(shape)
+    iz, iy, ix = np.indices(shape, sparse=True)
+    return ((iz // G.BZ) * nby + iy // G.BY) * nbx + ix // G.BX
+
+
+@functools.lru_cache(maxsize=None)
+def counted(name):
+    """How many voxels of a named case count (register_cases.counted_voxels: no histogram, no sums)."""
+    return int(K.counted_per_slab("capped2" if name == "capped2_constant" else name).sum())
+
+
+@functools.lru_cache(maxsize=None)
+def check_capped(name, n_f=7, n_m=9):
+    """What makes a capped case worth running, asserted with the statement alone: it has more bricks than the kernel has
+    workgroups, and the bricks a workgroup reaches on its second (for "capped5": also its third) trip change the histogram
+    -- with the fixed mask zeroed in the bricks of the first trip(s) the statement's histogram is neither zero nor the
+    whole one.  Returns the number of bricks."""
+    bins, moving, a, fmask, mmask = inputs(name, n_f)
+    lo_m, scale_m = moving_range(name, n_m)
+    counts = G.brick_counts(bins.shape)
+    n_bricks = int(np.prod(counts))
+    assert counts == CAPPED[name] and n_bricks > HIST_GRID, (name, counts)
+    whole = statement_hist(name, n_f, n_m)
+    brick = brick_index(bins.shape)
+    for trips in (1, 2) if name == "capped5" else (1,):
+        assert n_bricks > trips * HIST_GRID  # ("capped5" stays past the cap if the cap is doubled)
+        late = np.where(brick < trips * HIST_GRID, 0, fmask).astype(np.uint8)
+        h = G.joint_histogram(bins, moving, a, n_f, n_m, lo_m, scale_m, late, mmask)
+        assert h.any() and not np.array_equal(h, whole), (name, trips)
+        assert int(K.counted_per_slab(name)[trips * HIST_GRID:].sum()) > 1000
+    return n_bricks
 
 
 @functools.lru_cache(maxsize=None)

@@ -123,6 +123,8 @@ def loop_window_sum(a, r, dims):
 # between Jacobi's and LAPACK's eigenvalues; none of these cases has one: the smallest |b - a| / a, 'margin', is asserted)
 REF_CASES = [((6, 1, 14, 16), 2, 2, 11), ((3, 2, 9, 10), 2, 1, 12), ((4, 5, 7, 8), 3, 1, 13), ((8, 1, 12, 12), 2, 2, 14),
              ((2, 1, 7, 7), 2, 1, 15)]
+# .. and the echo counts in between and above: 5 and 7 (device kernels of their own), 9, 12 and 16 (the generic ones)
+REF_CASES += [((m, 3, 6, 8), 3, 1, 100 + m) for m in (5, 7, 9, 12, 16)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -148,6 +150,10 @@ GPU_CASES = [(3, 3, 3, 3, 3, 1),       # one centre
              (16, 5, 9, 13, 3, 1),     # the generic kernel at the documented maximum
              (3, 2, 64, 128, 2, 3)]    # tile-aligned
 BOTH_ESTIMATORS = [(6, 4, 37, 70, 2, 2), (8, 9, 11, 67, 3, 1)]
+# Every echo count: the device compiles its two kernels once per M = 2 .. 8 and once more for 9 .. 16.  The centres of each
+# case (544, 280 and 80) fill more than one wave and end in a ragged one.
+EVERY_M = ([(m, 2, 6, 70, 2, 1) for m in range(2, 9)] + [(m, 4, 6, 37, 3, 1) for m in range(9, MAX_TE + 1)]
+           + [(12, 2, 9, 12, 2, 2), (16, 2, 9, 12, 2, 2)])
 
 
 @functools.lru_cache(maxsize=None)

@@ -152,6 +152,27 @@ def _three_pass_case():
     return fixed, moving, a, fmask, mmask
 
 
+def _capped_case(seed, fshape):
+    """A fixed volume thin in x with more bricks than the joint histogram launches workgroups, under a moving volume that
+    covers it with a margin of one to two voxels and is slightly turned.  Both are measured in millimetres: the moving
+    grid of ``_centred_case`` has voxels of 0.9 mm against 1.2 mm along z and stands 4 degrees about y to the fixed one,
+    so the moving volume has more voxels along z and y, and the transform turns by 4 degrees about y and a twentieth of a
+    degree more about every axis.  A turn of whole degrees would carry the ends of a volume three voxels wide outside,
+    and the late bricks (the high z) would hold no voxel that counts."""
+    mshape = (int(np.ceil(fshape[0] * 1.2 / 0.9)) + 2, int(np.ceil(fshape[1] * 1.1 / 1.0)) + 3, 5)
+    return _centred_case(seed, fshape, mshape, angles=(0.05, 4.02, -0.04), shift=(0.2, -0.3, 0.1))
+
+
+def _thinned(out, seed, density=0.04):
+    """A case with its fixed mask thinned to ``density``, the first and the last brick left as they are (as in
+    "three_pass"): for a reference that is a Python loop per voxel."""
+    fixed, moving, a, fmask, mmask = out
+    thin = fmask * (np.random.default_rng(seed).random(fmask.shape) < density).astype(np.uint8)
+    z, y = (fmask.shape[0] - 1) // 8 * 8, (fmask.shape[1] - 1) // 4 * 4  # where the last brick of 64 x 4 x 8 begins (nx <= 64)
+    thin[:8, :4], thin[z:, y:] = fmask[:8, :4], fmask[z:, y:]
+    return fixed, moving, a, thin, mmask
+
+
 @functools.lru_cache(maxsize=None)
 def case(name):
     """(fixed, moving, A, fixed mask, moving mask) of a named case; the arrays are shared and must not be written."""
@@ -177,6 +198,13 @@ def case(name):
         out = _centred_case(34, (5, 1027, 7), (9, 640, 11), angles=(0.3, -0.2, 0.25), along_y=-270.0)
     elif name == "three_pass":
         out = _three_pass_case()
+    # more bricks than the joint histogram's 2048 workgroups: a workgroup walks several before it flushes its table
+    elif name == "capped2":  # 9 x 258 x 1 = 2322 bricks: 274 workgroups take a second one
+        out = _capped_case(44, (65, 1030, 3))
+    elif name == "capped5":  # 33 x 258 x 1 = 8514 bricks: every workgroup takes four, 322 a fifth; past twice the cap too
+        out = _capped_case(45, (257, 1030, 3))
+    elif name == "capped2_thin":
+        out = _thinned(case("capped2"), 46)
     elif name in ("moving_x1", "moving_y1", "moving_z1"):
         out = _thin_moving_case("xyz".index(name[7]))
     elif name == "fixed_1x1x1":

@@ -1,9 +1,9 @@
 """The N4 bias-field correction's device half (csrc/t2fit_n4.hip) against its numpy statement
 (fetal_t2mapping_amd/_bias.py): every step bit for bit where no transcendental is involved (mask, min/max, histogram,
 omega, delta, lattice, field, the new u), within 1 float32 ulp through log and exp, the convergence sums within the
-documented error of expm1; every step against a second call; raw calls on a caller's stream with a NaN workspace and
-buffers 4 bytes past a 256-byte boundary; whole calls; the recovery of a known field; recon.py --n4.
-tests/test_bias_host.py covers what needs no device."""
+documented error of expm1; every step against a second call; min/max and histogram of more voxels than their grid grows
+for; raw calls on a caller's stream with a NaN workspace and buffers 4 bytes past a 256-byte boundary; whole calls; the
+recovery of a known field; recon.py --n4.  tests/test_bias_host.py covers what needs no device."""
 import ctypes as C
 import functools
 import sys
@@ -118,6 +118,21 @@ def test_every_step_equals_the_statement_and_repeats(t2, shape, side):
     8 x 2.2e-16.  The largest seen on the MI355X: 4.16e-16."""
     worst = max(_steps(t2, shape, side, kind) for kind in ("rows", "one"))
     print(f"{shape} side {side}: convergence sums, |device - statement| / sum |terms| = {worst:.3e}")
+
+
+def test_minmax_and_histogram_past_the_grid_cap(t2):
+    """1024 x 2048 + 2049 voxels: the grid stays at its 1024 workgroups, every thread makes more than eight trips, and the
+    extremes (and the last voxel) are read on the ninth alone; the final kernel reads all 1024 partials."""
+    B = t2.bias
+    u, m = (np.array(a) for a in K.capped_case())  # (the shared case is read-only)
+    w_lo, w_hi, slope = K.check_capped()           # (numpy alone: the extremes are unique and lie in the tail)
+    want = _bias.histogram(u, m, float(w_lo), slope)
+    for call in ("first", "second"):
+        lo, hi = B.minmax(u, m)
+        _same(np.array([lo, hi]), np.array([w_lo, w_hi]), f"min / max, {call} call")
+        hist = B.histogram(u, m, float(lo), slope)
+        _same(hist, want, f"histogram, {call} call")
+        assert int(hist.sum()) == int(m.sum()) << 24
 
 
 def _offset(t, elements):

@@ -56,6 +56,20 @@ def test_bin_coordinate_and_histogram_edges():
         _bias.slope_of(1.0, 1.0)
 
 
+def test_histogram_of_the_case_past_the_grid_cap_equals_the_reference():
+    """The flat case of 1024 x 2048 + 2049 voxels that tests/test_bias_gpu.py holds the device to: its conditions (the
+    extremes unique and past the 1024 x 2048 voxels of the kernels' first eight trips), and the statement's histogram
+    against the Python loop."""
+    u, m = K.capped_case()
+    lo, hi, slope = K.check_capped()
+    hist = _bias.histogram(u, m, float(lo), slope)
+    assert [int(h) for h in hist] == K.ref_histogram(u, m, float(lo), slope, _bias.BINS)
+    assert int(hist.sum()) == int(m.sum()) << 24 and int(hist[0]) >= 1 << 24 and int(hist[-1]) >= 1 << 24
+    head = np.array(m)
+    head[..., K.CAPPED_GRID_VOXELS:] = 0  # without the tail: another range and another histogram
+    assert _bias.minmax(u, head) != (lo, hi) and not np.array_equal(_bias.histogram(u, head, float(lo), slope), hist)
+
+
 # ---- the table -------------------------------------------------------------------------------------------------------------
 def _dft(x, sign=-1.0):
     n = len(x)

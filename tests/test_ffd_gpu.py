@@ -1,10 +1,11 @@
 """The non-rigid alignment's device half (csrc/t2fit_ffd.hip: t2fit_ffd_joint_hist_dev, t2fit_ffd_gradient_dev,
 t2fit_ffd_warp_dev, t2fit_ffd_jacobian_dev) against its numpy statement (fetal_t2mapping_amd/_ffd.py): histogram integer
 for integer, gradient, warp and Jacobian bit for bit, on shapes chosen against the kernels' tile (64 lanes along x, four
-rows, one plane), the register tests' cases, every lattice side and four bin pairs; masks that empty tiles or everything;
-lattices that push the volume outside; the zero lattice against the existing device calls; raw calls on a second stream
-with a guarded workspace and offset outputs; tensors as input; the whole registration, the atlas stage and recon.py.
-tests/test_ffd_host.py covers what needs no device."""
+rows, one plane), shapes with more tiles than the histogram's launch has workgroups, the register tests' cases, every
+lattice side and four bin pairs; masks that empty tiles or everything; lattices that push the volume outside; the zero
+lattice against the existing device calls; raw calls on a second stream with a guarded workspace and offset outputs;
+tensors as input; the whole registration, the atlas stage and recon.py.  tests/test_ffd_host.py covers what needs no
+device."""
 import ctypes as C
 import sys
 
@@ -81,6 +82,26 @@ def test_tile_edges_at_every_side(t2, shape):
         hist, _ = _check_metric(t2, f"{shape} side {side}", bins, moving, a, fmask, mmask, phi, n_f, n_m, lo, sc)
         assert hist.any()
         _check_warp_and_jacobian(t2, f"{shape} side {side}", moving, a, fmask, phi, shape)
+
+
+@pytest.mark.parametrize("shape", FC.CAPPED_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_histogram_of_more_tiles_than_workgroups(t2, shape):
+    """2210, 8840 and 2100 tiles under the 2048 workgroups of the histogram's launch: a workgroup stages T1 of another
+    plane and T2 of another row on its second (up to fifth) trip, and its table gathers them all before its one flush."""
+    bins, moving, a, fmask, mmask = FC.shaped(shape, cover=True)
+    for i, side in enumerate((4, 19)):
+        # (the statement alone: the tiles past the first trip hold voxels that count)
+        assert FC.check_capped(shape, side) == {(130, 65, 5): 130 * 17, (520, 65, 5): 520 * 17, (2100, 1, 3): 2100}[shape]
+        n_f, n_m = FC.BIN_PAIRS[i]
+        lo_m, scale_m = G.moving_bin_range(moving, mmask, n_m)
+        hist, _ = _check_metric(t2, f"{shape} side {side}", bins, moving, a, fmask, mmask, FC.lattice(side, 0, 1.2), n_f, n_m, lo_m, scale_m)
+        assert hist.any()
+    if shape == (130, 65, 5):  # the zero lattice: the affine histogram's kernel, capped the same way over its bricks
+        kw = dict(fixed_mask=fmask, moving_mask=mmask)
+        want = t2.register.joint_histogram(bins, moving, a, n_f, n_m, lo_m, scale_m, **kw)
+        got = t2.register.ffd_joint_histogram(bins, moving, a, np.zeros((3, 4, 4, 4)), n_f, n_m, lo_m, scale_m, **kw)
+        assert got.tobytes() == want.tobytes() and want.any()
+        assert np.array_equal(want, G.joint_histogram(bins, moving, a, n_f, n_m, lo_m, scale_m, fmask, mmask))
 
 
 # ---- 2. the register tests' cases, four bin pairs, the metric's own table ------------------------------------------------------

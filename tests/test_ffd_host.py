@@ -130,6 +130,17 @@ def _loop_parzen(m, lo_m, scale_m, n_m):
     return i0, w, dw
 
 
+def _loop_counted(moving, a, fmask, mmask, phi):
+    """``(z, y, x, m, g)`` of every fixed voxel that counts, one at a time.  The coordinates are the statement's (checked
+    above); everything after them is redone."""
+    shape = fmask.shape
+    cs = [np.broadcast_to(c, shape).tolist() for c in F.coords(a, phi, shape)]
+    for z, y, x in zip(*(v.tolist() for v in np.nonzero(fmask))):
+        got = _loop_sample(moving, mmask, [cs[k][z][y][x] for k in range(3)])
+        if got is not None:
+            yield (z, y, x) + got
+
+
 CONTRACT_RATIO = 2.17e-16  # measured with the statement on the tiny case: largest |statement - math.fsum| / largest component
 CONTRACT_BOUND = 4 * CONTRACT_RATIO
 
@@ -139,26 +150,19 @@ def test_histogram_force_and_contraction_against_a_per_voxel_loop():
     n_f, n_m = 7, 9
     lo_m, scale_m = G.moving_bin_range(moving, mmask, n_m)
     table = FC.normal_table(n_f, n_m)
-    cs = F.coords(a, phi, TINY_F)  # the coordinates are the statement's (checked above); everything after them is redone
     hist = np.zeros((n_f, n_m), np.uint64)
     force = np.zeros((3,) + TINY_F)
     counted = 0
-    for z in range(TINY_F[0]):
-        for y in range(TINY_F[1]):
-            for x in range(TINY_F[2]):
-                got = _loop_sample(moving, mmask, [float(cs[k][z, y, x]) for k in range(3)]) if fmask[z, y, x] else None
-                if got is None:
-                    continue
-                counted += 1
-                m, g = got
-                i0, w, dw = _loop_parzen(m, lo_m, scale_m, n_m)
-                b = min(int(bins[z, y, x]), n_f - 1)
-                s = 0.0
-                for j in range(4):
-                    hist[b, i0 - 1 + j] += np.uint64(math.floor(w[j] * 2.0 ** 30 + 0.5))
-                    s = s + float(table[b, i0 - 1 + j]) * dw[j]
-                for j in range(3):
-                    force[j, z, y, x] = ((s * g[0]) * a[0, j] + (s * g[1]) * a[1, j]) + (s * g[2]) * a[2, j]
+    for z, y, x, m, g in _loop_counted(moving, a, fmask, mmask, phi):
+        counted += 1
+        i0, w, dw = _loop_parzen(m, lo_m, scale_m, n_m)
+        b = min(int(bins[z, y, x]), n_f - 1)
+        s = 0.0
+        for j in range(4):
+            hist[b, i0 - 1 + j] += np.uint64(math.floor(w[j] * 2.0 ** 30 + 0.5))
+            s = s + float(table[b, i0 - 1 + j]) * dw[j]
+        for j in range(3):
+            force[j, z, y, x] = ((s * g[0]) * a[0, j] + (s * g[1]) * a[1, j]) + (s * g[2]) * a[2, j]
     assert 40 < counted < fmask.size
     assert np.array_equal(F.joint_histogram(bins, moving, a, phi, n_f, n_m, lo_m, scale_m, fmask, mmask), hist)
     f = F.force(bins, table, moving, a, phi, n_m, lo_m, scale_m, fmask, mmask)
@@ -172,6 +176,30 @@ def test_histogram_force_and_contraction_against_a_per_voxel_loop():
     ratio = float(np.max(np.abs(grad - exact)) / np.max(np.abs(exact)))
     print(f"contraction: largest |statement - fsum| / largest component {ratio:.3g}")
     assert ratio <= CONTRACT_BOUND
+
+
+def test_histogram_of_a_shape_with_more_tiles_than_workgroups_against_the_per_voxel_loop():
+    """(130, 65, 5): the smallest of ffd_cases.CAPPED_SHAPES, which tests/test_ffd_gpu.py holds the device to.  The loop also
+    counts what the tiles past the histogram kernel's 2048 workgroups add."""
+    shape = FC.CAPPED_SHAPES[0]
+    bins, moving, a, fmask, mmask = FC.shaped(shape, cover=True)
+    a = np.asarray(a, np.float64).reshape(3, 4)
+    tile = np.broadcast_to(FC.tile_index(shape), shape)
+    (n_f, n_m), side = FC.BIN_PAIRS[1], 19
+    lo_m, scale_m = G.moving_bin_range(moving, mmask, n_m)
+    phi = FC.lattice(side, 0, 1.2)
+    hist, late = [[0] * n_m for _ in range(n_f)], 0
+    for z, y, x, m, _ in _loop_counted(moving, a, fmask, mmask, phi):
+        i0, w, _ = _loop_parzen(m, lo_m, scale_m, n_m)
+        row = hist[min(int(bins[z, y, x]), n_f - 1)]
+        for j in range(4):
+            row[i0 - 1 + j] += math.floor(w[j] * 2.0 ** 30 + 0.5)
+        late += int(tile[z, y, x] >= 2048)
+    assert F.joint_histogram(bins, moving, a, phi, n_f, n_m, lo_m, scale_m, fmask, mmask).tolist() == hist
+    assert late > 1000
+    for s in (4, 19):
+        for cap_shape in FC.CAPPED_SHAPES:
+            assert FC.check_capped(cap_shape, s) == cap_shape[0] * -(-cap_shape[1] // 4)
 
 
 def test_a_non_finite_force_stays_inside_its_support():

@@ -1,9 +1,9 @@
 """Mattes mutual information's device half (csrc/t2fit_register.hip: t2fit_register_joint_hist_dev,
 t2fit_register_mi_gradient_dev) against its numpy statement (fetal_t2mapping_amd/_register.py): the joint histogram integer
 for integer and the 12 gradient sums bit for bit on the named cases of the 43 sums at four bin pairs, histograms in which
-every voxel hits the same entries, raw calls through unaligned-but-legal pointers with a guarded workspace, the whole
-registration with 6 and 12 degrees of freedom, and every refusal of the ABI.  tests/test_mi_host.py covers what needs no
-device."""
+every voxel hits the same entries, volumes with more bricks than the histogram's launch has workgroups, raw calls through
+unaligned-but-legal pointers with a guarded workspace, the whole registration with 6 and 12 degrees of freedom, and every
+refusal of the ABI.  tests/test_mi_host.py covers what needs no device."""
 import ctypes as C
 
 import numpy as np
@@ -75,6 +75,24 @@ def test_histograms_in_which_the_lanes_of_a_wave_meet(t2, name):
             assert np.count_nonzero(got.sum(axis=0)) <= 4 and got.max() > 1000 * MC.ONE // 6
         else:
             assert np.count_nonzero(got.sum(axis=1)) > 32
+
+
+@pytest.mark.parametrize("name", tuple(MC.CAPPED) + ("capped2_constant",))
+def test_histogram_of_more_bricks_than_workgroups(t2, name):
+    """2322 and 8514 bricks under the 2048 workgroups of the launch: a workgroup's table gathers two (up to five) bricks
+    before its one flush.  'capped2_constant': every brick of a workgroup adds to the same four columns."""
+    of = "capped2" if name == "capped2_constant" else name
+    assert MC.check_capped(of) == {"capped2": 2322, "capped5": 8514}[of]  # (the statement alone: the late bricks count)
+    n = MC.counted(name)
+    for n_f, n_m in MC.BIN_PAIRS:
+        got, want = _hist(t2, name, n_f, n_m), MC.statement_hist(name, n_f, n_m)
+        assert got.dtype == np.uint64 and got.shape == (n_f, n_m)
+        bad = np.argwhere(got != want)
+        assert bad.size == 0, (name, n_f, n_m, bad[:8], got[got != want][:8], want[got != want][:8])
+        assert got.tobytes() == _hist(t2, name, n_f, n_m).tobytes()  # the same from call to call
+        assert abs(int(got.sum(dtype=np.uint64)) - n * MC.ONE) <= 2 * n
+        if name == "capped2_constant":
+            assert np.count_nonzero(got.sum(axis=0)) <= 4 and got.max() > 1000 * MC.ONE // 6
 
 
 # ---- 11. the gradient sums -----------------------------------------------------------------------------------------------------

@@ -105,6 +105,19 @@ def test_joint_histogram_equals_the_per_voxel_loop(name):
         else:
             assert got.any() and not got[:, 0].any()  # bin 0 is padding no window reaches
     assert (len(_counted(name)) == 0) == (name == "nothing") and len(_counted(name)) == K.statement_sums(name)[0]
+    if name == "capped2_thin":  # the thinned mask keeps voxels that count in the bricks past the kernel's 2048 workgroups
+        brick = MC.brick_index(MC.inputs(name, 64)[0].shape)
+        late = sum(1 for ix, iy, iz, _, _ in _counted(name) if brick[iz, iy, ix] >= MC.HIST_GRID)
+        assert late > 100 and late == K.counted_per_slab(name)[MC.HIST_GRID:].sum()
+
+
+@pytest.mark.parametrize("name", MC.CAPPED)
+def test_capped_cases_have_more_bricks_than_workgroups_and_their_late_bricks_count(name):
+    """The conditions tests/test_mi_gpu.py relies on, with the statement alone (mi_cases.check_capped)."""
+    assert MC.check_capped(name) == {"capped2": 9 * 258, "capped5": 33 * 258}[name]
+    n = MC.counted(name)
+    for n_f, n_m in ((32, 32), (1, 5)):  # the total the device test asserts: four roundings of half a unit per voxel
+        assert abs(sum(int(v) for v in MC.statement_hist(name, n_f, n_m).ravel().tolist()) - n * MC.ONE) <= 2 * n
 
 
 # ---- 2. the tie to the correlation ratio's counts --------------------------------------------------------------------------

@@ -1,8 +1,9 @@
 """The MP-PCA denoiser on the device (csrc/t2fit_mppca.hip: mppca_eigen_kernel, mppca_aggregate_kernel) against its numpy
 statement (fetal_t2mapping_amd/_mppca.py): the uint32 views of out and sigma, and rank, exactly, over the table of
-tests/mppca_cases.py, both estimators, degenerate blocks, a NaN, a mask, raw calls (in place, offset buffers, a caller's
-stream, a poisoned workspace, estimate-only without a workspace, repeats, refusals), slice groups and slabs, the CLI and
-the unchanged default path.  tests/test_mppca_host.py holds the statement to an independent reference."""
+tests/mppca_cases.py, every echo count from 2 to 16, both estimators, degenerate blocks, a NaN, a mask, raw calls (in
+place, offset buffers, a caller's stream, a poisoned workspace, estimate-only without a workspace, repeats, refusals),
+slice groups and slabs, the CLI and the unchanged default path.  tests/test_mppca_host.py holds the statement to an
+independent reference."""
 import ctypes as C
 import os
 
@@ -62,42 +63,73 @@ def test_both_estimators(t2, case):
     assert one[2].tobytes() != two[2].tobytes() and one[0].tobytes() != two[0].tobytes()
 
 
-def test_constant_and_zero_blocks_one_nan_and_a_mask_with_holes(t2):
+@pytest.mark.parametrize("case", K.EVERY_M, ids=["x".join(map(str, c[:4])) + f"-{c[4]}d-r{c[5]}" for c in K.EVERY_M])
+def test_every_echo_count_with_both_estimators(t2, case):
+    """M = 2 .. 8 each have kernels of their own (the matrices in registers, every index a constant), M = 9 .. 16 share
+    the generic pair: each launched, the centres more than one wave and the last wave ragged."""
+    a = np.array(K.gpu_stack(case))
+    for estimator in (2, 1):
+        want = K.gpu_want(case, estimator)
+        _same(_run(t2, a, case[5], case[4], estimator=estimator), want, (case, estimator))
+        assert np.isfinite(want[0]).all() and (want[1] > 0).all() and want[2].min() >= 1 and want[0].tobytes() != a.tobytes()
+    centres = np.prod([n - 2 * case[5] for n in case[2:4]]) * (case[1] - 2 * case[5] if case[4] == 3 else case[1])
+    assert centres > 64 and centres % 64 != 0
+
+
+def _degenerate_blocks(t2, m):
+    """A constant block, an all-zero block, one NaN and a mask with holes at ``m`` echoes, 2-D and 3-D.  Radius 1, but for
+    2-D above 8 echoes radius 2: a window holds more voxels than there are echoes, and 9 are not more than 12."""
     from fetal_t2mapping_amd import _mppca
 
-    shape = (4, 3, 13, 21)
+    shape = (m, 3, 13, 21)
+    cases = [(dims, 2 if dims == 2 and m >= 9 else 1) for dims in (2, 3)]
+    if m >= 9:
+        with pytest.raises(ValueError, match="more voxels"):
+            _mppca.check(shape, 1, 2, 2)
     a = np.array(K.picture(shape, seed=77))
     a[:, :, 3:9, 2:9] = 250.0                      # a constant block: G of rank 1 exactly, with ties in its spectrum
     a[:, :, 6:13, 12:21] = 0.0                     # an all-zero block: G = 0, no sweep, nothing cut
-    for dims in (2, 3):
-        want = _mppca.mppca(a, 1, dims)
-        _same(_run(t2, a, 1, dims), want, ("blocks", dims))
+    for dims, r in cases:
+        want = _mppca.mppca(a, r, dims)
+        _same(_run(t2, a, r, dims), want, ("blocks", m, dims))
         assert want[2][1, 9, 16] == shape[0] and want[1][1, 9, 16] == 0.0 and not want[0][:, 1, 9, 16].any()
     b = np.array(K.picture(shape, seed=78))
     b[2, 1, 6, 10] = np.nan
     mask = K.holes_mask(shape[1:])
-    for dims in (2, 3):
-        want = _mppca.mppca(b, 1, dims)
-        _same(_run(t2, b, 1, dims), want, ("nan", dims))
+    for dims, r in cases:
+        want = _mppca.mppca(b, r, dims)
+        _same(_run(t2, b, r, dims), want, ("nan", m, dims))
         assert np.isnan(want[0][2, 1, 6, 10]) and np.isnan(want[0]).sum() == 1 and want[1][1, 6, 10] == 0.0
-        want = _mppca.mppca(b, 1, dims, mask=mask)
-        _same(_run(t2, b, 1, dims, mask=mask), want, ("nan + mask", dims))
+        want = _mppca.mppca(b, r, dims, mask=mask)
+        _same(_run(t2, b, r, dims, mask=mask), want, ("nan + mask", m, dims))
         clean = np.array(K.picture(shape, seed=78))
-        want = _mppca.mppca(clean, 1, dims, mask=mask)
-        _same(_run(t2, clean, 1, dims, mask=mask), want, ("mask", dims))
+        want = _mppca.mppca(clean, r, dims, mask=mask)
+        _same(_run(t2, clean, r, dims, mask=mask), want, ("mask", m, dims))
         assert (want[1] == 0).any() and (want[1] > 0).any() and (want[0] == clean).all(axis=0).any()
-        sigma, rank = t2.mppca_noise_map(clean, radius=1, dims=dims, mask=mask)
+        sigma, rank = t2.mppca_noise_map(clean, radius=r, dims=dims, mask=mask)
         assert sigma.tobytes() == want[1].tobytes() and rank.tobytes() == want[2].tobytes()
-        none = _run(t2, clean, 1, dims, mask=np.zeros(shape[1:], np.uint8))
+        none = _run(t2, clean, r, dims, mask=np.zeros(shape[1:], np.uint8))
         assert none[0].tobytes() == clean.tobytes() and not none[1].any() and not none[2].any()
 
 
-@pytest.mark.parametrize("case", [(6, 3, 9, 68, 2, 1), (8, 5, 7, 12, 3, 1), (9, 4, 6, 8, 3, 1)], ids=["6-2d", "8-3d", "9-3d-generic"])
+def test_constant_and_zero_blocks_one_nan_and_a_mask_with_holes(t2):
+    _degenerate_blocks(t2, 4)
+
+
+@pytest.mark.parametrize("m", [5, 7, 12])
+def test_degenerate_blocks_at_the_echo_counts_no_other_test_launches_and_on_the_generic_path(t2, m):
+    _degenerate_blocks(t2, m)
+
+
+@pytest.mark.parametrize("case", [(6, 3, 9, 68, 2, 1), (8, 5, 7, 12, 3, 1), (9, 4, 6, 8, 3, 1), (5, 3, 7, 12, 3, 1), (7, 2, 9, 12, 2, 1),
+                                  (12, 3, 7, 12, 3, 1)], ids=["6-2d", "8-3d", "9-3d-generic", "5-3d", "7-2d", "12-3d-generic"])
 def test_raw_calls_on_another_stream_poisoned_workspace_offset_buffers_and_estimate_only(t2, case):
     """ctypes calls on a caller's stream, the workspace all 0xFF before each call: (a) in and out 4 bytes past a 256-byte
     boundary, (b) only out, (c) only in, (d) in place 4 bytes past, (e) aligned and in place, (f) aligned with sigma and
     rank NULL, (g) estimate-only: out NULL, workspace NULL and 0 bytes; (e) three times over.  Every result bit-equal to the
-    statement; the words around every buffer keep their bytes."""
+    statement; the words around every buffer keep their bytes.  Under the mask a centre that is not processed must still
+    write a zero projector over the poisoned words, for all M (M + 1) / 2 pairs: in the kernels of M = 5 and 7 as on the
+    generic path (M = 9, 12)."""
     import torch
 
     from fetal_t2mapping_amd import _abi, _mppca

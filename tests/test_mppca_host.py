@@ -41,6 +41,20 @@ def test_statement_against_the_patch_by_patch_reference(shape, dims, radius, see
         assert (kept == 1).any() and (kept == 2).any()
 
 
+def test_the_device_cases_of_every_echo_count_are_legal_ragged_and_not_degenerate():
+    """What tests/test_mppca_gpu.py assumes of mppca_cases.EVERY_M, with the statement alone: every M from 2 to 16 is there,
+    the centres fill more than one wave of 64 and end in a ragged one, every centre is processed and keeps a component."""
+    assert sorted({c[0] for c in K.EVERY_M}) == list(range(2, K.MAX_TE + 1))
+    for case in K.EVERY_M:
+        m, nz, ny, nx, dims, r = case
+        _mppca.check(case[:4], r, dims, 2)
+        centres = (nz - 2 * r if dims == 3 else nz) * (ny - 2 * r) * (nx - 2 * r)
+        assert centres > 64 and centres % 64 != 0, case
+        for estimator in (2, 1):
+            out, sigma, rank = K.gpu_want(case, estimator)
+            assert np.isfinite(out).all() and (sigma > 0).all() and 1 <= rank.min() and rank.max() < m, (case, estimator)
+
+
 def test_ordered_window_sum_against_a_triple_loop_bit_for_bit():
     rng = np.random.default_rng(5)
     a = rng.normal(size=(6, 9, 11)) * 10.0 ** rng.integers(-8, 8, size=(6, 9, 11))  # (rounding differs with the order)
